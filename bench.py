@@ -13,7 +13,10 @@ small all-gather.
   --scaling strong (default)  the SAME 512^3 grid on every N — the configuration the metric and its 1 -> 8 target are quoted on;
   --scaling weak              BASELINE config 5: all lengths x N^(1/3), every rank keeps the 512^3 voxel count (N = 8: 1024^3).
 
-Beside the headline, rank 0 at N = 1 reports (each with the oracle timed beside it and a parity verdict):
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`); --dump-outputs DIR also writes
+what the last timed step computed (dump_outputs). With --full, rank 0 also reports the stage times, the isolated step, the roofline and the
+remesh-only timing; at N > 1 the other scaling mode; at N = 1 the CPU baseline with the parity of the timed step, and (each with the
+oracle timed beside it and a parity verdict):
   dense    all-surface workload (32 perforated plates, every chunk NonUniform and meshed): here the per-voxel byte accounting of
            SURVEY §8d applies to the whole grid, so `roofline.frac` of this leg IS an HBM fraction
   config2  256^3 asteroid: Surface Nets remesh + mass/inertia
@@ -401,6 +404,58 @@ def remesh_only_ms(ctx, obj, steps=10):
 
     _, _, sm = time_steps(ctx, obj, capi.STAGE_REMESH, steps, 2)
     return float(sm[2] + sm[3] + sm[4])
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_MAX_VERTICES = 1 << 19    # vertex rows written; above it a fixed, seeded sample of them
+DUMP_MAX_TRIANGLES = 1 << 18   # triangle rows written; above it a fixed, seeded sample of them
+
+
+def _sample_rows(n, k, seed):
+    """the sorted row numbers of a fixed, seeded sample of k of n rows (every row when n <= k)"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(dirname, obj, res, body_world):
+    """--dump-outputs: what the last timed step hands its caller, as DIR/<name>.npy in float32 / float64 — the step record (mesh counts,
+    regions, occupied ranges, moments), the mesh buffers it left in HBM (positions, normals, triangles, index materials, submeshes) and the
+    state of the object's rigid body after its integrate. Integers are written as float64 (exact)."""
+    from numpy.lib import recfunctions as rfn
+
+    from impact_amd.voxel import VoxelObjectMesh
+
+    mesh = VoxelObjectMesh(obj)
+    mesh.counts = res["mesh"]
+    pos, nrm, idx, im, sub = mesh.download()
+    vrows = _sample_rows(pos.shape[0], DUMP_MAX_VERTICES, 1)
+    trows = _sample_rows(idx.size // 3, DUMP_MAX_TRIANGLES, 2)
+    body = body_world.bodies()[0][0]
+    arrays = {
+        "mesh_counts": np.array([res["mesh"][k] for k in ("n_vertices", "n_indices", "n_submeshes")], dtype=np.float64),
+        "region_count": np.array([res["region_count"]], dtype=np.float64),
+        "occupied_ranges": np.asarray(res["occupied"], dtype=np.float64),
+        "moments_m64": np.asarray(res["moments"]["m64"], dtype=np.float64),
+        "moments_m32": np.asarray(res["moments"]["m32"], dtype=np.float32),
+        "mesh_vertex_rows": vrows.astype(np.float64),
+        "mesh_positions": pos[vrows],
+        "mesh_normals": nrm[vrows],
+        "mesh_triangle_rows": trows.astype(np.float64),
+        "mesh_triangles": idx.reshape(-1, 3)[trows].astype(np.float64),
+        "mesh_triangle_materials": im.reshape(-1, 3, 8)[trows].astype(np.float32),
+        "mesh_submeshes": rfn.structured_to_unstructured(sub, dtype=np.float64),
+        "body_position": np.asarray(body["position"], dtype=np.float32),
+        "body_orientation": np.asarray(body["orientation"], dtype=np.float32),
+        "body_momentum": np.asarray(body["momentum"], dtype=np.float32),
+        "body_angular_momentum": np.asarray(body["angular_momentum"], dtype=np.float32),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def chunk_census(obj):
@@ -1437,7 +1492,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pile", action="store_true", help="skip the separate legs (dense, config2, config3, pile, frame, edit, collide)")
     ap.add_argument("--plain", action="store_true", help="profiling runs: nothing but full steps (no remesh-only timing pass), so that every kernel launch rocprofv3 sees belongs to a step")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: stage times, the isolated step, roofline, remesh-only timing, CPU baselines and parity, the "
+                         "other legs (N = 1) or the other scaling mode (N > 1). Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB; N = 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.profiles:
         global PROFILE_DIR
         PROFILE_DIR = os.path.abspath(args.profiles)
@@ -1449,6 +1511,8 @@ def main():
         if world == 1 and args.gpus > 1:
             raise SystemExit("launch with: python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py --gpus N ...")
         args.gpus = world
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs: single-GPU runs only (--gpus 1)")
 
     import torch
 
@@ -1587,19 +1651,26 @@ def main():
         dom_sum += float(res["stage_ms"][dom])
     barrier()
     elapsed = time.perf_counter() - t0
-    obj.set_stage_timing(0xFFFFFFFF)
-    stage_sum = np.zeros(capi.N_TIMED_STAGES, dtype=np.float64)
-    n_stage_pass = max(3, min(args.steps, 10))
-    for _ in range(n_stage_pass):
-        res = step()
-        stage_sum += res["stage_ms"]
-    barrier()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        if slabs:
+            raise SystemExit("--dump-outputs: not with the slab protocol")
+        dump_outputs(args.dump_outputs, obj, res, body_world)
+    # (a plain run ends its GPU work here: what follows up to the print is --full)
+    n_stage_pass = 0
+    if args.full:
+        obj.set_stage_timing(0xFFFFFFFF)
+        stage_sum = np.zeros(capi.N_TIMED_STAGES, dtype=np.float64)
+        n_stage_pass = max(3, min(args.steps, 10))
+        for _ in range(n_stage_pass):
+            res = step()
+            stage_sum += res["stage_ms"]
+        barrier()
     isolated = None
-    if not slabs and sample_ahead and not args.plain:
+    if args.full and not slabs and sample_ahead and not args.plain:
         # the same step with its pre-pass as its own first kernel (what a step that is not followed by another costs)
         obj.set_sample_ahead(False)
         n_iso = max(5, min(args.steps, 100))
@@ -1622,7 +1693,7 @@ def main():
 
     # N > 1: the other scaling mode in the same run (the metric's 1 -> 8 target is about the strong leg, config 5 is the weak one)
     other_leg = None
-    if slabs and args.workload == "asteroid":
+    if args.full and slabs and args.workload == "asteroid":
         mode2 = "weak" if scaling == "strong" else "strong"
         _, nm2, st2, obj2, step2, _ = slab_leg(mode2)
         for _ in range(max(2, min(args.warmup, 5))):
@@ -1652,11 +1723,32 @@ def main():
         n_vox_total, tris_total = int(t[0].item()), int(t[1].item())
     else:
         n_vox_total, tris_total = n_vox_rank, tris_rank
-    stage_ms = stage_sum / n_stage_pass
-    stage_ms[dom] = dom_sum / args.steps  # the dominant slot: measured inside the timed region
     ms_per_step = 1e3 * elapsed / args.steps
 
     if rank == 0:
+        out = {
+            "metric": "voxels stepped/sec + remesh tris/sec, 512^3 grid, 1/2/4/8 MI355X",
+            "value": n_vox_total / (elapsed / args.steps),
+            "unit": "voxels/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "i8 voxels, f32 SDF/mesh arithmetic, f64 moments",
+            "data": "synthetic",
+            "config": {"workload": workload, "parallelism": parallelism, "voxels_per_gpu": n_vox_rank, "regions": int(res["region_count"]), "triangles": tris_total},
+            "full": bool(args.full),
+        }
+        if slabs:
+            out["ranks"] = {"world_size": world, "backend": dist.get_backend(),
+                            "communicator_ranks": (native_comm.info()["nranks"] if native_comm is not None else dist.get_world_size()),
+                            "communicator": ("RCCL communicator made by the library (ncclCommCount)" if native_comm is not None else "torch.distributed process group")}
+    if rank == 0 and args.full:
+        stage_ms = stage_sum / n_stage_pass
+        stage_ms[dom] = dom_sum / args.steps  # the dominant slot: measured inside the timed region
         exposed, non_uniform = chunk_census(obj)
         counters = obj.stage_counters()
         # chunks whose voxels are touched per step: the ones that have planes (NonUniform) and the ones the sampler evaluates per voxel
@@ -1669,24 +1761,11 @@ def main():
         # N = 1: Surface Nets timed alone over the resident object; N > 1: the three launches that host it inside the step (they
         # also carry the region / moment table roles)
         remesh_ms = remesh_only_ms(ctx, obj) if not (slabs or args.plain) else float(stage_ms[2] + stage_ms[3] + stage_ms[4])
-        out = {
-            "metric": "voxels stepped/sec + remesh tris/sec, 512^3 grid, 1/2/4/8 MI355X",
-            "value": n_vox_total / (elapsed / args.steps),
-            "unit": "voxels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
+        out["config"].update({"active_voxels_rank0": active, "vertices_rank0": nv, "exposed_chunks_rank0": exposed,
+                              "non_uniform_chunks_rank0": non_uniform, "evaluated_chunks_rank0": counters["evaluated_chunks"],
+                              "meshed_chunks_rank0": counters["meshed_chunks"]})
+        out.update({
             "stage_timing": f"timed region: events around slot {dom} ({capi.STAGE_NAMES[dom]}) only; `stage_ms` of the other slots from {n_stage_pass} further steps with every slot timed",
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "i8 voxels, f32 SDF/mesh arithmetic, f64 moments",
-            "data": "synthetic",
-            "config": {"workload": workload, "parallelism": parallelism, "voxels_per_gpu": n_vox_rank, "active_voxels_rank0": active,
-                       "regions": int(res["region_count"]), "triangles": tris_total, "vertices_rank0": nv, "exposed_chunks_rank0": exposed,
-                       "non_uniform_chunks_rank0": non_uniform, "evaluated_chunks_rank0": counters["evaluated_chunks"],
-                       "meshed_chunks_rank0": counters["meshed_chunks"]},
             "remesh_tris_per_s": tris_rank / (remesh_ms * 1e-3) if remesh_ms > 0 else None,
             "remesh_ms": remesh_ms,
             "active_voxels_per_s": active * world / (elapsed / args.steps),
@@ -1699,7 +1778,7 @@ def main():
             "stage_gbs_accounting": "active-voxel algorithmic bytes / live HIP-event stage time (never above the 6.3 TB/s copy rate by construction of the bytes)",
             "roofline": rl,
             "step_roofline": srl,
-        }
+        })
         if not slabs:
             out["sample_ahead"] = {"on": bool(sample_ahead), "isolated": isolated,
                                    "what": "the sample stage's interval pre-pass (k_sdf_prepass: reads only the resident program) is enqueued one step ahead on the "
@@ -1714,9 +1793,6 @@ def main():
             out["scaling_legs"] = {main_leg["scaling"]: main_leg}
             if other_leg:
                 out["scaling_legs"][other_leg["scaling"]] = other_leg
-            out["ranks"] = {"world_size": world, "backend": dist.get_backend(),
-                            "communicator_ranks": (native_comm.info()["nranks"] if native_comm is not None else dist.get_world_size()),
-                            "communicator": ("RCCL communicator made by the library (ncclCommCount)" if native_comm is not None else "torch.distributed process group")}
         o_big = m_big = None
         if world == 1 and not args.no_cpu_baseline:
             what = "full N=1 workload" if args.workload == "asteroid" else "the timed scene"
@@ -1841,6 +1917,7 @@ def main():
             w.close()
         out = compact_parities(out)
         out["summary"] = summary_block(out)  # (last key: the tail of the line)
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -8,7 +8,7 @@ for rep in 1 2; do
     for wl in headline dense; do
       if [ "$which" != both ] && [ "$which" != $wl ]; then continue; fi
       if [ $wl = dense ]; then W="--workload dense"; else W=""; fi
-      IMPACT_VOXEL_HIP_LIB=$PWD/build/lib_$v.so python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-pile --plain $W 2>/dev/null | tail -1 > /tmp/ab.json
+      IMPACT_VOXEL_HIP_LIB=$PWD/build/lib_$v.so python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-pile --plain $W 2>/dev/null | tail -1 > /tmp/ab.json
       python - $v $wl <<'P'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

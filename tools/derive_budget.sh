@@ -7,7 +7,7 @@ out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 make -C impact_amd/csrc -j16 EXTRA=-DIVX_DERIVE_DEBUG > "$out/build.log" 2>&1 || { tail -5 "$out/build.log"; exit 1; }
-STEPS="--steps 6 --warmup 2 --no-cpu-baseline --no-pile --plain"
+STEPS="--full --steps 6 --warmup 2 --no-cpu-baseline --no-pile --plain"
 {
 for wl in headline dense; do
   if [ $wl = dense ]; then W="--workload dense"; else W=""; fi

@@ -5,7 +5,7 @@ tag=${1:-dw}
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-STEPS="--steps 10 --warmup 3 --no-cpu-baseline --no-pile --plain"
+STEPS="--full --steps 10 --warmup 3 --no-cpu-baseline --no-pile --plain"
 {
 for w in 7 6 5; do
   make -C impact_amd/csrc -j16 EXTRA=-DIVX_DERIVE_WAVES=$w > "$out/build_$w.log" 2>&1 || { tail -5 "$out/build_$w.log"; exit 1; }

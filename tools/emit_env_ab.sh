@@ -3,7 +3,7 @@
 tag=${1:-envab}
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
 one() {
   label=$1; shift
   env "$@" python3 bench.py $ARGS 2>/dev/null | tail -1 > /tmp/ab.json

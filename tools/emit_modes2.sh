@@ -10,7 +10,7 @@ n_pmc=${3:-4}
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
 smi() {  # one line: sclk / mclk / fclk / socclk, power, temperature (whatever this box's tools report to an ordinary user)
   (rocm-smi --showclocks --showpower --showtemp 2>/dev/null | grep -i "sclk\|mclk\|fclk\|socclk\|power\|Temperature (Sensor junction)\|Temperature (Sensor memory)" | sed 's/^.*GPU\[0\]\s*:\s*//' | tr '\n' ';') || true
 }

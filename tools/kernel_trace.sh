@@ -5,7 +5,7 @@ tag=${1:-kt}; shift
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$out/trace" -o trace -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pile "$@" > "$out/trace_stdout.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/trace" -o trace -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pile "$@" > "$out/trace_stdout.log" 2>&1
 python tools/rocpd_stats.py "$(ls "$out"/trace/*.db | tail -1)" > "$out/kernel_stats.csv"
 rm -rf "$out/trace"
 python - "$out/kernel_stats.csv" <<'PY'

@@ -4,7 +4,7 @@
 tag=${1:-phase}
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
 run() {  # label, env...
   label=$1; shift
   for i in 1 2 3; do

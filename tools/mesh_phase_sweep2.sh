@@ -2,7 +2,7 @@
 tag=${1:-phase2}
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-pile --plain --workload dense"
 run() {
   label=$1; n=$2; shift; shift
   for i in $(seq 1 $n); do

@@ -13,7 +13,7 @@ if [ "${2:-}" != "skip-tests" ]; then
   tail -2 "$out/${tag}_pytest_gpu.log"
 fi
 # --plain: full steps only: 2 warm-up + 10 timed + 10 with every slot timed = 22 steps
-STEPS="--steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain"
+STEPS="--full --steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain"
 NST=22
 for wl in headline dense; do
   if [ $wl = dense ]; then W="--workload dense"; else W=""; fi
@@ -32,7 +32,7 @@ for wl in headline dense; do
   rm -rf "$out/trace_$wl" "$out/pmc_fetch_$wl" "$out/pmc_write_$wl" "$out/pmc_valu_$wl"
 done
 # the default bench line LAST, quoting the counter summaries just made (same kernel sources: `roofline.traffic` is live)
-python bench.py --profiles "$out" 2> "$out/bench_stderr.log" | tail -1 > "$out/${tag}_bench_n1.json"
+python bench.py --full --profiles "$out" 2> "$out/bench_stderr.log" | tail -1 > "$out/${tag}_bench_n1.json"
 # the edit path, the incremental remesh and the many-object frame under the kernel trace (their own timing lines + kernel tables)
 bash tools/prof_edit.sh $tag > "$out/prof_edit.log" 2>&1
 bash tools/prof_sync.sh $tag > "$out/prof_sync.log" 2>&1

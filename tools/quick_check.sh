@@ -3,8 +3,8 @@
 set -u
 out=$PWD/gpurun_out/r2m
 mkdir -p "$out"
-python bench.py --plain --steps 200 2>/dev/null | tail -1 > "$out/plain.json"
-python bench.py --plain --steps 100 --workload dense 2>/dev/null | tail -1 > "$out/plain_dense.json"
+python bench.py --full --plain --steps 200 2>/dev/null | tail -1 > "$out/plain.json"
+python bench.py --full --plain --steps 100 --workload dense 2>/dev/null | tail -1 > "$out/plain_dense.json"
 python - <<'PY'
 import json
 for f in ('plain','plain_dense'):

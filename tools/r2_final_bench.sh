@@ -2,9 +2,9 @@
 # the bench lines that go into profiles/round2 (run after the PMC summaries of the same build are in place: bench.py reads them)
 out=$PWD/gpurun_out/${1:-r2q}
 mkdir -p "$out"
-python bench.py 2> "$out/bench_stderr.log" | tail -1 > "$out/bench_n1.json"
-python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain 2>/dev/null | tail -1 > "$out/bench_step_only_headline.json"
-python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain --workload dense 2>/dev/null | tail -1 > "$out/bench_step_only_dense.json"
+python bench.py --full 2> "$out/bench_stderr.log" | tail -1 > "$out/bench_n1.json"
+python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain 2>/dev/null | tail -1 > "$out/bench_step_only_headline.json"
+python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain --workload dense 2>/dev/null | tail -1 > "$out/bench_step_only_dense.json"
 python - "$out" <<'PY'
 import json, sys
 for f in ('bench_n1', 'bench_step_only_headline', 'bench_step_only_dense'):

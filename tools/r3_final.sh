@@ -10,7 +10,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 python -m pytest tests -m gpu -x -q > "$out/${tag}_pytest_gpu.log" 2>&1
 grep -E "passed|failed|error" "$out/${tag}_pytest_gpu.log" | tail -2
-STEPS="--steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain"
+STEPS="--full --steps 10 --warmup 2 --no-cpu-baseline --no-pile --plain"
 NST=22
 for wl in headline dense; do
   if [ $wl = dense ]; then W="--workload dense"; else W=""; fi
@@ -27,7 +27,7 @@ for wl in headline dense; do
 done
 mkdir -p profiles/round3
 cp "$out"/pmc_traffic_*.json "$out"/pmc_valu_*.json profiles/round3/
-python bench.py 2> "$out/bench_stderr.log" | tail -1 > "$out/${tag}_bench_n1.json"
+python bench.py --full 2> "$out/bench_stderr.log" | tail -1 > "$out/${tag}_bench_n1.json"
 for n in 1 2 4 8; do python tools/time_slab_overhead.py 200 $n 2>/dev/null | tail -2; done > "$out/${tag}_slab_overhead.log"
 python tools/time_pile.py 2>/dev/null | tail -1 > "$out/${tag}_time_pile.log"
 IVX_SOLVER_SERIAL=1 python tools/time_pile.py 2>/dev/null | tail -1 >> "$out/${tag}_time_pile.log"

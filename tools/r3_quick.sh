@@ -13,7 +13,7 @@ elif [ "$sel" != "none" ]; then
 fi
 for wl in headline dense; do
   if [ $wl = dense ]; then W="--workload dense"; else W=""; fi
-  python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-pile --plain $W 2> "$out/bench_$wl.err" | tail -1 > "$out/bench_$wl.json"
+  python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-pile --plain $W 2> "$out/bench_$wl.err" | tail -1 > "$out/bench_$wl.json"
   python - "$out/bench_$wl.json" $wl <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))

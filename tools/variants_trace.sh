@@ -7,7 +7,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 for v in "$@"; do
   if [ "$v" = default ]; then unset IMPACT_VOXEL_HIP_LIB; else export IMPACT_VOXEL_HIP_LIB=$PWD/impact_amd/lib/var_$v/libimpact_voxel_hip.so; fi
-  rocprofv3 --kernel-trace --stats -d "$out/trace_$v" -o trace -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pile --plain $BENCH_ARGS > "$out/bench_$v.json" 2> "$out/stderr_$v.log"
+  rocprofv3 --kernel-trace --stats -d "$out/trace_$v" -o trace -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-pile --plain $BENCH_ARGS > "$out/bench_$v.json" 2> "$out/stderr_$v.log"
   python tools/rocpd_stats.py "$(ls "$out"/trace_$v/*.db | tail -1)" > "$out/kernel_stats_$v.csv"
   rm -rf "$out/trace_$v"
   echo "== $v" | tee "$out/$v.txt"

@@ -38,6 +38,7 @@ struct SnParams {
     GridView g;
     float extent;
     uint32_t x_off;
+    uint32_t single_type;  // role_sn_emit<.., true>: the type of every voxel of every NonUniform chunk (ivx_grid::signs_type)
 };
 
 // What one padded row needs from memory, with every load ISSUED before any of them is used. Written the obvious way (record, then
@@ -1016,7 +1017,8 @@ __device__ __forceinline__ void edge_centroid(const float d[8], uint32_t neg, V3
 // uniform type: what the rows need of their three chunks, the upper-layer rule of its three, the submesh of the chunk itself). A mesher
 // workgroup issues them for its NEXT chunk before the quad phase of the current one (tile_issue), passes the records through LDS
 // (tile_records) and looks at the rows when that chunk's turn comes (tile_finish): the tile's trip to memory — a third of a workgroup's time
-// per chunk when it was taken at the start of the chunk — is then covered by the quad phase. 25 registers per thread while in flight.
+// per chunk when it was taken at the start of the chunk — is then covered by the quad phase. 25 registers per thread while in flight; 13
+// in the single-type form (ST: the grid's NonUniform chunks have one voxel type, ivx_grid::signs_type), which loads no type bytes at all.
 struct RowData {
     uint4 s4, t4;
     uint32_t b0s, b0t, b2s, b2t;
@@ -1033,6 +1035,7 @@ __device__ __forceinline__ void rim_row(int h, int& a, int& b) {
 // Thread t takes the chunk's OWN row t — row (i, j) = (t >> 4, t & 15), tile row (i + 1, j + 1): its planes at a uniform base + 16 t, its k-halo
 // bytes at a uniform base + t, its three chunk kinds the same for all 256 rows — and threads 0..67 a row of the tile's rim as well, which
 // belongs to one of eight other chunk columns and takes the per-row arithmetic (half of the instructions of both steps when every row did).
+template <bool ST>
 __device__ __forceinline__ void tile_issue(const GridView& g, uint32_t chunk, TileLoads& T, uint32_t tid) {
     tid = opaque(tid);
     const int ck = chunk % g.cz, cj = (chunk / g.cz) % g.cy, ci = chunk / (g.cz * g.cy);
@@ -1056,14 +1059,18 @@ __device__ __forceinline__ void tile_issue(const GridView& g, uint32_t chunk, Ti
         const uint32_t* kf0 = ck > 0 ? kf - 256 : kf;  // (clamped to the chunk itself where there is no neighbour; not consulted then)
         const uint32_t* kf2 = ck + 1 < (int)g.cz ? kf + 256 : kf;
         L.s4 = *reinterpret_cast<const uint4*>(g.sdf + o);
-        L.t4 = *reinterpret_cast<const uint4*>(g.type + o);
         L.b0s = kf0[64];
-        L.b0t = kf0[192];
         L.b2s = kf2[0];
-        L.b2t = kf2[128];
+        if constexpr (!ST) {
+            L.t4 = *reinterpret_cast<const uint4*>(g.type + o);
+            L.b0t = kf0[192];
+            L.b2t = kf2[128];
+        }
     }
-    {  // a rim row (straight-line: a thread without one, or whose row lies outside the grid or in a ghost layer, loads the chunk's own first
-       // row instead; with the loads under conditions the compiler merged the two rows' registers and waited for the first to copy it aside)
+    // a rim row: threads 0..67 have one. Waves 2 and 3 skip the loads (a wave-uniform branch); inside waves 0 and 1 the loads are straight-line
+    // (a lane without a rim row, or whose row lies outside the grid or in a ghost layer, loads the chunk's own first row instead; with the
+    // loads under per-lane conditions the compiler merged the two rows' registers and waited for the first to copy it aside)
+    if ((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) < 128u) {
         RowData& L = T.L[1];
         int a, b;
         rim_row((int)tid, a, b);
@@ -1078,20 +1085,23 @@ __device__ __forceinline__ void tile_issue(const GridView& g, uint32_t chunk, Ti
         const uint32_t* kf0 = ck > 0 ? kf - 256 : kf;
         const uint32_t* kf2 = ck + 1 < (int)g.cz ? kf + 256 : kf;
         L.s4 = *reinterpret_cast<const uint4*>(g.sdf + o);
-        L.t4 = *reinterpret_cast<const uint4*>(g.type + o);
         L.b0s = kf0[64];
-        L.b0t = kf0[192];
         L.b2s = kf2[0];
-        L.b2t = kf2[128];
+        if constexpr (!ST) {
+            L.t4 = *reinterpret_cast<const uint4*>(g.type + o);
+            L.b0t = kf0[192];
+            L.b2t = kf2[128];
+        }
     }
 }
 // the loads have to be in: the compiler's wait goes where this is called
+template <bool ST>
 __device__ __forceinline__ void tile_pin(TileLoads& T) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         RowData& L = T.L[r];
-        asm volatile("" : "+v"(L.s4.x), "+v"(L.s4.y), "+v"(L.s4.z), "+v"(L.s4.w), "+v"(L.t4.x), "+v"(L.t4.y), "+v"(L.t4.z), "+v"(L.t4.w));
-        asm volatile("" : "+v"(L.b0s), "+v"(L.b0t), "+v"(L.b2s), "+v"(L.b2t));
+        asm volatile("" : "+v"(L.s4.x), "+v"(L.s4.y), "+v"(L.s4.z), "+v"(L.s4.w), "+v"(L.b0s), "+v"(L.b2s));
+        if constexpr (!ST) asm volatile("" : "+v"(L.t4.x), "+v"(L.t4.y), "+v"(L.t4.z), "+v"(L.t4.w), "+v"(L.b0t), "+v"(L.b2t));
     }
     asm volatile("" : "+v"(T.rec));
 }
@@ -1100,44 +1110,51 @@ __device__ __forceinline__ void tile_records(TileLoads& T, uint32_t* s_rec, uint
     if (tid < 27u) s_rec[tid] = T.rec;
 }
 // one padded row into the LDS tile: `k0, k1, k2` the first record words of the row's chunks below / own / above along k
-// `rix`: the row's index in its chunk (its k-halo bytes are byte rix & 3 of the words fetched)
+// `rix`: the row's index in its chunk (its k-halo bytes are byte rix & 3 of the words fetched). ST: the types are not kept (`ty` untouched)
+template <bool ST>
 __device__ __forceinline__ void tile_row_store(RowData& L, uint32_t rix, uint32_t w0, uint32_t w1, uint32_t w2, bool has_lo, bool has_hi, uint32_t sd[6],
                                                uint32_t ty[6]) {
     // (the loaded registers pass through an empty asm first: the compiler may otherwise move the first operation on a loaded value — a
     // mask, a shift — up to the load, a phase ago, and wait for the load there)
-    asm volatile("" : "+v"(L.s4.x), "+v"(L.s4.y), "+v"(L.s4.z), "+v"(L.s4.w), "+v"(L.t4.x), "+v"(L.t4.y), "+v"(L.t4.z), "+v"(L.t4.w));
-    asm volatile("" : "+v"(L.b0s), "+v"(L.b0t), "+v"(L.b2s), "+v"(L.b2t));
+    asm volatile("" : "+v"(L.s4.x), "+v"(L.s4.y), "+v"(L.s4.z), "+v"(L.s4.w), "+v"(L.b0s), "+v"(L.b2s));
+    if constexpr (!ST) asm volatile("" : "+v"(L.t4.x), "+v"(L.t4.y), "+v"(L.t4.z), "+v"(L.t4.w), "+v"(L.b0t), "+v"(L.b2t));
     const ivx_chunk_info c0 = record_of(w0), c1 = record_of(w1), c2 = record_of(w2);
     const bool d1 = c1.kind == KIND_NONUNIFORM;
-    const uint32_t us = ivx_uniform_sdf(c1.kind) * 0x01010101u, ut = ivx_uniform_type(c1) * 0x01010101u;
+    const uint32_t us = ivx_uniform_sdf(c1.kind) * 0x01010101u;
     sd[1] = d1 ? L.s4.x : us, sd[2] = d1 ? L.s4.y : us, sd[3] = d1 ? L.s4.z : us, sd[4] = d1 ? L.s4.w : us;
-    ty[1] = d1 ? L.t4.x : ut, ty[2] = d1 ? L.t4.y : ut, ty[3] = d1 ? L.t4.z : ut, ty[4] = d1 ? L.t4.w : ut;
+    if constexpr (!ST) {
+        const uint32_t ut = ivx_uniform_type(c1) * 0x01010101u;
+        ty[1] = d1 ? L.t4.x : ut, ty[2] = d1 ? L.t4.y : ut, ty[3] = d1 ? L.t4.z : ut, ty[4] = d1 ? L.t4.w : ut;
+    }
     const uint32_t sh = 8u * (rix & 3u);
     if (has_lo) {
         const bool dense = c0.kind == KIND_NONUNIFORM;
         sd[0] = dense ? ((L.b0s >> sh) & 0xFFu) : ivx_uniform_sdf(c0.kind);
-        ty[0] = dense ? ((L.b0t >> sh) & 0xFFu) : ivx_uniform_type(c0);
+        if constexpr (!ST) ty[0] = dense ? ((L.b0t >> sh) & 0xFFu) : ivx_uniform_type(c0);
     }
     if (has_hi) {
         const bool dense = c2.kind == KIND_NONUNIFORM;
         sd[5] = dense ? ((L.b2s >> sh) & 0xFFu) : ivx_uniform_sdf(c2.kind);
-        ty[5] = dense ? ((L.b2t >> sh) & 0xFFu) : ivx_uniform_type(c2);
+        if constexpr (!ST) ty[5] = dense ? ((L.b2t >> sh) & 0xFFu) : ivx_uniform_type(c2);
     }
 }
+template <bool ST>
 __device__ __forceinline__ void tile_row_write(int r, const uint32_t sd[6], const uint32_t ty[6], uint8_t* s_sd, uint8_t* s_ty, uint32_t* s_neg) {
     s_neg[r] = ((sd[0] >> 7) & 1u) | (neg16(sd + 1) << 1) | (((sd[5] >> 7) & 1u) << 17);
     uint8_t* ds = s_sd + r * RS;
-    uint8_t* dt = s_ty + r * RS;
     ds[3] = (uint8_t)sd[0];
-    dt[3] = (uint8_t)ty[0];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        reinterpret_cast<uint32_t*>(ds + 4)[q] = sd[1 + q];
-        reinterpret_cast<uint32_t*>(dt + 4)[q] = ty[1 + q];
-    }
+    for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t*>(ds + 4)[q] = sd[1 + q];
     ds[20] = (uint8_t)sd[5];
-    dt[20] = (uint8_t)ty[5];
+    if constexpr (!ST) {
+        uint8_t* dt = s_ty + r * RS;
+        dt[3] = (uint8_t)ty[0];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t*>(dt + 4)[q] = ty[1 + q];
+        dt[20] = (uint8_t)ty[5];
+    }
 }
+template <bool ST>
 __device__ __forceinline__ void tile_finish(const GridView& g, uint32_t chunk, TileLoads& T, const uint32_t* s_rec, uint8_t* s_sd, uint8_t* s_ty, uint32_t* s_neg,
                                             uint32_t tid, int* upper) {
     tid = opaque(tid);
@@ -1147,8 +1164,8 @@ __device__ __forceinline__ void tile_finish(const GridView& g, uint32_t chunk, T
         uint32_t sd[6], ty[6];
         sd[0] = sd[5] = 0x7Fu;
         ty[0] = ty[5] = 0xFFu;
-        tile_row_store(T.L[0], tid, s_rec[12], s_rec[13], s_rec[14], has_lo, has_hi, sd, ty);
-        tile_row_write((int)(((tid >> 4) + 1u) * G + (tid & 15u) + 1u), sd, ty, s_sd, s_ty, s_neg);
+        tile_row_store<ST>(T.L[0], tid, s_rec[12], s_rec[13], s_rec[14], has_lo, has_hi, sd, ty);
+        tile_row_write<ST>((int)(((tid >> 4) + 1u) * G + (tid & 15u) + 1u), sd, ty, s_sd, s_ty, s_neg);
     }
     if (tid < 68u) {  // a rim row
         int a, b;
@@ -1165,9 +1182,9 @@ __device__ __forceinline__ void tile_finish(const GridView& g, uint32_t chunk, T
         } else if (mode == 1u) {
             // the row's chunk column in the neighbourhood: (gi >> 4) - ci and (gj >> 4) - cj are -1, 0 or 1
             const int col = (((gi >> 4) - ci + 1) * 3 + ((gj >> 4) - cj + 1)) * 3;
-            tile_row_store(T.L[1], (uint32_t)(((gi & 15) << 4) | (gj & 15)), s_rec[col], s_rec[col + 1], s_rec[col + 2], has_lo, has_hi, sd, ty);
+            tile_row_store<ST>(T.L[1], (uint32_t)(((gi & 15) << 4) | (gj & 15)), s_rec[col], s_rec[col + 1], s_rec[col + 2], has_lo, has_hi, sd, ty);
         }
-        tile_row_write(a * G + b, sd, ty, s_sd, s_ty, s_neg);
+        tile_row_write<ST>(a * G + b, sd, ty, s_sd, s_ty, s_neg);
     }
     // the upper layer of cubes belongs to the upper neighbour chunk when that chunk is non-uniform (surface_nets.rs:252-261); neighbourhood
     // entries (di, dj, dk) = (1,0,0), (0,1,0), (0,0,1); a chunk that is not there reads as Void
@@ -1177,10 +1194,13 @@ __device__ __forceinline__ void tile_finish(const GridView& g, uint32_t chunk, T
     if ((s_rec[14] & 0xFFu) == KIND_NONUNIFORM) upper[2] -= 1;
 }
 
-// Workgroups of a mesher launch: as many as stay resident (four per CU: 128 VGPRs, < 40 KB of LDS), each walking its share of the list —
-// only a workgroup that goes on to another chunk can fetch that chunk's tile ahead.
-static inline uint32_t ivx_emit_grid(const ivx_grid* g, uint32_t n_entries) {
-    const uint32_t resident = (uint32_t)g->ctx->n_cu * 4u;
+// Workgroups of a mesher launch: as many as stay resident (four per CU: 128 VGPRs, < 40 KB of LDS; the single-type form five: <= 96 VGPRs,
+// < 32 KB), each walking its share of the list — only a workgroup that goes on to another chunk can fetch that chunk's tile ahead.
+#ifndef IVX_EMIT_ST_PER_CU
+#define IVX_EMIT_ST_PER_CU 5  // (developer knob: tools/build_variant.sh <name> -DIVX_EMIT_ST_PER_CU=4)
+#endif
+static inline uint32_t ivx_emit_grid(const ivx_grid* g, uint32_t n_entries, uint32_t per_cu = 4u) {
+    const uint32_t resident = (uint32_t)g->ctx->n_cu * per_cu;
     return n_entries < resident ? (n_entries ? n_entries : 1u) : resident;
 }
 static inline uint32_t ivx_emit_general_grid(const ivx_grid* g, uint32_t n_entries) {
@@ -1198,7 +1218,7 @@ static inline uint32_t ivx_emit_general_grid(const ivx_grid* g, uint32_t n_entri
 // The mesher's main pass. One workgroup (256 threads, four per CU: <= 128 VGPRs by amdgpu_waves_per_eu(4) on the kernels) walks its share of
 // the chunks that have a mesh, as a two-stage pipeline over chunks — the tile of the walk's NEXT chunk is fetched while the current chunk is
 // meshed from the tile in LDS:
-//   0. next tile out  the loads of the next chunk's padded tile are issued (TileLoads: 25 registers per thread)
+//   0. next tile out  the loads of the next chunk's padded tile are issued (TileLoads: 25 registers per thread, 13 in the single-type form)
 //   1. order          cube rows in scan order, one ordered prefix for vertices and quads  (tile signs -> s_vrow, s_qrow, s_surf)
 //   2. vertices       one thread per vertex: position, normal, the one material; the vertex lists its quads (tile -> buffers, s_vpos, s_vsm, s_quad)
 //   4. quads          one thread per quad: diagonal, winding, indices, index materials    (reads nothing of the tile but its sign rows)
@@ -1208,7 +1228,13 @@ static inline uint32_t ivx_emit_general_grid(const ivx_grid* g, uint32_t n_entri
 // VPC vertices — and hands any other chunk on (`hard`) to role_sn_emit_general, which meshes that chunk again in full: kept apart so that
 // the general paths' registers are not live beside the loads in flight (with them in the same kernel the compiler sent the loaded rows to
 // scratch the moment they arrived, i.e. waited for them where they were issued).
-template <bool SLOTS>
+// ST (single type): every voxel of every NonUniform chunk of the grid has the type p.single_type (the sampler's one type, nothing rewritten
+// since: ivx_grid::signs_current) and there is no ghost layer. The mesher consults the types of negative corners only, and a negative
+// corner lies in a NonUniform chunk (type p.single_type) or a Uniform one (the type of its record): the tile then needs no type plane, no
+// k-halo type bytes and no LDS type tile — half of its bytes and twelve of its registers in flight. A chunk with a Uniform neighbour of
+// another type (none after sampling: the sampler's Uniform records and the derive sweep's demotions carry the same type) goes to the
+// general pass.
+template <bool SLOTS, bool ST = false>
 __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams p, float* __restrict__ positions, float* __restrict__ normals,
                                                  uint32_t* __restrict__ indices, unsigned long long* __restrict__ imats, ivx_submesh* __restrict__ submeshes,
                                                  const uint32_t* __restrict__ emit_count, const uint4* __restrict__ emit_items, uint32_t vcap, uint32_t icap,
@@ -1217,7 +1243,7 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
                                                  uint32_t walk_len = 0u) {
     __shared__ uint16_t s_quad[3 * VPC];  // the chunk's quads in emission order: cube id | axis << 13
     __shared__ __attribute__((aligned(16))) uint8_t s_sd[TILE_BYTES];
-    __shared__ __attribute__((aligned(16))) uint8_t s_ty[TILE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t s_ty[ST ? 16 : TILE_BYTES];  // (ST: not used)
     __shared__ uint32_t s_neg2[2][NROWS];  // the tile's sign rows, double-buffered (see the barriers of a round)
     __shared__ uint32_t s_vrow[NCROWS];   // per cube row: first vertex << 17 | which of its 17 cubes have a vertex (cube -> vertex: vertex_of)
     __shared__ uint16_t s_qrow[NCROWS];   // per cube row: its first quad
@@ -1225,7 +1251,7 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
     __shared__ uint32_t s_nq;             // the chunk's quads
     __shared__ uint16_t s_surf[VPC];      // vertex -> cube id (cube row * 17 + k)
     __shared__ float s_vpos[3][VPC];      // the chunk's vertex positions and materials for the quad phase
-    __shared__ uint8_t s_vsm[VPC];
+    __shared__ uint8_t s_vsm[ST ? 4 : VPC];  // (ST: every vertex has the one type)
     __shared__ uint32_t s_wsum[4];
     __shared__ uint32_t s_hard;  // this chunk needs the general pass
     __shared__ uint32_t s_rec[27];  // first words of the chunk records of the tile's 3 x 3 x 3 neighbourhood
@@ -1305,16 +1331,23 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
                                (uint32_t)__builtin_amdgcn_readfirstlane((int)s_ticket[3]), (uint32_t)__builtin_amdgcn_readfirstlane((int)s_ticket[4]));
     }
     const bool have_next = li_next < n_emit;
+    bool other_type = false;  // ST: a Uniform chunk of the tile's neighbourhood has a type other than p.single_type (s_rec: this chunk's records)
+    if constexpr (ST) {
+        if (tid < 64u) {
+            const uint32_t w = tid < 27u ? s_rec[tid] : 0u;
+            other_type = __builtin_amdgcn_ballot_w64((w & 0xFFu) == KIND_UNIFORM && (w >> 24) != p.single_type) != 0ull;
+        }
+    }
     if (tid == 0) {  // the previous chunk's verdict (its quad phase is over everywhere), then this chunk's starting value
         if (li_prev != NONE && s_hard) hard_list[atomicAdd(hard_count, 1u)] = li_prev;
-        s_hard = large ? 1u : 0u;
+        s_hard = (large || other_type) ? 1u : 0u;
     }
 
     uint32_t ticket = 0u;
     if (tid == TK && have_next) ticket = nb + 8u * atomicAdd(cursor + 32u * (bid & 7u), 1u) + (bid & 7u);
     // ---- 0. the next chunk's tile: its loads travel while this chunk's vertex order is built
     TileLoads T;
-    if (have_next) tile_issue(g, item_next.x, T, tid);
+    if (have_next) tile_issue<ST>(g, item_next.x, T, tid);
     uint4 drawn = make_uint4(0u, 0u, 0u, 0u);
     uint32_t drawn_li = 0u;
     // (straight-line from here to the vertices, also in a round without any — the first one, a chunk passed over —, where the order is built
@@ -1359,7 +1392,8 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
     // in order: behind the vertex and quad phases' stores — whose number the compiler cannot know, the loops' trip counts being data — the
     // wait for these loads was a wait for every store of the round to be acknowledged, once per chunk, in every wave. Here only the previous
     // round's quad stores are older, and the order phase has covered most of their trip and of the loads'.
-    if (have_next) tile_pin(T);
+    tile_pin<ST>(T);  // (also without a next tile: with the wait under a condition, the register of a row loaded a round ago counts as in flight
+                      // at the top of the next round, and the compiler waited there for all but the last few stores of the quad phase)
     if (have) IVX_T(g, li, 6);  // (order built and the next tile's loads in, this wave)
     __syncthreads();  // (3)
     if (have) IVX_T(g, li, 2);  // vertex order built
@@ -1401,13 +1435,13 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
         const int co[8] = {0, 1, RS, RS + 1, G * RS, G * RS + 1, G * RS + RS, G * RS + RS + 1};
         float d[8];
         uint32_t neg = 0u;
-        uint8_t mats[8];
+        [[maybe_unused]] uint8_t mats[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const int8_t e = (int8_t)s_sd[t0 + co[c]];
             d[c] = decode(e);
             neg |= (e < 0 ? 1u : 0u) << c;
-            mats[c] = s_ty[t0 + co[c]];
+            if constexpr (!ST) mats[c] = s_ty[t0 + co[c]];
         }
         int count;
         V3 sum;
@@ -1434,14 +1468,17 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
         }
         const V3 position = add(scale(add(centroid, mk((float)i, (float)j, (float)k)), p.extent), pos_offset);
         // the one material of the cube's negative corners; a vertex with several hands the chunk to the general pass
-        uint32_t m0 = 0xFFFFFFFFu;
+        // (ST: every negative corner has the one type — a vertex's cube has at least one)
+        uint32_t m0 = ST ? p.single_type : 0xFFFFFFFFu;
         bool single = true;
+        if constexpr (!ST) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if ((neg >> c) & 1u) {
-                if (m0 == 0xFFFFFFFFu) m0 = mats[c];
-                single = single && mats[c] == m0;
-            }
+            for (int c = 0; c < 8; ++c)
+                if ((neg >> c) & 1u) {
+                    if (m0 == 0xFFFFFFFFu) m0 = mats[c];
+                    single = single && mats[c] == m0;
+                }
+        }
         // the vertex's quads: at the row's first quad + the quads of the row's cubes below this one (the row's three masks from the order phase)
         const uint2 qb = s_qbits[cr];
         const uint32_t below = (1u << k) - 1u;
@@ -1457,8 +1494,10 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
             s_vpos[0][v] = position.x;
             s_vpos[1][v] = position.y;
             s_vpos[2][v] = position.z;
-            s_vsm[v] = (uint8_t)m0;
-            if (!single) s_hard = 1u;
+            if constexpr (!ST) {
+                s_vsm[v] = (uint8_t)m0;
+                if (!single) s_hard = 1u;
+            }
             uint32_t qslot = qslot0;
             if ((qb.x >> k) & 1u) s_quad[qslot++] = (uint16_t)cid;                                            // X
             if (k < 15 ? ((qb.x >> (17 + k)) & 1u) : ((qb.y >> (k - 15)) & 1u)) s_quad[qslot++] = (uint16_t)(cid | (1 << 13));  // Y
@@ -1501,7 +1540,7 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
                            v4 = vertex_of(s_vrow[cr - rb - rc], k - kb - kc);
             const V3 q1 = mk(s_vpos[0][v1], s_vpos[1][v1], s_vpos[2][v1]), q2 = mk(s_vpos[0][v2], s_vpos[1][v2], s_vpos[2][v2]);
             const V3 q3 = mk(s_vpos[0][v3], s_vpos[1][v3], s_vpos[2][v3]), q4 = mk(s_vpos[0][v4], s_vpos[1][v4], s_vpos[2][v4]);
-            const uint32_t b1 = s_vsm[v1], b2 = s_vsm[v2], b3 = s_vsm[v3], b4 = s_vsm[v4];
+            const uint32_t b1 = ST ? p.single_type : s_vsm[v1], b2 = ST ? b1 : s_vsm[v2], b3 = ST ? b1 : s_vsm[v3], b4 = ST ? b1 : s_vsm[v4];
             uint32_t quad[6];
             // the shorter diagonal: |q1 - q4| < |q2 - q3| on the rounded lengths (surface_nets.rs:360-381). Where the SQUARED lengths already
             // say "not shorter" the (correctly rounded, hence monotonic) roots cannot say otherwise; only a wave with a quad whose squared
@@ -1544,7 +1583,7 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
 
     // ---- 5. the next chunk's tile into LDS
     if (have_next) {
-        tile_finish(g, item_next.x, T, s_rec, s_sd, s_ty, s_neg2[buf ^ 1u], tid, upper);
+        tile_finish<ST>(g, item_next.x, T, s_rec, s_sd, s_ty, s_neg2[buf ^ 1u], tid, upper);
         info_w = s_rec[13];
     }
     if (have) IVX_T(g, li, 5);

@@ -90,7 +90,8 @@ struct StepArgs {
     uint32_t* needs_early;    // (optional) host-mapped twin of needs_out, a counter of finished workgroups, the bell behind them and its value
     uint32_t* needs_counter;
     uint32_t* needs_bell;
-    uint32_t needs_seq, pad_needs_;
+    uint32_t needs_seq;
+    uint32_t single_type;  // k_step_emit<true>: the one voxel type of the grid's NonUniform chunks (SnParams::single_type)
     const uint32_t* copy_src;
     uint32_t* copy_dst;
     uint32_t copy_words;
@@ -101,6 +102,7 @@ __device__ __forceinline__ sn::SnParams sn_params(const StepArgs& a) {
     p.g = a.g;
     p.extent = a.extent;
     p.x_off = a.x_off;
+    p.single_type = a.single_type;
     return p;
 }
 
@@ -225,6 +227,8 @@ __global__ __launch_bounds__(256) void k_step_post2(StepArgs a) { step_post2_bod
 IVX_MANY_TWIN(k_step_post2_many, StepArgs, step_post2_body, __launch_bounds__(256))
 
 // roles: 0 flatten the region forest, 1 mesher emit, 2 the slab protocol's record
+// ST: the mesher's single-type form (role_sn_emit; ivx_launch_step_emit says when)
+template <bool ST>
 __device__ __forceinline__ void step_emit_body(const StepArgs& a, uint32_t b, uint32_t) {
     if (b < a.nb[0]) {
         role_ccl_flatten(b, a.nb[0], a.g, a.rparent, a.multi_list /* root counts */, a.ccl_group_sums);
@@ -232,7 +236,7 @@ __device__ __forceinline__ void step_emit_body(const StepArgs& a, uint32_t b, ui
     }
     b -= a.nb[0];
     if (b < a.nb[1]) {
-        sn::role_sn_emit<false>(b, a.nb[1], sn_params(a), a.positions, a.normals, a.indices, a.imats, a.submeshes, a.offsets + 2 * (size_t)a.n_chunks + 2,
+        sn::role_sn_emit<false, ST>(b, a.nb[1], sn_params(a), a.positions, a.normals, a.indices, a.imats, a.submeshes, a.offsets + 2 * (size_t)a.n_chunks + 2,
                                 a.emit_items, a.vcap, a.icap, a.scap, nullptr, a.hard_count, a.hard_list, a.hard_count + 32, a.walk, a.n_chunks);
         return;
     }
@@ -246,8 +250,9 @@ __device__ __forceinline__ void step_emit_body(const StepArgs& a, uint32_t b, ui
         if (threadIdx.x < 64u) role_result_gather(a.rscalar, a.offsets + 2 * (size_t)a.n_chunks, a.moments_out, a.work_count, a.eval_count, a.host_block, false, 0u);
     }
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_step_emit(StepArgs a) { step_emit_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_step_emit_many, StepArgs, step_emit_body, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
+template <bool ST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST ? IVX_EMIT_ST_PER_CU : 4, ST ? IVX_EMIT_ST_PER_CU : 4))) void k_step_emit(StepArgs a) { step_emit_body<ST>(a, blockIdx.x, gridDim.x); }
+IVX_MANY_TWIN(k_step_emit_many, StepArgs, step_emit_body<false>, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
 
 // roles: 0 component ids, 1 the mesher's general pass over the chunks the main pass (k_step_emit) handed on — the launch after the main pass
 // anyway; as a launch of its own the general pass cost the step 4 us whether it had a chunk to do or not
@@ -448,9 +453,13 @@ int ivx_launch_step_post2(ivx_grid* g, uint32_t stages, const uint16_t* face_pai
 
 int ivx_launch_step_emit(ivx_grid* g, uint32_t stages, bool general_in_assign, void* slab_record, bool record_has_pairs) {
     StepArgs a = make_args(g);
+    // the mesher's single-type form: every chunk with planes has the sampler's one type (nothing has rewritten voxels since), no ghost layer
+    // is read, and the launch is not recorded into a batch of several objects (the twin k_step_emit_many is the general form)
+    const bool single_type = g->signs_current && !g->has_ghost[0] && !g->has_ghost[1] && !ivx_many_recording();
+    a.single_type = g->signs_type;
     if (stages & IVX_STAGE_REGIONS) a.nb[0] = (g->n_chunks + 255u) / 256u;
     if (stages & IVX_STAGE_REMESH) {
-        a.nb[1] = sn::ivx_emit_grid(g, g->n_chunks);
+        a.nb[1] = sn::ivx_emit_grid(g, g->n_chunks, single_type ? IVX_EMIT_ST_PER_CU : 4u);
         g->sn_tail_zero = 0;  // (the mesher's counter and cursors: the next incremental remesh clears them itself)
     }
     if (slab_record) {
@@ -463,7 +472,8 @@ int ivx_launch_step_emit(ivx_grid* g, uint32_t stages, bool general_in_assign, v
     }
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[2];
     if (total == 0) return IVX_OK;
-    if (!ivx_many_try(g->ctx, g, IVX_MK_EMIT, total, a)) IVX_KLAUNCH(k_step_emit, dim3(total), dim3(256), 0, g->ctx->stream, a);
+    if (single_type) IVX_KLAUNCH(k_step_emit<true>, dim3(total), dim3(256), 0, g->ctx->stream, a);
+    else if (!ivx_many_try(g->ctx, g, IVX_MK_EMIT, total, a)) IVX_KLAUNCH(k_step_emit<false>, dim3(total), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     // the chunks the main pass hands on: a role of k_step_assign when that launch follows (the caller says so), else a launch of its own
     if ((stages & IVX_STAGE_REMESH) && !general_in_assign) return ivx_launch_sn_emit_general(g);

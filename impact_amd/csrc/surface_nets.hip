@@ -196,6 +196,7 @@ static SnParams make_params(ivx_grid* g) {
     p.g = ivx_view(g);
     p.extent = g->extent;
     p.x_off = g->x_off;
+    p.single_type = 0xFFu;  // (the stand-alone mesher kernels are the general form)
     return p;
 }
 

@@ -626,6 +626,462 @@ IVX_MANY_TWIN(k_derive_signs_many, DeriveArgs, derive_body<true>, __launch_bound
 IVX_MANY_LAUNCHER(many_derive_planes, k_derive_planes_many, DeriveArgs, 256)
 IVX_MANY_LAUNCHER(many_derive_signs, k_derive_signs_many, DeriveArgs, 256)
 
+// ---- the step's sweep, one chunk per WAVE (k_derive_wave) ------------------------------------------------------------------------------
+// derive_body<true> for one grid with no ghost layers, where the workgroup form spends its time between barriers: the four waves of a
+// workgroup walk list entries of their own and meet only once, at the start (the density and moment tables). What the workgroup form holds
+// in LDS for its barriers is in the wave's registers or in 2 KB of LDS of the wave's own: the 18 x 18 halo of row masks (the flags need the
+// four neighbours of every row) and the 16 x 10 row totals of the moments. The union-find the region decision used (16 KB, the reason for six
+// workgroups per CU) is replaced by a flood over the row masks in registers: the chunk is one region iff the flood from one voxel reaches all
+// of them. A flood that has not settled after IVX_DERIVE_FLOOD_CAP rounds lists the chunk as one with several regions; role_ccl_local_exact
+// then numbers it from the flags plane as it numbers every listed chunk, and a chunk with one region comes out of it as from the direct path
+// (label 0, one root, the boundary count). Everything else the sweep writes is what derive_body<true> writes, bit for bit: the face counts,
+// ballots and ORs are integers, and the moment sums take the same DPP rows and the same order of the 16 row totals.
+//
+// Lane layout: lane l holds the four rows (i, j) = (4 (l >> 4) + q, l & 15), q = 0..3. A DPP row of 16 lanes is one i per q — the j sums of
+// the workgroup form, unchanged —, j neighbours are DPP row shifts, i neighbours are in the lane but across groups of four (a lane permute).
+#ifndef IVX_DERIVE_FLOOD_CAP
+#define IVX_DERIVE_FLOOD_CAP 32
+#endif
+// waves per SIMD the wave form is compiled for: 5 -> at most 96 VGPRs, twenty chunks in flight per CU
+#ifndef IVX_DERIVE_WAVE_WAVES
+#define IVX_DERIVE_WAVE_WAVES 5
+#endif
+
+#ifdef IVX_WG_TRACE
+#define IVX_TW(g, entry, slot)                                                                      \
+    do {                                                                                            \
+        if ((threadIdx.x & 63u) == 0u) (g).trace[(size_t)(entry) * 8 + (slot)] = wall_clock64();    \
+    } while (0)
+#else
+#define IVX_TW(g, entry, slot) \
+    do {                       \
+    } while (0)
+#endif
+
+// (a wave's own LDS is read by its own lanes only: its accesses are ordered by the wave's program order, and the compiler, which sees no
+// alias between one lane's store and another lane's load, is kept from moving them past this point)
+__device__ __forceinline__ void ivx_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+// voxels of the runs of `m` (bits along k) that hold a voxel of `x`: the carry of m + x runs from every seed to the end of its run; the
+// other way round in bit-reversed order
+__device__ __forceinline__ uint32_t ivx_run_fill_up(uint32_t m, uint32_t x) { return m & (((m + x) ^ m) | x); }
+__device__ __forceinline__ uint32_t ivx_run_fill(uint32_t m, uint32_t x) {
+    x &= m;
+    return ivx_run_fill_up(m, x) | __builtin_bitreverse32(ivx_run_fill_up(__builtin_bitreverse32(m), __builtin_bitreverse32(x)));
+}
+__device__ __forceinline__ uint32_t ivx_dpp_u32_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true); }  // row_shr:1
+__device__ __forceinline__ uint32_t ivx_dpp_u32_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xF, 0xF, true); }  // row_shl:1
+__device__ __forceinline__ uint32_t ivx_wave_or(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
+    return ((uint32_t)__builtin_amdgcn_readlane((int)v, 15) | (uint32_t)__builtin_amdgcn_readlane((int)v, 31)) |
+           ((uint32_t)__builtin_amdgcn_readlane((int)v, 47) | (uint32_t)__builtin_amdgcn_readlane((int)v, 63));
+}
+
+// Is the non-empty set of the wave's rows `M` (face-connected, not empty) one region? 1: yes, 0: several, or not settled within the cap.
+__device__ __forceinline__ uint32_t ivx_flood_connected(const uint32_t M[4], uint32_t lane) {
+    const uint32_t a = lane >> 4;
+    uint32_t F[4];
+    {
+        // (the first non-empty lane from lane 40 on, cyclically: rows i = 8..11, j = 8 first — a seed near the middle of the (i, j) plane
+        // reaches a region that spans the chunk in about half the rounds a seed in its corner needs)
+        const unsigned long long nz = __ballot((M[0] | M[1] | M[2] | M[3]) != 0u), rot = (nz >> 40) | (nz << 24);
+        const uint32_t seed_lane = ((uint32_t)__ffsll((long long)rot) - 1u + 40u) & 63u;
+        bool seeded = lane != seed_lane;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            F[q] = (!seeded && M[q] != 0u) ? (M[q] & (0u - M[q])) : 0u;
+            seeded = seeded || M[q] != 0u;
+        }
+    }
+    for (int round = 0; round < IVX_DERIVE_FLOOD_CAP; ++round) {
+        const uint32_t up = (uint32_t)__shfl_up((int)F[3], 16u, 64), dn = (uint32_t)__shfl_down((int)F[0], 16u, 64);
+        uint32_t N[4];
+        bool miss = false, grew = false;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t G = F[q] | ivx_dpp_u32_shr1(F[q]) | ivx_dpp_u32_shl1(F[q]);
+            G |= q > 0 ? F[q > 0 ? q - 1 : 0] : (a > 0u ? up : 0u);
+            G |= q < 3 ? F[q < 3 ? q + 1 : 3] : (a < 3u ? dn : 0u);
+            N[q] = ivx_run_fill(M[q], G);
+            miss = miss || N[q] != M[q];
+            grew = grew || N[q] != F[q];
+        }
+        if (!__ballot(miss)) return 1u;
+        if (!__ballot(grew)) return 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) F[q] = N[q];
+    }
+    return 0u;
+}
+
+// (lanes with j = 15 of each DPP row hold the row's totals: moments_reduce_rows up to its LDS stores, into the wave's s_red)
+__device__ __forceinline__ void moments_rows_wave(double D, double Dz1, double Dz2, double (*s_red)[10], uint32_t i, uint32_t j, int gi, int gj) {
+    const double I = (double)gi, J = (double)gj;
+    const double qx = 2.0 * I + 1.0, qy = 2.0 * J + 1.0;
+    const double cx = 3.0 * I * I + 3.0 * I + 1.0, cy = 3.0 * J * J + 3.0 * J + 1.0;
+    const double r0 = ivx_row16_sum_f64(D), r1 = ivx_row16_sum_f64(D * qy), r2 = ivx_row16_sum_f64(D * cy);
+    const double r3 = ivx_row16_sum_f64(Dz1), r4 = ivx_row16_sum_f64(qy * Dz1), r5 = ivx_row16_sum_f64(Dz2);
+    if (j == 15u) {
+        double* o = s_red[i];
+        o[0] = r0;
+        o[1] = r0 * qx;
+        o[2] = r1;
+        o[3] = r3;
+        o[4] = r2 + r5;
+        o[5] = r0 * cx + r5;
+        o[6] = r0 * cx + r2;
+        o[7] = r1 * qx;
+        o[8] = r4;
+        o[9] = r3 * qx;
+    }
+}
+
+__device__ __forceinline__ void derive_wave_body(const DeriveArgs& a_) {
+    const GridView& g = a_.g;
+    uint8_t* __restrict__ flags_out = a_.flags_out;
+    int8_t* __restrict__ sdf_rw = a_.sdf_rw;
+    uint8_t* __restrict__ type_rw = a_.type_rw;
+    ivx_chunk_info* __restrict__ info = a_.info;
+    uint16_t* __restrict__ signs = a_.signs;
+    uint8_t* __restrict__ kface_out = a_.kface_out;
+    uint32_t* __restrict__ active_list = a_.active_list;
+    const uint32_t* __restrict__ list_in = a_.list_in;
+    const DeriveFused& fz = a_.fz;
+    __shared__ float s_dens[256];
+    __shared__ uint16_t s_mtab[256];
+    __shared__ uint16_t s_occ[4][18 * 18 + 4];  // per wave: non-empty masks of rows (i+1, j+1), halo rows from neighbour chunks
+    __shared__ double s_red_all[4][16][10];     // per wave: the moments' row totals by i
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    uint16_t* occ = s_occ[wave];
+    double (*s_red)[10] = s_red_all[wave];
+    if (fz.parts & IVX_PART_MOMENTS) s_dens[tid] = fz.dens[tid], s_mtab[tid] = moments_table_entry(tid);
+    __syncthreads();  // the workgroup's one barrier
+    const uint32_t la = lane >> 4, j = lane & 15u;  // rows i = 4 la + q
+    const uint32_t n_active = a_.work_counts[0];
+    const uint32_t n_walk = gridDim.x * 4u;
+    const uint32_t sx = g.cy * g.cz;
+    const uint32_t* sw = reinterpret_cast<const uint32_t*>(g.signs);
+    for (uint32_t li = ivx_xcd_remap(blockIdx.x, gridDim.x) * 4u + wave; li < n_active; li += n_walk) {
+    IVX_TW(g, li, 0);
+    const uint32_t chunk = IVX_LIST_CHUNK(list_in[li]);
+    const int ck = chunk % g.cz, cj = (chunk / g.cz) % g.cy, ci = chunk / sx;
+    const size_t base = (size_t)chunk * IVX_CHUNK_VOXELS;
+    const bool has_zlo = ck > 0, has_zhi = ck + 1 < (int)g.cz;
+    const size_t c_lo = has_zlo ? (size_t)chunk - 1 : (size_t)chunk, c_hi = has_zhi ? (size_t)chunk + 1 : (size_t)chunk;
+    // the halo row of this lane: face nf (0 x-, 1 x+, 2 y-, 3 y+), row nr
+    const uint32_t nf = la, nr = j;
+    bool n_present;
+    size_t nc;
+    uint32_t noff;
+    if (nf == 0) n_present = ci > 0, nc = (size_t)chunk - sx, noff = 240u + nr;
+    else if (nf == 1) n_present = ci + 1 < (int)g.cx, nc = (size_t)chunk + sx, noff = nr;
+    else if (nf == 2) n_present = cj > 0, nc = (size_t)chunk - g.cz, noff = nr * 16u + 15u;
+    else n_present = cj + 1 < (int)g.cy, nc = (size_t)chunk + g.cz, noff = nr * 16u;
+    if (!n_present) nc = chunk;
+    // every load of the chunk in flight at once (see DeriveLoads)
+    uint2 own_rec = reinterpret_cast<const uint2*>(info)[chunk];
+    uint32_t gen_lo = reinterpret_cast<const uint32_t*>(info)[2 * c_lo], gen_hi = reinterpret_cast<const uint32_t*>(info)[2 * c_hi];
+    uint32_t ngen = reinterpret_cast<const uint32_t*>(info)[2 * nc];
+    uint32_t type0 = *reinterpret_cast<const uint32_t*>(g.type + base);
+    uint32_t nrow = sw[(nc * 256 + noff) >> 1];
+    uint32_t ow[4], bl[4], bh[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t r = (4u * la + q) * 16u + j;
+        ow[q] = sw[((size_t)chunk * 256 + r) >> 1];
+        bl[q] = sw[(c_lo * 256 + r) >> 1];
+        bh[q] = sw[(c_hi * 256 + r) >> 1];
+    }
+    asm volatile("" : "+v"(own_rec.x), "+v"(own_rec.y), "+v"(gen_lo), "+v"(gen_hi), "+v"(ngen), "+v"(type0), "+v"(nrow));
+    asm volatile("" : "+v"(ow[0]), "+v"(ow[1]), "+v"(ow[2]), "+v"(ow[3]), "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]));
+    asm volatile("" : "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]));
+    own_rec.x = (uint32_t)__builtin_amdgcn_readfirstlane((int)own_rec.x), own_rec.y = (uint32_t)__builtin_amdgcn_readfirstlane((int)own_rec.y);
+    gen_lo = ((uint32_t)__builtin_amdgcn_readfirstlane((int)gen_lo) >> 8) & 0xFFu, gen_hi = ((uint32_t)__builtin_amdgcn_readfirstlane((int)gen_hi) >> 8) & 0xFFu;
+    type0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)type0);
+    ngen = (ngen >> 8) & 0xFFu;
+    ivx_chunk_info own_info;
+    own_info.kind = (uint8_t)(own_rec.x & 0xFFu);
+    own_info.gen_kind = (uint8_t)((own_rec.x >> 8) & 0xFFu);
+    own_info.flags = (uint8_t)((own_rec.x >> 16) & 0xFFu);
+    own_info.uniform_type = (uint8_t)(own_rec.x >> 24);
+    own_info.face_dist = (uint16_t)(own_rec.y & 0xFFFFu);
+    own_info.region_count = (uint8_t)((own_rec.y >> 16) & 0xFFu);
+    own_info.boundary_region_count = (uint8_t)(own_rec.y >> 24);
+    const uint32_t gen = own_info.gen_kind;
+    const bool own_uniform = gen == KIND_UNIFORM;
+    // the four row masks, the neighbour voxels across the z faces (bit q), the halo row
+    uint32_t m[4], zl = 0u, zh = 0u;
+    const uint32_t half = 16u * (j & 1u);  // (row r = 16 i + j is the high half of its word for odd j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        m[q] = own_uniform ? 0xFFFFu : (gen == KIND_VOID ? 0u : ((ow[q] >> half) & 0xFFFFu));
+        const uint32_t lo = (bl[q] >> half >> 15) & 1u, hi = (bh[q] >> half) & 1u;
+        if (has_zlo && (gen_lo == KIND_NONUNIFORM ? lo : (gen_lo == KIND_UNIFORM ? 1u : 0u))) zl |= 1u << q;
+        if (has_zhi && (gen_hi == KIND_NONUNIFORM ? hi : (gen_hi == KIND_UNIFORM ? 1u : 0u))) zh |= 1u << q;
+        occ[(4u * la + q + 1u) * 18u + j + 1u] = (uint16_t)m[q];
+    }
+    uint32_t nm = 0u;
+    {
+        const uint32_t nrow_odd = nf == 2 ? 1u : (nf == 3 ? 0u : (nr & 1u));
+        const uint32_t rm = (nrow >> (16u * nrow_odd)) & 0xFFFFu;
+        if (n_present) nm = ngen == KIND_NONUNIFORM ? rm : (ngen == KIND_UNIFORM ? 0xFFFFu : 0u);
+        if (nf == 0) occ[0 * 18 + nr + 1] = (uint16_t)nm;
+        else if (nf == 1) occ[17 * 18 + nr + 1] = (uint16_t)nm;
+        else if (nf == 2) occ[(nr + 1) * 18 + 0] = (uint16_t)nm;
+        else occ[(nr + 1) * 18 + 17] = (uint16_t)nm;
+    }
+    // face populations, own faces and adjoining neighbour faces: all in registers
+    uint32_t cnt[12];
+    {
+        const uint32_t p0 = __popc(m[0]), p3 = __popc(m[3]), pc = (p0 + __popc(m[1])) + (__popc(m[2]) + p3);
+        cnt[0] = (uint32_t)__builtin_amdgcn_readlane((int)ivx_row16_sum(p0), 15);   // i = 0: q = 0 of lanes 0..15
+        cnt[1] = (uint32_t)__builtin_amdgcn_readlane((int)ivx_row16_sum(p3), 63);   // i = 15: q = 3 of lanes 48..63
+        cnt[2] = ((uint32_t)__builtin_amdgcn_readlane((int)pc, 0) + (uint32_t)__builtin_amdgcn_readlane((int)pc, 16)) +
+                 ((uint32_t)__builtin_amdgcn_readlane((int)pc, 32) + (uint32_t)__builtin_amdgcn_readlane((int)pc, 48));
+        cnt[3] = ((uint32_t)__builtin_amdgcn_readlane((int)pc, 15) + (uint32_t)__builtin_amdgcn_readlane((int)pc, 31)) +
+                 ((uint32_t)__builtin_amdgcn_readlane((int)pc, 47) + (uint32_t)__builtin_amdgcn_readlane((int)pc, 63));
+        uint32_t z0 = 0, z1 = 0, nz0 = 0, nz1 = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            z0 += (uint32_t)__popcll(__ballot((m[q] & 1u) != 0u));
+            z1 += (uint32_t)__popcll(__ballot(((m[q] >> 15) & 1u) != 0u));
+            nz0 += (uint32_t)__popcll(__ballot(((zl >> q) & 1u) != 0u));
+            nz1 += (uint32_t)__popcll(__ballot(((zh >> q) & 1u) != 0u));
+        }
+        cnt[4] = z0, cnt[5] = z1, cnt[10] = nz0, cnt[11] = nz1;
+        const uint32_t nfs = ivx_row16_sum(__popc(nm));  // the halo rows: face la in DPP row la
+        cnt[6] = (uint32_t)__builtin_amdgcn_readlane((int)nfs, 15), cnt[7] = (uint32_t)__builtin_amdgcn_readlane((int)nfs, 31);
+        cnt[8] = (uint32_t)__builtin_amdgcn_readlane((int)nfs, 47), cnt[9] = (uint32_t)__builtin_amdgcn_readlane((int)nfs, 63);
+    }
+    // occupied sub-box (bbox): the occupied lines i and rows j from the four ballots, the layers k from the OR of every row
+    {
+        uint32_t bi = 0, bjw = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned long long b = __ballot(m[q] != 0u);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if ((b >> (16 * s)) & 0xFFFFull) bi |= 1u << (4 * s + q);
+            bjw |= (uint32_t)b | (uint32_t)(b >> 32);
+        }
+        const uint32_t bj = (bjw | (bjw >> 16)) & 0xFFFFu;
+        const uint32_t ku = ivx_wave_or((m[0] | m[1]) | (m[2] | m[3]));
+        uint32_t packed = 0;
+        if (bi) {
+            packed = 0x80000000u | (uint32_t)(__ffs(bi) - 1) | ((uint32_t)(31 - __clz(bi)) << 4) | ((uint32_t)(__ffs(bj) - 1) << 8) |
+                     ((uint32_t)(31 - __clz(bj)) << 12) | ((uint32_t)(__ffs(ku) - 1) << 16) | ((uint32_t)(31 - __clz(ku)) << 20);
+        }
+        if (lane == 0u && IVX_DBG_KEEP(64u)) a_.bbox[chunk] = packed;
+    }
+    IVX_TW(g, li, 1);  // rows loaded, sub-box done
+    uint32_t own_fd[6], nbr_full = 0, own_mixed = 0;
+#pragma unroll
+    for (int f = 0; f < 6; ++f) {
+        const uint32_t c = cnt[f];
+        own_fd[f] = c == 0 ? FD_EMPTY : (c == 256 ? FD_FULL : FD_MIXED);
+        if (own_fd[f] == FD_MIXED) own_mixed |= 1u << f;
+        if (cnt[6 + f] == 256) nbr_full |= 1u << f;
+    }
+    uint32_t kind = gen;
+    if (gen == KIND_UNIFORM && nbr_full != 0x3Fu) kind = KIND_NONUNIFORM;
+    const uint32_t utype = own_uniform ? (own_info.kind == KIND_NONUNIFORM ? (type0 & 0xFFu) : (uint32_t)own_info.uniform_type) : 0u;
+    const bool fresh = own_uniform && own_info.kind != KIND_NONUNIFORM;
+    const uint32_t quirk = own_mixed & nbr_full;
+    ivx_wave_lds_sync();  // the halo is in
+    IVX_TW(g, li, 2);  // face counts done
+    // flags of the four rows (derive_body: the same masks and the same transposes), the touch bits on the way
+    bool t_x = false, t_y = false, t_z = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t i = 4u * la + q, r = i * 16u + j;
+        const uint32_t xdn = occ[i * 18u + j + 1u], xup = occ[(i + 2u) * 18u + j + 1u];
+        const uint32_t ydn = occ[(i + 1u) * 18u + j], yup = occ[(i + 1u) * 18u + j + 2u];
+        const uint32_t mq = m[q], zlo = (zl >> q) & 1u, zhi = (zh >> q) & 1u;
+        t_x = t_x || (i == 15u && (mq & xup) != 0u);
+        t_y = t_y || (j == 15u && (mq & yup) != 0u);
+        t_z = t_z || ((((mq >> 15) & 1u) & zhi) != 0u);
+        if (kind != KIND_NONUNIFORM) continue;
+        const uint32_t zdn = (mq << 1) | zlo, zup = (mq >> 1) | (zhi << 15);
+        const uint32_t e = ~mq & 0xFFFFu;
+        uint32_t dm[6];
+        dm[0] = (mq & xdn) | ((i == 0u && (quirk & 1u)) ? e : 0u);
+        dm[1] = (mq & ydn) | ((j == 0u && (quirk & 4u)) ? e : 0u);
+        dm[2] = (mq & zdn) | ((quirk & 16u) ? (e & 1u) : 0u);
+        dm[3] = (mq & xup) | ((i == 15u && (quirk & 2u)) ? e : 0u);
+        dm[4] = (mq & yup) | ((j == 15u && (quirk & 8u)) ? e : 0u);
+        dm[5] = (mq & zup) | ((quirk & 32u) ? (e & 0x8000u) : 0u);
+        uint32_t w[4];
+        {
+            const uint32_t p01 = dm[0] | (dm[1] << 16), p23 = dm[2] | (dm[3] << 16), p45 = dm[4] | (dm[5] << 16);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                uint32_t lo = __builtin_amdgcn_perm(p01, e, h ? 0x07050C01u : 0x06040C00u);
+                uint32_t hi = __builtin_amdgcn_perm(p45, p23, h ? 0x07050301u : 0x06040200u);
+                uint32_t t;
+                t = (lo ^ (lo >> 7)) & 0x00AA00AAu, lo = lo ^ t ^ (t << 7);
+                t = (hi ^ (hi >> 7)) & 0x00AA00AAu, hi = hi ^ t ^ (t << 7);
+                t = (lo ^ (lo >> 14)) & 0x0000CCCCu, lo = lo ^ t ^ (t << 14);
+                t = (hi ^ (hi >> 14)) & 0x0000CCCCu, hi = hi ^ t ^ (t << 14);
+                t = (lo ^ ((hi << 4) | (lo >> 28))) & 0xF0F0F0F0u, lo ^= t, hi ^= t >> 4;
+                w[2 * h] = lo, w[2 * h + 1] = hi;
+            }
+        }
+        if (IVX_DBG_KEEP(1u)) *reinterpret_cast<uint4*>(flags_out + base + (size_t)r * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (fresh && IVX_DBG_KEEP(2u)) {
+            const uint32_t t4 = utype * 0x01010101u;
+            *reinterpret_cast<uint4*>(sdf_rw + base + (size_t)r * 16) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+            *reinterpret_cast<uint4*>(type_rw + base + (size_t)r * 16) = make_uint4(t4, t4, t4, t4);
+        }
+        if (own_uniform && IVX_DBG_KEEP(4u)) {
+            signs[(size_t)chunk * 256 + r] = (uint16_t)0xFFFFu;
+            uint8_t* kf = kface_out + (size_t)chunk * 1024 + r;
+            kf[0] = (uint8_t)0x80u;
+            kf[256] = (uint8_t)0x80u;
+            kf[512] = (uint8_t)utype;
+            kf[768] = (uint8_t)utype;
+        }
+    }
+    const uint32_t tb = (__ballot(t_x) ? 1u : 0u) | (__ballot(t_y) ? 2u : 0u) | (__ballot(t_z) ? 4u : 0u);
+    IVX_TW(g, li, 3);  // flags written
+    // regions (ccl_local_chunk's decisions and stores, the union-find replaced by the flood)
+    uint32_t rc = own_info.region_count, brc = own_info.boundary_region_count;
+    if (fz.parts & IVX_PART_REGIONS) {
+        uint32_t* rp = fz.rparent + (size_t)chunk * 256;
+        const bool known = kind == KIND_VOID || gen == KIND_UNIFORM;
+        uint32_t R[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) R[q] = known ? 0u : m[q];
+        bool all_full = kind != KIND_VOID, any = all_full, touches = false, slab = false;
+        if (!known) {
+            bool not_full = false, nonempty = false, on_edge = false, runs2 = false;
+            uint32_t lack = 0u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t i = 4u * la + q, starts = R[q] & ~(R[q] << 1);
+                const bool edge_row = i == 0u || i == 15u || j == 0u || j == 15u;
+                not_full = not_full || R[q] != 0xFFFFu;
+                nonempty = nonempty || R[q] != 0u;
+                on_edge = on_edge || (edge_row ? (R[q] != 0u) : ((R[q] & 0x8001u) != 0u));
+                runs2 = runs2 || (starts & (starts - 1u)) != 0u;
+                lack |= R[q] ? (~R[q] & 0xFFFFu) : 0u;
+            }
+            all_full = !__ballot(not_full);
+            any = __ballot(nonempty) != 0ull;
+            touches = __ballot(on_edge) != 0ull;
+            const bool several_runs = __ballot(runs2) != 0ull;
+            const uint32_t lack_all = ivx_wave_or(lack);
+            if (any && !all_full && !several_runs && (~lack_all & 0xFFFFu) != 0u) {
+                // the slab test of ccl_local_chunk over the lines i: b[i] = the non-empty rows j of line i
+                uint32_t b[16];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const unsigned long long bq = __ballot(R[q] != 0u);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) b[4 * s + q] = (uint32_t)(bq >> (16 * s)) & 0xFFFFu;
+                }
+                bool ok = true;
+                uint32_t lines = 0u;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const uint32_t bn = i < 15 ? b[i < 15 ? i + 1 : 15] : 0u, runs = b[i] & ~(b[i] << 1);
+                    ok = ok && (b[i] == 0u || ((runs & (runs - 1u)) == 0u && (bn == 0u || (b[i] & bn) != 0u)));
+                    if (b[i]) lines |= 1u << i;
+                }
+                const uint32_t line_runs = lines & ~(lines << 1);
+                slab = ok && (line_runs & (line_runs - 1u)) == 0u;
+            }
+        }
+        if (!any || all_full) {
+            const uint32_t lab = any ? 0u : 0xFFFFFFFFu;
+            if (kind == KIND_NONUNIFORM && IVX_DBG_KEEP(8u)) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    *reinterpret_cast<uint4*>(fz.labels + base + (size_t)((4u * la + q) * 16u + j) * 16) = make_uint4(lab, lab, lab, lab);
+            }
+            if (lane == 0u) rp[0] = any ? chunk * 256u : NODE_NONE;
+            rc = any ? 1u : 0u;
+            brc = any ? 1u : 0u;
+        } else if (slab || ivx_flood_connected(R, lane)) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (!((R[q] >> k) & 1u)) w[k >> 2] |= 0xFFu << (8 * (k & 3));
+                if (IVX_DBG_KEEP(8u)) *reinterpret_cast<uint4*>(fz.labels + base + (size_t)((4u * la + q) * 16u + j) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            if (lane == 0u) rp[0] = chunk * 256u;
+            rc = 1u;
+            brc = touches ? 1u : 0u;
+        } else {
+            // several regions, or a flood the cap stopped: role_ccl_local_exact numbers the chunk and sets both counts (2: a provisional count
+            // — what the stages before it ask is only whether a chunk has one region or none)
+            if (lane == 0u) fz.multi_list[atomicAdd(&fz.rscalar[2], 1u)] = chunk;
+            rc = 2u;
+            brc = 0u;
+        }
+    }
+    IVX_TW(g, li, 4);  // regions labelled
+    if ((fz.parts & IVX_PART_MOMENTS) && kind == KIND_NONUNIFORM && IVX_DBG_KEEP(16u)) {
+        // (every voxel of the chunk has one type: the sampler's, or the record's for a chunk demoted in this pass — moments_row_sums_one_type)
+        const uint32_t type = fresh ? utype : a_.signs_type;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t i = 4u * la + q;
+            double D, Dz1, Dz2;
+            moments_row_sums_one_type(m[q], type, s_dens, s_mtab, ck * 16, D, Dz1, Dz2);
+            moments_rows_wave(D, Dz1, Dz2, s_red, i, j, (ci + (int)fz.x_off) * 16 + (int)i, cj * 16 + (int)j);
+        }
+        ivx_wave_lds_sync();
+        if (lane < 10u) {
+            double t = s_red[0][lane];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) t += s_red[r][lane];  // fixed order: derive_body's
+            fz.chunk_moments[(size_t)chunk * 10 + lane] = t;
+        }
+    }
+    if (lane == 0u && IVX_DBG_KEEP(32u)) {
+        a_.touch[chunk] = (uint8_t)tb;
+        const bool obscured = kind == KIND_NONUNIFORM && nbr_full == 0x3Fu;
+        active_list[li] = chunk | (kind << 24) | (gen << 26) | ((kind == KIND_NONUNIFORM && !obscured) ? (1u << 28) : 0u);
+        ivx_chunk_info ci_ = own_info;
+        ci_.kind = (uint8_t)kind;
+        ci_.region_count = (uint8_t)rc;
+        ci_.boundary_region_count = (uint8_t)brc;
+        if (kind == KIND_NONUNIFORM) {
+            uint32_t ob = 0;
+#pragma unroll
+            for (int f = 0; f < 6; ++f)
+                if ((nbr_full >> f) & 1u) ob |= 1u << ((f & 1) * 3 + (f >> 1));
+            const bool only_empty = (cnt[0] | cnt[1] | cnt[2] | cnt[3] | cnt[4] | cnt[5]) == 0 && (ci_.flags & CF_ONLY_EMPTY);
+            ci_.flags = (uint8_t)(ob | (only_empty ? CF_ONLY_EMPTY : 0u));
+            uint32_t fd = 0;
+#pragma unroll
+            for (int f = 0; f < 6; ++f) fd |= own_fd[f] << (2 * f);
+            ci_.face_dist = (uint16_t)fd;
+            ci_.uniform_type = 0;
+        } else if (kind == KIND_UNIFORM) {
+            ci_.flags = 0;
+            ci_.face_dist = 0x555;
+            ci_.uniform_type = (uint8_t)utype;
+        } else {
+            ci_.flags = 0;
+            ci_.face_dist = 0;
+        }
+        info[chunk] = ci_;
+    }
+    IVX_TW(g, li, 5);
+    ivx_wave_lds_sync();  // this chunk's LDS reads are over before the next chunk's stores
+    }
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVE_WAVES, 8))) void k_derive_wave(DeriveArgs a) { derive_wave_body(a); }
+
 // The active list anew from the chunk records alone (after a box sweep changed kinds: ivx_ensure_active_list): k_chunk_pre's rule for what is
 // settled — Void, or generated Uniform among six chunks generated Uniform —, entries with the kinds and the exposure bit the derive sweep would
 // have added, in chunk order. Writes nothing but the list and its counter: every chunk's per-step words are current (the box sweep kept them so).
@@ -871,10 +1327,23 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
     // (two forms of the sweep: from the sign rows the sampler left, while nothing else has rewritten voxels — no plane is read —, else from the planes)
     DeriveArgs da = derive_args(g, v, fz);
     if (g->signs_current) da.signs_type = (uint32_t)g->signs_type;
+    // The wave form (k_derive_wave) for the sign rows of a grid with no ghost layers: the same rule counted in waves — a whole number of
+    // entries per wave, as many as brings the waves nearest to the 4 x IVX_DERIVE_WAVE_WAVES a CU holds at once, and a workgroup per four.
+    uint32_t wave_grid;
+    {
+        const uint32_t per_round = (uint32_t)g->ctx->n_cu * 4u * IVX_DERIVE_WAVE_WAVES;
+        const uint32_t n = g->last_active ? g->last_active : per_round;
+        const uint32_t each = (n + per_round / 2u) / per_round > 1u ? (n + per_round / 2u) / per_round : 1u;
+        wave_grid = ((n + each - 1u) / each + 3u) / 4u;
+    }
     auto sweep = [&](uint32_t x_part) {
         da.x_part = x_part;
         if (g->signs_current) {
-            if (!ivx_many_try(g->ctx, g, IVX_MK_DERIVE_SIGNS, derive_grid, da)) IVX_KLAUNCH(k_derive<true>, dim3(derive_grid), dim3(256), 0, g->ctx->stream, da);
+            if (ivx_many_try(g->ctx, g, IVX_MK_DERIVE_SIGNS, derive_grid, da)) return;
+            if (x_part == IVX_XPART_ALL && v.ghost_sdf[0] == nullptr && v.ghost_sdf[1] == nullptr)
+                IVX_KLAUNCH(k_derive_wave, dim3(wave_grid), dim3(256), 0, g->ctx->stream, da);
+            else
+                IVX_KLAUNCH(k_derive<true>, dim3(derive_grid), dim3(256), 0, g->ctx->stream, da);
         } else {
             if (!ivx_many_try(g->ctx, g, IVX_MK_DERIVE_PLANES, derive_grid, da)) IVX_KLAUNCH(k_derive<false>, dim3(derive_grid), dim3(256), 0, g->ctx->stream, da);
         }

@@ -62,7 +62,9 @@ typedef struct {
     uint8_t flags;     /* VoxelChunkFlags bits 0-5 IS_OBSCURED_{X,Y,Z}_DN,{X,Y,Z}_UP, bit 6 HAS_ONLY_EMPTY_VOXELS; 0 for void/uniform */
     uint8_t uniform_type;
     uint16_t face_dist; /* FaceVoxelDistribution, 2 bits per face at bit 2*(2*dim+side): 0 empty 1 full 2 mixed */
-    uint8_t region_count, boundary_region_count; /* after ivx_label_regions */
+    uint8_t region_count, boundary_region_count; /* after ivx_label_regions. Inside a step, from the derive sweep to the exact numbering
+                                                    (k_step_post2), a chunk on the multi-region list holds a provisional 2 / 0: what runs
+                                                    between the two may test region_count against 0 and 1 only */
 } ivx_chunk_info;
 
 /* ChunkSubmesh (impact_voxel/src/mesh.rs:94-103) + the chunk's vertex range (mesh.rs:145). 64 bytes. */

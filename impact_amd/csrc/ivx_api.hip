@@ -756,13 +756,14 @@ int ivx_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* nodes, size_t n_no
     int depth = 0, max_depth = 0;
     for (size_t i = 0; i < n_nodes; ++i) {
         const uint32_t k = nodes[i].kind;
-        IVX_REQUIRE(k <= 9 && k != 6, IVX_ERR_INVALID, "ivx_sdf_sample: unsupported node kind %u", k);
+        IVX_REQUIRE(k <= 9, IVX_ERR_INVALID, "ivx_sdf_sample: unsupported node kind %u", k);
+        IVX_REQUIRE(k != 6 || nodes[i].reserved[1] <= 255u, IVX_ERR_INVALID, "ivx_sdf_sample: noise node with more than 255 octaves");
         if (k <= 2) max_depth = std::max(max_depth, ++depth);
         else if (k >= 7) {
             IVX_REQUIRE(depth >= 2, IVX_ERR_INVALID, "ivx_sdf_sample: malformed node program (combination without two operands)");
             --depth;
-        } else if (k == 5) {
-            IVX_REQUIRE(depth >= 1, IVX_ERR_INVALID, "ivx_sdf_sample: malformed node program (scaling without operand)");
+        } else if (k == 5 || k == 6) {
+            IVX_REQUIRE(depth >= 1, IVX_ERR_INVALID, "ivx_sdf_sample: malformed node program (scaling / noise without operand)");
         }
     }
     IVX_REQUIRE(n_nodes == 0 || depth == 1, IVX_ERR_INVALID, "ivx_sdf_sample: malformed node program (final stack depth %d)", depth);
@@ -775,7 +776,7 @@ int ivx_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* nodes, size_t n_no
         if ((rc = h2d(g, g->dev_scratch, annotated.data(), n_nodes * sizeof(ivx_sdf_processed_node)))) return rc;
     }
     rc = ivx_launch_sdf_sample(g, static_cast<const ivx_sdf_processed_node*>(g->dev_scratch), (uint32_t)n_nodes, (uint32_t)max_depth, grid_shape,
-                               shifted_grid_center, voxel_type);
+                               shifted_grid_center, voxel_type, 0u, false, ivx_sdf_has_noise(nodes, n_nodes));
     if (rc) return rc;
     g->mesh_valid = 0;
     g->mesh_built = 0;
@@ -3296,12 +3297,13 @@ int ivx_grid_set_sdf_program(ivx_grid* g, const ivx_sdf_processed_node* nodes, s
     int depth = 0, max_depth = 0;
     for (size_t i = 0; i < n_nodes; ++i) {
         const uint32_t k = nodes[i].kind;
-        IVX_REQUIRE(k <= 9 && k != 6, IVX_ERR_INVALID, "ivx_grid_set_sdf_program: unsupported node kind %u", k);
+        IVX_REQUIRE(k <= 9, IVX_ERR_INVALID, "ivx_grid_set_sdf_program: unsupported node kind %u", k);
+        IVX_REQUIRE(k != 6 || nodes[i].reserved[1] <= 255u, IVX_ERR_INVALID, "ivx_grid_set_sdf_program: noise node with more than 255 octaves");
         if (k <= 2) max_depth = std::max(max_depth, ++depth);
         else if (k >= 7) {
             IVX_REQUIRE(depth >= 2, IVX_ERR_INVALID, "ivx_grid_set_sdf_program: malformed node program");
             --depth;
-        } else if (k == 5) {
+        } else if (k == 5 || k == 6) {
             IVX_REQUIRE(depth >= 1, IVX_ERR_INVALID, "ivx_grid_set_sdf_program: malformed node program");
         }
     }
@@ -3335,6 +3337,7 @@ int ivx_grid_set_sdf_program(ivx_grid* g, const ivx_sdf_processed_node* nodes, s
         g->prog_center[d] = shifted_grid_center[d];
     }
     g->prog_type = voxel_type;
+    g->prog_noise = ivx_sdf_has_noise(nodes, n_nodes) ? 1 : 0;
     g->eval_len_valid = 0;
     g->eval_len_pending = 0;
     return IVX_OK;
@@ -3432,7 +3435,8 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
                                                               : 0u;
     if (front && (stages & IVX_STAGE_SAMPLE)) {
         T0(0);
-        if ((rc = ivx_launch_sdf_sample(g, g->prog_nodes, g->prog_n, g->prog_stack, g->prog_shape, g->prog_center, g->prog_type, preset_in_sample, true))) return rc;
+        if ((rc = ivx_launch_sdf_sample(g, g->prog_nodes, g->prog_n, g->prog_stack, g->prog_shape, g->prog_center, g->prog_type, preset_in_sample, true,
+                                        g->prog_noise != 0))) return rc;
         T1(0);
         g->eval_len_pending = 1;  // (the list lengths reach the result block once a derive sweep has rolled the counters over)
         g->occ_ref_valid = 0;

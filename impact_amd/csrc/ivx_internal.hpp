@@ -194,6 +194,7 @@ struct ivx_grid {
     uint32_t prog_shape[3];
     float prog_center[3];
     uint8_t prog_type;
+    uint8_t prog_noise;  // the resident program holds a noise node (kind 6): the sampler's noise forms run it
     // lengths of the sampler's three evaluation lists under the resident program, as the last collected step with a derive sweep reported them
     // (`eval_len_valid`; a function of the program and the grid alone): a class whose list is known to be empty is not launched
     uint32_t eval_len[3];
@@ -441,7 +442,8 @@ static inline GridView ivx_view(const ivx_grid* g) {
 int ivx_launch_classify(ivx_grid* g);
 int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, uint32_t n_nodes, uint32_t stack_size,
                           const uint32_t shape[3], const float shifted_center[3], uint8_t voxel_type, uint32_t preset_groups = 0,
-                          bool resident_program = false);
+                          bool resident_program = false, bool noise = false);
+bool ivx_sdf_has_noise(const ivx_sdf_processed_node* nodes, size_t n);  // sdf_compile.cpp
 // parts of the fused sweep: k_derive can label the chunk-local regions and compute the chunk moments of the chunks it visits
 #define IVX_PART_REGIONS 1u
 #define IVX_PART_MOMENTS 2u

@@ -50,6 +50,22 @@ F3 rotate(const float q[4], const F3& v) {
     return plus(plus(t0, t1), t2);
 }
 
+// theoretical_max_amplitude_of_fbm_noise (atomic.rs:1850-1858); f32::powi is the compiler's repeated squaring (__powisf2)
+float powi_f32(float a, uint32_t b) {
+    float r = 1.0f;
+    for (;;) {
+        if (b & 1u) r *= a;
+        b /= 2u;
+        if (b == 0u) break;
+        a *= a;
+    }
+    return r;
+}
+float fbm_max_amplitude(uint32_t octaves, float persistence) {
+    if (std::fabs(persistence - 1.0f) > 1e-6f) return (1.0f - powi_f32(persistence, octaves)) / (1.0f - persistence);
+    return (float)octaves;
+}
+
 // atomic.rs:1590-1598
 float soft_padding(float smoothness, uint32_t leaves) { return (0.25f * smoothness) * std::log2((float)leaves); }
 
@@ -113,6 +129,11 @@ struct Compiler {
                 leaves[id] = leaves[nd.child1];
                 padding[id] = padding[nd.child1];
                 break;
+            case 6:  // multifractal noise: the child's domain expanded about its centre by the amplitude (atomic.rs:373-383)
+                domain[id] = grown(domain[nd.child1], nd.p[3]);
+                leaves[id] = leaves[nd.child1];
+                padding[id] = padding[nd.child1];
+                break;
             case 7:
                 domain[id] = {lower(domain[nd.child1].lo, domain[nd.child2].lo), upper(domain[nd.child1].hi, domain[nd.child2].hi)};
                 break;
@@ -139,7 +160,9 @@ struct Compiler {
         const ivx_sdf_node& nd = in[id];
         const bool first = state[id] == 0;
         if (first) state[id] = 1;
-        if (nd.kind >= 3 && nd.kind <= 5) visit(nd.child1);
+        // (noise: the reference hands `octaves as u8` to simdnoise; counts beyond 255 are refused rather than wrapped)
+        if (nd.kind == 6 && nd.child2 > 255u) ok = false;
+        else if (nd.kind >= 3 && nd.kind <= 6) visit(nd.child1);
         else if (nd.kind >= 7 && nd.kind <= 9) {
             visit(nd.child1);
             visit(nd.child2);
@@ -164,6 +187,18 @@ struct Compiler {
             case 2: p.a = 0.5f * nd.p[0]; p.b = 0.5f * nd.p[1]; p.c = 0.5f * nd.p[2]; break;
             case 3: p.a = nd.p[0]; p.b = nd.p[1]; p.c = nd.p[2]; break;
             case 5: p.a = nd.p[0]; break;
+            case 6: {  // MultifractalNoiseSDFModifier::new (atomic.rs:1364-1391)
+                const uint32_t octaves = nd.child2;
+                const float persistence = nd.p[2], amplitude = nd.p[3];
+                const float inherent = fbm_max_amplitude(octaves, persistence);
+                p.a = std::fabs(inherent - 0.0f) > std::numeric_limits<float>::epsilon() ? amplitude / inherent : 0.0f;  // noise_scale
+                p.b = nd.p[0];  // frequency
+                p.c = nd.p[1];  // lacunarity
+                std::memcpy(&p.reserved[0], &persistence, 4);
+                p.reserved[1] = octaves;
+                p.reserved[2] = nd.pad;  // seed
+                break;
+            }
             case 7: case 8: case 9: p.a = nd.p[0]; p.b = 0.25f / nd.p[0]; break;
             default: break;
         }
@@ -225,7 +260,7 @@ extern "C" int ivx_sdf_compile(const ivx_sdf_node* nodes, size_t n_nodes, uint32
     c.padding.assign(n_nodes, 0.0f);
     c.state.assign(n_nodes, 0);
     c.visit(root);
-    IVX_REQUIRE(c.ok, IVX_ERR_INVALID, "ivx_sdf_compile: missing node, cycle or unsupported node kind in SDF graph");
+    IVX_REQUIRE(c.ok, IVX_ERR_INVALID, "ivx_sdf_compile: missing node, cycle, unsupported node kind or noise with more than 255 octaves in SDF graph");
     IVX_REQUIRE(c.out.size() <= cap, IVX_ERR_CAPACITY, "ivx_sdf_compile: %zu processed nodes exceed capacity %zu", c.out.size(), cap);
 
     // determine_transforms_and_margins (atomic.rs:495-596): walk parents before children
@@ -261,6 +296,10 @@ extern "C" int ivx_sdf_compile(const ivx_sdf_node* nodes, size_t n_nodes, uint32
             for (int col = 0; col < 4; ++col)
                 for (int row = 0; row < 3; ++row) cur[col * 4 + row] = inv * cur[col * 4 + row];
             mstack[top] = margin / src.p[0];
+        } else if (p.kind == 6) {
+            // the transform is the parent's; a point within this node's margin may come from a child point `amplitude` further out
+            // (atomic.rs:559-567)
+            mstack[top] = margin + src.p[3];
         } else {
             std::memcpy(&tstack[16 * (top + 1)], transform, sizeof(transform));
             const float mc = margin + 2.5f * soft_padding(src.p[0], p.leaf_count);
@@ -302,10 +341,18 @@ static inline float host_combine(uint32_t kind, float a, float b, float s, float
     return s == 0.0f ? rs_max(a, b) : -host_smooth_union(-a, -b, s, q);
 }
 
+// A noise node (kind 6) keeps persistence, octaves and seed in reserved[0..3) of the compiled program; in the uploaded copy they move to
+// the bottom row of its transform (transform[3], [7], [11]: an affine transform's bottom row is 0 0 0 1 and no kernel reads it), so that
+// reserved[] can take the annotations like every other node's.
 void ivx_sdf_annotate_host(ivx_sdf_processed_node* nodes, size_t n) {
     std::vector<uint32_t> root_stack;  // roots of the subtrees on the evaluation stack
     for (size_t i = 0; i < n; ++i) {
         ivx_sdf_processed_node& nd = nodes[i];
+        if (nd.kind == 6u) {
+            std::memcpy(&nd.transform[3], &nd.reserved[0], 4);
+            std::memcpy(&nd.transform[7], &nd.reserved[1], 4);
+            std::memcpy(&nd.transform[11], &nd.reserved[2], 4);
+        }
         const uint32_t kind = nd.kind;
         float f;
         uint32_t first;
@@ -367,7 +414,9 @@ void ivx_sdf_annotate_host(ivx_sdf_processed_node* nodes, size_t n) {
             if (kind <= 2u) continue;
             if (kind < 7u) {
                 float cu = U, cl = L;
-                if (kind == 5u) {
+                if (kind == 6u) {
+                    cu = inf, cl = -inf;  // (noise moves a value by a different amount at every voxel: no class survives it)
+                } else if (kind == 5u) {
                     if (nd.a > 0.0f) cu = U / nd.a * 1.00001f + 1e-6f, cl = L / nd.a * 1.00001f - 1e-6f;  // (U > 0 > L)
                     else cu = inf, cl = -inf;
                 }
@@ -391,6 +440,12 @@ void ivx_sdf_annotate_host(ivx_sdf_processed_node* nodes, size_t n) {
             }
         }
     }
+}
+
+bool ivx_sdf_has_noise(const ivx_sdf_processed_node* nodes, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (nodes[i].kind == 6u) return true;
+    return false;
 }
 
 extern "C" int ivx_sdf_grid_shape(const float domain[6], uint32_t grid_shape[3], float shifted_grid_center[3]) {

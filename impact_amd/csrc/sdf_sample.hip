@@ -18,6 +18,7 @@
 // The row is written back as one 16-byte store per plane per thread (4 KiB contiguous per workgroup).
 // HBM traffic: 2 B/voxel written (sdf + type), nothing read.
 #include "ivx_internal.hpp"
+#include "noise.hpp"
 #include "table_roles.hpp"
 
 namespace {
@@ -290,6 +291,81 @@ __device__ __forceinline__ uint32_t node_mode(const ivx_sdf_processed_node* nd, 
 }
 
 
+// ---- multifractal noise (SDF node kind 6, atomic.rs:1420-1571) ----------------------------------------------------------------------
+// Parameters of a noise node in the uploaded program: a = noise_scale, b = frequency, c = lacunarity, transform[3] / [7] / [11] = the bits of
+// persistence, octaves and seed (ivx_sdf_annotate_host). The noise is evaluated in "noise space": node space divided by the transform's
+// scale (the length of its first column), at the frequency multiplied by it.
+struct NoiseFrame {
+    V3 o, dx, dy, dz;  // origin_for_noise and the three voxel steps dx_for_noise ... (scale * column)
+    float freq, lacunarity, gain, noise_scale;
+    uint32_t octaves, seed;
+    bool rotated;  // the per-voxel fallback path (atomic.rs:1445-1482)
+};
+__device__ __forceinline__ NoiseFrame noise_frame(const ivx_sdf_processed_node* nd, V3 origin_root) {
+    const float* m = nd->transform;
+    NoiseFrame f;
+    const V3 on = xform_point(m, origin_root);
+    const V3 dx = mk(m[0], m[1], m[2]), dy = mk(m[4], m[5], m[6]), dz = mk(m[8], m[9], m[10]);
+    const float inverse_scale = len3(dx);
+    const float sc = 1.0f / inverse_scale;
+    f.freq = nd->b * inverse_scale;
+    f.o = scale(on, sc);
+    f.dx = scale(dx, sc), f.dy = scale(dy, sc), f.dz = scale(dz, sc);
+    // abs_diff_ne!(dx.x * inverse_scale, 1, epsilon = 1e-6) || abs_diff_ne!(dy.y * inverse_scale, 1, epsilon = 1e-6) — the reference's test,
+    // taken as it stands (a scaled transform takes the per-voxel path too)
+    f.rotated = !(fabsf(dx.x * inverse_scale - 1.0f) <= 1e-6f) || !(fabsf(dy.y * inverse_scale - 1.0f) <= 1e-6f);
+    f.noise_scale = nd->a;
+    f.lacunarity = nd->c;
+    f.gain = m[3];
+    f.octaves = __float_as_uint(m[7]);
+    f.seed = __float_as_uint(m[11]);
+    return f;
+}
+__device__ __forceinline__ float noise_at(const NoiseFrame& f, V3 p) {  // dimensions reversed, as the reference passes them to simdnoise
+    return ivx_noise::fbm3(p.z, p.y, p.x, f.octaves, f.freq, f.lacunarity, f.gain, f.seed);
+}
+// Test position l (0..25) of all_block_test_positions_with_indices (atomic.rs:1683-1797) in noise space, with the voxel (i, j, k) whose
+// child value it is tested with: 8 corners, 12 edge midpoints, 6 face centres, in the reference's order and f32 operation order
+// (s = 15, h = 7.5; `o + a * u + b * v` is (o + a * u) + b * v).
+__device__ __forceinline__ V3 noise_test_point(const NoiseFrame& f, uint32_t l, uint32_t& pi, uint32_t& pj, uint32_t& pk) {
+    const float S = 15.0f, H = 7.5f;
+    const V3 o = f.o, dx = f.dx, dy = f.dy, dz = f.dz;
+    switch (l) {
+        case 0: pi = 0, pj = 0, pk = 0; return o;
+        case 1: pi = 15, pj = 0, pk = 0; return add(o, scale(dx, S));
+        case 2: pi = 0, pj = 15, pk = 0; return add(o, scale(dy, S));
+        case 3: pi = 0, pj = 0, pk = 15; return add(o, scale(dz, S));
+        case 4: pi = 15, pj = 15, pk = 0; return add(o, scale(add(dx, dy), S));
+        case 5: pi = 15, pj = 0, pk = 15; return add(o, scale(add(dx, dz), S));
+        case 6: pi = 0, pj = 15, pk = 15; return add(o, scale(add(dy, dz), S));
+        case 7: pi = 15, pj = 15, pk = 15; return add(o, scale(add(add(dx, dy), dz), S));
+        case 8: pi = 0, pj = 0, pk = 0; return add(o, scale(dx, H));
+        case 9: pi = 0, pj = 15, pk = 0; return add(add(o, scale(dx, H)), scale(dy, S));
+        case 10: pi = 0, pj = 0, pk = 15; return add(add(o, scale(dx, H)), scale(dz, S));
+        case 11: pi = 0, pj = 15, pk = 15; return add(add(o, scale(dx, H)), scale(add(dy, dz), S));
+        case 12: pi = 0, pj = 0, pk = 0; return add(o, scale(dy, H));
+        case 13: pi = 15, pj = 0, pk = 0; return add(add(o, scale(dy, H)), scale(dx, S));
+        case 14: pi = 0, pj = 0, pk = 15; return add(add(o, scale(dy, H)), scale(dz, S));
+        case 15: pi = 15, pj = 0, pk = 15; return add(add(o, scale(dy, H)), scale(add(dx, dz), S));
+        case 16: pi = 0, pj = 0, pk = 0; return add(o, scale(dz, H));
+        case 17: pi = 15, pj = 0, pk = 0; return add(add(o, scale(dz, H)), scale(dx, S));
+        case 18: pi = 0, pj = 15, pk = 0; return add(add(o, scale(dz, H)), scale(dy, S));
+        case 19: pi = 15, pj = 15, pk = 0; return add(add(o, scale(dz, H)), scale(add(dx, dy), S));
+        case 20: pi = 0, pj = 8, pk = 8; return add(add(o, scale(dy, H)), scale(dz, H));
+        case 21: pi = 15, pj = 8, pk = 8; return add(add(add(o, scale(dx, S)), scale(dy, H)), scale(dz, H));
+        case 22: pi = 8, pj = 0, pk = 8; return add(add(o, scale(dx, H)), scale(dz, H));
+        case 23: pi = 8, pj = 15, pk = 8; return add(add(add(o, scale(dy, S)), scale(dx, H)), scale(dz, H));
+        case 24: pi = 8, pj = 8, pk = 0; return add(add(o, scale(dx, H)), scale(dy, H));
+        default: pi = 8, pj = 8, pk = 15; return add(add(add(o, scale(dz, S)), scale(dx, H)), scale(dy, H));
+    }
+}
+// the node's domain_with_margin lies outside the block (the first half of the reference's test)
+__device__ __forceinline__ bool node_outside(const ivx_sdf_processed_node* nd, Box block) {
+    const Box bn = aabb_of_transformed(block, nd->transform);
+    const Box dom{mk(nd->domain_lo[0], nd->domain_lo[1], nd->domain_lo[2]), mk(nd->domain_hi[0], nd->domain_hi[1], nd->domain_hi[2])};
+    return lies_outside(dom, bn);
+}
+
 // Per-chunk scalar pre-pass (one THREAD per chunk): runs the node program on a conservative INTERVAL
 // [lo, hi] of each stack level over the chunk, with exact tracking of block constants.
 //   * leaf in a fill mode (the reference's whole-block early-outs): exact constant +-margin;
@@ -342,6 +418,8 @@ constexpr uint32_t OP_CONST = 0u, OP_LEAF = 1u, OP_SCALE = 2u, OP_COMBINE = 3u, 
 // OP_SKIP: the evaluator jumps `second word` ops ahead (itself included): the steps of a first operand that the pre-pass found to be out of
 // its combination's reach stay in the stream behind one (the stream is append / truncate only), dead
 constexpr uint32_t OP_SKIP = 5u;
+// OP_NOISE: add the noise node's noise to the level (NOISE programs only); OP_NOISE_OUTSIDE: the same, if a test position fails (atomic.rs:755-787)
+constexpr uint32_t OP_NOISE = 6u, OP_NOISE_OUTSIDE = 7u;
 constexpr int PRE_T = 64;      // chunks per pre-pass block: one per lane
 constexpr int PRE_WAVES = 8;   // waves per pre-pass block: all of them take the nodes' box tests, the first walks the program
 struct PaddedNode {
@@ -369,6 +447,7 @@ __device__ __forceinline__ bool range_all_far(const uint32_t* mask, uint32_t a, 
 // the node takes its "domain lies outside the block" early-out for every chunk of the super-block `block`
 __device__ __forceinline__ bool super_far(const ivx_sdf_processed_node* nd, Box block) {
     const uint32_t kind = nd->kind;
+    if (kind == 6u) return false;  // noise: its early-out depends on the noise at the test positions — no folded constant stands for it
     if (kind > 2u && kind < 7u) return true;  // translation / rotation / scaling have no test of their own
     const Box bn = aabb_of_transformed(block, nd->transform);
     const float eps = 1e-2f;
@@ -426,6 +505,9 @@ __device__ __forceinline__ bool range_all_far(const uint32_t* mask, uint32_t a, 
 // `ahead`: the launch runs a step ahead of its sample stage (ivx_grid_set_sample_ahead): `info_out` is the grid's shadow record array, where
 // a chunk that is NOT settled here gets a record of kind AHEAD_OPEN, so that the evaluator launch that commits the shadow knows which are
 constexpr uint8_t AHEAD_OPEN = 0xFFu;
+// NOISE: the program holds a noise node (kind 6). Its form of the pre-pass lists every chunk it cannot settle for the general evaluator class
+// (k_sdf_eval<0, true>); programs without one keep the form below unchanged.
+template <bool NOISE>
 __global__ __launch_bounds__(PRE_T * PRE_WAVES) void k_sdf_prepass(SampleParams p, const ivx_sdf_processed_node* __restrict__ nodes,
                                                        uint32_t* __restrict__ prog_len,
                                                        uint2* __restrict__ prog_ops, uint32_t* __restrict__ eval_count,
@@ -526,6 +608,8 @@ __global__ __launch_bounds__(PRE_T * PRE_WAVES) void k_sdf_prepass(SampleParams 
                     if (mode == 0u) leaf_bounds(tn, aabb_of_transformed(vox_block, tn->transform), blo, bhi);
                 } else if (tk >= 7u) {
                     mode = (!tfar && node_mode(tn, block) == 0u) ? 1u : 0u;
+                } else if (NOISE && tk == 6u) {
+                    mode = node_outside(tn, block) ? 0u : 1u;  // 1 = must apply
                 }
                 t_mode[q][tid] = (uint8_t)mode;
                 t_lo[q][tid] = blo;
@@ -584,6 +668,42 @@ __global__ __launch_bounds__(PRE_T * PRE_WAVES) void k_sdf_prepass(SampleParams 
             } else {
                 emit((OP_SCALE << 28) | (kind << 24) | n, 0u);
             }
+        } else if (NOISE && kind == 6u) {
+            // Multifractal noise (atomic.rs:755-787): skipped only when the node's domain lies outside the block AND the child's value plus the
+            // noise passes `>= margin` at all 26 test positions. Decided here when the child is an exact constant (the noise at the test positions,
+            // as the evaluator would compute it) or its bounds decide the test either way; else the evaluator tests (OP_NOISE_OUTSIDE).
+            const uint32_t lv = top - 1;
+            const bool c = (cmask >> lv) & 1u;
+            const float lo = s_lo[lv][tid], hi = s_hi[lv][tid];
+            const NoiseFrame f = noise_frame(nd, block.lo);
+            const float nb = fabsf(f.noise_scale) * ivx_noise::fbm3_bound(f.octaves, f.gain) * 1.0001f;
+            const bool must_apply = t_mode[n % NODE_TILE][tid] != 0u;
+            bool decided = true, apply = true;
+            if (!must_apply) {
+                if (c) {
+                    bool all_pass = true;
+                    for (uint32_t l = 0; l < 26u && all_pass; ++l) {
+                        uint32_t pi, pj, pk;
+                        const V3 pt = noise_test_point(f, l, pi, pj, pk);
+                        all_pass = lo + noise_at(f, pt) * f.noise_scale >= nd->margin;
+                    }
+                    apply = !all_pass;
+                } else if ((lo - nb) - slack(lo) - slack(nb) >= nd->margin) {
+                    apply = false;
+                } else if (!((hi + nb) + slack(hi) + slack(nb) >= nd->margin)) {
+                    apply = true;
+                } else {
+                    decided = false;
+                }
+            }
+            if (decided && !apply) continue;  // the child's values stand
+            if (!decided && class_dropped) poisoned = true;  // (reads its operand at the test voxels, see the combinations below)
+            emit(((decided ? OP_NOISE : OP_NOISE_OUTSIDE) << 28) | (kind << 24) | n, 0u);
+            s_lo[lv][tid] = (lo - nb) - slack(lo) - slack(nb);
+            s_hi[lv][tid] = (hi + nb) + slack(hi) + slack(nb);
+            s_need[lv][tid] = (uint8_t)max((uint32_t)s_need[lv][tid], 1u);
+            cmask &= ~(1u << lv);
+            bare &= ~(1u << lv);
         } else if (kind >= 7u) {
             top -= 1;
             const bool c1 = (cmask >> (top - 1)) & 1u, c2 = (cmask >> top) & 1u;
@@ -776,7 +896,7 @@ __global__ __launch_bounds__(PRE_T * PRE_WAVES) void k_sdf_prepass(SampleParams 
         const unsigned long long below = (1ull << tid) - 1ull;
         const bool ev = mine && (out != out || to_fill);
         const uint32_t need = pos <= OP_CAP ? (uint32_t)s_need[0][tid] : max(p.stack_size, 2u);  // (the full program may use every level, unfused)
-        const uint32_t cls = need <= 1u ? 0u : (need == 2u ? 1u : 2u);
+        const uint32_t cls = NOISE ? 2u : (need <= 1u ? 0u : (need == 2u ? 1u : 2u));
         // The first class (nearly every chunk of a smooth body) is listed longest program first: programs of more than LONG_OPS steps from
         // the front of its list, the others from the back. Workgroups start in list order, so the evaluator's last workgroups are short
         // ones and its tail — a tenth of the kernel with the chunks in arbitrary order — shrinks. Counters: [c] = entries of class c,
@@ -1122,6 +1242,52 @@ __device__ __forceinline__ void combine_levels(uint32_t kind, float s, float q, 
     }
 }
 
+// A noise node over stack level `lv` (OP_NOISE / OP_NOISE_OUTSIDE, or the node in the full program): every voxel of the level gets
+// noise * noise_scale added (atomic.rs:1423-1508) unless `outside` and the child's value plus the noise passes `>= margin` at all 26 test
+// positions (atomic.rs:1510-1571). Only the general class runs these (k_sdf_eval<0, true>): no register-held row.
+__device__ __forceinline__ void noise_level(const ivx_sdf_processed_node* nd, bool outside, uint32_t lv, float* stack, float& cv, uint32_t& cmask, uint32_t tid,
+                                         V3 origin_root, uint32_t ti, uint32_t tj) {
+    const NoiseFrame f = noise_frame(nd, origin_root);
+    const bool c = (cmask >> lv) & 1u;
+    const float v1 = c ? cv_get(cv, lv) : 0.0f;
+    const float ns = f.noise_scale;
+    bool apply = !outside;
+    if (!apply) {  // workgroup-uniform branch: one lane per test position, every wave repeats the test
+        __syncthreads();
+        const uint32_t l = tid & 63u;
+        bool pass = true;
+        if (l < 26u) {
+            uint32_t pi, pj, pk;
+            const V3 pt = noise_test_point(f, l, pi, pj, pk);
+            const float x = c ? v1 : stack[(size_t)lds_level(cmask, lv) * IVX_CHUNK_VOXELS + pk * 256u + (pi * 16u + pj)];
+            pass = x + noise_at(f, pt) * ns >= nd->margin;
+        }
+        apply = __builtin_amdgcn_readfirstlane(__all(pass ? 1 : 0) != 0 ? 0 : 1) != 0;
+        __syncthreads();
+    }
+    if (!apply) return;
+    cmask &= ~(1u << lv);  // (the level is per voxel from here; it is the top one, so no level above moves)
+    float* d = stack + (size_t)lds_level(cmask, lv) * IVX_CHUNK_VOXELS + tid;
+    if (!f.rotated) {
+        // block path (atomic.rs:1485-1507): the voxel (i, j, k) at (o.z + k, o.y + j, o.x + i) — offset + index, one rounding each
+        const float py = f.o.y + (float)tj, pz = f.o.x + (float)ti;
+#pragma unroll 1
+        for (int k = 0; k < 16; ++k) {
+            const float nz = ivx_noise::fbm3(f.o.z + (float)k, py, pz, f.octaves, f.freq, f.lacunarity, f.gain, f.seed);
+            d[k * 256] = (c ? v1 : d[k * 256]) + nz * ns;
+        }
+    } else {
+        // per-voxel path (atomic.rs:1445-1482): pos = (o + i dx) + j dy, then pos += dz voxel by voxel
+        V3 pos = add(add(f.o, scale(f.dx, (float)ti)), scale(f.dy, (float)tj));
+#pragma unroll 1
+        for (int k = 0; k < 16; ++k) {
+            const float nz = noise_at(f, pos);
+            d[k * 256] = (c ? v1 : d[k * 256]) + nz * ns;
+            pos = add(pos, f.dz);
+        }
+    }
+}
+
 // MODE 0: the general class (as many levels as the program's stack). MODE 1 (TRIM): the two-level class, with row 15 of the second dense level in registers (IVX_LV_GET); `scratch_off`: offset (floats) of sixteen
 // words of LDS behind / at the tail of the stack: [0..5) the published test voxels of a register row, [8..12) the classification's votes
 // MODE 2: the one-level class (programs whose only operands with a level of their own are fused away, see eval_leaf_fused): 16 KB + the
@@ -1131,7 +1297,8 @@ __device__ __forceinline__ void combine_levels(uint32_t kind, float s, float q, 
 #ifndef IVX_EVAL_WAVES
 #define IVX_EVAL_WAVES 8
 #endif
-template <int MODE>
+// NOISE (MODE 0 only): programs with a noise node; the op and the node run in this instantiation alone.
+template <int MODE, bool NOISE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_EVAL_WAVES, 8))) void k_sdf_eval(SampleParams p, const uint32_t* __restrict__ eval_count, const uint32_t* __restrict__ eval_list,
                                                   const uint32_t* __restrict__ long_count, const uint32_t* __restrict__ first_count,
                                                   const uint32_t* __restrict__ first_list, uint32_t list_len, uint32_t scratch_off,
@@ -1299,6 +1466,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_EVAL_WA
                 }
             } else if (opc == OP_SKIP) {
                 i += v - 1u;  // (a first operand the pre-pass found out of its combination's reach)
+            } else if (NOISE && opc >= OP_NOISE) {
+                noise_level(nodes + (w & 0xFFFFFFu), opc == OP_NOISE_OUTSIDE, top - 1u, stack, cv, cmask, tid, origin_root, ti, tj);
             } else {
                 top -= 1;
                 combine_levels<TRIM>(kind, s, q, margin, opc == OP_COMBINE_OUTSIDE, top, stack, cv, cmask, tid, r15, s_pub);
@@ -1343,6 +1512,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_EVAL_WA
                 } else if (kind >= 7u) {
                     top -= 1;
                     combine_levels<TRIM>(kind, nd->a, nd->b, nd->margin, mode != 0u, top, stack, cv, cmask, tid, r15, s_pub);
+                } else if (NOISE && kind == 6u) {
+                    noise_level(nd, node_outside(nd, block), top - 1u, stack, cv, cmask, tid, origin_root, ti, tj);
                 }
             }
         }
@@ -1470,7 +1641,7 @@ ivx_roles::PresetArgs ivx_preset_args(ivx_grid* g, uint32_t groups);  // derive.
 
 int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, uint32_t n_nodes, uint32_t stack_size,
                           const uint32_t shape[3], const float shifted_center[3], uint8_t voxel_type, uint32_t preset_groups,
-                          bool resident_program) {
+                          bool resident_program, bool noise) {
     SampleParams p;
     p.cx = g->cc[0];
     p.cy = g->cc[1];
@@ -1488,7 +1659,8 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
     p.voxel_type = voxel_type;
     size_t lds = (size_t)(stack_size ? stack_size : 1) * IVX_CHUNK_VOXELS * sizeof(float);
     IVX_REQUIRE(lds <= 150 * 1024, IVX_ERR_CAPACITY, "SDF graph needs a forward stack of %u blocks (at most 9 fit the 160 KiB LDS)", stack_size);
-    IVX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sdf_eval<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    IVX_HIP_CHECK(hipFuncSetAttribute(noise ? reinterpret_cast<const void*>(k_sdf_eval<0, true>) : reinterpret_cast<const void*>(k_sdf_eval<0>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
         int rc_b = ivx_sampler_buffers(g);
         if (rc_b) return rc_b;
@@ -1507,10 +1679,11 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
     // this launcher and must launch every class that program can reach)
     const bool known = resident_program && g->eval_len_valid != 0;
     const uint32_t fill = 4u * 5u * (uint32_t)g->ctx->n_cu;
-    const bool merge01 = known && g->eval_len[0] && g->eval_len[1] && (g->eval_len[0] < fill || g->eval_len[1] < fill);
-    const bool launch2 = !merge01 && !(known && g->eval_len[0] == 0u);            // k_sdf_eval<2>: the one-level class
-    const bool launch1 = merge01 || !(known && g->eval_len[1] == 0u);             // k_sdf_eval<1>: the two-level class (or both)
-    const bool launch0 = stack_size >= 3u && !(known && g->eval_len[2] == 0u);    // k_sdf_eval<0>: the general class
+    // (a program with a noise node lists every chunk for the general class and runs in k_sdf_eval<0, true> alone)
+    const bool merge01 = !noise && known && g->eval_len[0] && g->eval_len[1] && (g->eval_len[0] < fill || g->eval_len[1] < fill);
+    const bool launch2 = !noise && !merge01 && !(known && g->eval_len[0] == 0u);            // k_sdf_eval<2>: the one-level class
+    const bool launch1 = !noise && (merge01 || !(known && g->eval_len[1] == 0u));           // k_sdf_eval<1>: the two-level class (or both)
+    const bool launch0 = (noise || stack_size >= 3u) && !(known && g->eval_len[2] == 0u);   // k_sdf_eval<0>: the general class
     // Sample-ahead: this stage's pre-pass may have run already, behind the evaluator of the step before (see below); the stage then starts at
     // its first evaluator launch, which commits the parked records and hosts the presets. Only with an evaluator launch to host them.
     const bool ahead_fits = resident_program && fused_super && (launch0 || launch1 || launch2);
@@ -1559,8 +1732,12 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
             IVX_KLAUNCH(k_sdf_super, dim3(sx * sy * sz), dim3(64), words * sizeof(uint32_t), g->ctx->stream, p, d_nodes, g->samp_super, super_skip, words, sy, sz,
                                ivx_preset_args(g, super_presets));
         }
-        IVX_KLAUNCH(k_sdf_prepass, dim3(sx * sy * sz), dim3(PRE_T * PRE_WAVES), 0, g->ctx->stream, p, d_nodes, g->samp_len, ops, eval_count, eval_list,
-                           g->n_chunks, g->info, g->samp_super, super_skip, words, sy, sz, sx * sy * sz, fused_super ? 1u : 0u, 0u, ivx_preset_args(g, prepass_presets));
+        if (noise)
+            IVX_KLAUNCH(k_sdf_prepass<true>, dim3(sx * sy * sz), dim3(PRE_T * PRE_WAVES), 0, g->ctx->stream, p, d_nodes, g->samp_len, ops, eval_count, eval_list,
+                               g->n_chunks, g->info, g->samp_super, super_skip, words, sy, sz, sx * sy * sz, fused_super ? 1u : 0u, 0u, ivx_preset_args(g, prepass_presets));
+        else
+            IVX_KLAUNCH(k_sdf_prepass<false>, dim3(sx * sy * sz), dim3(PRE_T * PRE_WAVES), 0, g->ctx->stream, p, d_nodes, g->samp_len, ops, eval_count, eval_list,
+                               g->n_chunks, g->info, g->samp_super, super_skip, words, sy, sz, sx * sy * sz, fused_super ? 1u : 0u, 0u, ivx_preset_args(g, prepass_presets));
     }
     g->scratch_dirty = (g->scratch_dirty & ~preset_groups) | IVX_SCRATCH_EVAL;
     g->planes_compact = 1;
@@ -1607,12 +1784,17 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
         if (launch0) {
             // (the scratch words are the last sixteen of the stack: rows 15 of the last level's threads 240..255, dead when they are used
             // — the votes — and never used as published test voxels, which only the trimmed launch has)
-            const uint32_t lv = stack_size;
+            const uint32_t lv = stack_size ? stack_size : 1u;
             const uint32_t scratch_off = lv * IVX_CHUNK_VOXELS - 16u;
             const ivx_chunk_info* sh = take_shadow();
-            IVX_KLAUNCH(k_sdf_eval<0>, dim3(fit(g->eval_len[2])), dim3(256), (size_t)lv * IVX_CHUNK_VOXELS * sizeof(float), g->ctx->stream, p, eval_count + 2,
-                               eval_list + 2 * (size_t)g->n_chunks, nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
-                               sh, g->n_chunks, sh ? first_presets : no_presets);
+            if (noise)
+                IVX_KLAUNCH((k_sdf_eval<0, true>), dim3(fit(g->eval_len[2])), dim3(256), (size_t)lv * IVX_CHUNK_VOXELS * sizeof(float), g->ctx->stream, p, eval_count + 2,
+                                   eval_list + 2 * (size_t)g->n_chunks, nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info,
+                                   g->chunk_signs, g->kface, sh, g->n_chunks, sh ? first_presets : no_presets);
+            else
+                IVX_KLAUNCH(k_sdf_eval<0>, dim3(fit(g->eval_len[2])), dim3(256), (size_t)lv * IVX_CHUNK_VOXELS * sizeof(float), g->ctx->stream, p, eval_count + 2,
+                                   eval_list + 2 * (size_t)g->n_chunks, nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info,
+                                   g->chunk_signs, g->kface, sh, g->n_chunks, sh ? first_presets : no_presets);
         }
     }
     IVX_HIP_CHECK(hipGetLastError());
@@ -1676,7 +1858,7 @@ int ivx_sampler_launch_ahead(ivx_grid* g, bool behind_stream) {
     }();
     const uint32_t n_sb = sx * sy * sz, blocks = std::min(n_sb, blocks_env ? blocks_env : 2u * (uint32_t)g->ctx->n_cu);
     g->shadow_sel ^= 1;
-    hipLaunchKernelGGL(k_sdf_prepass, dim3(blocks), dim3(PRE_T * PRE_WAVES), 0, aux, p, g->prog_nodes, g->samp_len_alt, reinterpret_cast<uint2*>(g->samp_ops_alt),
+    hipLaunchKernelGGL(g->prog_noise ? k_sdf_prepass<true> : k_sdf_prepass<false>, dim3(blocks), dim3(PRE_T * PRE_WAVES), 0, aux, p, g->prog_nodes, g->samp_len_alt, reinterpret_cast<uint2*>(g->samp_ops_alt),
                        alt_count, alt_count + 16, g->n_chunks, g->info_shadow + (size_t)g->shadow_sel * g->n_chunks, nullptr, nullptr, words, sy, sz, n_sb, 1u, 1u,
                        ivx_preset_args(g, 0u));
     IVX_HIP_CHECK(hipGetLastError());
@@ -1689,5 +1871,57 @@ int ivx_launch_classify(ivx_grid* g) {
     ivx_planes_touched(g);
     IVX_KLAUNCH(k_classify, dim3(g->n_chunks), dim3(256), 0, g->ctx->stream, g->n_chunks, g->sdf, g->type, g->info);
     IVX_HIP_CHECK(hipGetLastError());
+    return IVX_OK;
+}
+
+// ---- developer export: the noise functions over given points (tests) --------------------------------------------------------------
+namespace {
+struct NoiseEvalParams {
+    float freq, lacunarity, gain;
+    uint32_t octaves, seed;
+};
+__host__ __device__ inline NoiseEvalParams noise_eval_params(const float* params) {
+    NoiseEvalParams q;
+    q.freq = params[0], q.lacunarity = params[1], q.gain = params[2];
+    std::memcpy(&q.octaves, &params[3], 4);
+    std::memcpy(&q.seed, &params[4], 4);
+    return q;
+}
+__host__ __device__ inline float noise_eval_one(int which, const NoiseEvalParams& q, const float* pt) {
+    return which == 0 ? ivx_noise::fbm3(pt[0], pt[1], pt[2], q.octaves, q.freq, q.lacunarity, q.gain, q.seed)
+                      : ivx_noise::simplex4(pt[0], pt[1], pt[2], pt[3], q.seed);
+}
+__global__ __launch_bounds__(256) void k_noise_eval(int which, NoiseEvalParams q, const float* __restrict__ points, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    out[i] = noise_eval_one(which, q, points + i * (which == 0 ? 3u : 4u));
+}
+}  // namespace
+
+int ivx_noise_eval(ivx_ctx* ctx, int which, const float* params, const float* points, size_t n, float* out) {
+    IVX_REQUIRE(params && (n == 0 || (points && out)), IVX_ERR_INVALID, "ivx_noise_eval: null argument");
+    IVX_REQUIRE(which == 0 || which == 1, IVX_ERR_INVALID, "ivx_noise_eval: which must be 0 (fbm3) or 1 (simplex4)");
+    const NoiseEvalParams q = noise_eval_params(params);
+    const size_t dims = which == 0 ? 3u : 4u;
+    if (!ctx) {  // the host build of the same functions
+        for (size_t i = 0; i < n; ++i) out[i] = noise_eval_one(which, q, points + i * dims);
+        return IVX_OK;
+    }
+    if (n == 0) return IVX_OK;
+    struct Buffers {  // freed on every return
+        float *pts = nullptr, *out = nullptr;
+        ~Buffers() {
+            if (pts) (void)hipFree(pts);
+            if (out) (void)hipFree(out);
+        }
+    } b;
+    IVX_HIP_CHECK(hipMalloc(&b.pts, n * dims * sizeof(float)));
+    IVX_HIP_CHECK(hipMalloc(&b.out, n * sizeof(float)));
+    float *d_pts = b.pts, *d_out = b.out;
+    IVX_HIP_CHECK(ivx_memcpy_async(d_pts, points, n * dims * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    IVX_KLAUNCH(k_noise_eval, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, which, q, d_pts, n, d_out);
+    IVX_HIP_CHECK(hipGetLastError());
+    IVX_HIP_CHECK(ivx_memcpy_async(out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(ctx->stream));
     return IVX_OK;
 }

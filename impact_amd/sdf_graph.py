@@ -82,6 +82,15 @@ class SDFNode:
         return SDFNode._mk(SDF_SCALING, child_id, p=(scaling,))
 
     @staticmethod
+    def new_multifractal_noise(child_id, octaves, frequency, lacunarity, persistence, amplitude, seed):
+        """atomic.rs:1095-1114. The noise is this library's own (impact_amd/csrc/noise.hpp): the construction of the reference's
+        `simdnoise` (simplex noise summed over octaves), not its values; everything around it follows the reference."""
+        assert 0 <= int(octaves) <= 255 and 0 <= int(seed) < 2**32  # (the reference passes `octaves as u8`)
+        rec = SDFNode._mk(SDF_NOISE, child_id, int(octaves), (frequency, lacunarity, persistence, amplitude))
+        rec["pad"] = int(seed)
+        return rec
+
+    @staticmethod
     def new_union(child_1_id, child_2_id, smoothness):
         assert smoothness >= 0.0
         return SDFNode._mk(SDF_UNION, child_1_id, child_2_id, (smoothness,))

@@ -38,8 +38,11 @@ typedef struct ivx_grid ivx_grid;
 /* SDFNode — impact_voxel/src/generation/sdf/atomic.rs:62-181. 32 bytes.
  * kind: 0 sphere{p0=radius} 1 capsule{p0=segment_length,p1=radius} 2 box{p0..2=extents}
  *       3 translation{child1,p0..2} 4 rotation{child1,p=quat xyzw} 5 scaling{child1,p0}
+ *       6 multifractal noise{child1, child2=octaves, pad=seed, p=frequency,lacunarity,persistence,amplitude}
  *       7 union 8 subtraction 9 intersection {child1,child2,p0=smoothness}
- * (6 = multifractal noise is not supported: simdnoise is an un-vendored dependency) */
+ * Kind 6 (MultifractalNoiseSDFModifier, atomic.rs:165-181,1363-1571) follows the reference in its semantics, domains, margins,
+ * noise positions and per-block early-out, but its noise is this library's own (impact_amd/csrc/noise.hpp: Gustavson simplex
+ * noise summed over octaves, the construction of the reference's `simdnoise`, not simdnoise's values). */
 typedef struct {
     uint32_t kind, child1, child2, pad;
     float p[4];
@@ -51,8 +54,9 @@ typedef struct {
     float transform[16]; /* column-major root->node space */
     float domain_lo[3], domain_hi[3]; /* domain_with_margin */
     float margin;
-    float a, b, c; /* sphere a=r | capsule a=half_segment b=r | box half extents | scaling a=s | binary a=smoothness b=0.25/a */
-    uint32_t reserved[4];
+    float a, b, c; /* sphere a=r | capsule a=half_segment b=r | box half extents | scaling a=s | binary a=smoothness b=0.25/a
+                      | noise a=noise_scale b=frequency c=lacunarity */
+    uint32_t reserved[4]; /* noise: [0] persistence (f32 bits), [1] octaves, [2] seed */
 } ivx_sdf_processed_node;
 
 /* Per-chunk state (VoxelChunk / NonUniformVoxelChunk, object.rs:95-126,163-188; split_detection.rs:82-88). 8 bytes. */
@@ -512,6 +516,10 @@ int ivx_comm_selftest(ivx_ctx*);
  * with a short correctly-rounding sequence instead of the general f32 division; this runs both over the whole operand set (every pair of
  * decoded i8 distances of opposite sign, 1 / n for n = 1..256) on the device and returns the number of results that differ: must be 0. */
 int ivx_selftest_mesher_division(ivx_ctx*, uint32_t* mismatches);
+/* Developer export (tests): evaluates the library's noise functions (impact_amd/csrc/noise.hpp) at n given points — which = 0: fbm3 at
+ * points (x, y, z), params = {frequency, lacunarity, gain, octaves (u32 bits), seed (u32 bits)}; which = 1: simplex4 at points (x, y, z, w),
+ * params[4] = seed (u32 bits), the rest unused. Host arrays. On the device of `ctx`; ctx = NULL runs the host build of the same functions. */
+int ivx_noise_eval(ivx_ctx* ctx, int which, const float* params, const float* points, size_t n, float* out);
 int ivx_slab_create(ivx_comm*, ivx_grid* slab_grid, int rank, ivx_slab** out);
 void ivx_slab_destroy(ivx_slab*);
 int ivx_slabs_step_enqueue(ivx_slab** slabs, size_t n);

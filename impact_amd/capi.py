@@ -178,7 +178,7 @@ EXPORTED_SYMBOLS = [
     "ivx_inertia",
     "ivx_label_regions", "ivx_region_labels_download", "ivx_regions_describe", "ivx_split_off_smallest_region", "ivx_split_off_all", "ivx_clip_polyhedron", "ivx_copy_polyhedra", "ivx_mesh_sync", "ivx_mesh_export", "ivx_mesh_generation", "ivx_mesh_import_open", "ivx_mesh_import_close", "ivx_mesh_modifications", "ivx_mesh_report_synchronized", "ivx_absorb_sphere", "ivx_absorb_capsule", "ivx_absorb_mutual", "ivx_absorb_sphere_enqueue", "ivx_absorb_capsule_enqueue", "ivx_absorb_collect", "ivx_grid_set_early_mesh_needs", "ivx_mesh_sync_enqueue", "ivx_mesh_sync_collect",
     "ivx_many_begin", "ivx_many_flush", "ivx_many_stats", "ivx_voxel_step_many", "ivx_absorb_sphere_many", "ivx_absorb_capsule_many", "ivx_mesh_sync_many", "ivx_offset_reference_point", "ivx_apply_updated_inertial_properties", "ivx_extracted_object_dynamics", "ivx_handle_voxel_object_after_removing_voxels", "ivx_sphere_voxel_object_contacts", "ivx_plane_voxel_object_contacts", "ivx_capsule_voxel_object_contacts", "ivx_voxel_object_contacts_many", "ivx_collision_probes_recompute", "ivx_collision_probes_sync", "ivx_collision_probes_sync_many", "ivx_collision_probes_download", "ivx_mutual_voxel_object_contacts", "ivx_mutual_voxel_object_contacts_many",
-    "ivx_grid_set_sdf_program", "ivx_grid_set_densities", "ivx_voxel_step", "ivx_voxel_step_enqueue", "ivx_voxel_step_collect", "ivx_grid_set_stage_timing", "ivx_grid_set_sample_ahead",
+    "ivx_grid_set_sdf_program", "ivx_grid_set_densities", "ivx_grid_set_voxel_type_noise", "ivx_voxel_step", "ivx_voxel_step_enqueue", "ivx_voxel_step_collect", "ivx_grid_set_stage_timing", "ivx_grid_set_sample_ahead",
     "ivx_halo_pack_enqueue", "ivx_halo_unpack_enqueue", "ivx_halo_pack_both_enqueue", "ivx_region_face_labels_enqueue", "ivx_region_face_pairs_enqueue",
     "ivx_step_record_words", "ivx_step_record_enqueue", "ivx_slab_remesh_enqueue",
     "ivx_halo_bytes", "ivx_halo_pack", "ivx_halo_unpack", "ivx_halo_clear",
@@ -187,7 +187,7 @@ EXPORTED_SYMBOLS = [
     "ivx_world_set_spherical_joints", "ivx_world_step", "ivx_world_step_enqueue", "ivx_world_prepare", "ivx_world_advance_momenta", "ivx_world_solve", "ivx_world_advance_configurations",
     "ivx_impact_fracturing_config_default", "ivx_generate_impact_fracture_points", "ivx_delaunay_construct", "ivx_delaunay_destroy", "ivx_delaunay_counts",
     "ivx_delaunay_download", "ivx_delaunay_aabb", "ivx_delaunay_displace_vertices", "ivx_delaunay_boundary_face_planes", "ivx_voronoi_polyhedron", "ivx_voronoi_bounded_aabb",
-    "ivx_comm_unique_id", "ivx_comm_init", "ivx_comm_init_local", "ivx_comm_init_ipc", "ivx_comm_info", "ivx_comm_set_local_copies", "ivx_comm_selftest", "ivx_selftest_mesher_division", "ivx_noise_eval", "ivx_comm_destroy", "ivx_slab_create", "ivx_slab_destroy",
+    "ivx_comm_unique_id", "ivx_comm_init", "ivx_comm_init_local", "ivx_comm_init_ipc", "ivx_comm_info", "ivx_comm_set_local_copies", "ivx_comm_selftest", "ivx_selftest_mesher_division", "ivx_noise_eval", "ivx_voxel_types_eval", "ivx_comm_destroy", "ivx_slab_create", "ivx_slab_destroy",
     "ivx_slabs_step_enqueue", "ivx_slabs_step_collect", "ivx_slab_region_map",
     "ivx_world_set_solver_groups", "ivx_world_solver_info", "ivx_world_contact_state",
 ]
@@ -260,6 +260,7 @@ def lib():
         "ivx_sdf_compile": (i32, [vp, sz, u32, vp, sz, C.POINTER(sz), vp, C.POINTER(u32)]),
         "ivx_sdf_grid_shape": (i32, [vp, vp, vp]),
         "ivx_noise_eval": (i32, [vp, i32, vp, vp, sz, vp]),
+        "ivx_voxel_types_eval": (i32, [vp, u32, f32, f32, u32, vp, vp]),
         "ivx_sdf_sample": (i32, [vp, vp, sz, u32, vp, vp, C.c_uint8]),
         "ivx_derive_state": (i32, [vp]),
         "ivx_occupied_ranges": (i32, [vp, vp]),
@@ -276,6 +277,7 @@ def lib():
         "ivx_copy_polyhedra": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
         "ivx_grid_set_sdf_program": (i32, [vp, vp, sz, u32, vp, vp, C.c_uint8]),
         "ivx_grid_set_densities": (i32, [vp, vp]),
+        "ivx_grid_set_voxel_type_noise": (i32, [vp, u32, f32, f32, u32]),
         "ivx_voxel_step": (i32, [vp, u32, vp]),
         "ivx_voxel_step_enqueue": (i32, [vp, u32]),
         "ivx_voxel_step_collect": (i32, [vp, vp]),

@@ -3343,6 +3343,22 @@ int ivx_grid_set_sdf_program(ivx_grid* g, const ivx_sdf_processed_node* nodes, s
     return IVX_OK;
 }
 
+int ivx_grid_set_voxel_type_noise(ivx_grid* g, uint32_t n_voxel_types, float noise_frequency, float voxel_type_frequency, uint32_t seed) {
+    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_grid_set_voxel_type_noise: null grid");
+    IVX_REQUIRE(n_voxel_types <= 255u, IVX_ERR_INVALID, "ivx_grid_set_voxel_type_noise: %u voxel types (at most 255: 255 is the dummy type)", n_voxel_types);
+    IVX_REQUIRE(std::isfinite(noise_frequency) && std::isfinite(voxel_type_frequency), IVX_ERR_INVALID, "ivx_grid_set_voxel_type_noise: non-finite frequency");
+    if (g->vt_n == 0u && n_voxel_types == 0u) return IVX_OK;  // (SameVoxelTypeGenerator before and after: the parameters say nothing)
+    {  // the records a pre-pass that runs ahead has parked carry the type of the generator it ran under: wait for it, drop what it wrote
+        const int rc_a = ivx_sampler_ahead_cancel(g);
+        if (rc_a) return rc_a;
+    }
+    g->vt_n = n_voxel_types;
+    g->vt_noise_freq = noise_frequency;
+    g->vt_type_freq = voxel_type_frequency;
+    g->vt_seed = seed;
+    return IVX_OK;
+}
+
 int ivx_grid_set_densities(ivx_grid* g, const float densities[256]) {
     IVX_REQUIRE(g && densities, IVX_ERR_INVALID, "ivx_grid_set_densities: null argument");
     // (stream-ordered, no wait: the copy reads the grid's own host copy of the table, which lives as long as the grid — a table set again

@@ -157,6 +157,7 @@ struct ivx_grid {
     int planes_compact;  // planes of Void/Uniform chunks may be stale (see ivx_ensure_dense)
     // the sampler wrote `chunk_signs` and `kface` of every chunk it gave planes, all voxels of such a chunk have the type `signs_type`, and
     // nothing has rewritten voxels since (ivx_planes_touched): the derive sweep then reads those 2 + 4 bytes per row instead of the planes
+    // (a sample with gradient-noise voxel types of two or more types leaves it clear: the voxels' types are in the type plane alone)
     int signs_current;
     uint8_t signs_type;
     // a box sweep after an edit (ivx_launch_derive_box) has changed chunk kinds since the active list was made: whoever walks the list without
@@ -195,6 +196,10 @@ struct ivx_grid {
     float prog_center[3];
     uint8_t prog_type;
     uint8_t prog_noise;  // the resident program holds a noise node (kind 6): the sampler's noise forms run it
+    // voxel type generator of the sampler (ivx_grid_set_voxel_type_noise): vt_n = 0 SameVoxelTypeGenerator (the voxel_type argument of the sample
+    // calls), 1..255 GradientNoiseVoxelTypeGenerator over that many types (k_voxel_type_noise behind the evaluator launches, sdf_sample.hip)
+    uint32_t vt_n, vt_seed;
+    float vt_noise_freq, vt_type_freq;
     // lengths of the sampler's three evaluation lists under the resident program, as the last collected step with a derive sweep reported them
     // (`eval_len_valid`; a function of the program and the grid alone): a class whose list is known to be empty is not launched
     uint32_t eval_len[3];

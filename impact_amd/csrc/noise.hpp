@@ -131,6 +131,25 @@ IVX_NOISE_FN float simplex4(float x, float y, float z, float w, uint32_t seed) {
     return 27.0f * sum;
 }
 
+// Gradient-noise voxel types (GradientNoiseVoxelTypeGenerator, voxel_type.rs:125-168): one 4D noise value per candidate type, the
+// fourth dimension being the type index, and the voxel takes the first type whose value is greatest.
+// A voxel's coordinate along one axis: (o + (float)i) * noise_frequency, o the chunk origin's component in root space.
+IVX_NOISE_FN float type_coord(float o, uint32_t i, float noise_frequency) { return (o + (float)i) * noise_frequency; }
+// y, z, w: type_coord of the voxel's k, j, i (dimensions reversed, as the reference hands them to its noise builder); x = (float)t *
+// voxel_type_frequency. best = v_0; for t = 1 .. n - 1: v_t > best replaces it (strict: the first maximum stays, a NaN never wins).
+IVX_NOISE_FN uint32_t type_argmax4(float y, float z, float w, uint32_t n, float voxel_type_frequency, uint32_t seed) {
+    float best = simplex4((float)0u * voxel_type_frequency, y, z, w, seed);
+    uint32_t type = 0u;
+    for (uint32_t t = 1u; t < n; ++t) {
+        const float v = simplex4((float)t * voxel_type_frequency, y, z, w, seed);
+        if (v > best) {
+            best = v;
+            type = t;
+        }
+    }
+    return type;
+}
+
 // Fractal Brownian motion: x *= freq (y, z alike), amp = 1, sum = 0; per octave sum = sum + simplex3(x, y, z, seed) * amp, then
 // x *= lacunarity (y, z alike), amp *= gain. The seed is the same for every octave.
 IVX_NOISE_FN float fbm3(float x, float y, float z, uint32_t octaves, float freq, float lacunarity, float gain, uint32_t seed) {

@@ -17,6 +17,8 @@
 // loop, which keeps results bit-identical (no FMA: built with -ffp-contract=off; IEEE sqrt/div).
 // The row is written back as one 16-byte store per plane per thread (4 KiB contiguous per workgroup).
 // HBM traffic: 2 B/voxel written (sdf + type), nothing read.
+#include <cmath>
+
 #include "ivx_internal.hpp"
 #include "noise.hpp"
 #include "table_roles.hpp"
@@ -1582,6 +1584,98 @@ __global__ __launch_bounds__(256) void k_classify(uint32_t n_chunks, int8_t* __r
     classify_and_store(sd, t, types_uniform, first_type, sdf, type, info, chunk, tid, false, 0, false, s_votes);
 }
 
+// ---- gradient-noise voxel types (GradientNoiseVoxelTypeGenerator, voxel_type.rs:97-169; SDFVoxelGenerator::generate_chunk, generation.rs:293-371) ----
+// The reference types every voxel of a chunk that has a non-empty voxel — the empty ones and those beyond the generator's grid included —
+// and leaves the dummy type in every other chunk; a chunk is Uniform only if every voxel is maximally inside AND all 4096 types are equal
+// (object.rs:1906-1953). The noise values are this library's (noise.hpp), like those of SDF node kind 6.
+struct TypeNoiseParams {
+    uint32_t cy, cz, x_off, n;
+    float shifted_center[3];
+    float noise_freq, type_freq;
+    uint32_t seed;
+};
+
+// the 16 types of row (i, j) of the chunk whose root-space origin is (ox, oy, oz), k = 0 in the lowest byte. One voxel after the other,
+// the loops rolled: the work is VALU instructions alone (16 * n noise values a row), which the waves of a SIMD keep issuing without
+// help from unrolling, and the rolled form stays within 64 VGPRs
+__host__ __device__ inline uint4 type_noise_row(float ox, float oy, float oz, uint32_t i, uint32_t j, uint32_t n, float noise_freq, float type_freq, uint32_t seed) {
+    const float w = ivx_noise::type_coord(ox, i, noise_freq), z = ivx_noise::type_coord(oy, j, noise_freq);
+    uint32_t r0 = 0u, r1 = 0u, r2 = 0u, r3 = 0u;
+#pragma unroll 1
+    for (uint32_t q = 0; q < 4u; ++q) {
+        uint32_t word = 0u;
+#pragma unroll 1
+        for (uint32_t kk = 0; kk < 4u; ++kk)
+            word |= ivx_noise::type_argmax4(ivx_noise::type_coord(oz, 4u * q + kk, noise_freq), z, w, n, type_freq, seed) << (8u * kk);
+        r0 = q == 0u ? word : r0;  // (selects, not an indexed array: the words stay in registers)
+        r1 = q == 1u ? word : r1;
+        r2 = q == 2u ? word : r2;
+        r3 = q == 3u ? word : r3;
+    }
+    return make_uint4(r0, r1, r2, r3);
+}
+
+// The type pass of the sample stage, behind the evaluator launches: one workgroup per chunk, one thread per (i, j) row as in the evaluator.
+//   Void, or NonUniform with CF_ONLY_EMPTY: nothing (the dummy type stays).
+//   NonUniform: the type plane and the two k-face type rows of `kface`.
+//   Uniform (settled by the pre-pass or by the evaluator; no planes under compact planes): all types equal -> the record's uniform_type;
+//   mixed -> the chunk becomes NonUniform: sdf plane (-128), type plane, sign rows (all negative), the four k-face rows, the record.
+__global__ __launch_bounds__(256) void k_voxel_type_noise(TypeNoiseParams p, int8_t* __restrict__ sdf_out, uint8_t* __restrict__ type_out,
+                                                          ivx_chunk_info* __restrict__ info, uint16_t* __restrict__ signs_out, uint8_t* __restrict__ kface_out) {
+    __shared__ uint32_t s_first, s_votes[4];
+    const uint32_t tid = threadIdx.x, chunk = blockIdx.x;
+    const ivx_chunk_info rec = info[chunk];
+    const uint32_t kind = rec.kind;
+    if (kind == KIND_VOID || (kind == KIND_NONUNIFORM && (rec.flags & CF_ONLY_EMPTY))) return;
+    const uint32_t ck = chunk % p.cz, cj = (chunk / p.cz) % p.cy, ci = chunk / (p.cz * p.cy);
+    const float ox = (float)((ci + p.x_off) * 16u) - p.shifted_center[0], oy = (float)(cj * 16u) - p.shifted_center[1], oz = (float)(ck * 16u) - p.shifted_center[2];
+    const uint4 types = type_noise_row(ox, oy, oz, tid >> 4, tid & 15u, p.n, p.noise_freq, p.type_freq, p.seed);
+    const size_t base = (size_t)chunk * IVX_CHUNK_VOXELS + (size_t)tid * 16;
+    uint8_t* kf = kface_out + (size_t)chunk * 1024 + tid;
+    if (kind == KIND_NONUNIFORM) {
+        *reinterpret_cast<uint4*>(type_out + base) = types;
+        kf[512] = (uint8_t)(types.x & 0xFFu);
+        kf[768] = (uint8_t)(types.w >> 24);
+        return;
+    }
+    // (`kind` is the same for the whole workgroup: the barriers below are met by all of it, and the record is rewritten behind them)
+    if (tid == 0u) s_first = types.x & 0xFFu;
+    __syncthreads();
+    const uint32_t first = s_first, ft = first * 0x01010101u;
+    const bool same = types.x == ft && types.y == ft && types.z == ft && types.w == ft;
+    const unsigned long long b = __ballot(same);
+    if ((tid & 63u) == 0u) s_votes[tid >> 6] = b == ~0ull ? 1u : 0u;
+    __syncthreads();
+    if ((s_votes[0] & s_votes[1]) & (s_votes[2] & s_votes[3])) {
+        if (tid == 0u) info[chunk].uniform_type = (uint8_t)first;
+        return;
+    }
+    *reinterpret_cast<uint4*>(sdf_out + base) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+    *reinterpret_cast<uint4*>(type_out + base) = types;
+    signs_out[(size_t)chunk * 256 + tid] = (uint16_t)0xFFFFu;
+    kf[0] = (uint8_t)0x80u;
+    kf[256] = (uint8_t)0x80u;
+    kf[512] = (uint8_t)(types.x & 0xFFu);
+    kf[768] = (uint8_t)(types.w >> 24);
+    if (tid == 0u) {
+        ivx_chunk_info ci_;
+        ci_.kind = ci_.gen_kind = (uint8_t)KIND_NONUNIFORM;
+        ci_.flags = 0;
+        ci_.uniform_type = 0;
+        ci_.face_dist = 0;
+        ci_.region_count = 0;
+        ci_.boundary_region_count = 0;
+        info[chunk] = ci_;
+    }
+}
+
+// developer export (ivx_voxel_types_eval): the rows of one chunk
+__global__ __launch_bounds__(256) void k_voxel_types_eval(TypeNoiseParams p, uint8_t* __restrict__ out) {
+    const uint32_t tid = threadIdx.x;
+    *reinterpret_cast<uint4*>(out + (size_t)tid * 16) =
+        type_noise_row(p.shifted_center[0], p.shifted_center[1], p.shifted_center[2], tid >> 4, tid & 15u, p.n, p.noise_freq, p.type_freq, p.seed);
+}
+
 }  // namespace
 
 int ivx_sampler_buffers(ivx_grid* g) {
@@ -1656,6 +1750,9 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
 #ifdef IVX_WG_TRACE
     p.trace = reinterpret_cast<unsigned long long*>(g->chunk_moments);
 #endif
+    // (gradient-noise voxel types, ivx_grid_set_voxel_type_noise: the argument is ignored; the evaluator writes type 0 — all there is to a
+    // generator of one type — and the type pass below puts the noise types of two or more in its place)
+    if (g->vt_n) voxel_type = 0;
     p.voxel_type = voxel_type;
     size_t lds = (size_t)(stack_size ? stack_size : 1) * IVX_CHUNK_VOXELS * sizeof(float);
     IVX_REQUIRE(lds <= 150 * 1024, IVX_ERR_CAPACITY, "SDF graph needs a forward stack of %u blocks (at most 9 fit the 160 KiB LDS)", stack_size);
@@ -1797,6 +1894,16 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
                                    g->chunk_signs, g->kface, sh, g->n_chunks, sh ? first_presets : no_presets);
         }
     }
+    const bool type_noise = g->vt_n >= 2u;
+    if (type_noise) {
+        // behind the evaluator launches: every chunk record is in place (those a pre-pass that ran ahead parked in the shadow array were
+        // committed by the first of them)
+        TypeNoiseParams tp;
+        tp.cy = g->cc[1], tp.cz = g->cc[2], tp.x_off = g->x_off, tp.n = g->vt_n;
+        for (int d = 0; d < 3; ++d) tp.shifted_center[d] = shifted_center[d];
+        tp.noise_freq = g->vt_noise_freq, tp.type_freq = g->vt_type_freq, tp.seed = g->vt_seed;
+        IVX_KLAUNCH(k_voxel_type_noise, dim3(g->n_chunks), dim3(256), 0, g->ctx->stream, tp, g->sdf, g->type, g->info, g->chunk_signs, g->kface);
+    }
     IVX_HIP_CHECK(hipGetLastError());
     g->ahead_wanted = (g->ahead_on && ahead_fits) ? 1 : 0;
     // (everything enqueued before this call has been collected: the sampler's other set of buffers is idle and the pre-pass needs no place in
@@ -1805,9 +1912,10 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
         const int rc_a = ivx_sampler_launch_ahead(g, false);
         if (rc_a) return rc_a;
     }
-    // every chunk that has planes now has its sign rows and k-face bytes too, and one type throughout (SameVoxelTypeGenerator): the derive
-    // sweep may work from those (until something else rewrites voxels: ivx_planes_touched)
-    g->signs_current = 1;
+    // every chunk that has planes now has its sign rows and k-face bytes too, and one type throughout (SameVoxelTypeGenerator, or noise
+    // types of one type): the derive sweep may work from those (until something else rewrites voxels: ivx_planes_touched). With noise types
+    // of two or more the types are in the type plane alone, and the sweep and the mesher run their general forms.
+    g->signs_current = type_noise ? 0 : 1;
     g->signs_type = voxel_type;
     return IVX_OK;
 }
@@ -1842,7 +1950,7 @@ int ivx_sampler_launch_ahead(ivx_grid* g, bool behind_stream) {
 #ifdef IVX_WG_TRACE
     p.trace = reinterpret_cast<unsigned long long*>(g->chunk_moments);
 #endif
-    p.voxel_type = g->prog_type;
+    p.voxel_type = g->vt_n ? 0u : (uint32_t)g->prog_type;
     const uint32_t words = (g->prog_n + 31u) / 32u > 0u ? (g->prog_n + 31u) / 32u : 1u;
     const uint32_t sx = (g->cc[0] + SUPER - 1) / SUPER, sy = (g->cc[1] + SUPER - 1) / SUPER, sz = (g->cc[2] + SUPER - 1) / SUPER;
     if (behind_stream) {
@@ -1922,6 +2030,37 @@ int ivx_noise_eval(ivx_ctx* ctx, int which, const float* params, const float* po
     IVX_KLAUNCH(k_noise_eval, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, which, q, d_pts, n, d_out);
     IVX_HIP_CHECK(hipGetLastError());
     IVX_HIP_CHECK(ivx_memcpy_async(out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(ctx->stream));
+    return IVX_OK;
+}
+
+int ivx_voxel_types_eval(ivx_ctx* ctx, uint32_t n_voxel_types, float noise_frequency, float voxel_type_frequency, uint32_t seed, const float chunk_origin[3],
+                         uint8_t out[4096]) {
+    IVX_REQUIRE(chunk_origin && out, IVX_ERR_INVALID, "ivx_voxel_types_eval: null argument");
+    IVX_REQUIRE(n_voxel_types >= 1u && n_voxel_types <= 255u, IVX_ERR_INVALID, "ivx_voxel_types_eval: %u voxel types (1 .. 255)", n_voxel_types);
+    IVX_REQUIRE(std::isfinite(noise_frequency) && std::isfinite(voxel_type_frequency), IVX_ERR_INVALID, "ivx_voxel_types_eval: non-finite frequency");
+    if (!ctx) {  // the host build of the same function
+        for (uint32_t r = 0; r < 256u; ++r) {
+            const uint4 t = type_noise_row(chunk_origin[0], chunk_origin[1], chunk_origin[2], r >> 4, r & 15u, n_voxel_types, noise_frequency, voxel_type_frequency, seed);
+            std::memcpy(out + (size_t)r * 16, &t, 16);
+        }
+        return IVX_OK;
+    }
+    TypeNoiseParams tp;
+    tp.cy = tp.cz = 1u, tp.x_off = 0u, tp.n = n_voxel_types;
+    for (int d = 0; d < 3; ++d) tp.shifted_center[d] = chunk_origin[d];  // (k_voxel_types_eval takes the origin itself from here)
+    tp.noise_freq = noise_frequency, tp.type_freq = voxel_type_frequency, tp.seed = seed;
+    struct Buffer {  // freed on every return
+        uint8_t* p = nullptr;
+        ~Buffer() {
+            if (p) (void)hipFree(p);
+        }
+    } b;
+    IVX_HIP_CHECK(hipMalloc(&b.p, IVX_CHUNK_VOXELS));
+    uint8_t* d_out = b.p;
+    IVX_KLAUNCH(k_voxel_types_eval, dim3(1), dim3(256), 0, ctx->stream, tp, d_out);
+    IVX_HIP_CHECK(hipGetLastError());
+    IVX_HIP_CHECK(ivx_memcpy_async(out, d_out, IVX_CHUNK_VOXELS, hipMemcpyDeviceToHost, ctx->stream));
     IVX_HIP_CHECK(ivx_stream_sync(ctx->stream));
     return IVX_OK;
 }

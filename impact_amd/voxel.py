@@ -93,16 +93,47 @@ class SDFGenerator:
         return len(self.nodes) == 0
 
 
-class SDFVoxelGenerator:
-    """`SDFVoxelGenerator::new(voxel_extent, sdf_generator, SameVoxelTypeGenerator(voxel_type))`."""
+class SameVoxelTypeGenerator:
+    """`SameVoxelTypeGenerator` (generation/voxel_type.rs:18-25, 88-96): every voxel gets the one type."""
 
-    def __init__(self, voxel_extent: float, sdf_generator: SDFGenerator | SDFGraph, voxel_type: int = 0):
+    def __init__(self, voxel_type: int = 0):
+        assert 0 <= int(voxel_type) <= 255
+        self.voxel_type = int(voxel_type)
+
+    def _noise_args(self):
+        return (0, 0.0, 0.0, 0)
+
+
+class GradientNoiseVoxelTypeGenerator:
+    """`GradientNoiseVoxelTypeGenerator` (generation/voxel_type.rs:27-36, 97-169): a 4D gradient noise value per candidate type, the
+    voxel takes the index of the greatest. The reference's list of voxel types enters by its length alone."""
+
+    def __init__(self, n_voxel_types: int, noise_frequency: float, voxel_type_frequency: float, seed: int):
+        self.n_voxel_types = int(n_voxel_types)
+        self.noise_frequency = float(noise_frequency)
+        self.voxel_type_frequency = float(voxel_type_frequency)
+        self.seed = int(seed) & 0xFFFFFFFF
+        self.voxel_type = 0  # (the sample calls' voxel_type argument, ignored under this generator)
+
+    def _noise_args(self):
+        return (self.n_voxel_types, self.noise_frequency, self.voxel_type_frequency, self.seed)
+
+
+class SDFVoxelGenerator:
+    """`SDFVoxelGenerator::new(voxel_extent, sdf_generator, voxel_type_generator)`; an int as the third argument stands for
+    `SameVoxelTypeGenerator(voxel_type)`."""
+
+    def __init__(self, voxel_extent: float, sdf_generator: SDFGenerator | SDFGraph,
+                 voxel_type: "int | SameVoxelTypeGenerator | GradientNoiseVoxelTypeGenerator" = 0):
         assert voxel_extent > 0.0
         if isinstance(sdf_generator, SDFGraph):
             sdf_generator = SDFGenerator(sdf_generator)
         self.voxel_extent = float(voxel_extent)
         self.sdf_generator = sdf_generator
-        self.voxel_type = int(voxel_type)
+        if not isinstance(voxel_type, (SameVoxelTypeGenerator, GradientNoiseVoxelTypeGenerator)):
+            voxel_type = SameVoxelTypeGenerator(int(voxel_type))
+        self.voxel_type_generator = voxel_type
+        self.voxel_type = voxel_type.voxel_type
         shape = np.zeros(3, dtype=np.uint32)
         centre = np.zeros(3, dtype=np.float32)
         check(capi.lib().ivx_sdf_grid_shape(ptr(sdf_generator.domain), ptr(shape), ptr(centre)))
@@ -159,8 +190,14 @@ class VoxelObject:
         obj.sample(generator)
         return obj
 
+    def set_voxel_type_generator(self, voxel_type_generator):
+        """`ivx_grid_set_voxel_type_noise`: the voxel type generator of every later sample of this object"""
+        n, nf, vtf, seed = voxel_type_generator._noise_args()
+        check(capi.lib().ivx_grid_set_voxel_type_noise(self.h, n, nf, vtf, seed))
+
     def sample(self, generator: SDFVoxelGenerator):
         g = generator.sdf_generator
+        self.set_voxel_type_generator(generator.voxel_type_generator)
         shape = np.asarray(generator.grid_shape(), dtype=np.uint32)
         check(capi.lib().ivx_sdf_sample(self.h, ptr(g.nodes) if len(g.nodes) else None, len(g.nodes), g.required_forward_stack_size,
                                         ptr(shape), ptr(generator.shifted_grid_center), generator.voxel_type))
@@ -184,6 +221,7 @@ class VoxelObject:
     # ---- whole step over resident inputs ----------------------------------------------------
     def set_sdf_program(self, generator: SDFVoxelGenerator):
         g = generator.sdf_generator
+        self.set_voxel_type_generator(generator.voxel_type_generator)
         shape = np.asarray(generator.grid_shape(), dtype=np.uint32)
         check(capi.lib().ivx_grid_set_sdf_program(self.h, ptr(g.nodes) if len(g.nodes) else None, len(g.nodes), g.required_forward_stack_size,
                                                   ptr(shape), ptr(generator.shifted_grid_center), generator.voxel_type))

@@ -100,12 +100,31 @@ private:
     float domain_[6] = {0, 0, 0, 0, 0, 0};
     uint32_t stack_size_ = 0;
 };
-class SDFVoxelGenerator {  // generation.rs:204-258 with a SameVoxelTypeGenerator
+// the two voxel type generators (generation/voxel_type.rs:18-36): what ivx_grid_set_voxel_type_noise is handed
+struct SameVoxelTypeGenerator {
+    uint8_t voxel_type = 0;
+};
+struct GradientNoiseVoxelTypeGenerator {  // (the reference's list of voxel types enters by its length alone)
+    uint32_t n_voxel_types = 1;
+    float noise_frequency = 0.0f;
+    float voxel_type_frequency = 0.0f;
+    uint32_t seed = 0;
+};
+class SDFVoxelGenerator {  // generation.rs:204-258
 public:
     SDFVoxelGenerator(float voxel_extent, SDFGenerator generator, uint8_t voxel_type = 0)
         : extent_(voxel_extent), gen_(std::move(generator)), type_(voxel_type) {
         check(ivx_sdf_grid_shape(gen_.domain(), shape_, center_));
     }
+    SDFVoxelGenerator(float voxel_extent, SDFGenerator generator, SameVoxelTypeGenerator types)
+        : SDFVoxelGenerator(voxel_extent, std::move(generator), types.voxel_type) {}
+    SDFVoxelGenerator(float voxel_extent, SDFGenerator generator, GradientNoiseVoxelTypeGenerator types)
+        : SDFVoxelGenerator(voxel_extent, std::move(generator), (uint8_t)0) {
+        noise_ = types;
+        noise_on_ = true;
+    }
+    // n_voxel_types = 0: SameVoxelTypeGenerator(voxel_type())
+    GradientNoiseVoxelTypeGenerator type_noise() const { return noise_on_ ? noise_ : GradientNoiseVoxelTypeGenerator{0, 0.0f, 0.0f, 0}; }
     float voxel_extent() const { return extent_; }
     std::array<uint32_t, 3> grid_shape() const { return {shape_[0], shape_[1], shape_[2]}; }
     std::array<uint32_t, 3> chunk_counts() const { return {(shape_[0] + 15) / 16, (shape_[1] + 15) / 16, (shape_[2] + 15) / 16}; }
@@ -118,6 +137,8 @@ private:
     float extent_;
     SDFGenerator gen_;
     uint8_t type_;
+    GradientNoiseVoxelTypeGenerator noise_;
+    bool noise_on_ = false;
     uint32_t shape_[3] = {0, 0, 0};
     float center_[3] = {0, 0, 0};
 };
@@ -153,6 +174,8 @@ public:
     static std::unique_ptr<VoxelObject> generate_without_derived_state(Context& ctx, const SDFVoxelGenerator& gen) {
         auto o = std::make_unique<VoxelObject>(ctx, gen.chunk_counts(), gen.voxel_extent());
         const auto& n = gen.sdf_generator().nodes();
+        const GradientNoiseVoxelTypeGenerator tn = gen.type_noise();
+        check(ivx_grid_set_voxel_type_noise(o->g_, tn.n_voxel_types, tn.noise_frequency, tn.voxel_type_frequency, tn.seed));
         check(ivx_sdf_sample(o->g_, n.data(), n.size(), gen.sdf_generator().stack_size(), gen.shape(), gen.shifted_grid_center(), gen.voxel_type()));
         return o;
     }

@@ -365,6 +365,15 @@ int ivx_mesh_sync_many(ivx_grid* const* grids, size_t n, const uint8_t* const* i
 int ivx_grid_set_sdf_program(ivx_grid*, const ivx_sdf_processed_node* nodes, size_t n_nodes, uint32_t stack_size,
                              const uint32_t grid_shape[3], const float shifted_grid_center[3], uint8_t voxel_type);
 int ivx_grid_set_densities(ivx_grid*, const float densities[256]);
+/* voxel type generator of the grid's sampler: n_voxel_types = 0 -> SameVoxelTypeGenerator (the voxel_type argument of ivx_sdf_sample /
+ * ivx_grid_set_sdf_program, the default); 1..255 -> GradientNoiseVoxelTypeGenerator (voxel_type.rs:97-169), the voxel_type argument is
+ * then ignored. Holds for every later ivx_sdf_sample and sample stage of the grid until set again.
+ * The type of a voxel is the index t < n_voxel_types of the greatest of the noise values simplex4(t * voxel_type_frequency, z * f, y * f,
+ * x * f, seed), f = noise_frequency, (x, y, z) the voxel's indices relative to the shifted grid centre (the first maximum; the seed's bits
+ * as the reference's `as i32` keeps them). The construction is the reference's, the noise values are this library's
+ * (impact_amd/csrc/noise.hpp), whose coordinate range applies: |coordinate * frequency| < 2^31.
+ * IVX_ERR_INVALID for n_voxel_types > 255 (255 is VoxelType::dummy()) or a non-finite frequency; the generator then stays as it was. */
+int ivx_grid_set_voxel_type_noise(ivx_grid*, uint32_t n_voxel_types, float noise_frequency, float voxel_type_frequency, uint32_t seed);
 int ivx_voxel_step(ivx_grid*, uint32_t stages, ivx_step_result* out);
 /* The same in two halves: enqueue launches the kernels of `stages` and returns without waiting (several calls may follow
  * each other, e.g. the phases of the multi-GPU protocol with halo traffic in between); collect waits once, fetches the
@@ -520,6 +529,11 @@ int ivx_selftest_mesher_division(ivx_ctx*, uint32_t* mismatches);
  * points (x, y, z), params = {frequency, lacunarity, gain, octaves (u32 bits), seed (u32 bits)}; which = 1: simplex4 at points (x, y, z, w),
  * params[4] = seed (u32 bits), the rest unused. Host arrays. On the device of `ctx`; ctx = NULL runs the host build of the same functions. */
 int ivx_noise_eval(ivx_ctx* ctx, int which, const float* params, const float* points, size_t n, float* out);
+/* Developer export (tests), beside ivx_noise_eval: the 4096 gradient-noise voxel types (ivx_grid_set_voxel_type_noise, n_voxel_types 1..255)
+ * of the chunk whose root-space origin is given, i << 8 | j << 4 | k order. On the device of ctx; ctx = NULL runs the host build of the
+ * same function. */
+int ivx_voxel_types_eval(ivx_ctx* ctx, uint32_t n_voxel_types, float noise_frequency, float voxel_type_frequency, uint32_t seed,
+                         const float chunk_origin[3], uint8_t out[4096]);
 int ivx_slab_create(ivx_comm*, ivx_grid* slab_grid, int rank, ivx_slab** out);
 void ivx_slab_destroy(ivx_slab*);
 int ivx_slabs_step_enqueue(ivx_slab** slabs, size_t n);

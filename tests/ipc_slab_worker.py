@@ -17,11 +17,17 @@ def main():
     from impact_amd.distributed import NativeComm, NativeSlabStepper, native_step
     from impact_amd.voxel import Context, VoxelObjectMesh
 
-    graph = {"asteroid": scenes.asteroid_scene, "fracture": scenes.fracture_scene}[scene]()
-    dens = np.linspace(0.5, 2.0, 256).astype(np.float32)
+    voxel_type = 0
+    if scene == "typed_sphere":  # (four gradient-noise types on the sphere of radius 60, densities 1 + t: tests/typed_util.py)
+        import typed_util as tu
+
+        graph, dens, voxel_type = tu.sphere60(), tu.DENSITIES, tu.noise_generator(tu.SPHERE60_NOISE)
+    else:
+        graph = {"asteroid": scenes.asteroid_scene, "fracture": scenes.fracture_scene}[scene]()
+        dens = np.linspace(0.5, 2.0, 256).astype(np.float32)
     ctx = Context(0)
     comm = NativeComm(ctx, world, rank, ipc_name=name)
-    st = NativeSlabStepper(ctx, comm, graph, dens, rank)
+    st = NativeSlabStepper(ctx, comm, graph, dens, rank, 1.0, voxel_type)
     for _ in range(steps):  # (the second step starts from a dirty state: ghosts, labels, mesh buffers, sequence numbers)
         r = native_step([st])[0]
     sdf, typ, flg, lab, info = st.obj.download()

@@ -39,29 +39,51 @@ def assert_synced_meshes_equal(om: ol.OracleMesh, gm):
         np.testing.assert_array_equal(im[ioff:ioff + icnt], om.index_materials[ioff:ioff + icnt])
 
 
-@pytest.mark.parametrize("case", ["bites", "cut_through", "capsule_then_sphere", "eaten_whole"])
-def test_sync_after_edits(ctx, case):
-    o, g = both(ctx, scenes.sphere_scene(30.0))
+SYNC_CASES = ["bites", "cut_through", "capsule_then_sphere", "eaten_whole"]
+
+
+def edit_sequence(case, ctr, radius=30.0):
+    """the edits of a case on a sphere of `radius` about `ctr` (written for radius 30, scaled with the sphere)"""
+    s = np.float32(radius / 30.0)
+    top = ctr + np.float32(radius) * np.array([0.0, 0.0, 1.0], np.float32)
+    return {
+        "bites": [("s", top, 7.0 * float(s)), ("s", top, 20.0 * float(s)),
+                  ("s", ctr + np.float32(radius) * np.array([0.6, 0.0, 0.8], np.float32), 11.0 * float(s))],
+        "cut_through": [("s", ctr + np.array([0.0, float(y) * float(s), 0.0], np.float32), 12.0 * float(s)) for y in (-24, -8, 8, 24)],
+        "capsule_then_sphere": [("c", ctr + s * np.array([-40.0, 3.0, 20.0], np.float32), s * np.array([80.0, -6.0, 4.0], np.float32), 6.0 * float(s)),
+                                ("s", top, 9.0 * float(s))],
+        "eaten_whole": [("s", ctr, 50.0 * float(s))],
+    }[case]
+
+
+def sync_after_edits(o, g, case, radius=30.0, dens=None, overlapped=False):
+    """`overlapped`: the sphere edits in their enqueue / collect form with the early mesh needs on, the sync placed while the edit is in flight
+    (ivx_absorb_sphere_enqueue -> ivx_mesh_sync_enqueue(NULL) -> ivx_absorb_collect -> ivx_mesh_sync_collect)"""
     om = ol.OracleMeshHandle(o)
     gm = VoxelObjectMesh.create(g)
     ctr = np.array([0.5 * (a + b) for a, b in o.info()["occupied_voxel_ranges"]], dtype=np.float32)
-    top = ctr + np.float32(30.0) * np.array([0.0, 0.0, 1.0], np.float32)
-    edits = {
-        "bites": [("s", top, 7.0), ("s", top, 20.0), ("s", ctr + np.float32(30.0) * np.array([0.6, 0.0, 0.8], np.float32), 11.0)],
-        "cut_through": [("s", ctr + np.array([0.0, float(y), 0.0], np.float32), 12.0) for y in (-24, -8, 8, 24)],
-        "capsule_then_sphere": [("c", ctr + np.array([-40.0, 3.0, 20.0], np.float32), np.array([80.0, -6.0, 4.0], np.float32), 6.0), ("s", top, 9.0)],
-        "eaten_whole": [("s", ctr, 50.0)],
-    }[case]
+    edits = edit_sequence(case, ctr, radius)
+    if overlapped:
+        g.set_early_mesh_needs(True)
     for e in edits:
+        in_flight = overlapped and e[0] == "s"
         if e[0] == "s":
-            ro = o.absorb_sphere(e[1], e[2] + 2.0, e[2])
-            rg = g.absorb_sphere(e[1], e[2] + 2.0, e[2])
+            ro = o.absorb_sphere(e[1], e[2] + 2.0, e[2], dens)
+            if in_flight:
+                g.absorb_sphere_enqueue(e[1], e[2] + 2.0, e[2], dens)
+                gm.sync_enqueue(None)
+                rg = g.absorb_collect()
+                gm.sync_collect()
+            else:
+                rg = g.absorb_sphere(e[1], e[2] + 2.0, e[2], dens)
         else:
-            ro = o.absorb_capsule(e[1], e[2], e[3] + 2.0, e[3])
-            rg = g.absorb_capsule(e[1], e[2], e[3] + 2.0, e[3])
+            ro = o.absorb_capsule(e[1], e[2], e[3] + 2.0, e[3], dens)
+            rg = g.absorb_capsule(e[1], e[2], e[3] + 2.0, e[3], dens)
         np.testing.assert_array_equal(rg["invalidated"], ro["invalidated"])
+        np.testing.assert_array_equal(rg["emptied_by_type"], ro["emptied_by_type"])
         om.sync(ro["invalidated"])
-        gm.sync_with_voxel_object(rg["invalidated"])
+        if not in_flight:
+            gm.sync_with_voxel_object(rg["invalidated"])
         assert_synced_meshes_equal(om.get(), gm.download())
         # what the renderer is told to re-upload (VoxelMeshModifications, mesh.rs:113-123)
         want_ranges, want_removed = om.modifications()
@@ -90,7 +112,14 @@ def test_sync_after_edits(ctx, case):
             nv, ni = int(s["vertex_count"]), int(s["index_count"])
             np.testing.assert_array_equal(pos[a0:a0 + nv].view(np.uint32), fpos[b0:b0 + nv].view(np.uint32))
             np.testing.assert_array_equal(idx[a1:a1 + ni].astype(np.int64) - a0, fidx[b1:b1 + ni].astype(np.int64) - b0)
+            np.testing.assert_array_equal(im[a1:a1 + ni], fim[b1:b1 + ni])
     g.close()
+
+
+@pytest.mark.parametrize("case", SYNC_CASES)
+def test_sync_after_edits(ctx, case):
+    o, g = both(ctx, scenes.sphere_scene(30.0))
+    sync_after_edits(o, g, case)
 
 
 def test_sync_after_full_remesh_restarts_the_bookkeeping(ctx):

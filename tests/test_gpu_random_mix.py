@@ -7,6 +7,7 @@ import pytest
 import oracle_lib as ol
 import parity_util as pu
 import test_gpu_contacts as tcon
+import typed_util as tu
 from impact_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -18,18 +19,33 @@ def rand_q(rng):
     return (q / np.linalg.norm(q)).astype(f32)
 
 
-@pytest.mark.parametrize("seed", pu.fuzz_seeds([11, 12, 13, 14, 15]))
-def test_random_operation_mix(ctx, seed):
+SEEDS = pu.fuzz_seeds([11, 12, 13, 14, 15])
+
+
+# (the cases of one type keep the ids they had before the other kind was added: the seed alone)
+@pytest.mark.parametrize("seed, types", [(s, t) for t in ("same", "noise") for s in SEEDS],
+                         ids=[str(s) if t == "same" else f"{s}-noise" for t in ("same", "noise") for s in SEEDS])
+def test_random_operation_mix(ctx, seed, types):
+    """`types`: every voxel of type 0, or four gradient-noise types (tests/typed_util.py) with a density per type — the same seeds, so the
+    same operations"""
     rng = np.random.default_rng(seed)
     ext = [1.0, 0.5, 0.25][seed % 3]
     graph = [scenes.asteroid_scene(0.28), scenes.two_spheres_scene(14.0, 26.0), scenes.box_scene((36.0, 22.0, 28.0))][seed % 3]
-    o = pu.oracle_from_graph(graph, ext)
-    g = pu.gpu_from_graph(ctx, graph, ext)
-    o.update_occupied_voxel_ranges()
-    o.compute_all_derived_state()
-    g.compute_all_derived_state()
-    g.update_occupied_voxel_ranges()
-    g.label_regions()
+    if types == "noise":
+        dens, noise = tu.DENSITIES, (4, 0.04, 1.0, seed)
+        o = tu.typed_oracle(graph, ext, noise)
+        _, o_typ, o_flg, _, _ = o.export_dense()
+        assert len(tu.types_of_non_empty(o_typ, o_flg)) >= 3
+        g = tu.typed_gpu(ctx, graph, ext, noise)
+    else:
+        dens = None
+        o = pu.oracle_from_graph(graph, ext)
+        g = pu.gpu_from_graph(ctx, graph, ext)
+        o.update_occupied_voxel_ranges()
+        o.compute_all_derived_state()
+        g.compute_all_derived_state()
+        g.update_occupied_voxel_ranges()
+        g.label_regions()
     ops_done = {k: 0 for k in ("sphere", "capsule", "csphere", "cplane", "ccapsule", "split", "ranges")}
     for step in range(16):
         occ = np.array(o.info()["occupied_voxel_ranges"], dtype=np.float64)
@@ -39,14 +55,14 @@ def test_random_operation_mix(ctx, seed):
         if kind in ("sphere", "capsule"):
             r = float(f32(rng.uniform(2.0, 8.0)))
             if kind == "sphere":
-                ro, rg = o.absorb_sphere(p_norm, r + 2.0, r), g.absorb_sphere(p_norm, r + 2.0, r)
+                ro, rg = o.absorb_sphere(p_norm, r + 2.0, r, dens), g.absorb_sphere(p_norm, r + 2.0, r, dens)
             else:
                 v = (rng.normal(size=3) * rng.uniform(0.0, 20.0)).astype(f32)
-                ro, rg = o.absorb_capsule(p_norm, v, r + 2.0, r), g.absorb_capsule(p_norm, v, r + 2.0, r)
+                ro, rg = o.absorb_capsule(p_norm, v, r + 2.0, r, dens), g.absorb_capsule(p_norm, v, r + 2.0, r, dens)
             assert rg["touched_chunks"] == ro["touched_chunks"] and rg["removed_chunks"] == ro["removed_chunks"], (step, kind)
             np.testing.assert_array_equal(rg["emptied_by_type"], ro["emptied_by_type"])
             np.testing.assert_array_equal(rg["invalidated"], ro["invalidated"])
-            pu.assert_edited_objects_equal(o, g, what=f"step {step} {kind}: ")
+            pu.assert_edited_objects_equal(o, g, what=f"step {step} {kind}: ", densities=dens)
         elif kind in ("csphere", "cplane", "ccapsule"):
             q, t = rand_q(rng), rng.normal(size=3).astype(f32) * f32(3.0)
             qi = np.array([-q[0], -q[1], -q[2], q[3]], dtype=np.float64)
@@ -77,9 +93,9 @@ def test_random_operation_mix(ctx, seed):
             rc_o, child_o, origin_o = o.split_off_smallest_region()
             rc_g, child_g, origin_g, _ = g.extract_any_disconnected_region()
             assert rc_o == rc_g and (rc_o != 1 or tuple(int(x) for x in origin_g) == tuple(origin_o))  # the origin is the child's: only outcome 1 has one
-            pu.assert_edited_objects_equal(o, g, what=f"step {step} split parent: ")
+            pu.assert_edited_objects_equal(o, g, what=f"step {step} split parent: ", densities=dens)
             if rc_o == 1:
-                pu.assert_edited_objects_equal(child_o, child_g, what=f"step {step} split child: ")
+                pu.assert_edited_objects_equal(child_o, child_g, what=f"step {step} split child: ", densities=dens)
                 child_g.close()
         else:
             o.update_occupied_voxel_ranges()

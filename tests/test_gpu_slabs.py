@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import typed_util as tu
 from impact_amd import capi, scenes
 from impact_amd.distributed import NativeComm, NativeSlabStepper, SlabStepper, native_step, run_slabs_in_process
 
@@ -23,13 +24,23 @@ def driver(request):
     return request.param
 
 
-def run_and_compare(ctx, graph, world, expect_regions=None, extent=1.0, driver="native"):
+def run_and_compare(ctx, graph, world, expect_regions=None, extent=1.0, driver="native", voxel_types=None, need_uniform=False):
+    """`voxel_types`: (n, noise frequency, voxel type frequency, seed) of a gradient-noise type generator — the slabs sample with it, the
+    whole-grid oracle is tests/typed_util.typed_oracle, the densities are 1 + t, and the oracle must show several types at every cut (and,
+    with `need_uniform`, a Uniform chunk of a non-zero type on a face layer) before anything runs on the device"""
     import torch
 
-    dens = np.linspace(0.5, 2.0, 256).astype(np.float32)
-    o = ol.OracleObject.from_sdf(graph, extent, 0)
-    o.update_occupied_voxel_ranges()
-    o.compute_all_derived_state()
+    if voxel_types is None:
+        dens = np.linspace(0.5, 2.0, 256).astype(np.float32)
+        o = ol.OracleObject.from_sdf(graph, extent, 0)
+        o.update_occupied_voxel_ranges()
+        o.compute_all_derived_state()
+        vt = 0
+    else:
+        dens = tu.DENSITIES
+        o = tu.typed_oracle(graph, extent, voxel_types)
+        tu.assert_slab_case_shows_types(o, world, need_uniform)
+        vt = tu.noise_generator(voxel_types)
     comm = None
     if driver.startswith("native"):
         comm = NativeComm(ctx, world, local=True)
@@ -37,9 +48,9 @@ def run_and_compare(ctx, graph, world, expect_regions=None, extent=1.0, driver="
             comm.set_local_copies(1 if driver == "native_overlap" else 2)
         # (native_overlap also runs every slab's sampler pre-pass a step ahead, ivx_grid_set_sample_ahead: three steps, so the second and third
         # find theirs done)
-        steppers = [NativeSlabStepper(ctx, comm, graph, dens, r, extent, sample_ahead=driver == "native_overlap") for r in range(world)]
+        steppers = [NativeSlabStepper(ctx, comm, graph, dens, r, extent, vt, sample_ahead=driver == "native_overlap") for r in range(world)]
     else:
-        steppers = [SlabStepper(ctx, graph, dens, r, world, torch, extent) for r in range(world)]
+        steppers = [SlabStepper(ctx, graph, dens, r, world, torch, extent, vt) for r in range(world)]
     try:
         for _ in range(3 if driver == "native_overlap" else 2):  # again: a later pass starts from a dirty state (ghosts, labels, mesh buffers, receive buffers)
             results = native_step(steppers) if driver.startswith("native") else run_slabs_in_process(steppers)
@@ -136,6 +147,27 @@ def test_two_spheres_cut_between(ctx, driver):
     run_and_compare(ctx, scenes.two_spheres_scene(25.0, 60.0), 2, expect_regions=2, extent=0.5, driver=driver)
 
 
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_typed_sphere_in_slabs(ctx, world, driver):
+    """four noise types on the sphere of radius 60 (8^3 chunks): the halo's type planes and chunk records carry all four, Uniform chunks of
+    non-zero types lie on the face layers (their ghost faces are expanded from the record's uniform_type), and the submeshes beside every
+    cut have quads of mixed materials whose corners lie in the ghost layer"""
+    run_and_compare(ctx, tu.sphere60(), world, expect_regions=1, driver=driver, voxel_types=tu.SPHERE60_NOISE, need_uniform=True)
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_typed_asteroid_in_slabs(ctx, world, driver):
+    run_and_compare(ctx, scenes.asteroid_scene(0.5), world, expect_regions=1, driver=driver, voxel_types=(4, 0.02, 1.0, 0))
+
+
+def test_typed_fracture_in_3_slabs(ctx, driver):
+    run_and_compare(ctx, scenes.fracture_scene(0.5), 3, expect_regions=8, driver=driver, voxel_types=(3, 0.03, 0.7, 5))
+
+
+def test_typed_two_spheres_in_2_slabs(ctx, driver):
+    run_and_compare(ctx, scenes.two_spheres_scene(25.0, 60.0), 2, expect_regions=2, extent=0.5, driver=driver, voxel_types=(5, 0.02, 1.0, 7))
+
+
 @pytest.mark.parametrize("overlap", [False, True])
 def test_headline_512_in_8_slabs(ctx, overlap):
     """the strong-scaling configuration of the metric — the 512^3 asteroid in 8 x-slabs of 4 chunk planes — through the native driver,
@@ -169,6 +201,7 @@ def test_headline_512_in_8_slabs(ctx, overlap):
             x0, x1 = s.x_range
             g_sdf, g_typ, g_flg, _, _ = s.obj.download(labels=False, info=False)
             np.testing.assert_array_equal(g_sdf, w_sdf[x0 * per:x1 * per])
+            np.testing.assert_array_equal(g_typ, w_typ[x0 * per:x1 * per])
             np.testing.assert_array_equal(g_flg, w_flg[x0 * per:x1 * per])
     finally:
         for s in steppers:

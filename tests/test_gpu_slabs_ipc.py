@@ -12,16 +12,25 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import typed_util as tu
 from impact_amd import scenes
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-@pytest.mark.parametrize("scene,world,regions", [("asteroid", 2, 1), ("fracture", 3, 8)])
+@pytest.mark.parametrize("scene,world,regions", [("asteroid", 2, 1), ("fracture", 3, 8), ("typed_sphere", 3, 1)])
 def test_native_protocol_as_separate_processes(scene, world, regions):
-    graph = {"asteroid": scenes.asteroid_scene, "fracture": scenes.fracture_scene}[scene]()
-    dens = np.linspace(0.5, 2.0, 256).astype(np.float32)
+    if scene == "typed_sphere":  # (the worker builds the same scene under this name: four noise types, densities 1 + t)
+        graph, dens = tu.sphere60(), tu.DENSITIES
+        o = tu.typed_oracle(graph, 1.0, tu.SPHERE60_NOISE)
+        tu.assert_slab_case_shows_types(o, world, need_uniform=True)
+    else:
+        graph = {"asteroid": scenes.asteroid_scene, "fracture": scenes.fracture_scene}[scene]()
+        dens = np.linspace(0.5, 2.0, 256).astype(np.float32)
+        o = ol.OracleObject.from_sdf(graph, 1.0, 0)
+        o.update_occupied_voxel_ranges()
+        o.compute_all_derived_state()
     with tempfile.TemporaryDirectory() as tmp:
         name = f"/ivx_ipc_{os.getpid()}_{scene}"
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -38,9 +47,6 @@ def test_native_protocol_as_separate_processes(scene, world, regions):
         assert all(p.returncode == 0 for p in procs), "\n".join(o[-3000:] for o in outs)
         ranks = [np.load(os.path.join(tmp, f"r{r}.npz")) for r in range(world)]
         # ---- against the oracle on the whole grid
-        o = ol.OracleObject.from_sdf(graph, 1.0, 0)
-        o.update_occupied_voxel_ranges()
-        o.compute_all_derived_state()
         cc = o.chunk_counts
         assert tuple(ranks[0]["chunk_counts"]) == tuple(cc)
         o_sdf, o_typ, o_flg, o_lab, o_info = o.export_dense()

@@ -167,6 +167,10 @@ PHYSICS_STAGE_NAMES = ["prepare", "pre_solve", "solve", "post_solve", "total"]
 KINEMATIC_BIT = 0x80000000
 CONTACT_MANIFOLD_START = 1
 assert RIGID_BODY_DTYPE.itemsize == 152 and KINEMATIC_BODY_DTYPE.itemsize == 56 and CONTACT_DTYPE.itemsize == 64
+# detailed drag (impact_physics/src/force/detailed_drag): `ivx_drag_load` (DragLoad) and the numeric fields of DragLoadMapConfig
+DRAG_LOAD_DTYPE = np.dtype([("force", "<f4", (3,)), ("torque", "<f4", (3,))])
+DRAG_MAP_CONFIG_DTYPE = np.dtype([("n_direction_samples", "<u4"), ("n_theta_coords", "<u4"), ("smoothness", "<f4"), ("reserved", "<u4")])
+assert DRAG_LOAD_DTYPE.itemsize == 24 and DRAG_MAP_CONFIG_DTYPE.itemsize == 16
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -190,6 +194,8 @@ EXPORTED_SYMBOLS = [
     "ivx_comm_unique_id", "ivx_comm_init", "ivx_comm_init_local", "ivx_comm_init_ipc", "ivx_comm_info", "ivx_comm_set_local_copies", "ivx_comm_selftest", "ivx_selftest_mesher_division", "ivx_noise_eval", "ivx_voxel_types_eval", "ivx_comm_destroy", "ivx_slab_create", "ivx_slab_destroy",
     "ivx_slabs_step_enqueue", "ivx_slabs_step_collect", "ivx_slab_region_map",
     "ivx_world_set_solver_groups", "ivx_world_solver_info", "ivx_world_contact_state",
+    "ivx_drag_map_config_default", "ivx_drag_directions", "ivx_drag_map_indices", "ivx_drag_force_and_torque",
+    "ivx_drag_loads_triangles", "ivx_drag_loads", "ivx_drag_load_map_from_samples", "ivx_drag_load_map",
 ]
 
 
@@ -216,6 +222,7 @@ def extra_struct_sizes():
         "ivx_rigid_body": (RIGID_BODY_DTYPE, 152), "ivx_kinematic_body": (KINEMATIC_BODY_DTYPE, 56), "ivx_contact": (CONTACT_DTYPE, 64),
         "ivx_solver_config": (SOLVER_CONFIG_DTYPE, 16), "ivx_physics_result": (PHYSICS_RESULT_DTYPE, 48),
         "ivx_absorb_result": (ABSORB_RESULT_DTYPE, 96), "ivx_extracted_object": (EXTRACTED_OBJECT_DTYPE, 272),
+        "ivx_drag_load": (DRAG_LOAD_DTYPE, 24), "ivx_drag_map_config": (DRAG_MAP_CONFIG_DTYPE, 16),
     }
 
 
@@ -375,6 +382,14 @@ def lib():
         "ivx_slab_region_map": (i32, [vp, i32, vp, sz, C.POINTER(sz)]),
         "ivx_world_set_solver_groups": (i32, [vp, u32]),
         "ivx_world_solver_info": (i32, [vp, vp]),
+        "ivx_drag_map_config_default": (None, [vp]),
+        "ivx_drag_directions": (i32, [sz, vp]),
+        "ivx_drag_map_indices": (i32, [u32, f32, f32, C.POINTER(u32), C.POINTER(u32)]),
+        "ivx_drag_force_and_torque": (i32, [vp, u32, vp, vp, f32, f32, f32]),
+        "ivx_drag_loads_triangles": (i32, [vp, vp, sz, vp, sz, vp, vp, sz, vp]),
+        "ivx_drag_loads": (i32, [vp, vp, vp, sz, vp]),
+        "ivx_drag_load_map_from_samples": (i32, [vp, vp, vp, sz, u32, f32, vp]),
+        "ivx_drag_load_map": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

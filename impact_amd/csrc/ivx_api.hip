@@ -474,6 +474,7 @@ void ivx_shutdown(ivx_ctx* c) {
     ivx_many_release(c);  // (the launch recorder of the many-object calls and its staging ring)
     if (c->pinned_scratch) (void)hipHostFree(c->pinned_scratch);
     if (c->dev_scratch) (void)hipFree(c->dev_scratch);
+    if (c->drag_scratch) (void)hipFree(c->drag_scratch);
     if (c->aux_stream) {
         (void)hipStreamSynchronize(c->aux_stream);
         (void)hipStreamDestroy(c->aux_stream);

@@ -72,6 +72,8 @@ struct ivx_ctx {
     hipStream_t aux_stream;  // made on first use (ivx_aux_stream): the sampler's pre-pass one step ahead (ivx_grid_set_sample_ahead)
     void* many_recorder;  // the launch recorder of ivx_many_begin / _flush and its staging ring (many.cpp); made on first use, freed by ivx_shutdown
     int many_error;       // a flush of recorded launches failed on this context (sticky until reported: ivx_many_error)
+    void* drag_scratch;   // device scratch of the drag entry points (drag.hip: triangle records, per-tile partials, samples, map); grown on demand, freed by ivx_shutdown
+    size_t drag_scratch_bytes;
 };
 
 // A device allocation (and / or a pinned host allocation) shared by several grids that came into being together — the fragments of an impact

@@ -757,6 +757,61 @@ int ivx_world_set_solver_groups(ivx_world*, uint32_t groups);
 int ivx_world_solver_info(ivx_world*, uint32_t out[8]);
 int ivx_world_contact_state(ivx_world*, uint64_t* ids, float* impulses3, size_t cap, size_t* n_out);
 
+/* ---- detailed drag: drag load maps (impact_physics/src/force/detailed_drag.rs, detailed_drag/drag_load.rs, detailed_drag/equirectangular_map.rs) ----
+ * The reference computes a map once per static TriangleMesh asset and caches it on disk; here the map comes from a triangle list or from the
+ * mesh that is resident on the device, so a voxel object can have one after every bite. */
+/* DragLoad: force on the centre of mass and torque about it, without the factors that do not depend on the triangles. 24 bytes. */
+typedef struct {
+    float force[3];
+    float torque[3];
+} ivx_drag_load;
+/* the numeric fields of DragLoadMapConfig. 16 bytes. ivx_drag_map_config_default fills in 5000 / 64 / 2.0 (DragLoadMapConfig::default). */
+typedef struct {
+    uint32_t n_direction_samples, n_theta_coords;
+    float smoothness;
+    uint32_t reserved;
+} ivx_drag_map_config;
+void ivx_drag_map_config_default(ivx_drag_map_config*);
+/* A map is n_theta x 2 n_theta loads, theta-major: cell = theta_idx * n_phi + phi_idx, n_phi = 2 n_theta.
+ *
+ * Host arithmetic (no device needed):
+ * compute_uniformly_distributed_radial_directions (impact_geometry/src/lib.rs:59-91) in f32: z = 1 - 2 i / (n - 1) (the norm is 1 when n = 1),
+ * r = sqrt(1 - z z), azimuth i pi (3 - sqrt 5), (r cos, r sin, z) normalised. Deliberate difference: 1 - z z is clamped at 0 (the last z can
+ * round to just below -1, which makes the reference's direction NaN). */
+int ivx_drag_directions(size_t n, float* dirs3);
+/* EquirectangularMap::compute_phi_idx / compute_theta_idx (equirectangular_map.rs:86-98): rem_euclid(2 pi), theta above pi folded back,
+ * floor(angle * (1 / cell)) with cell = pi / n_theta, theta clamped to n_theta - 1. Deliberate difference: phi is clamped to n_phi - 1 as
+ * well (the reference indexes one past the row when the remainder of a tiny negative angle rounds to 2 pi). */
+int ivx_drag_map_indices(uint32_t n_theta, float phi, float theta, uint32_t* phi_idx, uint32_t* theta_idx);
+/* DetailedDragForce::apply + DragLoad::compute_world_space_drag_force_and_torque (detailed_drag.rs:200-243, drag_load.rs:42-67): v = momentum /
+ * mass relative to the medium, s2 = |v_rel|^2; nothing happens when s2 <= 0; else the map cell at the body-space direction of v_rel (phi =
+ * atan2(y, x), theta = acos z) scaled by fs = scaling^2 rho C_d s2 (torque: scaling fs), rotated to world space and ADDED to the body's
+ * total_force / total_torque. */
+int ivx_drag_force_and_torque(const ivx_drag_load* map, uint32_t n_theta, ivx_rigid_body* body, const float medium_velocity[3],
+                              float medium_mass_density, float drag_coefficient, float scaling);
+/* Device entry points (HIP kernels, drag.hip). Per triangle (drag_load.rs:212-245): c = e1 x e2, kept only if |c| > f32::EPSILON; normal = c / |c|,
+ * area = |c| / 2, centre = (v1 + v2 + v3) / 3. Load of a direction d (drag_load.rs:174-208): over the triangles with cos = d . n > 0,
+ * force += -(cos area) n, torque += (centre - com) x that force. f32 products, sums of 128 triangles in f32, everything above that in f64 in a
+ * fixed order: results do not depend on timing (no float atomics). All arrays are host arrays.
+ * ivx_drag_loads_triangles: a caller's triangle list (n_indices a multiple of 3, every index < n_vertices; an empty list gives zero loads).
+ * ivx_drag_loads: the grid's resident mesh — the triangles of the live submeshes only (index_offset .. + index_count of every entry of the
+ * submesh table; after ivx_mesh_sync the buffers also hold freed ranges with stale triangles). IVX_ERR_STATE without a current mesh. */
+int ivx_drag_loads_triangles(ivx_ctx*, const float* positions3, size_t n_vertices, const uint32_t* indices, size_t n_indices, const float com[3],
+                             const float* dirs3, size_t n_dirs, ivx_drag_load* out);
+int ivx_drag_loads(ivx_grid*, const float com[3], const float* dirs3, size_t n_dirs, ivx_drag_load* out);
+/* generate_map_from_drag_loads (detailed_drag.rs:401-471, equirectangular_map.rs:108-160), the smoothing stage alone. For sample s in order:
+ * scaled = distance / (1 - 0.75 |d.z|), ext = max(scaled, cell / 2), n_across = ceil(2 ext / cell); rows theta_k = theta_s - ext + cell / 2 +
+ * k cell, columns the same in phi, cell indices by ivx_drag_map_indices; angular distance = acos(sin theta_s sin theta_k + cos theta_s cos theta_k
+ * cos(phi_j - phi_s)); w = max(0, 1 - (distance / scaled)^2)^2; the cell accumulates w load and w, every hit counting (near the poles a sample
+ * meets a cell several times); afterwards each cell is sum / weight where weight > 0. One lane per cell gathers the samples in order, rows before
+ * columns: the reference's summation order. Deliberate differences: the acos argument is clamped to [-1, 1] (the reference lets 1 + ulp become
+ * NaN and then weight 0), and a distance above pi is refused (the region would wrap the map several times over). */
+int ivx_drag_load_map_from_samples(ivx_ctx*, const float* dirs3, const ivx_drag_load* loads, size_t n, uint32_t n_theta,
+                                   float angular_interpolation_distance, ivx_drag_load* map);
+/* DragLoadMap::compute_from_mesh (detailed_drag.rs:362-398) over the resident mesh: directions, loads and map in one call, the samples never
+ * leaving the device; angular_interpolation_distance = smoothness sqrt(4 pi / n_direction_samples). */
+int ivx_drag_load_map(ivx_grid*, const float com[3], const ivx_drag_map_config*, ivx_drag_load* map);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,20 @@ assert RIGID_BODY_DTYPE.itemsize == 152 and KINEMATIC_BODY_DTYPE.itemsize == 56 
 DRAG_LOAD_DTYPE = np.dtype([("force", "<f4", (3,)), ("torque", "<f4", (3,))])
 DRAG_MAP_CONFIG_DTYPE = np.dtype([("n_direction_samples", "<u4"), ("n_theta_coords", "<u4"), ("smoothness", "<f4"), ("reserved", "<u4")])
 assert DRAG_LOAD_DTYPE.itemsize == 24 and DRAG_MAP_CONFIG_DTYPE.itemsize == 16
+# chunk culling (csrc/cull.hip): the records of include/impact_voxel_hip.h
+CULLING_FRUSTUM_DTYPE = np.dtype([("planes", "<f4", (6, 4)), ("most_inside_corners", "<u4", (6,)), ("apex", "<f4", (3,)), ("instance_idx", "<u4")])
+CULL_VIEW_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("planes", "<f4", (6, 4)), ("box_center", "<f4", (3,)), ("box_orientation", "<f4", (4,)),
+                            ("box_half_extents", "<f4", (3,)), ("apex_distance", "<f4"), ("reserved", "<u4")])
+CULL_PAIR_DTYPE = np.dtype([("rotation", "<f4", (4,)), ("translation", "<f4", (3,)), ("scaling", "<f4"), ("instance_idx", "<u4"), ("flags", "<u4")])
+CULL_OBJECT_DTYPE = np.dtype([("first_index_base", "<u4"), ("base_vertex", "<i4")])
+DRAW_ARGS_DTYPE = np.dtype([("index_count", "<u4"), ("instance_count", "<u4"), ("first_index", "<u4"), ("first_instance", "<u4")])
+DRAW_INDEXED_ARGS_DTYPE = np.dtype([("index_count", "<u4"), ("instance_count", "<u4"), ("first_index", "<u4"), ("base_vertex", "<i4"), ("first_instance", "<u4")])
+CULL_REGION_DTYPE = np.dtype([("offset", "<u8"), ("stride", "<u4"), ("n_slots", "<u4")])
+CULL_COUNT_DTYPE = np.dtype([("draws", "<u4"), ("indices", "<u4")])
+CULL_VIEW_INDEXED, CULL_PAIR_SKIP, CULL_ZEROED, CULL_COMPACTED, CULL_MAX_VIEWS = 1, 1, 0, 1, 64
+CULL_PTR_ARGS, CULL_PTR_COUNTS, CULL_PTR_FRUSTA = 0, 1, 2
+assert CULLING_FRUSTUM_DTYPE.itemsize == 136 and CULL_VIEW_DTYPE.itemsize == 152 and CULL_PAIR_DTYPE.itemsize == 40 and CULL_OBJECT_DTYPE.itemsize == 8
+assert DRAW_ARGS_DTYPE.itemsize == 16 and DRAW_INDEXED_ARGS_DTYPE.itemsize == 20 and CULL_REGION_DTYPE.itemsize == 16 and CULL_COUNT_DTYPE.itemsize == 8
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -196,6 +210,8 @@ EXPORTED_SYMBOLS = [
     "ivx_world_set_solver_groups", "ivx_world_solver_info", "ivx_world_contact_state",
     "ivx_drag_map_config_default", "ivx_drag_directions", "ivx_drag_map_indices", "ivx_drag_force_and_torque",
     "ivx_drag_loads_triangles", "ivx_drag_loads", "ivx_drag_load_map_from_samples", "ivx_drag_load_map",
+    "ivx_culling_frustum_from_view", "ivx_cull_frusta", "ivx_cull_submesh_tables", "ivx_cull_submesh_tables_frusta", "ivx_cull_many", "ivx_cull_many_enqueue",
+    "ivx_cull_collect", "ivx_cull_many_frusta", "ivx_cull_download", "ivx_cull_device_ptr",
 ]
 
 
@@ -223,6 +239,9 @@ def extra_struct_sizes():
         "ivx_solver_config": (SOLVER_CONFIG_DTYPE, 16), "ivx_physics_result": (PHYSICS_RESULT_DTYPE, 48),
         "ivx_absorb_result": (ABSORB_RESULT_DTYPE, 96), "ivx_extracted_object": (EXTRACTED_OBJECT_DTYPE, 272),
         "ivx_drag_load": (DRAG_LOAD_DTYPE, 24), "ivx_drag_map_config": (DRAG_MAP_CONFIG_DTYPE, 16),
+        "ivx_culling_frustum": (CULLING_FRUSTUM_DTYPE, 136), "ivx_cull_view": (CULL_VIEW_DTYPE, 152), "ivx_cull_pair": (CULL_PAIR_DTYPE, 40),
+        "ivx_cull_object": (CULL_OBJECT_DTYPE, 8), "ivx_draw_args": (DRAW_ARGS_DTYPE, 16), "ivx_draw_indexed_args": (DRAW_INDEXED_ARGS_DTYPE, 20),
+        "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
     }
 
 
@@ -390,6 +409,16 @@ def lib():
         "ivx_drag_loads": (i32, [vp, vp, vp, sz, vp]),
         "ivx_drag_load_map_from_samples": (i32, [vp, vp, vp, sz, u32, f32, vp]),
         "ivx_drag_load_map": (i32, [vp, vp, vp, vp]),
+        "ivx_culling_frustum_from_view": (i32, [vp, vp, f32, vp]),
+        "ivx_cull_frusta": (i32, [vp, vp, sz, vp, vp, sz, vp]),
+        "ivx_cull_submesh_tables": (i32, [vp, vp, vp, sz, vp, vp, vp, sz, vp, u32, vp, vp]),
+        "ivx_cull_submesh_tables_frusta": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, sz, u32, vp, vp]),
+        "ivx_cull_many": (i32, [vp, sz, vp, vp, sz, vp, u32, vp, vp]),
+        "ivx_cull_many_enqueue": (i32, [vp, sz, vp, vp, sz, vp, u32, vp]),
+        "ivx_cull_collect": (i32, [vp, vp, sz]),
+        "ivx_cull_many_frusta": (i32, [vp, sz, vp, vp, vp, vp, sz, u32, vp, vp]),
+        "ivx_cull_download": (i32, [vp, u32, vp, sz, vp, vp, sz]),
+        "ivx_cull_device_ptr": (vp, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -475,6 +475,7 @@ void ivx_shutdown(ivx_ctx* c) {
     if (c->pinned_scratch) (void)hipHostFree(c->pinned_scratch);
     if (c->dev_scratch) (void)hipFree(c->dev_scratch);
     if (c->drag_scratch) (void)hipFree(c->drag_scratch);
+    ivx_cull_release(c);
     if (c->aux_stream) {
         (void)hipStreamSynchronize(c->aux_stream);
         (void)hipStreamDestroy(c->aux_stream);

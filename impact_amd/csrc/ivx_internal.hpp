@@ -74,6 +74,7 @@ struct ivx_ctx {
     int many_error;       // a flush of recorded launches failed on this context (sticky until reported: ivx_many_error)
     void* drag_scratch;   // device scratch of the drag entry points (drag.hip: triangle records, per-tile partials, samples, map); grown on demand, freed by ivx_shutdown
     size_t drag_scratch_bytes;
+    void* cull_state;  // chunk culling (cull.hip): argument, count and frustum buffers, staging block, the last call's layout; made on first use, freed by ivx_cull_release
 };
 
 // A device allocation (and / or a pinned host allocation) shared by several grids that came into being together — the fragments of an impact
@@ -280,6 +281,7 @@ struct ivx_mutual_pass {
 };
 
 void ivx_set_error(const char* fmt, ...);
+void ivx_cull_release(ivx_ctx* c);  // cull.hip (ivx_shutdown)
 
 #define IVX_HIP_CHECK(expr)                                                                          \
     do {                                                                                             \

@@ -9,6 +9,7 @@
 //   apply_sphere_absorption & co             impact_voxel/src/interaction/absorption.rs:801-1079
 //   for_each_*_voxel_object_contact          impact_voxel/src/collidable.rs:859-1286
 //   perform_physics_step / ConstraintSolver  impact_physics/src/lib.rs:31-110
+//   CullingFrustum / VoxelChunkCullingPass   impact_voxel/src/mesh.rs:638-696, render_commands.rs:392-589
 // Errors: every C status other than IVX_OK becomes an impact_voxel::Error carrying ivx_last_error() — where the reference would
 // return Err or panic on a violated precondition. Nothing here computes: it owns handles, sizes buffers and forwards.
 #pragma once
@@ -335,6 +336,77 @@ public:
 
 private:
     ivx_moments moments_{};
+};
+
+// ---- chunk culling (impact_voxel/src/mesh.rs:638-696, render_commands.rs:392-589): the draw arguments of every object under every view ----
+struct CullingFrustum {
+    // CullingFrustum::for_transformed_frustum / ::for_transformed_orthographic_frustum with the transform to normalised object space folded in
+    static ivx_culling_frustum from_view(const ivx_cull_view& view, const ivx_cull_pair& object_to_view, float chunk_extent) {
+        ivx_culling_frustum f{};
+        check(ivx_culling_frustum_from_view(&view, &object_to_view, chunk_extent, &f));
+        return f;
+    }
+};
+class VoxelChunkCullingPass {
+public:
+    struct Result {
+        std::vector<ivx_cull_region> layout;  // per view: where its region lies in the argument buffer
+        std::vector<ivx_cull_count> counts;   // per view: draws, indices drawn (empty after `enqueue` until `collect`)
+    };
+    explicit VoxelChunkCullingPass(Context& ctx) : ctx_(&ctx) {}
+    // pairs are view-major (views.size() x objects.size()); `offsets` empty: per-object buffers; mode IVX_CULL_ZEROED or IVX_CULL_COMPACTED
+    Result record(const std::vector<VoxelObject*>& objects, const std::vector<ivx_cull_view>& views, const std::vector<ivx_cull_pair>& pairs, uint32_t mode,
+                  const std::vector<ivx_cull_object>& offsets = {}) {
+        Result r = sized(views.size(), true);
+        const std::vector<ivx_grid*> g = handles(objects);
+        check(ivx_cull_many(g.data(), g.size(), offsets.empty() ? nullptr : offsets.data(), views.data(), views.size(), pairs.data(), mode, r.layout.data(), r.counts.data()));
+        return r;
+    }
+    Result enqueue(const std::vector<VoxelObject*>& objects, const std::vector<ivx_cull_view>& views, const std::vector<ivx_cull_pair>& pairs, uint32_t mode,
+                   const std::vector<ivx_cull_object>& offsets = {}) {
+        Result r = sized(views.size(), false);
+        const std::vector<ivx_grid*> g = handles(objects);
+        check(ivx_cull_many_enqueue(g.data(), g.size(), offsets.empty() ? nullptr : offsets.data(), views.data(), views.size(), pairs.data(), mode, r.layout.data()));
+        return r;
+    }
+    void collect(Result& r) {
+        r.counts.resize(r.layout.size());
+        check(ivx_cull_collect(ctx_->handle(), r.counts.data(), r.counts.size()));
+    }
+    Result record_with_frusta(const std::vector<VoxelObject*>& objects, const std::vector<ivx_culling_frustum>& frusta, const std::vector<uint32_t>& view_flags, uint32_t mode,
+                              const std::vector<uint32_t>& pair_flags = {}, const std::vector<ivx_cull_object>& offsets = {}) {
+        Result r = sized(view_flags.size(), true);
+        const std::vector<ivx_grid*> g = handles(objects);
+        check(ivx_cull_many_frusta(g.data(), g.size(), offsets.empty() ? nullptr : offsets.data(), frusta.data(), view_flags.data(), pair_flags.empty() ? nullptr : pair_flags.data(),
+                                   view_flags.size(), mode, r.layout.data(), r.counts.data()));
+        return r;
+    }
+    std::vector<ivx_culling_frustum> frusta(const std::vector<ivx_cull_view>& views, const std::vector<ivx_cull_pair>& pairs, const std::vector<float>& chunk_extents) {
+        std::vector<ivx_culling_frustum> out(views.size() * chunk_extents.size());
+        check(ivx_cull_frusta(ctx_->handle(), views.data(), views.size(), pairs.data(), chunk_extents.data(), chunk_extents.size(), out.data()));
+        return out;
+    }
+    // one view's region as raw bytes (ivx_draw_args or ivx_draw_indexed_args by the region's stride)
+    std::vector<uint8_t> download(const Result& r, uint32_t view, ivx_cull_count* count = nullptr) {
+        std::vector<uint8_t> args((size_t)r.layout.at(view).n_slots * r.layout.at(view).stride);
+        check(ivx_cull_download(ctx_->handle(), view, args.data(), args.size(), count, nullptr, 0));
+        return args;
+    }
+    void* device_ptr(int which) const { return ivx_cull_device_ptr(ctx_->handle(), which); }
+
+private:
+    static Result sized(size_t n_views, bool with_counts) {
+        Result r;
+        r.layout.resize(n_views);
+        if (with_counts) r.counts.resize(n_views);
+        return r;
+    }
+    static std::vector<ivx_grid*> handles(const std::vector<VoxelObject*>& objects) {
+        std::vector<ivx_grid*> g;
+        for (VoxelObject* o : objects) g.push_back(o->handle());
+        return g;
+    }
+    Context* ctx_;
 };
 
 // ---- rigid bodies + constraint solver (impact_physics/src/lib.rs:31-110) --------------------------------------------------------------

@@ -812,6 +812,123 @@ int ivx_drag_load_map_from_samples(ivx_ctx*, const float* dirs3, const ivx_drag_
  * leaving the device; angular_interpolation_distance = smoothness sqrt(4 pi / n_direction_samples). */
 int ivx_drag_load_map(ivx_grid*, const float com[3], const ivx_drag_map_config*, ivx_drag_load* map);
 
+/* ---- chunk culling: indirect draw arguments for all objects and views of a frame (impact_voxel/shaders/compute/voxel_chunk_culling.template.wgsl,
+ * impact_voxel/src/render_commands.rs:392-598, mesh.rs:128-131, 638-696) ----
+ * The reference records one dispatch with push constants and a bind group per object per view; here ONE call culls every chunk submesh of every
+ * object against every view and leaves a region of draw arguments per view in a context-owned device buffer (csrc/cull.hip). */
+/* CullingFrustum + the shader's instanceIdx (its push-constant block without chunkCount), in NORMALISED OBJECT SPACE: chunk extent 1, the lower
+ * corner of chunk (i, j, k) at (i, j, k). planes: unit normal xyz, displacement. most_inside_corners: the low three bits select the corner, bit 2 / 1 / 0
+ * = upper x / y / z (AxisAlignedBox::corner, the shader's CORNERS_OFFSETS). 136 bytes. */
+typedef struct {
+    float planes[6][4];
+    uint32_t most_inside_corners[6];
+    float apex[3];
+    uint32_t instance_idx;
+} ivx_culling_frustum;
+#define IVX_CULL_VIEW_INDEXED 1u /* ivx_cull_view.flags: the view's pass draws indexed (shadow passes; the geometry pass does not) */
+/* One view of the frame, in view space. kind 0: a frustum with its apex at the origin, the six planes in the order of Frustum (left, right, bottom,
+ * top, near, far; unit normal xyz, displacement). kind 1: an orthographic frustum as an oriented box (centre, orientation quaternion xyzw, half
+ * extents) looking along its negative depth axis, the apex emulated `apex_distance` chunks behind the centre (the reference passes 10 000).
+ * 152 bytes. */
+typedef struct {
+    uint32_t kind, flags;
+    float planes[6][4];
+    float box_center[3];
+    float box_orientation[4];
+    float box_half_extents[3];
+    float apex_distance;
+    uint32_t reserved;
+} ivx_cull_view;
+#define IVX_CULL_PAIR_SKIP 1u /* ivx_cull_pair.flags: the object is not visible in this view, every one of its slots is culled */
+/* One (view, object) pair, view-major (pair v * n_objects + o): the object-to-view similarity (rotation quaternion xyzw, translation, scaling), the
+ * instance index the view's draws of this object carry, flags. 40 bytes. */
+typedef struct {
+    float rotation[4];
+    float translation[3];
+    float scaling;
+    uint32_t instance_idx, flags;
+} ivx_cull_pair;
+/* Added to what the submesh says: 0 / 0 for per-object buffers, the object's arena offsets for a pooled renderer. 8 bytes. */
+typedef struct {
+    uint32_t first_index_base;
+    int32_t base_vertex;
+} ivx_cull_object;
+/* wgpu's DrawIndirectArgs (the shader's non-indexed layout: index_count is `vertex_count`, first_index is `first_vertex`). 16 bytes. */
+typedef struct {
+    uint32_t index_count, instance_count, first_index, first_instance;
+} ivx_draw_args;
+/* wgpu's DrawIndexedIndirectArgs. 20 bytes. */
+typedef struct {
+    uint32_t index_count, instance_count, first_index;
+    int32_t base_vertex;
+    uint32_t first_instance;
+} ivx_draw_indexed_args;
+/* Where a view's region lies in the argument buffer: byte offset, 16 or 20 bytes per slot, slots (the submeshes of all objects). 16 bytes. */
+typedef struct {
+    uint64_t offset;
+    uint32_t stride, n_slots;
+} ivx_cull_region;
+/* A view's record in the count buffer: draws (what multi_draw_indirect_count reads) and the sum of their index counts (mod 2^32). 8 bytes. */
+typedef struct {
+    uint32_t draws, indices;
+} ivx_cull_count;
+/* The derivation, host arithmetic (the device runs the same function and gives the same bytes): T = inverse of the similarity with its scaling
+ * multiplied by chunk_extent (16 x the voxel extent); kind 0: every plane through Plane::transformed (point n d through T, normal through T's
+ * rotation, displacement n' . p'), apex = T's translation; kind 1: the box through OrientedBox::transformed, planes in the order and with the signs of
+ * compute_bounding_planes, apex = centre + apex_distance x depth axis; most_inside_corners[p]: bit 2 / 1 / 0 set where the normal's x / y / z does
+ * NOT have its sign bit set. A restatement in f32 with a fixed operation order, not a bit-parity target (glam's is unpinned).
+ * IVX_ERR_INVALID for a kind other than 0 / 1 and for a chunk_extent or scaling that is not positive. */
+int ivx_culling_frustum_from_view(const ivx_cull_view*, const ivx_cull_pair*, float chunk_extent, ivx_culling_frustum* out);
+/* The decision, per submesh s of object o under view v, from the record f of (v, o): with p = float(chunk_indices) + corner offset, plane q culls
+ * when ((nx px + ny py) + nz pz) - d < -0.05f (strict, f32, no contraction); the chunk is obscured when is_obscured_from_direction[ix][iy][iz] > 0
+ * with i* = (lower + 0.5 - apex).* < 0 ? 1 : 0; a NaN compares false both times (drawn). Culled = frustum-culled, or obscured, or IVX_CULL_PAIR_SKIP.
+ * Slots: base[o] = exclusive prefix of the objects' submesh counts in call order, slot base[o] + s belongs to submesh s of object o; a view's
+ * region holds that many slots of 16 or 20 bytes (IVX_CULL_VIEW_INDEXED); out_layout[v] says where it starts.
+ * mode 0, zeroed in place (the reference's semantics): every slot is written; a drawn chunk gets index_count, instance_count 1, first_index =
+ *   index_offset + first_index_base, base_vertex, first_instance = instance_idx; a culled one the same with index_count = instance_count = 0
+ *   (the reference leaves the other fields stale).
+ * mode 1, compacted: the drawn entries dense from slot 0 in (object, submesh) order, every slot from the count on all zero.
+ * Both modes leave counts[v] in the count buffer. No atomics decide anything: two calls leave the same bytes.
+ * At most 64 views per call (IVX_ERR_INVALID above); n_objects == 0 or n_views == 0 succeeds with empty regions.
+ *   (ivx_cull_many* with n == 0, a frame without voxel objects, touch no context: out_layout gets offset 0, the view's stride and 0 slots, out_counts
+ *   zeros, from the call itself; ivx_cull_download / ivx_cull_collect keep describing the context's last call that had objects or used the context.)
+ * A call that fails leaves nothing to download (ivx_cull_download then refuses every view).
+ * ivx_cull_submesh_tables: host tables, uploaded for the call (counts[o] entries each), chunk_extents[o] per object.
+ * ivx_cull_many: the grids' RESIDENT submesh tables, the live mesh_counts.n_submeshes entries (what ivx_mesh_sync keeps current); chunk extent = 16 x
+ *   the grid's voxel extent; `objects` may be NULL (all zero); a grid without a current mesh is IVX_ERR_STATE, a current mesh without submeshes
+ *   contributes no slot. ivx_cull_many_enqueue does not wait and reads nothing back (the consumer is on the device); ivx_cull_collect waits and copies
+ *   the counts of the last call's views; ivx_cull_many is both.
+ * The *_frusta forms take ready records (frusta[v * n_objects + o], what VoxelChunkCullingPass::record computes today) with view_flags[v] and
+ *   pair_flags[v * n_objects + o] (may be NULL) in place of views and pairs.
+ * ivx_cull_frusta: the derivation stage alone on the device, records[v * n_objects + o] back to the host.
+ * ivx_cull_download: one view's region (args_bytes >= n_slots x stride), its count record and its n_objects frustum records of the last call; each
+ *   may be NULL.
+ * ivx_cull_device_ptr: the argument buffer, the count buffer (64 records), the frustum records of the last call. The buffers belong to the context,
+ *   only grow (a pointer is stale after a call that needed more) and go with ivx_shutdown. Export as ipc / dma-buf handles (cf. ivx_mesh_export) is
+ *   not provided yet: this pointer is the hand-off. */
+#define IVX_CULL_ZEROED 0u
+#define IVX_CULL_COMPACTED 1u
+#define IVX_CULL_PTR_ARGS 0
+#define IVX_CULL_PTR_COUNTS 1
+#define IVX_CULL_PTR_FRUSTA 2
+int ivx_cull_frusta(ivx_ctx*, const ivx_cull_view* views, size_t n_views, const ivx_cull_pair* pairs, const float* chunk_extents, size_t n_objects,
+                    ivx_culling_frustum* out);
+int ivx_cull_submesh_tables(ivx_ctx*, const ivx_submesh* const* tables, const uint32_t* counts, size_t n_objects, const ivx_cull_object* objects,
+                            const float* chunk_extents, const ivx_cull_view* views, size_t n_views, const ivx_cull_pair* pairs, uint32_t mode,
+                            ivx_cull_region* out_layout, ivx_cull_count* out_counts);
+int ivx_cull_submesh_tables_frusta(ivx_ctx*, const ivx_submesh* const* tables, const uint32_t* counts, size_t n_objects, const ivx_cull_object* objects,
+                                   const ivx_culling_frustum* frusta, const uint32_t* view_flags, const uint32_t* pair_flags, size_t n_views, uint32_t mode,
+                                   ivx_cull_region* out_layout, ivx_cull_count* out_counts);
+int ivx_cull_many(ivx_grid* const* grids, size_t n, const ivx_cull_object* objects, const ivx_cull_view* views, size_t n_views, const ivx_cull_pair* pairs,
+                  uint32_t mode, ivx_cull_region* out_layout, ivx_cull_count* out_counts);
+int ivx_cull_many_enqueue(ivx_grid* const* grids, size_t n, const ivx_cull_object* objects, const ivx_cull_view* views, size_t n_views,
+                          const ivx_cull_pair* pairs, uint32_t mode, ivx_cull_region* out_layout);
+int ivx_cull_collect(ivx_ctx*, ivx_cull_count* out_counts, size_t n_views);
+int ivx_cull_many_frusta(ivx_grid* const* grids, size_t n, const ivx_cull_object* objects, const ivx_culling_frustum* frusta, const uint32_t* view_flags,
+                         const uint32_t* pair_flags, size_t n_views, uint32_t mode, ivx_cull_region* out_layout, ivx_cull_count* out_counts);
+int ivx_cull_download(ivx_ctx*, uint32_t view, void* args, size_t args_bytes, ivx_cull_count* count, ivx_culling_frustum* frusta, size_t n_frusta);
+void* ivx_cull_device_ptr(ivx_ctx*, int which);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,23 @@ CULL_VIEW_INDEXED, CULL_PAIR_SKIP, CULL_ZEROED, CULL_COMPACTED, CULL_MAX_VIEWS =
 CULL_PTR_ARGS, CULL_PTR_COUNTS, CULL_PTR_FRUSTA = 0, 1, 2
 assert CULLING_FRUSTUM_DTYPE.itemsize == 136 and CULL_VIEW_DTYPE.itemsize == 152 and CULL_PAIR_DTYPE.itemsize == 40 and CULL_OBJECT_DTYPE.itemsize == 8
 assert DRAW_ARGS_DTYPE.itemsize == 16 and DRAW_INDEXED_ARGS_DTYPE.itemsize == 20 and CULL_REGION_DTYPE.itemsize == 16 and CULL_COUNT_DTYPE.itemsize == 8
+# bounding volumes (csrc/bvol.hip): `ivx_aabb`, `ivx_similarity`, and `ivx_bv_query` — the kind, then the members of its union side by side at
+# their offsets (box / sphere / frustum / oriented box all start at byte 4; `words`, the whole payload, comes last so that a field-by-field copy
+# of a record ends with the right bytes; bvol.query_array stacks records as bytes)
+AABB_DTYPE = np.dtype([("lower", "<f4", (3,)), ("upper", "<f4", (3,))])
+SIMILARITY_DTYPE = np.dtype([("rotation", "<f4", (4,)), ("translation", "<f4", (3,)), ("scaling", "<f4")])
+BV_QUERY_DTYPE = np.dtype({
+    "names": ["kind", "lower", "upper", "center", "radius", "planes", "corners", "axes", "box_center", "half_extents", "words"],
+    "formats": ["<u4", ("<f4", (3,)), ("<f4", (3,)), ("<f4", (3,)), "<f4", ("<f4", (6, 4)), ("<u4", (6,)), ("<f4", (3, 3)), ("<f4", (3,)), ("<f4", (3,)), ("<u4", (31,))],
+    "offsets": [0, 4, 16, 4, 16, 4, 100, 4, 40, 52, 4],
+    "itemsize": 128,
+})
+BV_DYNAMIC, BV_STATIC, BV_PHANTOM = 0, 1, 2
+BV_QUERY_BOX, BV_QUERY_SPHERE, BV_QUERY_FRUSTUM, BV_QUERY_ORIENTED_BOX = 0, 1, 2, 3
+BV_ALL_PAIRS, BV_DYNAMIC_PAIRS = 0, 1
+BV_PTR_WORLD_BOXES, BV_PTR_PAIRS, BV_PTR_MASKS = 0, 1, 2
+BV_MAX_OBJECTS, BV_MAX_QUERIES = 1 << 20, 1024
+assert AABB_DTYPE.itemsize == 24 and SIMILARITY_DTYPE.itemsize == 32 and BV_QUERY_DTYPE.itemsize == 128
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -212,6 +229,8 @@ EXPORTED_SYMBOLS = [
     "ivx_drag_loads_triangles", "ivx_drag_loads", "ivx_drag_load_map_from_samples", "ivx_drag_load_map",
     "ivx_culling_frustum_from_view", "ivx_cull_frusta", "ivx_cull_submesh_tables", "ivx_cull_submesh_tables_frusta", "ivx_cull_many", "ivx_cull_many_enqueue",
     "ivx_cull_collect", "ivx_cull_many_frusta", "ivx_cull_download", "ivx_cull_device_ptr",
+    "ivx_bv_world_aabb", "ivx_bv_frustum_query", "ivx_grid_model_aabb", "ivx_bv_set", "ivx_bv_set_grids", "ivx_bv_download", "ivx_bv_pairs", "ivx_bv_queries",
+    "ivx_bv_device_ptr",
 ]
 
 
@@ -242,6 +261,7 @@ def extra_struct_sizes():
         "ivx_culling_frustum": (CULLING_FRUSTUM_DTYPE, 136), "ivx_cull_view": (CULL_VIEW_DTYPE, 152), "ivx_cull_pair": (CULL_PAIR_DTYPE, 40),
         "ivx_cull_object": (CULL_OBJECT_DTYPE, 8), "ivx_draw_args": (DRAW_ARGS_DTYPE, 16), "ivx_draw_indexed_args": (DRAW_INDEXED_ARGS_DTYPE, 20),
         "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
+        "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128),
     }
 
 
@@ -419,6 +439,15 @@ def lib():
         "ivx_cull_many_frusta": (i32, [vp, sz, vp, vp, vp, vp, sz, u32, vp, vp]),
         "ivx_cull_download": (i32, [vp, u32, vp, sz, vp, vp, sz]),
         "ivx_cull_device_ptr": (vp, [vp, i32]),
+        "ivx_bv_world_aabb": (i32, [vp, vp, vp]),
+        "ivx_bv_frustum_query": (i32, [vp, vp]),
+        "ivx_grid_model_aabb": (i32, [vp, vp]),
+        "ivx_bv_set": (i32, [vp, vp, vp, vp, sz]),
+        "ivx_bv_set_grids": (i32, [vp, sz, vp, vp]),
+        "ivx_bv_download": (i32, [vp, vp, sz, vp]),
+        "ivx_bv_pairs": (i32, [vp, u32, vp, sz, C.POINTER(sz)]),
+        "ivx_bv_queries": (i32, [vp, vp, sz, vp, vp]),
+        "ivx_bv_device_ptr": (vp, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1,0 +1,620 @@
+// Bounding volumes: the world-space boxes of a frame's objects, every intersecting pair of them, and region queries over them.
+//
+// Reference: impact_intersection/src/lib.rs (IntersectionManager: add_bounding_volume_to_hierarchy :39-54, total_bounding_volume, for_each_*),
+//   impact_geometry/src/axis_aligned_box.rs:350-363 (aabb_of_transformed), :619-623 (box_lies_outside), sphere.rs:167-181, frustum.rs:456-471,
+//   oriented_box.rs:129-143, impact_physics/src/collision.rs:215-262, 317-349 (which pairs a frame asks for), impact_voxel/src/object.rs:886-907 and
+//   interaction.rs:202-222 (a voxel object's entry). The reference answers all of these from a bounding volume hierarchy; its tests and fuzz targets
+//   use the `_brute_force` forms as ground truth. This file IS the brute-force form: no hierarchy, no sort, no atomics.
+//
+// WORLD — k_bv_world, one wave per 64 consecutive objects: a lane derives its object's world box (world_aabb below, the very function the host
+//   export runs) or takes it as given, then a shuffle min / max tree in input order leaves the block's box. Minima and maxima are taken in the total
+//   order of the bit patterns (-0.0 below +0.0), which keeps the block test below conservative under the sign-bit decision; a box with a NaN bound
+//   intersects nothing and stays out of the block box. k_bv_total, one wave: the box around the block boxes.
+// COUNT — k_bv_pair_walk<false>: a wave owns the row block of 64 objects (a row's box per lane, in registers) x one column segment of SEG_BLOCKS
+//   column blocks. Per column block at or right of the diagonal: skipped when the two block boxes lie outside each other (wave-uniform, a scalar
+//   branch); else the 64 column boxes are walked — their addresses depend on the block and the loop counter only, so they arrive by scalar loads, no
+//   LDS — and each lane tests its row, with b > a and the mode's kind filter. Leaves count[segment][row].
+// ROWS, SCAN — k_bv_rows, one lane per row: exclusive prefix over the row's segments in place, and the row's total. k_bv_scan, one workgroup:
+//   exclusive prefix of the row totals, SCAN_ROUND rows a round with a carry. (row, segment) in row-major order IS the lexicographic order of (a, b).
+//   The host reads the grand total (the call's one wait before the emit), grows the pair buffer and launches
+// EMIT — k_bv_pair_walk<true>: the same walk; each lane writes its hits from its own offset in column order.
+// QUERY — k_bv_query, one wave per 64 consecutive objects, a world box per lane: walks the queries (the record's address is wave-uniform: scalar
+//   loads), __ballot is the mask word of (query, tile). k_bv_query_counts, one wave per query: the popcounts of its words.
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "ivx_internal.hpp"
+
+namespace {
+
+constexpr uint32_t SEG_BLOCKS = 8;     // column blocks per segment (512 columns)
+constexpr uint32_t SCAN_ROUND = 1024;  // rows per round of k_bv_scan (its workgroup)
+
+// ---- shared host / device arithmetic (f32, fixed operation order; the file is compiled without contraction) ---------------------------------
+__host__ __device__ __forceinline__ uint32_t f_bits(float v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __float_as_uint(v);
+#else
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    return u;
+#endif
+}
+__host__ __device__ __forceinline__ float f_abs(float v) { return __builtin_fabsf(v); }  // (clears the sign bit)
+
+__host__ __device__ inline void world_aabb(const ivx_aabb& m, const ivx_similarity& s, ivx_aabb* out) {
+    const float c[3] = {0.5f * (m.lower[0] + m.upper[0]), 0.5f * (m.lower[1] + m.upper[1]), 0.5f * (m.lower[2] + m.upper[2])};
+    const float h[3] = {0.5f * (m.upper[0] - m.lower[0]), 0.5f * (m.upper[1] - m.lower[1]), 0.5f * (m.upper[2] - m.lower[2])};
+    const float x = s.rotation[0], y = s.rotation[1], z = s.rotation[2], w = s.rotation[3];
+    const float xx = x * x, yy = y * y, zz = z * z, ww = w * w;
+    const float n2 = ((xx + yy) + zz) + ww;
+    const float xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+    const float N[3][3] = {{((ww + xx) - yy) - zz, 2.0f * (xy - wz), 2.0f * (xz + wy)},
+                           {2.0f * (xy + wz), ((ww - xx) + yy) - zz, 2.0f * (yz - wx)},
+                           {2.0f * (xz - wy), 2.0f * (yz + wx), ((ww - xx) - yy) + zz}};
+    for (int i = 0; i < 3; ++i) {
+        const float m0 = s.scaling * (N[i][0] / n2), m1 = s.scaling * (N[i][1] / n2), m2 = s.scaling * (N[i][2] / n2);
+        const float ct = ((m0 * c[0] + m1 * c[1]) + m2 * c[2]) + s.translation[i];
+        const float ht = (f_abs(m0) * h[0] + f_abs(m1) * h[1]) + f_abs(m2) * h[2];
+        out->lower[i] = ct - ht;
+        out->upper[i] = ct + ht;
+    }
+}
+
+// ---- device side -------------------------------------------------------------------------------------------------------------------------
+// "has its sign bit set, or is a NaN" for any of six differences
+__device__ __forceinline__ bool any_negative(float d0, float d1, float d2, float d3, float d4, float d5) {
+    const uint32_t bits = ((__float_as_uint(d0) | __float_as_uint(d1)) | (__float_as_uint(d2) | __float_as_uint(d3))) | (__float_as_uint(d4) | __float_as_uint(d5));
+    const bool nan = __builtin_isunordered(d0, d1) || __builtin_isunordered(d2, d3) || __builtin_isunordered(d4, d5);
+    return (bits >> 31) != 0u || nan;
+}
+// box_lies_outside
+__device__ __forceinline__ bool lies_outside(const ivx_aabb& self, const ivx_aabb& other) {
+    return any_negative(other.upper[0] - self.lower[0], other.upper[1] - self.lower[1], other.upper[2] - self.lower[2], self.upper[0] - other.lower[0],
+                        self.upper[1] - other.lower[1], self.upper[2] - other.lower[2]);
+}
+// the bit pattern of a float as a signed integer that orders like the float, with -0.0 below +0.0
+__device__ __forceinline__ int32_t order_key(float v) {
+    const int32_t b = (int32_t)__float_as_uint(v);
+    return b < 0 ? (int32_t)((uint32_t)b ^ 0x7FFFFFFFu) : b;
+}
+__device__ __forceinline__ float order_min(float a, float b) { return order_key(b) < order_key(a) ? b : a; }
+__device__ __forceinline__ float order_max(float a, float b) { return order_key(b) > order_key(a) ? b : a; }
+__device__ __forceinline__ bool has_nan(const ivx_aabb& b) {
+    return __builtin_isunordered(b.lower[0], b.lower[1]) || __builtin_isunordered(b.lower[2], b.upper[0]) || __builtin_isunordered(b.upper[1], b.upper[2]);
+}
+// the box that is outside everything and neutral under order_min / order_max
+__device__ __forceinline__ ivx_aabb neutral_box() {
+    ivx_aabb b;
+    for (int k = 0; k < 3; ++k) b.lower[k] = INFINITY, b.upper[k] = -INFINITY;
+    return b;
+}
+// min / max over the wave, lane l with lane l ^ d, d = 1, 2, .. 32: every lane ends with the result
+__device__ __forceinline__ ivx_aabb wave_union(ivx_aabb b) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            b.lower[k] = order_min(b.lower[k], __shfl_xor(b.lower[k], d, 64));
+            b.upper[k] = order_max(b.upper[k], __shfl_xor(b.upper[k], d, 64));
+        }
+    return b;
+}
+__device__ __forceinline__ uint32_t wave_index() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6))); }
+
+template <bool DERIVE>
+__global__ __launch_bounds__(256) void k_bv_world(const ivx_aabb* __restrict__ model, const ivx_similarity* __restrict__ sims, uint32_t n, ivx_aabb* __restrict__ world,
+                                                  ivx_aabb* __restrict__ blocks) {
+    const uint32_t lane = threadIdx.x & 63u, blk = wave_index();
+    if (blk * 64u >= n) return;  // (whole waves)
+    const uint32_t o = blk * 64u + lane;
+    ivx_aabb b = neutral_box();
+    if (o < n) {
+        if (DERIVE) world_aabb(model[o], sims[o], &b);
+        else b = model[o];
+    }
+    world[o] = b;  // (the buffer holds whole blocks: the slots behind n get the neutral box, which the pair walk reads and finds outside)
+    if (has_nan(b)) b = neutral_box();
+    b = wave_union(b);
+    if (lane == 0u) blocks[blk] = b;
+}
+
+__global__ __launch_bounds__(64) void k_bv_total(const ivx_aabb* __restrict__ blocks, uint32_t n_blocks, ivx_aabb* __restrict__ total) {
+    const uint32_t lane = threadIdx.x;
+    ivx_aabb t = neutral_box();
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64u)
+        if (b0 + lane < n_blocks) {
+            const ivx_aabb b = blocks[b0 + lane];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) t.lower[k] = order_min(t.lower[k], b.lower[k]), t.upper[k] = order_max(t.upper[k], b.upper[k]);
+        }
+    t = wave_union(t);
+    if (order_key(t.lower[0]) > order_key(t.upper[0]))  // no box without a NaN bound at all
+        for (int k = 0; k < 3; ++k) t.lower[k] = 0.0f, t.upper[k] = 0.0f;
+    if (lane == 0u) *total = t;
+}
+
+// counts: [n_seg][n]. EMIT: counts hold the exclusive prefix over a row's segments, row_base the exclusive prefix of the row totals
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_bv_pair_walk(const ivx_aabb* __restrict__ world, const uint32_t* __restrict__ kinds, const ivx_aabb* __restrict__ blocks, uint32_t n,
+                                                      uint32_t n_blocks, uint32_t n_seg, uint32_t mode, uint32_t* __restrict__ counts, const uint32_t* __restrict__ row_base,
+                                                      uint2* __restrict__ pairs) {
+    const uint32_t lane = threadIdx.x & 63u, w = wave_index();
+    if (w >= n_blocks * n_seg) return;  // (whole waves; n_blocks x n_seg <= 2^14 x 2^11)
+    const uint32_t rb = w / n_seg, seg = w - rb * n_seg;
+    const uint32_t cb_end = min(n_blocks, (seg + 1u) * SEG_BLOCKS);
+    if (cb_end <= rb) return;  // wholly left of the diagonal: k_bv_rows starts behind these segments
+    const uint32_t row = rb * 64u + lane;
+    const bool live = row < n;
+    ivx_aabb self = neutral_box();
+    uint32_t row_kind = 0u;
+    if (live) self = world[row], row_kind = kinds[row];
+    const bool row_ok = live & ((mode == 0u) | (row_kind != IVX_BV_PHANTOM));
+    const size_t slot = (size_t)seg * n + row;
+    uint32_t count = 0u, at = 0u;
+    if (EMIT && live) at = row_base[row] + counts[slot];
+    const ivx_aabb row_block = blocks[rb];
+    for (uint32_t cb = max(seg * SEG_BLOCKS, rb); cb < cb_end; ++cb) {
+        const ivx_aabb col_block = blocks[cb];
+        if (lies_outside(row_block, col_block)) continue;  // wave-uniform
+        const uint32_t b0 = cb * 64u;
+#pragma unroll 8
+        for (uint32_t j = 0; j < 64u; ++j) {  // (whole blocks: see k_bv_world)
+            const uint32_t b = b0 + j;
+            const ivx_aabb other = world[b];  // (uniform address)
+            const uint32_t col_kind = kinds[b];
+            const bool kinds_ok = (mode == 0u) | ((col_kind != IVX_BV_PHANTOM) & ((col_kind == IVX_BV_DYNAMIC) | (row_kind == IVX_BV_DYNAMIC)));
+            const bool hit = (b > row) & row_ok & kinds_ok & !lies_outside(self, other);
+            if (EMIT) {
+                if (hit) pairs[at++] = make_uint2(row, b);
+            } else {
+                count += hit ? 1u : 0u;
+            }
+        }
+    }
+    if (!EMIT && live) counts[slot] = count;
+}
+
+__global__ __launch_bounds__(256) void k_bv_rows(uint32_t* __restrict__ counts, uint32_t n, uint32_t n_seg, uint32_t* __restrict__ row_total) {
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+    if (row >= n) return;
+    uint32_t run = 0u;
+    for (uint32_t seg = (row >> 6) / SEG_BLOCKS; seg < n_seg; ++seg) {
+        const size_t slot = (size_t)seg * n + row;
+        const uint32_t c = counts[slot];
+        counts[slot] = run;
+        run += c;
+    }
+    row_total[row] = run;
+}
+
+// in place: row_total -> exclusive prefix (mod 2^32; the host refuses a grand total of 2^31 or more before anything reads it)
+__global__ __launch_bounds__(SCAN_ROUND) void k_bv_scan(uint32_t* __restrict__ row_total, uint32_t n, unsigned long long* __restrict__ grand_total) {
+    __shared__ uint32_t wave_totals[SCAN_ROUND / 64u];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+    unsigned long long carry = 0ull;
+    for (uint32_t r0 = 0; r0 < n; r0 += SCAN_ROUND) {
+        const uint32_t row = r0 + t;
+        const uint32_t c = row < n ? row_total[row] : 0u;
+        uint32_t incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        if (lane == 63u) wave_totals[wv] = incl;
+        __syncthreads();
+        uint32_t before = 0u, round_total = 0u;
+        for (uint32_t k = 0; k < SCAN_ROUND / 64u; ++k) {
+            const uint32_t wt = wave_totals[k];
+            before += k < wv ? wt : 0u;
+            round_total += wt;
+        }
+        if (row < n) row_total[row] = (uint32_t)carry + before + (incl - c);
+        carry += round_total;
+        __syncthreads();
+    }
+    if (t == 0u) *grand_total = carry;
+}
+
+__device__ __forceinline__ bool query_hits(const ivx_bv_query* __restrict__ q, const ivx_aabb& b, const float c[3], const float h[3]) {
+    switch (q->kind) {  // (uniform)
+        case IVX_BV_QUERY_BOX: {
+            ivx_aabb self;
+            for (int k = 0; k < 3; ++k) self.lower[k] = q->u.box.lower[k], self.upper[k] = q->u.box.upper[k];
+            return !lies_outside(self, b);
+        }
+        case IVX_BV_QUERY_SPHERE: {
+            float s = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float ck = q->u.sphere.center[k];
+                if (b.upper[k] < ck) {
+                    const float d = ck - b.upper[k];
+                    s += d * d;
+                } else if (b.lower[k] > ck) {
+                    const float d = b.lower[k] - ck;
+                    s += d * d;
+                }
+            }
+            return !(s > q->u.sphere.radius * q->u.sphere.radius);
+        }
+        case IVX_BV_QUERY_FRUSTUM: {
+            bool hit = true;
+#pragma unroll
+            for (int p = 0; p < 6; ++p) {
+                const uint32_t corner = q->u.frustum.corners[p];
+                const float px = (corner & 4u) ? b.upper[0] : b.lower[0], py = (corner & 2u) ? b.upper[1] : b.lower[1], pz = (corner & 1u) ? b.upper[2] : b.lower[2];
+                const float dist = ((q->u.frustum.planes[p][0] * px + q->u.frustum.planes[p][1] * py) + q->u.frustum.planes[p][2] * pz) - q->u.frustum.planes[p][3];
+                hit = hit && dist >= 0.0f;
+            }
+            return hit;
+        }
+        default: {  // IVX_BV_QUERY_ORIENTED_BOX
+            const float dx = c[0] - q->u.oriented_box.center[0], dy = c[1] - q->u.oriented_box.center[1], dz = c[2] - q->u.oriented_box.center[2];
+            float diff[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float a0 = q->u.oriented_box.axes[a][0], a1 = q->u.oriented_box.axes[a][1], a2 = q->u.oriented_box.axes[a][2];
+                const float e = ((f_abs(a0) * h[0] + f_abs(a1) * h[1]) + f_abs(a2) * h[2]) + q->u.oriented_box.half_extents[a];
+                const float l = (a0 * dx + a1 * dy) + a2 * dz;
+                diff[a] = e - f_abs(l);
+            }
+            return !any_negative(diff[0], diff[1], diff[2], 0.0f, 0.0f, 0.0f);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bv_query(const ivx_aabb* __restrict__ world, uint32_t n, const ivx_bv_query* __restrict__ queries, uint32_t n_queries,
+                                                  unsigned long long* __restrict__ masks) {
+    const uint32_t lane = threadIdx.x & 63u, tile = wave_index();
+    const uint32_t n_words = (n + 63u) / 64u;
+    if (tile >= n_words) return;  // (whole waves)
+    const uint32_t o = tile * 64u + lane;
+    const bool live = o < n;
+    ivx_aabb b = neutral_box();
+    if (live) b = world[o];
+    const float c[3] = {0.5f * (b.lower[0] + b.upper[0]), 0.5f * (b.lower[1] + b.upper[1]), 0.5f * (b.lower[2] + b.upper[2])};
+    const float h[3] = {0.5f * (b.upper[0] - b.lower[0]), 0.5f * (b.upper[1] - b.lower[1]), 0.5f * (b.upper[2] - b.lower[2])};
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        const bool hit = live && query_hits(queries + q, b, c, h);
+        const unsigned long long mask = __ballot(hit);
+        if (lane == 0u) masks[(size_t)q * n_words + tile] = mask;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_bv_query_counts(const unsigned long long* __restrict__ masks, uint32_t n_words, uint32_t* __restrict__ counts) {
+    const uint32_t lane = threadIdx.x, q = blockIdx.x;
+    const unsigned long long* __restrict__ m = masks + (size_t)q * n_words;
+    uint32_t c = 0u;
+    for (uint32_t w0 = 0; w0 < n_words; w0 += 64u)
+        if (w0 + lane < n_words) c += (uint32_t)__popcll(m[w0 + lane]);
+    c = ivx_wave_sum(c);
+    if (lane == 0u) counts[q] = c;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// context-owned state: device buffers that only grow, a pinned staging block for the one upload of a call, and the set the context holds
+struct BvState {
+    Buf set;      // input boxes | similarities || kinds | world boxes | block boxes | total  (the part before || is the upload's scratch)
+    Buf scratch;  // pairs: counts | row totals | grand total;  queries: records | counts
+    Buf pairs, masks;
+    void* staging = nullptr;  // pinned
+    size_t staging_bytes = 0;
+    hipEvent_t staged = nullptr;  // behind the last upload from `staging`
+    bool staged_pending = false;
+    bool has_set = false;
+    uint32_t n = 0;
+    size_t o_kinds = 0, o_world = 0, o_blocks = 0, o_total = 0;
+};
+
+struct Layout {
+    size_t bytes = 0;
+    size_t take(size_t n) {
+        const size_t at = bytes;
+        bytes += (n + 255u) & ~(size_t)255u;
+        return at;
+    }
+};
+
+int state_of(ivx_ctx* c, BvState** out) {
+    if (!c->bvol_state) {
+        BvState* s = new (std::nothrow) BvState();
+        IVX_REQUIRE(s, IVX_ERR_CAPACITY, "bounding volumes: out of host memory");
+        const hipError_t e = hipEventCreateWithFlags(&s->staged, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            delete s;
+            ivx_set_error("bounding volumes: %s", hipGetErrorString(e));
+            return IVX_ERR_HIP;
+        }
+        c->bvol_state = s;
+    }
+    *out = static_cast<BvState*>(c->bvol_state);
+    return IVX_OK;
+}
+
+int grow(ivx_ctx* c, Buf* b, size_t bytes, size_t floor_bytes) {
+    if (b->bytes >= bytes) return IVX_OK;
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    if (b->p) (void)hipFree(b->p);
+    b->p = nullptr, b->bytes = 0;
+    bytes = bytes + bytes / 2;
+    if (bytes < floor_bytes) bytes = floor_bytes;
+    IVX_HIP_CHECK(hipMalloc(&b->p, bytes));
+    b->bytes = bytes;
+    return IVX_OK;
+}
+
+int staging_for(BvState* st, size_t bytes) {
+    if (st->staged_pending) {  // the last call's upload has left the block
+        IVX_HIP_CHECK(hipEventSynchronize(st->staged));
+        st->staged_pending = false;
+    }
+    if (st->staging_bytes >= bytes) return IVX_OK;
+    if (st->staging) (void)hipHostFree(st->staging);
+    st->staging = nullptr, st->staging_bytes = 0;
+    bytes = bytes + bytes / 2;
+    if (bytes < (1u << 16)) bytes = 1u << 16;
+    IVX_HIP_CHECK(hipHostMalloc(&st->staging, bytes, hipHostMallocDefault));
+    st->staging_bytes = bytes;
+    return IVX_OK;
+}
+
+int check_set_arguments(const char* who, const ivx_similarity* sims, const uint32_t* kinds, size_t n) {
+    IVX_REQUIRE(n <= IVX_BV_MAX_OBJECTS, IVX_ERR_CAPACITY, "%s: %zu objects exceed %u", who, n, IVX_BV_MAX_OBJECTS);
+    for (size_t o = 0; o < n && sims; ++o)
+        IVX_REQUIRE(sims[o].scaling > 0.0f, IVX_ERR_INVALID, "%s: the scaling %g of object %zu is not positive", who, (double)sims[o].scaling, o);
+    for (size_t o = 0; o < n && kinds; ++o)
+        IVX_REQUIRE(kinds[o] <= IVX_BV_PHANTOM, IVX_ERR_INVALID, "%s: object %zu has kind %u (0 dynamic, 1 static, 2 phantom)", who, o, kinds[o]);
+    return IVX_OK;
+}
+
+int set_enqueue(ivx_ctx* c, const ivx_aabb* boxes, const ivx_similarity* sims, const uint32_t* kinds, size_t n) {
+    BvState* st;
+    if (int rc = state_of(c, &st)) return rc;
+    st->has_set = false, st->n = 0;  // (until this call's set stands)
+    if (n == 0) {
+        st->has_set = true;
+        return IVX_OK;
+    }
+    const size_t n_blocks = (n + 63u) / 64u;
+    Layout l;
+    const size_t o_in = l.take(n * sizeof(ivx_aabb)), o_sims = l.take(sims ? n * sizeof(ivx_similarity) : 0), o_kinds = l.take(n_blocks * 64u * 4);  // (kinds and world boxes: whole blocks)
+    const size_t upload_bytes = l.bytes;
+    const size_t o_world = l.take(n_blocks * 64u * sizeof(ivx_aabb)), o_blocks = l.take(n_blocks * sizeof(ivx_aabb)), o_total = l.take(sizeof(ivx_aabb));
+    if (int rc = staging_for(st, upload_bytes)) return rc;
+    if (int rc = grow(c, &st->set, l.bytes, 1u << 16)) return rc;
+    char* h = static_cast<char*>(st->staging);
+    char* d = static_cast<char*>(st->set.p);
+    memcpy(h + o_in, boxes, n * sizeof(ivx_aabb));
+    if (sims) memcpy(h + o_sims, sims, n * sizeof(ivx_similarity));
+    memset(h + o_kinds, 0, n_blocks * 64u * 4);
+    if (kinds) memcpy(h + o_kinds, kinds, n * 4);
+    IVX_HIP_CHECK(ivx_memcpy_async(d, h, upload_bytes, hipMemcpyHostToDevice, c->stream));
+    IVX_HIP_CHECK(ivx_event_record(st->staged, c->stream));
+    st->staged_pending = true;
+    const dim3 grid((uint32_t)((n_blocks + 3u) / 4u));
+    ivx_aabb* d_world = reinterpret_cast<ivx_aabb*>(d + o_world);
+    ivx_aabb* d_blocks = reinterpret_cast<ivx_aabb*>(d + o_blocks);
+    if (sims)
+        IVX_KLAUNCH(k_bv_world<true>, grid, dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(d + o_in), reinterpret_cast<const ivx_similarity*>(d + o_sims), (uint32_t)n,
+                    d_world, d_blocks);
+    else
+        IVX_KLAUNCH(k_bv_world<false>, grid, dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(d + o_in), (const ivx_similarity*)nullptr, (uint32_t)n, d_world, d_blocks);
+    IVX_KLAUNCH(k_bv_total, dim3(1), dim3(64), 0, c->stream, (const ivx_aabb*)d_blocks, (uint32_t)n_blocks, reinterpret_cast<ivx_aabb*>(d + o_total));
+    IVX_HIP_CHECK(hipGetLastError());
+    st->o_kinds = o_kinds, st->o_world = o_world, st->o_blocks = o_blocks, st->o_total = o_total;
+    st->n = (uint32_t)n, st->has_set = true;
+    return IVX_OK;
+}
+
+int model_aabb(ivx_grid* g, const char* who, ivx_aabb* out) {
+    uint32_t occ[12];
+    if (int rc = ivx_reference_occupied(g, who, occ)) return rc;
+    bool empty = false;
+    for (int d = 0; d < 3; ++d) empty = empty || occ[6 + 2 * d] >= occ[7 + 2 * d];
+    for (int d = 0; d < 3; ++d) {
+        out->lower[d] = empty ? 0.0f : (float)occ[6 + 2 * d] * g->extent;
+        out->upper[d] = empty ? 0.0f : (float)occ[7 + 2 * d] * g->extent;
+    }
+    return IVX_OK;
+}
+
+int set_state(ivx_ctx* c, const char* who, BvState** out) {
+    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
+    BvState* st = static_cast<BvState*>(c->bvol_state);
+    IVX_REQUIRE(st && st->has_set, IVX_ERR_STATE, "%s: the context holds no set of bounding volumes (call ivx_bv_set or ivx_bv_set_grids first)", who);
+    *out = st;
+    return IVX_OK;
+}
+
+}  // namespace
+
+void ivx_bvol_release(ivx_ctx* c) {
+    if (!c || !c->bvol_state) return;
+    BvState* s = static_cast<BvState*>(c->bvol_state);
+    for (Buf* b : {&s->set, &s->scratch, &s->pairs, &s->masks})
+        if (b->p) (void)hipFree(b->p);
+    if (s->staging) (void)hipHostFree(s->staging);
+    if (s->staged) (void)hipEventDestroy(s->staged);
+    delete s;
+    c->bvol_state = nullptr;
+}
+
+extern "C" {
+
+int ivx_bv_world_aabb(const ivx_aabb* model, const ivx_similarity* similarity, ivx_aabb* out) {
+    IVX_REQUIRE(model && similarity && out, IVX_ERR_INVALID, "ivx_bv_world_aabb: null argument");
+    IVX_REQUIRE(similarity->scaling > 0.0f, IVX_ERR_INVALID, "ivx_bv_world_aabb: the scaling %g is not positive", (double)similarity->scaling);
+    ivx_aabb b;
+    world_aabb(*model, *similarity, &b);
+    *out = b;
+    return IVX_OK;
+}
+
+int ivx_bv_frustum_query(const float planes[6][4], ivx_bv_query* out) {
+    IVX_REQUIRE(planes && out, IVX_ERR_INVALID, "ivx_bv_frustum_query: null argument");
+    memset(out, 0, sizeof(*out));
+    out->kind = IVX_BV_QUERY_FRUSTUM;
+    for (int p = 0; p < 6; ++p) {
+        for (int k = 0; k < 4; ++k) out->u.frustum.planes[p][k] = planes[p][k];
+        out->u.frustum.corners[p] = (((f_bits(planes[p][0]) >> 31) ^ 1u) << 2) | (((f_bits(planes[p][1]) >> 31) ^ 1u) << 1) | ((f_bits(planes[p][2]) >> 31) ^ 1u);
+    }
+    return IVX_OK;
+}
+
+int ivx_grid_model_aabb(ivx_grid* g, ivx_aabb* out) {
+    IVX_REQUIRE(g && out, IVX_ERR_INVALID, "ivx_grid_model_aabb: null argument");
+    ivx_many_other_context other_(g->ctx);
+    return model_aabb(g, "ivx_grid_model_aabb", out);
+}
+
+int ivx_bv_set(ivx_ctx* c, const ivx_aabb* model_boxes, const ivx_similarity* similarities, const uint32_t* kinds, size_t n) {
+    IVX_REQUIRE(c, IVX_ERR_INVALID, "ivx_bv_set: null context");
+    IVX_REQUIRE(model_boxes || n == 0, IVX_ERR_INVALID, "ivx_bv_set: null boxes");
+    if (int rc = check_set_arguments("ivx_bv_set", similarities, kinds, n)) return rc;
+    ivx_many_other_context other_(c);
+    return set_enqueue(c, model_boxes, similarities, kinds, n);
+}
+
+int ivx_bv_set_grids(ivx_grid* const* grids, size_t n, const ivx_similarity* similarities, const uint32_t* kinds) {
+    const char* who = "ivx_bv_set_grids";
+    IVX_REQUIRE(grids || n == 0, IVX_ERR_INVALID, "%s: null object list", who);
+    if (int rc = check_set_arguments(who, similarities, kinds, n)) return rc;
+    if (n == 0) return IVX_OK;  // (no object names a context)
+    for (size_t i = 0; i < n; ++i) {
+        IVX_REQUIRE(grids[i], IVX_ERR_INVALID, "%s: object %zu is null", who, i);
+        IVX_REQUIRE(grids[i]->ctx == grids[0]->ctx, IVX_ERR_INVALID, "%s: object %zu belongs to another context", who, i);
+    }
+    ivx_ctx* c = grids[0]->ctx;
+    ivx_many_other_context other_(c);
+    (void)ivx_many_break();  // the ranges below are the objects' after everything recorded so far
+    if (int rc = ivx_many_error(c, false)) {
+        ivx_set_error("%s: a flush of recorded launches failed on this context", who);
+        return rc;
+    }
+    std::vector<ivx_aabb> boxes(n);
+    for (size_t i = 0; i < n; ++i)
+        if (int rc = model_aabb(grids[i], who, &boxes[i])) return rc;
+    return set_enqueue(c, boxes.data(), similarities, kinds, n);
+}
+
+int ivx_bv_download(ivx_ctx* c, ivx_aabb* world_boxes, size_t cap, ivx_aabb* total) {
+    BvState* st;
+    if (int rc = set_state(c, "ivx_bv_download", &st)) return rc;
+    IVX_REQUIRE(!world_boxes || cap >= st->n, IVX_ERR_CAPACITY, "ivx_bv_download: the set has %u boxes, the buffer holds %zu", st->n, cap);
+    if (st->n == 0) {
+        if (total) memset(total, 0, sizeof(*total));
+        return IVX_OK;
+    }
+    ivx_many_other_context other_(c);
+    const char* d = static_cast<const char*>(st->set.p);
+    if (world_boxes) IVX_HIP_CHECK(ivx_memcpy_async(world_boxes, d + st->o_world, (size_t)st->n * sizeof(ivx_aabb), hipMemcpyDeviceToHost, c->stream));
+    if (total) IVX_HIP_CHECK(ivx_memcpy_async(total, d + st->o_total, sizeof(ivx_aabb), hipMemcpyDeviceToHost, c->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    return IVX_OK;
+}
+
+int ivx_bv_pairs(ivx_ctx* c, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n_out) {
+    const char* who = "ivx_bv_pairs";
+    IVX_REQUIRE(n_out, IVX_ERR_INVALID, "%s: null argument", who);
+    *n_out = 0;
+    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
+    IVX_REQUIRE(mode <= IVX_BV_DYNAMIC_PAIRS, IVX_ERR_INVALID, "%s: mode %u (0 = all pairs, 1 = no phantom and at least one dynamic member)", who, mode);
+    IVX_REQUIRE(pairs || cap == 0, IVX_ERR_INVALID, "%s: null pair buffer of capacity %zu", who, cap);
+    BvState* st;
+    if (int rc = set_state(c, who, &st)) return rc;
+    const uint32_t n = st->n;
+    if (n < 2u) return IVX_OK;
+    ivx_many_other_context other_(c);
+    const uint32_t n_blocks = (n + 63u) / 64u, n_seg = (n_blocks + SEG_BLOCKS - 1u) / SEG_BLOCKS;
+    Layout l;
+    const size_t o_counts = l.take((size_t)n_seg * n * 4), o_rows = l.take((size_t)n * 4), o_grand = l.take(8);
+    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
+    char* s = static_cast<char*>(st->scratch.p);
+    const char* d = static_cast<const char*>(st->set.p);
+    const ivx_aabb* d_world = reinterpret_cast<const ivx_aabb*>(d + st->o_world);
+    const ivx_aabb* d_blocks = reinterpret_cast<const ivx_aabb*>(d + st->o_blocks);
+    const uint32_t* d_kinds = reinterpret_cast<const uint32_t*>(d + st->o_kinds);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(s + o_counts);
+    uint32_t* d_rows = reinterpret_cast<uint32_t*>(s + o_rows);
+    unsigned long long* d_grand = reinterpret_cast<unsigned long long*>(s + o_grand);
+    const dim3 walk_grid((uint32_t)(((size_t)n_blocks * n_seg + 3u) / 4u));
+    IVX_KLAUNCH(k_bv_pair_walk<false>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)nullptr, (uint2*)nullptr);
+    IVX_KLAUNCH(k_bv_rows, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, d_counts, n, n_seg, d_rows);
+    IVX_KLAUNCH(k_bv_scan, dim3(1), dim3(SCAN_ROUND), 0, c->stream, d_rows, n, d_grand);
+    IVX_HIP_CHECK(hipGetLastError());
+    unsigned long long grand = 0;
+    IVX_HIP_CHECK(ivx_memcpy_async(&grand, d_grand, 8, hipMemcpyDeviceToHost, c->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    IVX_REQUIRE(grand < (1ull << 31), IVX_ERR_CAPACITY, "%s: %llu intersecting pairs: too many for one call", who, grand);
+    *n_out = (size_t)grand;
+    IVX_REQUIRE(!pairs || grand <= cap, IVX_ERR_CAPACITY, "%s: %llu intersecting pairs, the buffer holds %zu", who, grand, cap);
+    if (grand == 0) return IVX_OK;
+    if (int rc = grow(c, &st->pairs, (size_t)grand * 8, 1u << 16)) return rc;
+    IVX_KLAUNCH(k_bv_pair_walk<true>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)d_rows,
+                static_cast<uint2*>(st->pairs.p));
+    IVX_HIP_CHECK(hipGetLastError());
+    if (pairs) IVX_HIP_CHECK(ivx_memcpy_async(pairs, st->pairs.p, (size_t)grand * 8, hipMemcpyDeviceToHost, c->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    return IVX_OK;
+}
+
+int ivx_bv_queries(ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, uint32_t* counts) {
+    const char* who = "ivx_bv_queries";
+    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
+    IVX_REQUIRE(n_queries <= IVX_BV_MAX_QUERIES, IVX_ERR_CAPACITY, "%s: %zu queries exceed %u per call", who, n_queries, IVX_BV_MAX_QUERIES);
+    IVX_REQUIRE(queries || n_queries == 0, IVX_ERR_INVALID, "%s: null queries", who);
+    for (size_t q = 0; q < n_queries; ++q)
+        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    BvState* st;
+    if (int rc = set_state(c, who, &st)) return rc;
+    if (n_queries == 0) return IVX_OK;
+    const uint32_t n = st->n, n_words = (n + 63u) / 64u;
+    if (n == 0) {
+        for (size_t q = 0; q < n_queries && counts; ++q) counts[q] = 0u;
+        return IVX_OK;
+    }
+    IVX_REQUIRE(masks, IVX_ERR_INVALID, "%s: null mask buffer", who);
+    ivx_many_other_context other_(c);
+    Layout l;
+    const size_t o_q = l.take(n_queries * sizeof(ivx_bv_query)), o_c = l.take(n_queries * 4);
+    if (int rc = staging_for(st, n_queries * sizeof(ivx_bv_query))) return rc;
+    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
+    const size_t mask_bytes = n_queries * (size_t)n_words * 8;
+    if (int rc = grow(c, &st->masks, mask_bytes, 1u << 16)) return rc;
+    char* s = static_cast<char*>(st->scratch.p);
+    memcpy(st->staging, queries, n_queries * sizeof(ivx_bv_query));
+    IVX_HIP_CHECK(ivx_memcpy_async(s + o_q, st->staging, n_queries * sizeof(ivx_bv_query), hipMemcpyHostToDevice, c->stream));
+    IVX_HIP_CHECK(ivx_event_record(st->staged, c->stream));
+    st->staged_pending = true;
+    unsigned long long* d_masks = static_cast<unsigned long long*>(st->masks.p);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(s + o_c);
+    IVX_KLAUNCH(k_bv_query, dim3((n_words + 3u) / 4u), dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(static_cast<const char*>(st->set.p) + st->o_world), n,
+                reinterpret_cast<const ivx_bv_query*>(s + o_q), (uint32_t)n_queries, d_masks);
+    IVX_KLAUNCH(k_bv_query_counts, dim3((uint32_t)n_queries), dim3(64), 0, c->stream, (const unsigned long long*)d_masks, n_words, d_counts);
+    IVX_HIP_CHECK(hipGetLastError());
+    IVX_HIP_CHECK(ivx_memcpy_async(masks, d_masks, mask_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (counts) IVX_HIP_CHECK(ivx_memcpy_async(counts, d_counts, n_queries * 4, hipMemcpyDeviceToHost, c->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    return IVX_OK;
+}
+
+void* ivx_bv_device_ptr(ivx_ctx* c, int which) {
+    if (!c || !c->bvol_state) return nullptr;
+    BvState* st = static_cast<BvState*>(c->bvol_state);
+    switch (which) {
+        case IVX_BV_PTR_WORLD_BOXES: return st->has_set && st->n ? static_cast<char*>(st->set.p) + st->o_world : nullptr;
+        case IVX_BV_PTR_PAIRS: return st->pairs.p;
+        case IVX_BV_PTR_MASKS: return st->masks.p;
+        default: return nullptr;
+    }
+}
+
+}  // extern "C"

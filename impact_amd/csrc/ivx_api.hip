@@ -298,6 +298,11 @@ static int reference_occupied(ivx_grid* g, uint32_t occ[12]) {
     return IVX_OK;
 }
 
+int ivx_reference_occupied(ivx_grid* g, const char* who, uint32_t occ[12]) {
+    IVX_REQUIRE(g->occ_ref_valid || g->bbox_valid, IVX_ERR_STATE, "%s: the object holds no occupied ranges yet (call ivx_derive_state or a step first)", who);
+    return reference_occupied(g, occ);
+}
+
 struct ivx_range_allocator {
     std::map<size_t, size_t> free_ranges;  // start -> end; a second range with the same start is dropped, as BTreeSet::insert does
     void free_range(size_t a, size_t b) {
@@ -476,6 +481,7 @@ void ivx_shutdown(ivx_ctx* c) {
     if (c->dev_scratch) (void)hipFree(c->dev_scratch);
     if (c->drag_scratch) (void)hipFree(c->drag_scratch);
     ivx_cull_release(c);
+    ivx_bvol_release(c);
     if (c->aux_stream) {
         (void)hipStreamSynchronize(c->aux_stream);
         (void)hipStreamDestroy(c->aux_stream);

@@ -10,6 +10,7 @@
 //   for_each_*_voxel_object_contact          impact_voxel/src/collidable.rs:859-1286
 //   perform_physics_step / ConstraintSolver  impact_physics/src/lib.rs:31-110
 //   CullingFrustum / VoxelChunkCullingPass   impact_voxel/src/mesh.rs:638-696, render_commands.rs:392-589
+//   IntersectionManager (BoundingVolumeSet)  impact_intersection/src/lib.rs:39-150
 // Errors: every C status other than IVX_OK becomes an impact_voxel::Error carrying ivx_last_error() — where the reference would
 // return Err or panic on a violated precondition. Nothing here computes: it owns handles, sizes buffers and forwards.
 #pragma once
@@ -406,6 +407,70 @@ private:
         for (VoxelObject* o : objects) g.push_back(o->handle());
         return g;
     }
+    Context* ctx_;
+};
+
+// ---- bounding volumes (impact_intersection/src/lib.rs): world boxes, all intersecting pairs, region queries --------------------------------
+// add_bounding_volume_to_hierarchy's box: aabb_of_transformed of the model box under the similarity
+inline ivx_aabb world_aabb(const ivx_aabb& model, const ivx_similarity& model_to_world) {
+    ivx_aabb out{};
+    check(ivx_bv_world_aabb(&model, &model_to_world, &out));
+    return out;
+}
+// the flat form of the IntersectionManager: one set of world boxes per context, resident on the device until the next `set`
+class BoundingVolumeSet {
+public:
+    explicit BoundingVolumeSet(Context& ctx) : ctx_(&ctx) {}
+    // `similarities` empty: the boxes are world boxes already; `kinds` empty: all dynamic (IVX_BV_DYNAMIC / _STATIC / _PHANTOM)
+    void set(const std::vector<ivx_aabb>& model_boxes, const std::vector<ivx_similarity>& similarities = {}, const std::vector<uint32_t>& kinds = {}) {
+        check(ivx_bv_set(ctx_->handle(), model_boxes.data(), similarities.empty() ? nullptr : similarities.data(), kinds.empty() ? nullptr : kinds.data(), model_boxes.size()));
+    }
+    // sync_voxel_object_bounding_volume for every object, then the same
+    void set(const std::vector<VoxelObject*>& objects, const std::vector<ivx_similarity>& similarities = {}, const std::vector<uint32_t>& kinds = {}) {
+        std::vector<ivx_grid*> g;
+        for (VoxelObject* o : objects) g.push_back(o->handle());
+        check(ivx_bv_set_grids(g.data(), g.size(), similarities.empty() ? nullptr : similarities.data(), kinds.empty() ? nullptr : kinds.data()));
+    }
+    static ivx_aabb model_aabb(VoxelObject& object) {
+        ivx_aabb out{};
+        check(ivx_grid_model_aabb(object.handle(), &out));
+        return out;
+    }
+    std::vector<ivx_aabb> world_boxes(size_t n) {
+        std::vector<ivx_aabb> out(n);
+        check(ivx_bv_download(ctx_->handle(), out.data(), out.size(), nullptr));
+        return out;
+    }
+    ivx_aabb total_bounding_volume() {
+        ivx_aabb out{};
+        check(ivx_bv_download(ctx_->handle(), nullptr, 0, &out));
+        return out;
+    }
+    // for_each_intersecting_bounding_volume_pair: (a, b), a < b, sorted; mode IVX_BV_ALL_PAIRS or IVX_BV_DYNAMIC_PAIRS
+    std::vector<std::array<uint32_t, 2>> intersecting_pairs(uint32_t mode = IVX_BV_ALL_PAIRS) {
+        std::vector<std::array<uint32_t, 2>> out;
+        size_t n = 0;
+        int rc = ivx_bv_pairs(ctx_->handle(), mode, nullptr, 0, &n);  // (counts, and leaves the pairs on the device)
+        check(rc);
+        out.resize(n);
+        if (n) check(ivx_bv_pairs(ctx_->handle(), mode, &out[0][0], out.size(), &n));
+        return out;
+    }
+    // for_each_bounding_volume_in_axis_aligned_box / _in_sphere / _maybe_in_frustum / _maybe_in_oriented_box: ceil(n / 64) mask words per query
+    std::vector<uint64_t> query(const std::vector<ivx_bv_query>& queries, size_t n_objects, std::vector<uint32_t>* counts = nullptr) {
+        std::vector<uint64_t> masks(queries.size() * ((n_objects + 63) / 64));
+        if (counts) counts->resize(queries.size());
+        check(ivx_bv_queries(ctx_->handle(), queries.data(), queries.size(), masks.data(), counts ? counts->data() : nullptr));
+        return masks;
+    }
+    static ivx_bv_query frustum_query(const float planes[6][4]) {
+        ivx_bv_query q{};
+        check(ivx_bv_frustum_query(planes, &q));
+        return q;
+    }
+    void* device_ptr(int which) const { return ivx_bv_device_ptr(ctx_->handle(), which); }
+
+private:
     Context* ctx_;
 };
 

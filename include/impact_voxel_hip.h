@@ -929,6 +929,123 @@ int ivx_cull_many_frusta(ivx_grid* const* grids, size_t n, const ivx_cull_object
 int ivx_cull_download(ivx_ctx*, uint32_t view, void* args, size_t args_bytes, ivx_cull_count* count, ivx_culling_frustum* frusta, size_t n_frusta);
 void* ivx_cull_device_ptr(ivx_ctx*, int which);
 
+/* ---- bounding volumes: world boxes, all intersecting pairs, region queries (impact_intersection/src/lib.rs IntersectionManager;
+ * impact_geometry/src/axis_aligned_box.rs, sphere.rs, frustum.rs, oriented_box.rs; impact_physics/src/collision.rs:215-349) ----
+ * What the batched calls above take as input and nothing else here produced: the pairs of ivx_*_contacts_many (ivx_bv_pairs), the objects an absorber
+ * touches (ivx_bv_queries with a box or a sphere), the per-(view, object) IVX_CULL_PAIR_SKIP bit (ivx_bv_queries with frusta / oriented boxes).
+ * No hierarchy: the pair pass is the exact upper triangle (the reference's own `_brute_force` form), csrc/bvol.hip. */
+/* AxisAlignedBoxC. 24 bytes. */
+typedef struct {
+    float lower[3], upper[3];
+} ivx_aabb;
+/* A model-to-world similarity: rotation quaternion xyzw, translation, scaling — the leading fields of ivx_cull_pair, with the same meaning. 32 bytes. */
+typedef struct {
+    float rotation[4];
+    float translation[3];
+    float scaling;
+} ivx_similarity;
+/* CollidableKind (ivx_bv_set's `kinds`; NULL: all dynamic) */
+#define IVX_BV_DYNAMIC 0u
+#define IVX_BV_STATIC 1u
+#define IVX_BV_PHANTOM 2u
+/* ivx_bv_query.kind */
+#define IVX_BV_QUERY_BOX 0u
+#define IVX_BV_QUERY_SPHERE 1u
+#define IVX_BV_QUERY_FRUSTUM 2u
+#define IVX_BV_QUERY_ORIENTED_BOX 3u
+/* One region of world space. 128 bytes: the kind, then 31 words of which the kind's member uses the leading ones (the rest is ignored).
+ * frustum: planes in world space (unit normal xyz, displacement) and per plane the box corner with the largest signed distance, in the convention of
+ * ivx_culling_frustum.most_inside_corners (bit 2 / 1 / 0 = upper x / y / z); ivx_bv_frustum_query fills both.
+ * oriented_box: axes[a] = row a of the rotation from world space into the box frame, the box's centre in world space, its half extents. */
+typedef struct {
+    uint32_t kind;
+    union {
+        struct {
+            float lower[3], upper[3];
+        } box;
+        struct {
+            float center[3], radius;
+        } sphere;
+        struct {
+            float planes[6][4];
+            uint32_t corners[6];
+        } frustum;
+        struct {
+            float axes[3][3], center[3], half_extents[3];
+        } oriented_box;
+        uint32_t words[31];
+    } u;
+} ivx_bv_query;
+/* add_bounding_volume_to_hierarchy (lib.rs:39-54) = aabb_of_transformed (axis_aligned_box.rs:350-363) of the model box under the similarity's matrix.
+ * Host arithmetic; the device runs the same function and gives the same bytes. All f32, this order, no contraction:
+ *   c = 0.5 (lower + upper), h = 0.5 (upper - lower)                                        (center_of, half_extents)
+ *   with q = rotation: n2 = ((x x + y y) + z z) + w w, and the nine numerators of the homogeneous rotation matrix
+ *     N00 = ((w w + x x) - y y) - z z   N01 = 2 (x y - w z)             N02 = 2 (x z + w y)
+ *     N10 = 2 (x y + w z)               N11 = ((w w - x x) + y y) - z z N12 = 2 (y z - w x)
+ *     N20 = 2 (x z - w y)               N21 = 2 (y z + w x)             N22 = ((w w - x x) - y y) + z z
+ *   M[i][j] = scaling (N[i][j] / n2)      (IEEE division: a quaternion that is unit only to rounding gives an exact 0 / 1 where the rotation has one)
+ *   c'[i] = ((M[i][0] c.x + M[i][1] c.y) + M[i][2] c.z) + translation[i],   h'[i] = (|M[i][0]| h.x + |M[i][1]| h.y) + |M[i][2]| h.z
+ *   out = (c' - h', c' + h').
+ * The identity similarity returns the box's own bytes whenever lower + upper and upper - lower are exact in f32 (the operation order of the reference,
+ * which has the same property); a restatement, not a bit-parity target (glam's order is unpinned).
+ * IVX_ERR_INVALID for a scaling that is not positive (a NaN included). */
+int ivx_bv_world_aabb(const ivx_aabb* model, const ivx_similarity* similarity, ivx_aabb* out);
+/* A kind-2 record from six world-space planes: corners[p] has bit 2 / 1 / 0 set where the normal's x / y / z does NOT have its sign bit set
+ * (-0.0 chooses the lower corner); the words behind `corners` are zeroed. */
+int ivx_bv_frustum_query(const float planes[6][4], ivx_bv_query* out);
+/* VoxelObject::compute_aabb (object.rs:886-907) as sync_voxel_object_bounding_volume stores it (interaction.rs:202-222): voxel_extent x (start, end)
+ * of the occupied voxel ranges THE OBJECT CURRENTLY HOLDS — what ivx_occupied_ranges, a step, a split or a clip last left, refreshed first if an edit
+ * that removed a chunk has invalidated them (the reference refreshes at that point) —, as float(start) x extent, float(end) x extent; the all-zero
+ * box when a range is empty. An edit that empties voxels without making a chunk Void leaves the ranges, and so the box, as they were — even when
+ * no voxel is left — until ivx_occupied_ranges is called, as in the reference. IVX_ERR_STATE when the grid holds no ranges yet (nothing has
+ * derived its state). */
+int ivx_grid_model_aabb(ivx_grid*, ivx_aabb* out);
+/* The set of a context: n world boxes with their kinds, resident until the next ivx_bv_set* on the context.
+ * ivx_bv_set: one upload from pinned staging, one launch (ivx_bv_world_aabb per object, and the box of every 64 consecutive objects) and one wave
+ *   for the total; similarities == NULL: the boxes are in world space already and are stored as given. kinds == NULL: all IVX_BV_DYNAMIC. Refused
+ *   (IVX_ERR_INVALID): a kind above 2, a scaling that is not positive; IVX_ERR_CAPACITY: n above IVX_BV_MAX_OBJECTS. n == 0 is a set (an empty
+ *   one). A refused call leaves the context's set as it was; a call that fails later leaves none.
+ * ivx_bv_set_grids: the same with model boxes from ivx_grid_model_aabb of every grid (one context); inside an ivx_many_begin bracket what has been
+ *   recorded is flushed first, as by ivx_cull_many. n == 0 names no context and does nothing.
+ * ivx_bv_download: the world boxes (cap >= n, else IVX_ERR_CAPACITY; may be NULL) and `total`, the box around all of them (total_bounding_volume:
+ *   per component the minimum of the lowers and the maximum of the uppers, reduced 64 objects at a time in input order; the all-zero box for n == 0;
+ *   may be NULL).
+ * ivx_bv_pairs: every (a, b), a < b, whose world boxes intersect, as uint32_t[2], SORTED LEXICOGRAPHICALLY BY (a, b) — an order of our own (the
+ *   reference's is an artefact of its tree) that no tiling shows through. mode 0: all pairs (cache_all_collisions); mode 1: only pairs with no phantom
+ *   member and at least one dynamic member (collision.rs:317-349). *n_out is the number found even when it exceeds cap; the call then returns
+ *   IVX_ERR_CAPACITY and writes nothing to `pairs`. The pairs also stay in the context's pair buffer; pairs == NULL with cap == 0 leaves them there
+ *   only (the call succeeds). 2^31 pairs or more: IVX_ERR_CAPACITY. Device scratch: 4 n ceil(n / 512) bytes.
+ * ivx_bv_queries: masks[q * W + w], W = ceil(n / 64): bit o % 64 of word o / 64 set when object o is hit by query q, bits past n zero; counts[q] the
+ *   number hit (may be NULL). At most IVX_BV_MAX_QUERIES per call; a kind above 3 is IVX_ERR_INVALID. The masks also stay in the context's mask buffer.
+ * ivx_bv_device_ptr: the world boxes (ivx_aabb[n]), the pair buffer (uint32_t[2] per pair of the last ivx_bv_pairs), the masks of the last
+ *   ivx_bv_queries. Context-owned and grow-only, under the rules ivx_cull_device_ptr documents. NULL before the first call that fills the buffer.
+ * Every call that produces results (download, pairs, queries) without a set on the context is IVX_ERR_STATE; n == 0 / n_queries == 0 succeed with
+ * empty results.
+ * The decisions — f32, this order, no contraction; d(x) below means "x has its sign bit set, or is a NaN":
+ *   box against box (pairs, kind 0; box_lies_outside, axis_aligned_box.rs:619-623): outside when d() holds for any component of
+ *     other.upper - self.lower or of self.upper - other.lower. The sign bit of the difference, not a `<`: touching faces intersect, and
+ *     (-0.0) - (+0.0) = -0.0 does not. A box with a NaN bound intersects nothing.
+ *   sphere (sphere.rs:167-181): s = 0; per axis x, y, z: if upper < c then s += (c - upper)^2, else if lower > c then s += (lower - c)^2; outside when
+ *     s > radius x radius. A NaN compares false each time (a NaN bound adds nothing; a NaN sum or radius is a hit).
+ *   frustum (frustum.rs:456-471): hit when ((nx px + ny py) + nz pz) - d >= 0 for all six planes, p the box corner corners[p] selects. A NaN is a miss.
+ *   oriented box (oriented_box.rs:129-143), c and h of the world box as in ivx_bv_world_aabb, dx = c - center:
+ *     e[a] = ((|A[a][0]| h.x + |A[a][1]| h.y) + |A[a][2]| h.z) + half[a],  l[a] = (A[a][0] dx.x + A[a][1] dx.y) + A[a][2] dx.z;
+ *     hit when d(e[a] - |l[a]|) holds for no a. A NaN is a miss.
+ * No atomic decides anything: two calls leave the same bytes. */
+#define IVX_BV_MAX_OBJECTS (1u << 20)
+#define IVX_BV_MAX_QUERIES 1024u
+#define IVX_BV_ALL_PAIRS 0u
+#define IVX_BV_DYNAMIC_PAIRS 1u
+#define IVX_BV_PTR_WORLD_BOXES 0
+#define IVX_BV_PTR_PAIRS 1
+#define IVX_BV_PTR_MASKS 2
+int ivx_bv_set(ivx_ctx*, const ivx_aabb* model_boxes, const ivx_similarity* similarities, const uint32_t* kinds, size_t n);
+int ivx_bv_set_grids(ivx_grid* const* grids, size_t n, const ivx_similarity* similarities, const uint32_t* kinds);
+int ivx_bv_download(ivx_ctx*, ivx_aabb* world_boxes, size_t cap, ivx_aabb* total);
+int ivx_bv_pairs(ivx_ctx*, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n_out);
+int ivx_bv_queries(ivx_ctx*, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, uint32_t* counts);
+void* ivx_bv_device_ptr(ivx_ctx*, int which);
+
 #ifdef __cplusplus
 }
 #endif

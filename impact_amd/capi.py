@@ -202,6 +202,12 @@ BV_ALL_PAIRS, BV_DYNAMIC_PAIRS = 0, 1
 BV_PTR_WORLD_BOXES, BV_PTR_PAIRS, BV_PTR_MASKS = 0, 1, 2
 BV_MAX_OBJECTS, BV_MAX_QUERIES = 1 << 20, 1024
 assert AABB_DTYPE.itemsize == 24 and SIMILARITY_DTYPE.itemsize == 32 and BV_QUERY_DTYPE.itemsize == 128
+# primitive collidables (csrc/narrow.hip): `ivx_collidable`, in its body's frame or in world space
+COLLIDABLE_DTYPE = np.dtype([("shape", "<u4"), ("kind", "<u4"), ("body", "<u4"), ("reserved", "<u4"), ("id", "<u8"), ("a", "<f4", (3,)), ("b", "<f4", (3,)), ("s", "<f4"),
+                             ("response", "<f4", (3,))])
+CW_SPHERE, CW_PLANE, CW_CAPSULE, CW_VOXEL_OBJECT = 0, 1, 2, 3
+CW_PTR_WORLD_COLLIDABLES, CW_PTR_CONTACTS, CW_PTR_DEFERRED_PAIRS = 0, 1, 2
+assert COLLIDABLE_DTYPE.itemsize == 64
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -231,6 +237,7 @@ EXPORTED_SYMBOLS = [
     "ivx_cull_collect", "ivx_cull_many_frusta", "ivx_cull_download", "ivx_cull_device_ptr",
     "ivx_bv_world_aabb", "ivx_bv_frustum_query", "ivx_grid_model_aabb", "ivx_bv_set", "ivx_bv_set_grids", "ivx_bv_download", "ivx_bv_pairs", "ivx_bv_queries",
     "ivx_bv_device_ptr",
+    "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
 ]
 
 
@@ -262,6 +269,7 @@ def extra_struct_sizes():
         "ivx_cull_object": (CULL_OBJECT_DTYPE, 8), "ivx_draw_args": (DRAW_ARGS_DTYPE, 16), "ivx_draw_indexed_args": (DRAW_INDEXED_ARGS_DTYPE, 20),
         "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
         "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128),
+        "ivx_collidable": (COLLIDABLE_DTYPE, 64),
     }
 
 
@@ -448,6 +456,13 @@ def lib():
         "ivx_bv_pairs": (i32, [vp, u32, vp, sz, C.POINTER(sz)]),
         "ivx_bv_queries": (i32, [vp, vp, sz, vp, vp]),
         "ivx_bv_device_ptr": (vp, [vp, i32]),
+        "ivx_cw_transform": (i32, [vp, vp, vp, vp, vp]),
+        "ivx_cw_contact": (i32, [vp, vp, vp, C.POINTER(i32)]),
+        "ivx_cw_set_collidables": (i32, [vp, vp, sz]),
+        "ivx_cw_synchronize": (i32, [vp]),
+        "ivx_cw_download": (i32, [vp, vp, sz]),
+        "ivx_cw_collide": (i32, [vp, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]),
+        "ivx_cw_device_ptr": (vp, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

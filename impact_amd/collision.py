@@ -1,0 +1,117 @@
+"""Host-side mirror of the primitive collidable calls (`ivx_cw_*`, impact_amd/csrc/narrow.hip): the reference's `CollisionWorld` for sphere,
+plane and capsule collidables (impact_physics/src/collision.rs, collision/collidable/basic.rs) on top of a `PhysicsWorld`:
+
+  synchronize_collidables_with_rigid_bodies                                collision.rs:175-209   (`CollisionWorld.synchronize`)
+  cache_all_collisions / for_each_non_phantom_collision_involving_dynamic  collision.rs:215-373   (`CollisionWorld.collide`, modes 0 / 1)
+  generate_contact_manifold                                                basic.rs:57-151        (`contact`, host arithmetic of the library)
+  Collidable::from_descriptor                                              basic.rs:42-55         (`transform`)
+
+A frame: `synchronize()` -> `collide()` -> `PhysicsWorld.prepare_constraints(contacts)` -> `PhysicsWorld.step(dt)`. The world-space collidables,
+the world boxes, the pairs, the contacts and the deferred pairs stay in device buffers. Nothing here computes, and nothing falls back to the CPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .bvol import BoundingVolumeSet
+from .capi import AABB_DTYPE, COLLIDABLE_DTYPE, CONTACT_DTYPE, check, ptr
+
+NO_CONTACT, CONTACT, DEFERRED = 0, 1, 2  # `ivx_cw_contact`'s verdicts
+
+
+def _collidable(shape, body, collidable_id, kind, response, kinematic):
+    c = np.zeros((), dtype=COLLIDABLE_DTYPE)
+    c["shape"], c["kind"], c["id"], c["response"] = shape, kind, collidable_id, response
+    c["body"] = int(body) | (capi.KINEMATIC_BIT if kinematic else 0)
+    return c
+
+
+def sphere(center, radius, body, collidable_id, kind=capi.BV_DYNAMIC, response=(0.0, 0.0, 0.0), kinematic=False) -> np.ndarray:
+    c = _collidable(capi.CW_SPHERE, body, collidable_id, kind, response, kinematic)
+    c["a"], c["s"] = center, radius
+    return c
+
+
+def plane(unit_normal, displacement, body, collidable_id, kind=capi.BV_STATIC, response=(0.0, 0.0, 0.0), kinematic=False) -> np.ndarray:
+    c = _collidable(capi.CW_PLANE, body, collidable_id, kind, response, kinematic)
+    c["a"], c["s"] = unit_normal, displacement
+    return c
+
+
+def capsule(segment_start, segment_vector, radius, body, collidable_id, kind=capi.BV_DYNAMIC, response=(0.0, 0.0, 0.0), kinematic=False) -> np.ndarray:
+    c = _collidable(capi.CW_CAPSULE, body, collidable_id, kind, response, kinematic)
+    c["a"], c["b"], c["s"] = segment_start, segment_vector, radius
+    return c
+
+
+def voxel_object(model_lower, model_upper, body, collidable_id, kind=capi.BV_DYNAMIC, response=(0.0, 0.0, 0.0), kinematic=False) -> np.ndarray:
+    """a voxel object's place in the broad phase (`bvol.grid_model_aabb` gives its model box); its pairs come back deferred"""
+    c = _collidable(capi.CW_VOXEL_OBJECT, body, collidable_id, kind, response, kinematic)
+    c["a"], c["b"] = model_lower, model_upper
+    return c
+
+
+def _one(record):
+    a = np.ascontiguousarray(record, dtype=COLLIDABLE_DTYPE).reshape(-1)
+    assert a.size == 1, a.size
+    return a
+
+
+def transform(local, position, orientation_xyzw):
+    """`ivx_cw_transform`: one collidable under its body's position and orientation -> (world-space collidable, world box)"""
+    world, box = np.zeros(1, dtype=COLLIDABLE_DTYPE), np.zeros(1, dtype=AABB_DTYPE)
+    p, q = np.ascontiguousarray(position, dtype=np.float32).reshape(3), np.ascontiguousarray(orientation_xyzw, dtype=np.float32).reshape(4)
+    check(capi.lib().ivx_cw_transform(ptr(_one(local)), ptr(p), ptr(q), ptr(world), ptr(box)))
+    return world[0], box[0]
+
+
+def contact(a_world, b_world):
+    """`ivx_cw_contact`: one pair of world-space collidables -> (verdict, the contact record when the verdict is CONTACT, else None)"""
+    out, hit = np.zeros(1, dtype=CONTACT_DTYPE), C.c_int(0)
+    check(capi.lib().ivx_cw_contact(ptr(_one(a_world)), ptr(_one(b_world)), ptr(out), C.byref(hit)))
+    return hit.value, (out[0] if hit.value == CONTACT else None)
+
+
+class CollisionWorld:
+    """The collidables of a `PhysicsWorld`. List planes last: a block of 64 consecutive collidables that holds one is never rejected as a whole."""
+
+    def __init__(self, physics_world):
+        self.world = physics_world
+        self.n = 0
+
+    def set_collidables(self, collidables) -> None:
+        """`ivx_cw_set_collidables`: local records (body frame), resident until replaced"""
+        c = np.ascontiguousarray(collidables, dtype=COLLIDABLE_DTYPE).reshape(-1)
+        check(capi.lib().ivx_cw_set_collidables(self.world.h, ptr(c) if c.size else None, c.size))
+        self.n = c.size
+
+    def synchronize(self) -> BoundingVolumeSet:
+        """`ivx_cw_synchronize`: enqueued behind whatever the stream holds -> the context's bounding-volume set of the world boxes"""
+        check(capi.lib().ivx_cw_synchronize(self.world.h))
+        return BoundingVolumeSet(self.world.ctx.h, self.n)
+
+    def download(self) -> np.ndarray:
+        """`ivx_cw_download`: the world-space collidables of the last synchronize"""
+        out = np.zeros(self.n, dtype=COLLIDABLE_DTYPE)
+        check(capi.lib().ivx_cw_download(self.world.h, ptr(out) if self.n else None, self.n))
+        return out
+
+    def collide(self, mode: int = capi.BV_DYNAMIC_PAIRS, capacity: int | None = None, deferred_capacity: int | None = None):
+        """`ivx_cw_collide` -> (contacts [n] CONTACT_DTYPE, deferred pairs [m, 2] uint32), both in pair order. A capacity of None: sized by a first
+        call that only counts."""
+        lib = capi.lib()
+        n, m = C.c_size_t(0), C.c_size_t(0)
+        if capacity is None or deferred_capacity is None:
+            check(lib.ivx_cw_collide(self.world.h, int(mode), None, 0, C.byref(n), None, 0, C.byref(m)))
+            capacity = n.value if capacity is None else capacity
+            deferred_capacity = m.value if deferred_capacity is None else deferred_capacity
+        contacts, deferred = np.zeros(max(1, capacity), dtype=CONTACT_DTYPE), np.zeros((max(1, deferred_capacity), 2), dtype=np.uint32)
+        check(lib.ivx_cw_collide(self.world.h, int(mode), ptr(contacts), capacity, C.byref(n), ptr(deferred), deferred_capacity, C.byref(m)))
+        return contacts[: n.value], deferred[: m.value]
+
+    def device_ptr(self, which: int) -> int:
+        """`ivx_cw_device_ptr`: capi.CW_PTR_WORLD_COLLIDABLES / _CONTACTS / _DEFERRED_PAIRS"""
+        return int(capi.lib().ivx_cw_device_ptr(self.world.h, int(which)) or 0)

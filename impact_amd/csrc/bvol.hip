@@ -24,6 +24,7 @@
 #include <new>
 #include <vector>
 
+#include "bvol_internal.hpp"
 #include "ivx_internal.hpp"
 
 namespace {
@@ -41,26 +42,8 @@ __host__ __device__ __forceinline__ uint32_t f_bits(float v) {
     return u;
 #endif
 }
-__host__ __device__ __forceinline__ float f_abs(float v) { return __builtin_fabsf(v); }  // (clears the sign bit)
-
-__host__ __device__ inline void world_aabb(const ivx_aabb& m, const ivx_similarity& s, ivx_aabb* out) {
-    const float c[3] = {0.5f * (m.lower[0] + m.upper[0]), 0.5f * (m.lower[1] + m.upper[1]), 0.5f * (m.lower[2] + m.upper[2])};
-    const float h[3] = {0.5f * (m.upper[0] - m.lower[0]), 0.5f * (m.upper[1] - m.lower[1]), 0.5f * (m.upper[2] - m.lower[2])};
-    const float x = s.rotation[0], y = s.rotation[1], z = s.rotation[2], w = s.rotation[3];
-    const float xx = x * x, yy = y * y, zz = z * z, ww = w * w;
-    const float n2 = ((xx + yy) + zz) + ww;
-    const float xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-    const float N[3][3] = {{((ww + xx) - yy) - zz, 2.0f * (xy - wz), 2.0f * (xz + wy)},
-                           {2.0f * (xy + wz), ((ww - xx) + yy) - zz, 2.0f * (yz - wx)},
-                           {2.0f * (xz - wy), 2.0f * (yz + wx), ((ww - xx) - yy) + zz}};
-    for (int i = 0; i < 3; ++i) {
-        const float m0 = s.scaling * (N[i][0] / n2), m1 = s.scaling * (N[i][1] / n2), m2 = s.scaling * (N[i][2] / n2);
-        const float ct = ((m0 * c[0] + m1 * c[1]) + m2 * c[2]) + s.translation[i];
-        const float ht = (f_abs(m0) * h[0] + f_abs(m1) * h[1]) + f_abs(m2) * h[2];
-        out->lower[i] = ct - ht;
-        out->upper[i] = ct + ht;
-    }
-}
+__host__ __device__ __forceinline__ float f_abs(float v) { return ivx_bv_abs(v); }
+__host__ __device__ __forceinline__ void world_aabb(const ivx_aabb& m, const ivx_similarity& s, ivx_aabb* out) { ivx_bv_world_aabb_of(m, s, out); }  // (bvol_internal.hpp: narrow.hip runs it too)
 
 // ---- device side -------------------------------------------------------------------------------------------------------------------------
 // "has its sign bit set, or is a NaN" for any of six differences
@@ -311,6 +294,7 @@ struct BvState {
     bool staged_pending = false;
     bool has_set = false;
     uint32_t n = 0;
+    uint64_t serial = 0;  // counts the sets the context has held (ivx_bvol_set_serial)
     size_t o_kinds = 0, o_world = 0, o_blocks = 0, o_total = 0;
 };
 
@@ -375,43 +359,62 @@ int check_set_arguments(const char* who, const ivx_similarity* sims, const uint3
     return IVX_OK;
 }
 
+// the set buffer of n objects: the inputs of the world launch (boxes, similarities if any, kinds), then what the set keeps
+struct SetLayout {
+    size_t o_in = 0, o_sims = 0, o_kinds = 0, upload_bytes = 0, o_world = 0, o_blocks = 0, o_total = 0, bytes = 0;
+};
+SetLayout set_layout(size_t n, bool with_sims) {
+    const size_t n_blocks = (n + 63u) / 64u;
+    Layout l;
+    SetLayout s;
+    s.o_in = l.take(n * sizeof(ivx_aabb)), s.o_sims = l.take(with_sims ? n * sizeof(ivx_similarity) : 0), s.o_kinds = l.take(n_blocks * 64u * 4);  // (kinds and world boxes: whole blocks)
+    s.upload_bytes = l.bytes;
+    s.o_world = l.take(n_blocks * 64u * sizeof(ivx_aabb)), s.o_blocks = l.take(n_blocks * sizeof(ivx_aabb)), s.o_total = l.take(sizeof(ivx_aabb));
+    s.bytes = l.bytes;
+    return s;
+}
+
+// the launches behind the inputs, wherever they came from (an upload: set_enqueue; a kernel of the caller: ivx_bvol_set_finish)
+int set_launch(ivx_ctx* c, BvState* st, const SetLayout& l, size_t n, bool derive) {
+    const size_t n_blocks = (n + 63u) / 64u;
+    char* d = static_cast<char*>(st->set.p);
+    const dim3 grid((uint32_t)((n_blocks + 3u) / 4u));
+    ivx_aabb* d_world = reinterpret_cast<ivx_aabb*>(d + l.o_world);
+    ivx_aabb* d_blocks = reinterpret_cast<ivx_aabb*>(d + l.o_blocks);
+    if (derive)
+        IVX_KLAUNCH(k_bv_world<true>, grid, dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(d + l.o_in), reinterpret_cast<const ivx_similarity*>(d + l.o_sims), (uint32_t)n,
+                    d_world, d_blocks);
+    else
+        IVX_KLAUNCH(k_bv_world<false>, grid, dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(d + l.o_in), (const ivx_similarity*)nullptr, (uint32_t)n, d_world, d_blocks);
+    IVX_KLAUNCH(k_bv_total, dim3(1), dim3(64), 0, c->stream, (const ivx_aabb*)d_blocks, (uint32_t)n_blocks, reinterpret_cast<ivx_aabb*>(d + l.o_total));
+    IVX_HIP_CHECK(hipGetLastError());
+    st->o_kinds = l.o_kinds, st->o_world = l.o_world, st->o_blocks = l.o_blocks, st->o_total = l.o_total;
+    st->n = (uint32_t)n, st->has_set = true, ++st->serial;
+    return IVX_OK;
+}
+
 int set_enqueue(ivx_ctx* c, const ivx_aabb* boxes, const ivx_similarity* sims, const uint32_t* kinds, size_t n) {
     BvState* st;
     if (int rc = state_of(c, &st)) return rc;
     st->has_set = false, st->n = 0;  // (until this call's set stands)
     if (n == 0) {
-        st->has_set = true;
+        st->has_set = true, ++st->serial;
         return IVX_OK;
     }
     const size_t n_blocks = (n + 63u) / 64u;
-    Layout l;
-    const size_t o_in = l.take(n * sizeof(ivx_aabb)), o_sims = l.take(sims ? n * sizeof(ivx_similarity) : 0), o_kinds = l.take(n_blocks * 64u * 4);  // (kinds and world boxes: whole blocks)
-    const size_t upload_bytes = l.bytes;
-    const size_t o_world = l.take(n_blocks * 64u * sizeof(ivx_aabb)), o_blocks = l.take(n_blocks * sizeof(ivx_aabb)), o_total = l.take(sizeof(ivx_aabb));
-    if (int rc = staging_for(st, upload_bytes)) return rc;
+    const SetLayout l = set_layout(n, sims != nullptr);
+    if (int rc = staging_for(st, l.upload_bytes)) return rc;
     if (int rc = grow(c, &st->set, l.bytes, 1u << 16)) return rc;
     char* h = static_cast<char*>(st->staging);
     char* d = static_cast<char*>(st->set.p);
-    memcpy(h + o_in, boxes, n * sizeof(ivx_aabb));
-    if (sims) memcpy(h + o_sims, sims, n * sizeof(ivx_similarity));
-    memset(h + o_kinds, 0, n_blocks * 64u * 4);
-    if (kinds) memcpy(h + o_kinds, kinds, n * 4);
-    IVX_HIP_CHECK(ivx_memcpy_async(d, h, upload_bytes, hipMemcpyHostToDevice, c->stream));
+    memcpy(h + l.o_in, boxes, n * sizeof(ivx_aabb));
+    if (sims) memcpy(h + l.o_sims, sims, n * sizeof(ivx_similarity));
+    memset(h + l.o_kinds, 0, n_blocks * 64u * 4);
+    if (kinds) memcpy(h + l.o_kinds, kinds, n * 4);
+    IVX_HIP_CHECK(ivx_memcpy_async(d, h, l.upload_bytes, hipMemcpyHostToDevice, c->stream));
     IVX_HIP_CHECK(ivx_event_record(st->staged, c->stream));
     st->staged_pending = true;
-    const dim3 grid((uint32_t)((n_blocks + 3u) / 4u));
-    ivx_aabb* d_world = reinterpret_cast<ivx_aabb*>(d + o_world);
-    ivx_aabb* d_blocks = reinterpret_cast<ivx_aabb*>(d + o_blocks);
-    if (sims)
-        IVX_KLAUNCH(k_bv_world<true>, grid, dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(d + o_in), reinterpret_cast<const ivx_similarity*>(d + o_sims), (uint32_t)n,
-                    d_world, d_blocks);
-    else
-        IVX_KLAUNCH(k_bv_world<false>, grid, dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(d + o_in), (const ivx_similarity*)nullptr, (uint32_t)n, d_world, d_blocks);
-    IVX_KLAUNCH(k_bv_total, dim3(1), dim3(64), 0, c->stream, (const ivx_aabb*)d_blocks, (uint32_t)n_blocks, reinterpret_cast<ivx_aabb*>(d + o_total));
-    IVX_HIP_CHECK(hipGetLastError());
-    st->o_kinds = o_kinds, st->o_world = o_world, st->o_blocks = o_blocks, st->o_total = o_total;
-    st->n = (uint32_t)n, st->has_set = true;
-    return IVX_OK;
+    return set_launch(c, st, l, n, sims != nullptr);
 }
 
 int model_aabb(ivx_grid* g, const char* who, ivx_aabb* out) {
@@ -445,6 +448,71 @@ void ivx_bvol_release(ivx_ctx* c) {
     if (s->staged) (void)hipEventDestroy(s->staged);
     delete s;
     c->bvol_state = nullptr;
+}
+
+int ivx_bvol_set_begin(ivx_ctx* c, size_t n, ivx_aabb** d_boxes, uint32_t** d_kinds) {
+    *d_boxes = nullptr, *d_kinds = nullptr;
+    BvState* st;
+    if (int rc = state_of(c, &st)) return rc;
+    st->has_set = false, st->n = 0;  // (until ivx_bvol_set_finish)
+    if (n == 0) return IVX_OK;
+    const SetLayout l = set_layout(n, false);
+    if (int rc = grow(c, &st->set, l.bytes, 1u << 16)) return rc;
+    char* d = static_cast<char*>(st->set.p);
+    *d_boxes = reinterpret_cast<ivx_aabb*>(d + l.o_in), *d_kinds = reinterpret_cast<uint32_t*>(d + l.o_kinds);
+    return IVX_OK;
+}
+
+int ivx_bvol_set_finish(ivx_ctx* c, size_t n) {
+    BvState* st;
+    if (int rc = state_of(c, &st)) return rc;
+    if (n == 0) {
+        st->has_set = true, ++st->serial;
+        return IVX_OK;
+    }
+    return set_launch(c, st, set_layout(n, false), n, false);
+}
+
+uint64_t ivx_bvol_set_serial(const ivx_ctx* c) {
+    const BvState* st = static_cast<const BvState*>(c->bvol_state);
+    return st && st->has_set ? st->serial : 0u;
+}
+
+int ivx_bvol_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool check_cap, size_t cap, size_t* n_pairs) {
+    *n_pairs = 0;
+    BvState* st;
+    if (int rc = set_state(c, who, &st)) return rc;
+    const uint32_t n = st->n;
+    if (n < 2u) return IVX_OK;
+    const uint32_t n_blocks = (n + 63u) / 64u, n_seg = (n_blocks + SEG_BLOCKS - 1u) / SEG_BLOCKS;
+    Layout l;
+    const size_t o_counts = l.take((size_t)n_seg * n * 4), o_rows = l.take((size_t)n * 4), o_grand = l.take(8);
+    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
+    char* s = static_cast<char*>(st->scratch.p);
+    const char* d = static_cast<const char*>(st->set.p);
+    const ivx_aabb* d_world = reinterpret_cast<const ivx_aabb*>(d + st->o_world);
+    const ivx_aabb* d_blocks = reinterpret_cast<const ivx_aabb*>(d + st->o_blocks);
+    const uint32_t* d_kinds = reinterpret_cast<const uint32_t*>(d + st->o_kinds);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(s + o_counts);
+    uint32_t* d_rows = reinterpret_cast<uint32_t*>(s + o_rows);
+    unsigned long long* d_grand = reinterpret_cast<unsigned long long*>(s + o_grand);
+    const dim3 walk_grid((uint32_t)(((size_t)n_blocks * n_seg + 3u) / 4u));
+    IVX_KLAUNCH(k_bv_pair_walk<false>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)nullptr, (uint2*)nullptr);
+    IVX_KLAUNCH(k_bv_rows, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, d_counts, n, n_seg, d_rows);
+    IVX_KLAUNCH(k_bv_scan, dim3(1), dim3(SCAN_ROUND), 0, c->stream, d_rows, n, d_grand);
+    IVX_HIP_CHECK(hipGetLastError());
+    unsigned long long grand = 0;
+    IVX_HIP_CHECK(ivx_memcpy_async(&grand, d_grand, 8, hipMemcpyDeviceToHost, c->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    IVX_REQUIRE(grand < (1ull << 31), IVX_ERR_CAPACITY, "%s: %llu intersecting pairs: too many for one call", who, grand);
+    *n_pairs = (size_t)grand;
+    IVX_REQUIRE(!check_cap || grand <= cap, IVX_ERR_CAPACITY, "%s: %llu intersecting pairs, the buffer holds %zu", who, grand, cap);
+    if (grand == 0) return IVX_OK;
+    if (int rc = grow(c, &st->pairs, (size_t)grand * 8, 1u << 16)) return rc;
+    IVX_KLAUNCH(k_bv_pair_walk<true>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)d_rows,
+                static_cast<uint2*>(st->pairs.p));
+    IVX_HIP_CHECK(hipGetLastError());
+    return IVX_OK;
 }
 
 extern "C" {
@@ -530,38 +598,11 @@ int ivx_bv_pairs(ivx_ctx* c, uint32_t mode, uint32_t* pairs, size_t cap, size_t*
     IVX_REQUIRE(pairs || cap == 0, IVX_ERR_INVALID, "%s: null pair buffer of capacity %zu", who, cap);
     BvState* st;
     if (int rc = set_state(c, who, &st)) return rc;
-    const uint32_t n = st->n;
-    if (n < 2u) return IVX_OK;
+    if (st->n < 2u) return IVX_OK;
     ivx_many_other_context other_(c);
-    const uint32_t n_blocks = (n + 63u) / 64u, n_seg = (n_blocks + SEG_BLOCKS - 1u) / SEG_BLOCKS;
-    Layout l;
-    const size_t o_counts = l.take((size_t)n_seg * n * 4), o_rows = l.take((size_t)n * 4), o_grand = l.take(8);
-    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
-    char* s = static_cast<char*>(st->scratch.p);
-    const char* d = static_cast<const char*>(st->set.p);
-    const ivx_aabb* d_world = reinterpret_cast<const ivx_aabb*>(d + st->o_world);
-    const ivx_aabb* d_blocks = reinterpret_cast<const ivx_aabb*>(d + st->o_blocks);
-    const uint32_t* d_kinds = reinterpret_cast<const uint32_t*>(d + st->o_kinds);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(s + o_counts);
-    uint32_t* d_rows = reinterpret_cast<uint32_t*>(s + o_rows);
-    unsigned long long* d_grand = reinterpret_cast<unsigned long long*>(s + o_grand);
-    const dim3 walk_grid((uint32_t)(((size_t)n_blocks * n_seg + 3u) / 4u));
-    IVX_KLAUNCH(k_bv_pair_walk<false>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)nullptr, (uint2*)nullptr);
-    IVX_KLAUNCH(k_bv_rows, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, d_counts, n, n_seg, d_rows);
-    IVX_KLAUNCH(k_bv_scan, dim3(1), dim3(SCAN_ROUND), 0, c->stream, d_rows, n, d_grand);
-    IVX_HIP_CHECK(hipGetLastError());
-    unsigned long long grand = 0;
-    IVX_HIP_CHECK(ivx_memcpy_async(&grand, d_grand, 8, hipMemcpyDeviceToHost, c->stream));
-    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
-    IVX_REQUIRE(grand < (1ull << 31), IVX_ERR_CAPACITY, "%s: %llu intersecting pairs: too many for one call", who, grand);
-    *n_out = (size_t)grand;
-    IVX_REQUIRE(!pairs || grand <= cap, IVX_ERR_CAPACITY, "%s: %llu intersecting pairs, the buffer holds %zu", who, grand, cap);
-    if (grand == 0) return IVX_OK;
-    if (int rc = grow(c, &st->pairs, (size_t)grand * 8, 1u << 16)) return rc;
-    IVX_KLAUNCH(k_bv_pair_walk<true>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)d_rows,
-                static_cast<uint2*>(st->pairs.p));
-    IVX_HIP_CHECK(hipGetLastError());
-    if (pairs) IVX_HIP_CHECK(ivx_memcpy_async(pairs, st->pairs.p, (size_t)grand * 8, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = ivx_bvol_pairs_enqueue(c, who, mode, pairs != nullptr, cap, n_out)) return rc;
+    if (*n_out == 0) return IVX_OK;
+    if (pairs) IVX_HIP_CHECK(ivx_memcpy_async(pairs, st->pairs.p, *n_out * 8, hipMemcpyDeviceToHost, c->stream));
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
     return IVX_OK;
 }

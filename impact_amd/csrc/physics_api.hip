@@ -628,6 +628,7 @@ void ivx_world_destroy(ivx_world* w) {
         (void)hipEventDestroy(w->ev_join);
         (void)hipStreamDestroy(w->side_stream);
     }
+    ivx_cw_release(w);
     if (w->stage_sched) (void)hipHostFree(w->stage_sched);  // pinned staging of the general path's uploads
     if (w->stage_sched_ev_ready) (void)hipEventDestroy(w->stage_sched_ev);
     if (w->stage_contacts) (void)hipHostFree(w->stage_contacts);  // pinned staging of the set_contacts fast path

@@ -166,8 +166,10 @@ struct ivx_world {
     int cs_feasible[2];
     uint32_t forms_built;
     std::vector<uint32_t> chain_bodies, prev_chain_start, prev_chain_bodies;  // body pair per chain; last frame's chains (an unchanged contact structure keeps its schedule)
+    void* cw_state;  // primitive collidables (narrow.hip): local and world-space records, wave masks and offsets, contact and deferred buffers; made on first use, freed by ivx_cw_release
 };
 
+void ivx_cw_release(ivx_world* w);  // narrow.hip (ivx_world_destroy)
 int ivx_launch_phys_prepare_bodies(ivx_world* w);
 int ivx_launch_phys_prepare_contacts(ivx_world* w, const int32_t* d_prev_slot);
 int ivx_launch_phys_mark_joint_bodies(ivx_world* w);

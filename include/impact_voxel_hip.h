@@ -1046,6 +1046,93 @@ int ivx_bv_pairs(ivx_ctx*, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n
 int ivx_bv_queries(ivx_ctx*, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, uint32_t* counts);
 void* ivx_bv_device_ptr(ivx_ctx*, int which);
 
+/* ---- primitive collidables: follow the bodies, narrow phase over the pairs (impact_physics/src/collision.rs:175-261, 317-373
+ * synchronize_collidables_with_rigid_bodies and the collision pass; collision/collidable/basic.rs:57-151, sphere.rs:105-157, capsule.rs:142-303;
+ * impact_geometry/src/line.rs:26-145; material.rs:43-51) ----
+ * A frame of primitive bodies: ivx_cw_synchronize -> ivx_cw_collide -> ivx_world_set_contacts -> ivx_world_step. Only the contact list crosses
+ * to the host (the constraint cache lives there); world boxes are never computed on the host. csrc/narrow.hip. */
+#define IVX_CW_SPHERE 0u
+#define IVX_CW_PLANE 1u
+#define IVX_CW_CAPSULE 2u
+#define IVX_CW_VOXEL_OBJECT 3u /* broad phase only: its pairs are deferred to ivx_voxel_object_contacts_many / ivx_mutual_voxel_object_contacts_many */
+/* One collidable, in its body's frame (ivx_cw_set_collidables) or in world space (ivx_cw_download). 64 bytes. */
+typedef struct {
+    uint32_t shape;    /* IVX_CW_* */
+    uint32_t kind;     /* IVX_BV_DYNAMIC / _STATIC / _PHANTOM */
+    uint32_t body;     /* index of the dynamic body it follows; IVX_KINEMATIC_BODY bit set: of the kinematic body */
+    uint32_t reserved;
+    uint64_t id;       /* CollidableID */
+    float a[3];        /* sphere centre | plane unit normal | capsule segment start | voxel object: model box lower (world space: world box lower) */
+    float b[3];        /* capsule segment vector | voxel object: model box upper (world space: world box upper); unused otherwise */
+    float s;           /* sphere radius | plane displacement | capsule radius; unused for a voxel object */
+    float response[3]; /* restitution, static friction, dynamic friction of THIS collidable (ContactResponseParameters) */
+} ivx_collidable;
+#define IVX_CW_PTR_WORLD_COLLIDABLES 0
+#define IVX_CW_PTR_CONTACTS 1
+#define IVX_CW_PTR_DEFERRED_PAIRS 2
+/* Host arithmetic; the kernels run the same functions and give the same bytes. All f32, the order below, no contraction.
+ *   dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z;  u + v, u - v, u k component-wise;  cross(u, v) = (u.y v.z - v.y u.z, u.z v.x - v.z u.x, u.x v.y - v.x u.y)
+ *   qrot(q, v), q = (x, y, z, w), b = (x, y, z): ((v (w w - dot(b, b))) + (b (dot(v, b) 2))) + (cross(b, v) (w 2))      (glam Quat::mul_vec3a)
+ *   max0(x) = x > 0 ? x : 0 (f32::max(0.0, x): a NaN gives 0);  clamp01(x) = x < 0 ? 0 : (x > 1 ? 1 : x) (f32::clamp: a NaN and -0.0 pass through)
+ *   EPS = 1e-8f
+ * ivx_cw_transform — Collidable::from_descriptor under the body's isometry (position p, orientation q), and the world box:
+ *   sphere:  a' = qrot(q, a) + p;  box = (a' - s, a' + s) per component
+ *   capsule: a' = qrot(q, a) + p, b' = qrot(q, b);  e = a' + b';  box.lower = min(a' - s, e - s), box.upper = max(a' + s, e + s) with
+ *            min(u, v) = v < u ? v : u, max(u, v) = v > u ? v : u (capsule.rs:132-137)
+ *   plane (plane.rs:197-203):  a' = qrot(q, a);  s' = dot(a', qrot(q, a s) + p);  box = (-FLT_MAX, +FLT_MAX) on every axis — the reference gives a
+ *            plane no bounding volume; here it pairs with every box that has no NaN bound. PLANES BELONG AT THE END OF THE LIST: a block of 64
+ *            consecutive objects that holds one has an unbounded block box and is never rejected as a whole by the pair pass.
+ *   voxel object: (a', b') = ivx_bv_world_aabb of the model box (a, b) under (q, p, scaling 1) — also its box
+ *   Everything else of the record is copied. `box` may be NULL.
+ * ivx_cw_contact — generate_contact_manifold (basic.rs:57-151) for one pair of WORLD-SPACE collidables A, B. *hit = 0: no contact (plane against
+ *   plane always); 1: `out` holds it; 2: a member is a voxel object, nothing is tested. Where the reference answers CollidableOrder::Swapped —
+ *   (sphere, capsule), (plane, sphere), (plane, capsule) — the two members swap first; "first / second" below are the members after the swap.
+ *     id = splitmix(id_first ^ splitmix(id_second)) (random/splitmix.rs:4-15), body_a / body_b = the members' bodies, flags = IVX_CONTACT_MANIFOLD_START
+ *     restitution = r2 > r1 ? r2 : r1;  static / dynamic friction = sqrt(f1 f2)                               (ContactResponseParameters::combined)
+ *   sphere (c1, r1), sphere (c2, r2):  d = c1 - c2, d2 = dot(d, d), m = r1 + r2;  miss when d2 > m m;  dist = sqrt(d2);
+ *     normal = dist > EPS ? d (1 / dist) : (0, 0, 1);  position = c2 + normal r2;  depth = max0(m - dist)
+ *   sphere (c, r), plane (n, k):  sd = dot(n, c) - k, depth = r - sd;  miss when depth < 0;  position = c - n sd, normal = n
+ *   capsule (a, v, rc), sphere (c, r):  l2 = dot(v, v);  t = l2 <= EPS ? 0 : clamp01(dot(v, c - a) / l2);  d = c - (a + v t), d2 = dot(d, d), m = r + rc;
+ *     miss when d2 > m m;  dist = sqrt(d2);  dist > EPS: cn = d (1 / dist), depth = max0(m - dist);  else cn = ortho(v), depth = max0(m);
+ *     normal = -cn, position = c + normal r
+ *     ortho(v) (glam any_orthogonal_vector, normalized_from_if_above; parity with glam unpinned): o = |v.x| > |v.y| ? (-v.z, 0, v.x) : (0, v.z, -v.y),
+ *       o2 = dot(o, o);  o2 > EPS EPS ? (o.x / sqrt(o2), o.y / sqrt(o2), o.z / sqrt(o2)) : (0, 0, 1)
+ *   capsule (a1, v1, r1), capsule (a2, v2, r2) — parameters_of_closest_points_on_line_segments (line.rs:75-145):
+ *     l1 = dot(v1, v1), l2 = dot(v2, v2);  both <= EPS: s = t = 0.  Else r = a1 - a2, f = dot(v2, r), and
+ *       l1 <= EPS: s = 0, t = clamp01(f / l2);  else c = dot(v1, r) and
+ *       l2 <= EPS: t = 0, s = clamp01(c / (-l1));  else g = dot(v1, v2), den = l1 l2 - g g,
+ *         s = den != 0 ? clamp01((g f - c l2) / den) : 0;  t = (g s + f) / l2;
+ *         t has its sign bit set (-0.0 included): t = 0, s = clamp01(c / (-l1));  else t > 1: t = 1, s = clamp01((g - c) / l1)
+ *     p1 = a1 + v1 s, p2 = a2 + v2 t, d = p1 - p2, d2 = dot(d, d), m = r1 + r2;  miss when d2 > m m;  dist = sqrt(d2);
+ *     dist > EPS: normal = d (1 / dist), depth = max0(m - dist);
+ *     else (the segments intersect): normal = ortho(v2), w = dot(v1, normal), shift = w has no sign bit ? (1 - s) w : (-s) w, depth = max0(m + shift);
+ *     position = p2 + normal r2
+ *   capsule (a, v, r), plane (n, k):  e = a + v;  d0 = dot(n, a) - k, d1 = dot(n, e) - k;  (p, low) = d0 <= d1 ? (a, d0) : (e, d1);  depth = r - low;
+ *     miss when depth < 0;  position = p - n low, normal = n */
+int ivx_cw_transform(const ivx_collidable* local, const float position[3], const float orientation_xyzw[4], ivx_collidable* world, ivx_aabb* box);
+int ivx_cw_contact(const ivx_collidable* a_world, const ivx_collidable* b_world, ivx_contact* out, int* hit);
+/* The collidables of a world: n local records, resident until replaced (n == 0: an empty set). IVX_ERR_INVALID: a shape above 3, a kind above 2, a
+ * body index past the world's body counts; IVX_ERR_CAPACITY: n above IVX_BV_MAX_OBJECTS. A refused call leaves the world's collidables as they were.
+ * Index i of the set is object i of the bounding-volume set and of the pairs. */
+int ivx_cw_set_collidables(ivx_world*, const ivx_collidable*, size_t n);
+/* synchronize_collidables_with_rigid_bodies: one launch on the context's stream, a lane per collidable — ivx_cw_transform under the position and
+ * orientation its body has in the world's resident arrays (behind ivx_world_step_enqueue it sees that step's bodies; nothing waits) — then the
+ * launches of ivx_bv_set: the world boxes and kinds become the context's bounding-volume set without a host round trip, and ivx_bv_pairs,
+ * ivx_bv_queries and ivx_bv_download work on it. IVX_ERR_STATE: no collidables set, or the world's bodies have been replaced by fewer since. */
+int ivx_cw_synchronize(ivx_world*);
+/* The world-space collidables of the last ivx_cw_synchronize (cap >= n, else IVX_ERR_CAPACITY). Waits for the stream. */
+int ivx_cw_download(ivx_world*, ivx_collidable* world_space, size_t cap);
+/* The pair pass of ivx_bv_pairs (same code, same modes) over the context's set, then ivx_cw_contact over the resident pair buffer, a lane per pair.
+ * out: the contacts; deferred_pairs: uint32_t[2] = (a, b) of every pair with a voxel-object member, for the `_many` voxel generators. BOTH COMPACTED IN
+ * PAIR ORDER, lexicographic in (a, b): wave ballots, a scan of the per-wave counts, no atomic — two calls leave the same bytes. The call waits twice:
+ * for the pair pass's grand total and, at the end, for the two counts together with the results. *n_out / *n_deferred are the numbers found even
+ * when one exceeds its capacity; the call then returns IVX_ERR_CAPACITY and writes neither list. out == NULL with cap == 0 (and likewise the
+ * deferred list) leaves that list on the device only (ivx_cw_device_ptr). Inside an ivx_many_begin bracket what has been recorded is flushed first,
+ * as by ivx_bv_pairs. IVX_ERR_STATE before ivx_cw_synchronize, or when the context's set has been replaced since. */
+int ivx_cw_collide(ivx_world*, uint32_t mode, ivx_contact* out, size_t cap, size_t* n_out, uint32_t* deferred_pairs, size_t deferred_cap, size_t* n_deferred);
+/* IVX_CW_PTR_*: the world collidables, the contacts and the deferred pairs of the last calls; world-owned and grow-only, NULL before they exist */
+void* ivx_cw_device_ptr(ivx_world*, int which);
+
 #ifdef __cplusplus
 }
 #endif

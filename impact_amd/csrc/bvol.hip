@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "bvol_internal.hpp"
-#include "ivx_internal.hpp"
+#include "device_common.hpp"
 
 namespace {
 
@@ -175,30 +175,8 @@ __global__ __launch_bounds__(256) void k_bv_rows(uint32_t* __restrict__ counts, 
 // in place: row_total -> exclusive prefix (mod 2^32; the host refuses a grand total of 2^31 or more before anything reads it)
 __global__ __launch_bounds__(SCAN_ROUND) void k_bv_scan(uint32_t* __restrict__ row_total, uint32_t n, unsigned long long* __restrict__ grand_total) {
     __shared__ uint32_t wave_totals[SCAN_ROUND / 64u];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-    unsigned long long carry = 0ull;
-    for (uint32_t r0 = 0; r0 < n; r0 += SCAN_ROUND) {
-        const uint32_t row = r0 + t;
-        const uint32_t c = row < n ? row_total[row] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
-            if (lane >= (uint32_t)d) incl += up;
-        }
-        if (lane == 63u) wave_totals[wv] = incl;
-        __syncthreads();
-        uint32_t before = 0u, round_total = 0u;
-        for (uint32_t k = 0; k < SCAN_ROUND / 64u; ++k) {
-            const uint32_t wt = wave_totals[k];
-            before += k < wv ? wt : 0u;
-            round_total += wt;
-        }
-        if (row < n) row_total[row] = (uint32_t)carry + before + (incl - c);
-        carry += round_total;
-        __syncthreads();
-    }
-    if (t == 0u) *grand_total = carry;
+    const unsigned long long total = ivx_scan_rounds<SCAN_ROUND, unsigned long long>(row_total, row_total, n, wave_totals);
+    if (threadIdx.x == 0u) *grand_total = total;
 }
 
 __device__ __forceinline__ bool query_hits(const ivx_bv_query* __restrict__ q, const ivx_aabb& b, const float c[3], const float h[3]) {
@@ -278,40 +256,23 @@ __global__ __launch_bounds__(64) void k_bv_query_counts(const unsigned long long
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-// context-owned state: device buffers that only grow, a pinned staging block for the one upload of a call, and the set the context holds
+// context-owned state: device buffers that only grow, a pinned staging block for the one upload of a call (device_common.hpp), and the set the context holds
 struct BvState {
-    Buf set;      // input boxes | similarities || kinds | world boxes | block boxes | total  (the part before || is the upload's scratch)
-    Buf scratch;  // pairs: counts | row totals | grand total;  queries: records | counts
-    Buf pairs, masks;
-    void* staging = nullptr;  // pinned
-    size_t staging_bytes = 0;
-    hipEvent_t staged = nullptr;  // behind the last upload from `staging`
-    bool staged_pending = false;
+    ivx_buf set;      // input boxes | similarities || kinds | world boxes | block boxes | total  (the part before || is the upload's scratch)
+    ivx_buf scratch;  // pairs: counts | row totals | grand total;  queries: records | counts
+    ivx_buf pairs, masks;
+    ivx_staging staging;  // (with its event: behind the last upload from the block)
     bool has_set = false;
     uint32_t n = 0;
     uint64_t serial = 0;  // counts the sets the context has held (ivx_bvol_set_serial)
     size_t o_kinds = 0, o_world = 0, o_blocks = 0, o_total = 0;
 };
 
-struct Layout {
-    size_t bytes = 0;
-    size_t take(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 255u) & ~(size_t)255u;
-        return at;
-    }
-};
-
 int state_of(ivx_ctx* c, BvState** out) {
     if (!c->bvol_state) {
         BvState* s = new (std::nothrow) BvState();
         IVX_REQUIRE(s, IVX_ERR_CAPACITY, "bounding volumes: out of host memory");
-        const hipError_t e = hipEventCreateWithFlags(&s->staged, hipEventDisableTiming);
+        const hipError_t e = hipEventCreateWithFlags(&s->staging.staged, hipEventDisableTiming);
         if (e != hipSuccess) {
             delete s;
             ivx_set_error("bounding volumes: %s", hipGetErrorString(e));
@@ -320,33 +281,6 @@ int state_of(ivx_ctx* c, BvState** out) {
         c->bvol_state = s;
     }
     *out = static_cast<BvState*>(c->bvol_state);
-    return IVX_OK;
-}
-
-int grow(ivx_ctx* c, Buf* b, size_t bytes, size_t floor_bytes) {
-    if (b->bytes >= bytes) return IVX_OK;
-    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr, b->bytes = 0;
-    bytes = bytes + bytes / 2;
-    if (bytes < floor_bytes) bytes = floor_bytes;
-    IVX_HIP_CHECK(hipMalloc(&b->p, bytes));
-    b->bytes = bytes;
-    return IVX_OK;
-}
-
-int staging_for(BvState* st, size_t bytes) {
-    if (st->staged_pending) {  // the last call's upload has left the block
-        IVX_HIP_CHECK(hipEventSynchronize(st->staged));
-        st->staged_pending = false;
-    }
-    if (st->staging_bytes >= bytes) return IVX_OK;
-    if (st->staging) (void)hipHostFree(st->staging);
-    st->staging = nullptr, st->staging_bytes = 0;
-    bytes = bytes + bytes / 2;
-    if (bytes < (1u << 16)) bytes = 1u << 16;
-    IVX_HIP_CHECK(hipHostMalloc(&st->staging, bytes, hipHostMallocDefault));
-    st->staging_bytes = bytes;
     return IVX_OK;
 }
 
@@ -365,7 +299,7 @@ struct SetLayout {
 };
 SetLayout set_layout(size_t n, bool with_sims) {
     const size_t n_blocks = (n + 63u) / 64u;
-    Layout l;
+    ivx_layout l;
     SetLayout s;
     s.o_in = l.take(n * sizeof(ivx_aabb)), s.o_sims = l.take(with_sims ? n * sizeof(ivx_similarity) : 0), s.o_kinds = l.take(n_blocks * 64u * 4);  // (kinds and world boxes: whole blocks)
     s.upload_bytes = l.bytes;
@@ -403,17 +337,17 @@ int set_enqueue(ivx_ctx* c, const ivx_aabb* boxes, const ivx_similarity* sims, c
     }
     const size_t n_blocks = (n + 63u) / 64u;
     const SetLayout l = set_layout(n, sims != nullptr);
-    if (int rc = staging_for(st, l.upload_bytes)) return rc;
-    if (int rc = grow(c, &st->set, l.bytes, 1u << 16)) return rc;
-    char* h = static_cast<char*>(st->staging);
+    if (int rc = ivx_staging_for(&st->staging, l.upload_bytes)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->set, l.bytes, 1u << 16)) return rc;
+    char* h = static_cast<char*>(st->staging.p);
     char* d = static_cast<char*>(st->set.p);
     memcpy(h + l.o_in, boxes, n * sizeof(ivx_aabb));
     if (sims) memcpy(h + l.o_sims, sims, n * sizeof(ivx_similarity));
     memset(h + l.o_kinds, 0, n_blocks * 64u * 4);
     if (kinds) memcpy(h + l.o_kinds, kinds, n * 4);
     IVX_HIP_CHECK(ivx_memcpy_async(d, h, l.upload_bytes, hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staged, c->stream));
-    st->staged_pending = true;
+    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
+    st->staging.pending = true;
     return set_launch(c, st, l, n, sims != nullptr);
 }
 
@@ -442,10 +376,8 @@ int set_state(ivx_ctx* c, const char* who, BvState** out) {
 void ivx_bvol_release(ivx_ctx* c) {
     if (!c || !c->bvol_state) return;
     BvState* s = static_cast<BvState*>(c->bvol_state);
-    for (Buf* b : {&s->set, &s->scratch, &s->pairs, &s->masks})
-        if (b->p) (void)hipFree(b->p);
-    if (s->staging) (void)hipHostFree(s->staging);
-    if (s->staged) (void)hipEventDestroy(s->staged);
+    for (ivx_buf* b : {&s->set, &s->scratch, &s->pairs, &s->masks}) ivx_buf_free(b);
+    ivx_staging_release(&s->staging);
     delete s;
     c->bvol_state = nullptr;
 }
@@ -457,7 +389,7 @@ int ivx_bvol_set_begin(ivx_ctx* c, size_t n, ivx_aabb** d_boxes, uint32_t** d_ki
     st->has_set = false, st->n = 0;  // (until ivx_bvol_set_finish)
     if (n == 0) return IVX_OK;
     const SetLayout l = set_layout(n, false);
-    if (int rc = grow(c, &st->set, l.bytes, 1u << 16)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->set, l.bytes, 1u << 16)) return rc;
     char* d = static_cast<char*>(st->set.p);
     *d_boxes = reinterpret_cast<ivx_aabb*>(d + l.o_in), *d_kinds = reinterpret_cast<uint32_t*>(d + l.o_kinds);
     return IVX_OK;
@@ -485,9 +417,9 @@ int ivx_bvol_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool chec
     const uint32_t n = st->n;
     if (n < 2u) return IVX_OK;
     const uint32_t n_blocks = (n + 63u) / 64u, n_seg = (n_blocks + SEG_BLOCKS - 1u) / SEG_BLOCKS;
-    Layout l;
+    ivx_layout l;
     const size_t o_counts = l.take((size_t)n_seg * n * 4), o_rows = l.take((size_t)n * 4), o_grand = l.take(8);
-    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
     char* s = static_cast<char*>(st->scratch.p);
     const char* d = static_cast<const char*>(st->set.p);
     const ivx_aabb* d_world = reinterpret_cast<const ivx_aabb*>(d + st->o_world);
@@ -508,7 +440,7 @@ int ivx_bvol_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool chec
     *n_pairs = (size_t)grand;
     IVX_REQUIRE(!check_cap || grand <= cap, IVX_ERR_CAPACITY, "%s: %llu intersecting pairs, the buffer holds %zu", who, grand, cap);
     if (grand == 0) return IVX_OK;
-    if (int rc = grow(c, &st->pairs, (size_t)grand * 8, 1u << 16)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->pairs, (size_t)grand * 8, 1u << 16)) return rc;
     IVX_KLAUNCH(k_bv_pair_walk<true>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)d_rows,
                 static_cast<uint2*>(st->pairs.p));
     IVX_HIP_CHECK(hipGetLastError());
@@ -624,17 +556,17 @@ int ivx_bv_queries(ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries, ui
     }
     IVX_REQUIRE(masks, IVX_ERR_INVALID, "%s: null mask buffer", who);
     ivx_many_other_context other_(c);
-    Layout l;
+    ivx_layout l;
     const size_t o_q = l.take(n_queries * sizeof(ivx_bv_query)), o_c = l.take(n_queries * 4);
-    if (int rc = staging_for(st, n_queries * sizeof(ivx_bv_query))) return rc;
-    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
+    if (int rc = ivx_staging_for(&st->staging, n_queries * sizeof(ivx_bv_query))) return rc;
+    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
     const size_t mask_bytes = n_queries * (size_t)n_words * 8;
-    if (int rc = grow(c, &st->masks, mask_bytes, 1u << 16)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->masks, mask_bytes, 1u << 16)) return rc;
     char* s = static_cast<char*>(st->scratch.p);
-    memcpy(st->staging, queries, n_queries * sizeof(ivx_bv_query));
-    IVX_HIP_CHECK(ivx_memcpy_async(s + o_q, st->staging, n_queries * sizeof(ivx_bv_query), hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staged, c->stream));
-    st->staged_pending = true;
+    memcpy(st->staging.p, queries, n_queries * sizeof(ivx_bv_query));
+    IVX_HIP_CHECK(ivx_memcpy_async(s + o_q, st->staging.p, n_queries * sizeof(ivx_bv_query), hipMemcpyHostToDevice, c->stream));
+    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
+    st->staging.pending = true;
     unsigned long long* d_masks = static_cast<unsigned long long*>(st->masks.p);
     uint32_t* d_counts = reinterpret_cast<uint32_t*>(s + o_c);
     IVX_KLAUNCH(k_bv_query, dim3((n_words + 3u) / 4u), dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(static_cast<const char*>(st->set.p) + st->o_world), n,

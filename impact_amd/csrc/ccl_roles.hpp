@@ -16,24 +16,6 @@ __device__ __forceinline__ uint32_t flags_mask(uint4 f) {
     return m;
 }
 
-__device__ __forceinline__ uint32_t prefix_ordered(uint32_t val, uint32_t* s_wsum, uint32_t tid, uint32_t& total) {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    uint32_t incl = val;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t n = __shfl_up(incl, o, 64);
-        if (lane >= (uint32_t)o) incl += n;
-    }
-    if (lane == 63u) s_wsum[wave] = incl;
-    __syncthreads();
-    uint32_t w0 = s_wsum[0], w1 = s_wsum[1], w2 = s_wsum[2], w3 = s_wsum[3];
-    uint32_t wbase = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
-    total = w0 + w1 + w2 + w3;
-    __syncthreads();
-    return wbase + incl - val;
-}
-
-
 // Exact chunk-local numbering of the chunks with several regions (the list ccl_local_chunk made): one workgroup per listed chunk,
 // all 256 threads (ccl_exact_chunk, chunk_passes.hpp). The non-empty masks come from the flags plane.
 __device__ __forceinline__ void role_ccl_local_exact(uint32_t bid, uint32_t nb, CclShared& sh, const uint8_t* __restrict__ flags, uint8_t* __restrict__ labels,
@@ -221,12 +203,7 @@ __device__ __forceinline__ void role_ccl_flatten(uint32_t bid, uint32_t nb, Grid
     // exclusive prefix of the root counts inside this group of 256 chunks (ordered) and the group's total: the two levels of
     // the scan; k_ccl_assign adds the totals of the groups before
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if (lane >= (uint32_t)o) incl += t;
-    }
+    const uint32_t incl = ivx_wave_incl_scan(n);
     if (lane == 63u) s_w[wave] = incl;
     __syncthreads();
     const uint32_t w0 = s_w[0], w1 = s_w[1], w2 = s_w[2], w3 = s_w[3];
@@ -279,7 +256,7 @@ __device__ __forceinline__ void role_ccl_assign(uint32_t bid, uint32_t nb, GridV
             const uint32_t v = gi < n_groups ? group_sums[gi] : 0u;
             uint32_t tot;
             __shared__ uint32_t s_ws[4];
-            const uint32_t ex = prefix_ordered(v, s_ws, threadIdx.x, tot);
+            const uint32_t ex = ivx_block_prefix(v, s_ws, threadIdx.x, tot);
             if (gi < n_groups) s_gpre[gi] = s_carry + ex;
             __syncthreads();
             if (threadIdx.x == 0) s_carry += tot;

@@ -197,12 +197,7 @@ __device__ __forceinline__ void ccl_exact_chunk(CclShared& sh, uint32_t tid, uin
     uint32_t src_first, n_sources;
     {
         const uint32_t n_s = __popc(sources);
-        uint32_t incl = n_s;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o, 64);
-            if (lane >= (uint32_t)o) incl += t;
-        }
+        const uint32_t incl = ivx_wave_incl_scan(n_s);
         if (lane == 63u) sh.w[wave] = incl;
         __syncthreads();
         const uint32_t w0 = sh.w[0], w1 = sh.w[1], w2 = sh.w[2], w3 = sh.w[3];
@@ -250,12 +245,7 @@ __device__ __forceinline__ void ccl_exact_chunk(CclShared& sh, uint32_t tid, uin
     }
     uint32_t n_mine = __popc(evy) + __popc(evz), first, total;
     {   // ordered block prefix (thread order = voxel order)
-        uint32_t incl = n_mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o, 64);
-            if (lane >= (uint32_t)o) incl += t;
-        }
+        const uint32_t incl = ivx_wave_incl_scan(n_mine);
         if (lane == 63u) sh.w[4 + wave] = incl;
         __syncthreads();
         const uint32_t w0 = sh.w[4], w1 = sh.w[5], w2 = sh.w[6], w3 = sh.w[7];
@@ -389,12 +379,7 @@ __device__ __forceinline__ void ccl_exact_chunk(CclShared& sh, uint32_t tid, uin
     uint32_t id0, n_sets;
     {
         const uint32_t n_r = __popc(roots);
-        uint32_t incl = n_r;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o, 64);
-            if (lane >= (uint32_t)o) incl += t;
-        }
+        const uint32_t incl = ivx_wave_incl_scan(n_r);
         __syncthreads();
         if (lane == 63u) sh.w[wave] = incl;
         __syncthreads();
@@ -444,12 +429,7 @@ __device__ __forceinline__ void ccl_exact_chunk(CclShared& sh, uint32_t tid, uin
     uint32_t inner_rank, n_inner;
     {   // rank of the interior-only sets among themselves (ids are in root order)
         const uint32_t is_inner = (tid < n_sets && !touches) ? 1u : 0u;
-        uint32_t incl = is_inner;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o, 64);
-            if (lane >= (uint32_t)o) incl += t;
-        }
+        const uint32_t incl = ivx_wave_incl_scan(is_inner);
         __syncthreads();
         if (lane == 63u) sh.w[wave] = incl;
         __syncthreads();

@@ -21,38 +21,16 @@
 // order: count per workgroup of 256 probes, one scan over the workgroups of both passes (A's probes first, then B's), ordered
 // emit.
 #include "ivx_internal.hpp"
+#include "vec3.hpp"
 
 namespace {
+
+using namespace ivx_vec;  // V3, Q4, ld3, the operators, dot, cross, qrot, splitmix
 
 constexpr uint32_t PROBE_MAXV = 4928u;  // a chunk's Surface Nets vertices: one per cube of the 17^3 the chunk owns, at most
 constexpr uint32_t PROBE_SMALLV = 1024u;
 
-struct V3 {
-    float x, y, z;
-};
-__device__ __forceinline__ V3 mk(float x, float y, float z) { return {x, y, z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ V3 cmul(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
-struct Q4 {
-    float x, y, z, w;
-};
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {  // glam Quat::mul_vec3a
-    const V3 b = mk(q.x, q.y, q.z);
-    const float b2 = dot(b, b);
-    return (v * (q.w * q.w - b2) + b * (dot(v, b) * 2.0f)) + cross(b, v) * (q.w * 2.0f);
-}
-__device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ unsigned long long splitmix(unsigned long long state) {  // impact_math/src/random/splitmix.rs:4-10
-    state += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = state;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 // `f32 as usize`, as far as a voxel index can matter: negative and NaN give 0, anything beyond the grid stays beyond it
 __device__ __forceinline__ uint32_t as_index(float f) {
     const uint32_t u = (uint32_t)f;  // v_cvt_u32_f32 saturates
@@ -60,24 +38,6 @@ __device__ __forceinline__ uint32_t as_index(float f) {
 }
 
 // ---- probes ----------------------------------------------------------------------------------------------------------------------
-// exclusive scan of `mine` over the 256 threads of the workgroup; total in *total
-__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t mine, uint32_t* s_w, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if (lane >= (uint32_t)o) incl += t;
-    }
-    __syncthreads();  // (s_w may still be read from a previous call)
-    if (lane == 63u) s_w[wave] = incl;
-    __syncthreads();
-    const uint32_t w0 = s_w[0], w1 = s_w[1], w2 = s_w[2], w3 = s_w[3];
-    const uint32_t wbase = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
-    *total = (w0 + w1) + (w2 + w3);
-    return wbase + incl - mine;
-}
-
 // MAXV = the most vertices a workgroup of this variant takes (its LDS footprint: 12 B per vertex). Chunk meshes have a few hundred
 // vertices, the worst case is 4913: the launcher runs a small variant (1024 vertices, 12 KB: many workgroups per CU) for the chunks that fit
 // it and the full-size one for the rest; a workgroup whose chunk belongs to the other variant leaves at once.
@@ -135,7 +95,8 @@ __device__ __forceinline__ void probe_select_body(const ProbeSelectArgs& a, uint
         uint32_t mine = 0;
         for (uint32_t v = v0; v < v1; ++v) mine += s_fill[v];
         uint32_t total;
-        uint32_t run = wg_exclusive_scan(mine, s_w, &total);
+        __syncthreads();  // (s_w may still be read from a previous scan)
+        uint32_t run = ivx_block_prefix<false>(mine, s_w, tid, total);
         for (uint32_t v = v0; v < v1; ++v) {
             s_start[v] = run;
             run += s_fill[v];
@@ -201,7 +162,8 @@ __device__ __forceinline__ void probe_select_body(const ProbeSelectArgs& a, uint
         uint32_t mine = 0;
         for (uint32_t b = b0; b < b1; ++b) mine += s_best[b] != ~0ull ? 1u : 0u;
         uint32_t total;
-        uint32_t run = wg_exclusive_scan(mine, s_w, &total);
+        __syncthreads();  // (s_w may still be read from the scan above)
+        uint32_t run = ivx_block_prefix<false>(mine, s_w, tid, total);
         for (uint32_t b = b0; b < b1; ++b) {
             const unsigned long long k = s_best[b];
             if (k != ~0ull) sel[(size_t)s * n_blocks + run++] = voff + (uint32_t)(k & 0xFFFFFFFFull);
@@ -231,27 +193,11 @@ struct ScanCountsArgs {
     uint32_t n, pad;
 };
 __device__ __forceinline__ void scan_counts_body(const ScanCountsArgs& a, uint32_t, uint32_t) {
-    const uint32_t n = a.n;
-    const uint32_t* __restrict__ counts = a.counts;
-    uint32_t* __restrict__ offsets = a.offsets;
     __shared__ uint32_t s_w[4];
-    __shared__ uint32_t s_carry;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < n; b0 += 256u) {
-        const uint32_t b = b0 + tid;
-        const uint32_t v = b < n ? counts[b] : 0u;
-        uint32_t total;
-        const uint32_t ex = wg_exclusive_scan(v, s_w, &total);
-        if (b < n) offsets[b] = s_carry + ex;
-        __syncthreads();
-        if (tid == 0) s_carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        offsets[n] = s_carry;
-        if (a.total_out) *a.total_out = s_carry;
+    const uint32_t total = ivx_scan_rounds<256u>(a.counts, a.offsets, a.n, s_w);
+    if (threadIdx.x == 0) {
+        a.offsets[a.n] = total;
+        if (a.total_out) *a.total_out = total;
     }
 }
 __global__ __launch_bounds__(256) void k_scan_counts(ScanCountsArgs a) { scan_counts_body(a, 0u, 1u); }

@@ -17,35 +17,11 @@
 // solver's result depends on that order, so the emit pass is an ordered compaction: counts per chunk, a scan over the chunks
 // of the box, then thread-ordered prefix sums inside each chunk.
 #include "ivx_internal.hpp"
+#include "vec3.hpp"
 
 namespace {
 
-struct V3 {
-    float x, y, z;
-};
-__device__ __forceinline__ V3 mk(float x, float y, float z) { return {x, y, z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
-struct Q4 {
-    float x, y, z, w;
-};
-// glam Quat::mul_vec3a
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
-    const V3 b = mk(q.x, q.y, q.z);
-    const float b2 = dot(b, b);
-    return (v * (q.w * q.w - b2) + b * (dot(v, b) * 2.0f)) + cross(b, v) * (q.w * 2.0f);
-}
-// impact_math/src/random/splitmix.rs:4-10
-__device__ __forceinline__ unsigned long long splitmix(unsigned long long state) {
-    state += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = state;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+using namespace ivx_vec;  // V3, Q4, the operators, dot, cross, qrot, splitmix
 
 struct SvcParams {
     GridView g;
@@ -202,34 +178,9 @@ IVX_MANY_LAUNCHER(many_svc_count, k_svc_count_many, SvcCountArgs, 256)
 
 // exclusive scan over the chunks of the box (one workgroup; the box of a collidable is a few dozen chunks)
 __device__ __forceinline__ void svc_scan_body(const SvcScanArgs& a, uint32_t, uint32_t) {
-    const uint32_t n = a.n;
-    const uint32_t* __restrict__ counts = a.counts;
-    uint32_t* __restrict__ offsets = a.offsets;
-    uint32_t* __restrict__ total = a.total;
     __shared__ uint32_t s_w[4];
-    __shared__ uint32_t s_carry;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < n; b0 += 256u) {
-        const uint32_t b = b0 + tid;
-        const uint32_t v = b < n ? counts[b] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o, 64);
-            if (lane >= (uint32_t)o) incl += t;
-        }
-        if (lane == 63u) s_w[wave] = incl;
-        __syncthreads();
-        const uint32_t w0 = s_w[0], w1 = s_w[1], w2 = s_w[2], w3 = s_w[3];
-        const uint32_t wbase = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
-        if (b < n) offsets[b] = s_carry + wbase + incl - v;
-        __syncthreads();
-        if (tid == 0) s_carry += (w0 + w1) + (w2 + w3);
-        __syncthreads();
-    }
-    if (tid == 0) *total = s_carry;
+    const uint32_t sum = ivx_scan_rounds<256u>(a.counts, a.offsets, a.n, s_w);
+    if (threadIdx.x == 0) *a.total = sum;
 }
 __global__ __launch_bounds__(256) void k_svc_scan(SvcScanArgs a) { svc_scan_body(a, 0u, 1u); }
 IVX_MANY_TWIN(k_svc_scan_many, SvcScanArgs, svc_scan_body, __launch_bounds__(256))
@@ -245,21 +196,11 @@ __device__ __forceinline__ void svc_emit_body(const SvcEmitArgs& a, uint32_t bid
     uint32_t ci, cj, ck;
     const uint32_t chunk = box_chunk(p, bid, ci, cj, ck);
     if (p.g.info[chunk].kind != KIND_NONUNIFORM) return;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     Hit hits[16];
     const uint32_t mask = row_contacts<true>(p, p.g.sdf, flags, chunk, ci, cj, ck, tid, hits);
-    const uint32_t v = __popc(mask);
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if (lane >= (uint32_t)o) incl += t;
-    }
-    if (lane == 63u) s_w[wave] = incl;
-    __syncthreads();
-    const uint32_t w0 = s_w[0], w1 = s_w[1], w2 = s_w[2];
-    const uint32_t wbase = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
-    uint32_t slot = offsets[bid] + wbase + incl - v;
+    uint32_t chunk_total;  // (not needed: the count pass has it)
+    uint32_t slot = offsets[bid] + ivx_block_prefix<false>(__popc(mask), s_w, tid, chunk_total);
     const unsigned long long gi = ci * 16u + (tid >> 4), gj = cj * 16u + (tid & 15u);
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -320,16 +261,7 @@ int ivx_launch_sphere_contacts(ivx_grid* g, const uint32_t lo[3], const uint32_t
     p.q_inv = Q4{-rotation_xyzw[0], -rotation_xyzw[1], -rotation_xyzw[2], rotation_xyzw[3]};
     p.r = radius;
     p.extent = g->extent;
-    {  // ContactID::from_two_u64_and_n_indices: the part that does not depend on the voxel
-        auto mix = [](uint64_t state) {
-            state += 0x9E3779B97F4A7C15ull;
-            uint64_t z = state;
-            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-            return z ^ (z >> 31);
-        };
-        p.id_ab = mix(id_a ^ mix(id_b));
-    }
+    p.id_ab = splitmix(id_a ^ splitmix(id_b));  // ContactID::from_two_u64_and_n_indices: the part that does not depend on the voxel
     p.body_a = body_a;
     p.body_b = body_b;
     p.restitution = response[0];

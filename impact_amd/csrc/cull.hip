@@ -21,7 +21,7 @@
 #include <new>
 #include <vector>
 
-#include "ivx_internal.hpp"
+#include "device_common.hpp"
 
 namespace {
 
@@ -200,12 +200,7 @@ __global__ __launch_bounds__(64) void k_cull_scan(uint4* __restrict__ tile_info,
             const uint4 r = info[t];
             c = (uint32_t)__popc(r.x) + (uint32_t)__popc(r.y), ic = r.z;
         }
-        uint32_t incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
-            if (lane >= (uint32_t)d) incl += up;
-        }
+        const uint32_t incl = ivx_wave_incl_scan(c);
         if (t < n_tiles) info[t].w = draws + incl - c;
         draws += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         indices += ivx_wave_sum(ic);
@@ -237,30 +232,13 @@ __global__ __launch_bounds__(256) void k_cull_place(const uint2* __restrict__ ti
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-// context-owned state: device buffers that only grow, a pinned staging block for the one upload of a call, and the layout of the last call
+// context-owned state: device buffers that only grow, a pinned staging block for the one upload of a call (device_common.hpp), and the layout of the last call
 struct CullState {
-    Buf args, frusta, scratch;
+    ivx_buf args, frusta, scratch;
     void* d_counts = nullptr;  // MAX_VIEWS records
-    void* staging = nullptr;   // pinned
-    size_t staging_bytes = 0;
-    hipEvent_t staged = nullptr;  // behind the last upload from `staging`
-    bool staged_pending = false;
+    ivx_staging staging;       // (with its event: behind the last upload from the block)
     uint32_t n_views = 0, n_obj = 0, total = 0;
     ivx_cull_region regions[MAX_VIEWS];
-};
-
-struct Layout {
-    size_t bytes = 0;
-    size_t take(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 255u) & ~(size_t)255u;
-        return at;
-    }
 };
 
 int state_of(ivx_ctx* c, CullState** out) {
@@ -268,7 +246,7 @@ int state_of(ivx_ctx* c, CullState** out) {
         CullState* s = new (std::nothrow) CullState();
         IVX_REQUIRE(s, IVX_ERR_CAPACITY, "chunk culling: out of host memory");
         hipError_t e = hipMalloc(&s->d_counts, MAX_VIEWS * sizeof(ivx_cull_count));
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->staged, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->staging.staged, hipEventDisableTiming);
         if (e != hipSuccess) {
             if (s->d_counts) (void)hipFree(s->d_counts);
             delete s;
@@ -278,33 +256,6 @@ int state_of(ivx_ctx* c, CullState** out) {
         c->cull_state = s;
     }
     *out = static_cast<CullState*>(c->cull_state);
-    return IVX_OK;
-}
-
-int grow(ivx_ctx* c, Buf* b, size_t bytes, size_t floor_bytes) {
-    if (b->bytes >= bytes) return IVX_OK;
-    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr, b->bytes = 0;
-    bytes = bytes + bytes / 2;
-    if (bytes < floor_bytes) bytes = floor_bytes;
-    IVX_HIP_CHECK(hipMalloc(&b->p, bytes));
-    b->bytes = bytes;
-    return IVX_OK;
-}
-
-int staging_for(CullState* st, size_t bytes) {
-    if (st->staged_pending) {  // the last call's upload has left the block
-        IVX_HIP_CHECK(hipEventSynchronize(st->staged));
-        st->staged_pending = false;
-    }
-    if (st->staging_bytes >= bytes) return IVX_OK;
-    if (st->staging) (void)hipHostFree(st->staging);
-    st->staging = nullptr, st->staging_bytes = 0;
-    bytes = bytes + bytes / 2;
-    if (bytes < (1u << 16)) bytes = 1u << 16;
-    IVX_HIP_CHECK(hipHostMalloc(&st->staging, bytes, hipHostMallocDefault));
-    st->staging_bytes = bytes;
     return IVX_OK;
 }
 
@@ -352,7 +303,7 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
     IVX_REQUIRE(total64 < (1ull << 31) && n_pairs < (1ull << 31), IVX_ERR_CAPACITY, "%s: %llu submeshes in all, %zu (view, object) pairs: too many for one call", j.who,
                 (unsigned long long)total64, n_pairs);
     const uint32_t total = (uint32_t)total64;
-    Layout regions;
+    ivx_layout regions;
     for (size_t v = 0; v < n_views; ++v) {
         const bool indexed = ((j.records ? j.view_flags[v] : j.views[v].flags) & IVX_CULL_VIEW_INDEXED) != 0u;
         st->regions[v].stride = indexed ? 20u : 16u;
@@ -366,17 +317,17 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
     };
     if (n_views == 0) return done();
     // one staging block: views | pairs | records | pair flags | objects | view regions | tiles | tables
-    Layout l;
+    ivx_layout l;
     const size_t o_views = l.take(j.records ? 0 : n_views * sizeof(ivx_cull_view)), o_pairs = l.take(j.records ? 0 : n_pairs * sizeof(ivx_cull_pair)),
                  o_recs = l.take(j.records ? n_pairs * sizeof(ivx_culling_frustum) : 0), o_flags = l.take(n_pairs * 4), o_objs = l.take(n_obj * sizeof(CullObj)),
                  o_vout = l.take(n_views * sizeof(CullViewOut)), o_tiles = l.take(n_tiles * sizeof(uint2)), o_tables = l.take(table_bytes);
     const size_t upload_bytes = l.bytes;
     const size_t o_info = l.take(n_views * n_tiles * sizeof(uint4));
-    if (int rc = staging_for(st, upload_bytes)) return rc;
-    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
-    if (int rc = grow(c, &st->args, regions.bytes, 1u << 20)) return rc;
-    if (int rc = grow(c, &st->frusta, n_pairs * sizeof(ivx_culling_frustum), 1u << 16)) return rc;
-    char* h = static_cast<char*>(st->staging);
+    if (int rc = ivx_staging_for(&st->staging, upload_bytes)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->args, regions.bytes, 1u << 20)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->frusta, n_pairs * sizeof(ivx_culling_frustum), 1u << 16)) return rc;
+    char* h = static_cast<char*>(st->staging.p);
     char* d = static_cast<char*>(st->scratch.p);
     if (j.records) {
         if (n_pairs) memcpy(h + o_recs, j.frusta, n_pairs * sizeof(ivx_culling_frustum));
@@ -410,8 +361,8 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
     CullViewOut* vout = reinterpret_cast<CullViewOut*>(h + o_vout);
     for (size_t v = 0; v < n_views; ++v) vout[v].offset = st->regions[v].offset, vout[v].indexed = st->regions[v].stride == 20u ? 1u : 0u, vout[v].pad = 0u;
     IVX_HIP_CHECK(ivx_memcpy_async(d, h, upload_bytes, hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staged, c->stream));
-    st->staged_pending = true;
+    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
+    st->staging.pending = true;
     ivx_culling_frustum* d_frusta = static_cast<ivx_culling_frustum*>(st->frusta.p);
     const CullObj* d_objs = reinterpret_cast<const CullObj*>(d + o_objs);
     if (n_pairs) {
@@ -518,12 +469,9 @@ int many_enqueue(const char* who, ivx_grid* const* grids, size_t n, const ivx_cu
 void ivx_cull_release(ivx_ctx* c) {
     if (!c || !c->cull_state) return;
     CullState* s = static_cast<CullState*>(c->cull_state);
-    if (s->args.p) (void)hipFree(s->args.p);
-    if (s->frusta.p) (void)hipFree(s->frusta.p);
-    if (s->scratch.p) (void)hipFree(s->scratch.p);
+    for (ivx_buf* b : {&s->args, &s->frusta, &s->scratch}) ivx_buf_free(b);
     if (s->d_counts) (void)hipFree(s->d_counts);
-    if (s->staging) (void)hipHostFree(s->staging);
-    if (s->staged) (void)hipEventDestroy(s->staged);
+    ivx_staging_release(&s->staging);
     delete s;
     c->cull_state = nullptr;
 }

@@ -23,7 +23,7 @@
 #include <cmath>
 #include <vector>
 
-#include "ivx_internal.hpp"
+#include "device_common.hpp"
 
 namespace {
 
@@ -317,27 +317,8 @@ __global__ __launch_bounds__(64) void k_drag_map(const SampleRec* __restrict__ r
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-int ensure_scratch(ivx_ctx* c, size_t bytes) {
-    if (c->drag_scratch_bytes >= bytes) return IVX_OK;
-    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
-    if (c->drag_scratch) (void)hipFree(c->drag_scratch);
-    c->drag_scratch = nullptr;
-    c->drag_scratch_bytes = 0;
-    if (bytes < (1u << 20)) bytes = 1u << 20;
-    IVX_HIP_CHECK(hipMalloc(&c->drag_scratch, bytes));
-    c->drag_scratch_bytes = bytes;
-    return IVX_OK;
-}
-
-// parts of the scratch allocation, each on a 256-byte boundary: reserve all, then `base`
-struct Layout {
-    size_t bytes = 0;
-    size_t take(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 255u) & ~(size_t)255u;
-        return at;
-    }
-};
+// the context's scratch allocation (the parts of a call each on a 256-byte boundary: ivx_layout), at least 1 MiB
+int ensure_scratch(ivx_ctx* c, size_t bytes) { return ivx_buf_grow(c, &c->drag_scratch, bytes, 1u << 20); }
 
 // how the load pass tiles `n_tris` triangles for `n_dirs` directions (a function of the two counts alone)
 struct LoadPlan {
@@ -498,11 +479,11 @@ int ivx_drag_loads_triangles(ivx_ctx* c, const float* positions3, size_t n_verti
         return IVX_OK;
     }
     const LoadPlan p = plan_loads((uint32_t)(n_indices / 3), (uint32_t)n_dirs);
-    Layout l;
+    ivx_layout l;
     const size_t o_pos = l.take(n_vertices * 12), o_idx = l.take(n_indices * 4), o_dirs = l.take(n_dirs * 12), o_recs = l.take(p.recs_bytes()),
                  o_part = l.take(p.partials_bytes()), o_out = l.take(n_dirs * sizeof(ivx_drag_load));
     if (int rc = ensure_scratch(c, l.bytes)) return rc;
-    char* base = static_cast<char*>(c->drag_scratch);
+    char* base = static_cast<char*>(c->drag_scratch.p);
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_pos, positions3, n_vertices * 12, hipMemcpyHostToDevice, c->stream));
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_idx, indices, n_indices * 4, hipMemcpyHostToDevice, c->stream));
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_dirs, dirs3, n_dirs * 12, hipMemcpyHostToDevice, c->stream));
@@ -526,10 +507,10 @@ int ivx_drag_loads(ivx_grid* g, const float com[3], const float* dirs3, size_t n
         return IVX_OK;
     }
     const LoadPlan p = plan_loads(g->mesh_counts.n_indices / 3u, (uint32_t)n_dirs);
-    Layout l;
+    ivx_layout l;
     const size_t o_dirs = l.take(n_dirs * 12), o_recs = l.take(p.recs_bytes()), o_part = l.take(p.partials_bytes()), o_out = l.take(n_dirs * sizeof(ivx_drag_load));
     if (int rc = ensure_scratch(c, l.bytes)) return rc;
-    char* base = static_cast<char*>(c->drag_scratch);
+    char* base = static_cast<char*>(c->drag_scratch.p);
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_dirs, dirs3, n_dirs * 12, hipMemcpyHostToDevice, c->stream));
     float4* d_recs = reinterpret_cast<float4*>(base + o_recs);
     if (int rc = launch_records_resident(g, p, com, d_recs)) return rc;
@@ -546,10 +527,10 @@ int ivx_drag_load_map_from_samples(ivx_ctx* c, const float* dirs3, const ivx_dra
     if (int rc = check_map_shape("ivx_drag_load_map_from_samples", n_theta, angular_interpolation_distance)) return rc;
     ivx_many_other_context other_(c);
     const size_t map_bytes = 2u * (size_t)n_theta * n_theta * sizeof(ivx_drag_load);
-    Layout l;
+    ivx_layout l;
     const size_t o_dirs = l.take(n * 12), o_loads = l.take(n * sizeof(ivx_drag_load)), o_samples = l.take(n * sizeof(SampleRec)), o_map = l.take(map_bytes);
     if (int rc = ensure_scratch(c, l.bytes)) return rc;
-    char* base = static_cast<char*>(c->drag_scratch);
+    char* base = static_cast<char*>(c->drag_scratch.p);
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_dirs, dirs3, n * 12, hipMemcpyHostToDevice, c->stream));
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_loads, loads, n * sizeof(ivx_drag_load), hipMemcpyHostToDevice, c->stream));
     if (int rc = launch_map(c, reinterpret_cast<const float*>(base + o_dirs), reinterpret_cast<const float*>(base + o_loads), (uint32_t)n, n_theta, angular_interpolation_distance,
@@ -579,11 +560,11 @@ int ivx_drag_load_map(ivx_grid* g, const float com[3], const ivx_drag_map_config
     std::vector<float> dirs(3 * (size_t)n);
     if (int rc = ivx_drag_directions(n, dirs.data())) return rc;
     const LoadPlan p = plan_loads(g->mesh_counts.n_indices / 3u, n);
-    Layout l;
+    ivx_layout l;
     const size_t o_dirs = l.take((size_t)n * 12), o_recs = l.take(p.recs_bytes()), o_part = l.take(p.partials_bytes()), o_loads = l.take((size_t)n * sizeof(ivx_drag_load)),
                  o_samples = l.take((size_t)n * sizeof(SampleRec)), o_map = l.take(map_bytes);
     if (int rc = ensure_scratch(c, l.bytes)) return rc;
-    char* base = static_cast<char*>(c->drag_scratch);
+    char* base = static_cast<char*>(c->drag_scratch.p);
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_dirs, dirs.data(), (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));  // (`dirs` is pageable memory of this call)
     float4* d_recs = reinterpret_cast<float4*>(base + o_recs);

@@ -18,7 +18,7 @@
 
 #include <dlfcn.h>
 
-#include "ivx_internal.hpp"
+#include "device_common.hpp"
 
 static thread_local char g_error[512] = "";
 
@@ -479,7 +479,7 @@ void ivx_shutdown(ivx_ctx* c) {
     ivx_many_release(c);  // (the launch recorder of the many-object calls and its staging ring)
     if (c->pinned_scratch) (void)hipHostFree(c->pinned_scratch);
     if (c->dev_scratch) (void)hipFree(c->dev_scratch);
-    if (c->drag_scratch) (void)hipFree(c->drag_scratch);
+    ivx_buf_free(&c->drag_scratch);
     ivx_cull_release(c);
     ivx_bvol_release(c);
     if (c->aux_stream) {

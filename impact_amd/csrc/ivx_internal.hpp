@@ -57,6 +57,12 @@ static inline hipError_t ivx_event_record(hipEvent_t e, hipStream_t s) {
 #define TYPE_DUMMY 255
 #define SD_VOID_LIMIT 100
 
+// a device allocation that only grows (ivx_buf_grow / ivx_buf_free, device_common.hpp)
+struct ivx_buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
 struct ivx_ctx {
     int device;
     hipStream_t stream;
@@ -72,8 +78,7 @@ struct ivx_ctx {
     hipStream_t aux_stream;  // made on first use (ivx_aux_stream): the sampler's pre-pass one step ahead (ivx_grid_set_sample_ahead)
     void* many_recorder;  // the launch recorder of ivx_many_begin / _flush and its staging ring (many.cpp); made on first use, freed by ivx_shutdown
     int many_error;       // a flush of recorded launches failed on this context (sticky until reported: ivx_many_error)
-    void* drag_scratch;   // device scratch of the drag entry points (drag.hip: triangle records, per-tile partials, samples, map); grown on demand, freed by ivx_shutdown
-    size_t drag_scratch_bytes;
+    ivx_buf drag_scratch;  // device scratch of the drag entry points (drag.hip: triangle records, per-tile partials, samples, map); grown on demand, freed by ivx_shutdown
     void* cull_state;  // chunk culling (cull.hip): argument, count and frustum buffers, staging block, the last call's layout; made on first use, freed by ivx_cull_release
     void* bvol_state;  // bounding volumes (bvol.hip): world boxes, kinds, block boxes, pair and mask buffers, staging block; made on first use, freed by ivx_bvol_release
 };
@@ -338,6 +343,58 @@ __device__ __forceinline__ uint32_t ivx_wave_sum(uint32_t v) {
     v = ivx_row16_sum(v);
     return ((uint32_t)__builtin_amdgcn_readlane((int)v, 15) + (uint32_t)__builtin_amdgcn_readlane((int)v, 31)) +
            ((uint32_t)__builtin_amdgcn_readlane((int)v, 47) + (uint32_t)__builtin_amdgcn_readlane((int)v, 63));
+}
+
+// Ordered prefix sums (thread order = output order), for the compactions that must keep the reference's traversal order. Unsigned sums only.
+//   ivx_wave_incl_scan: inclusive prefix over the 64 lanes of a wave (of a one-dimensional workgroup); lane 63 = wave total.
+//   ivx_block_prefix:   exclusive prefix of `val` over a workgroup of 256 threads; `total` = block sum, the same in every thread. s_wsum: four
+//                       words of LDS. TRAILING = false: no barrier behind the read of the wave sums — for a caller that does not write them
+//                       again before another barrier.
+//   ivx_scan_rounds:    exclusive prefix of counts[0, n) into offsets[0, n) (which may be the same array) by ONE workgroup of ROUND threads,
+//                       ROUND counts a round, what the rounds before added up to carried in a register. Returns the total in every thread;
+//                       offsets are mod 2^32, Total = unsigned long long keeps a total that may pass that. s_wsum: ROUND / 64 words of LDS.
+__device__ __forceinline__ uint32_t ivx_wave_incl_scan(uint32_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(v, o, 64);
+        if (lane >= (uint32_t)o) v += t;
+    }
+    return v;
+}
+template <bool TRAILING = true>
+__device__ __forceinline__ uint32_t ivx_block_prefix(uint32_t val, uint32_t* s_wsum, uint32_t tid, uint32_t& total) {
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    const uint32_t incl = ivx_wave_incl_scan(val);
+    if (lane == 63u) s_wsum[wave] = incl;
+    __syncthreads();
+    const uint32_t w0 = s_wsum[0], w1 = s_wsum[1], w2 = s_wsum[2], w3 = s_wsum[3];
+    const uint32_t wbase = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
+    total = w0 + w1 + w2 + w3;
+    if (TRAILING) __syncthreads();
+    return wbase + incl - val;
+}
+template <uint32_t ROUND, typename Total = uint32_t>
+__device__ __forceinline__ Total ivx_scan_rounds(const uint32_t* counts, uint32_t* offsets, uint32_t n, uint32_t* s_wsum) {
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+    Total carry = 0;
+    for (uint32_t r0 = 0; r0 < n; r0 += ROUND) {
+        const uint32_t i = r0 + t;
+        const uint32_t c = i < n ? counts[i] : 0u;
+        const uint32_t incl = ivx_wave_incl_scan(c);
+        if (lane == 63u) s_wsum[wv] = incl;
+        __syncthreads();
+        uint32_t before = 0u, round_total = 0u;
+        for (uint32_t k = 0; k < ROUND / 64u; ++k) {
+            const uint32_t wt = s_wsum[k];
+            before += k < wv ? wt : 0u;
+            round_total += wt;
+        }
+        if (i < n) offsets[i] = (uint32_t)carry + before + (incl - c);
+        carry += round_total;
+        __syncthreads();
+    }
+    return carry;
 }
 
 // Workgroup timeline probes for the list-driven kernels: IVX_T(g, entry, slot) stores the 100 MHz wall clock of wave 0.

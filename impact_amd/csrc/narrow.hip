@@ -19,7 +19,9 @@
 #include <new>
 
 #include "bvol_internal.hpp"
+#include "device_common.hpp"
 #include "physics_internal.hpp"
+#include "vec3.hpp"
 
 namespace {
 
@@ -29,23 +31,9 @@ constexpr uint32_t SCAN_ROUND = 256;  // waves per round of k_cw_scan (its workg
 #define CW_HD __host__ __device__ __forceinline__
 
 // ---- shared host / device arithmetic (f32, fixed operation order; the file is compiled without contraction) ---------------------------------
-struct V3 {
-    float x, y, z;
-};
-CW_HD V3 mk(float x, float y, float z) { return {x, y, z}; }
-CW_HD V3 ld(const float* p) { return {p[0], p[1], p[2]}; }
-CW_HD void st(float* p, V3 v) { p[0] = v.x, p[1] = v.y, p[2] = v.z; }
-CW_HD V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-CW_HD V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-CW_HD V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-CW_HD float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-CW_HD V3 cross(V3 a, V3 b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
-// glam Quat::mul_vec3a
-CW_HD V3 qrot(const float q[4], V3 v) {
-    const V3 b = mk(q[0], q[1], q[2]);
-    const float b2 = dot(b, b);
-    return (v * (q[3] * q[3] - b2) + b * (dot(v, b) * 2.0f)) + cross(b, v) * (q[3] * 2.0f);
-}
+using namespace ivx_vec;  // V3, the operators, dot, cross, qrot, min_rs, max_rs, splitmix
+CW_HD V3 ld(const float* p) { return ld3(p); }
+CW_HD void st(float* p, V3 v) { st3(p, v); }
 CW_HD bool sign_bit(float v) {
 #ifdef __HIP_DEVICE_COMPILE__
     return (__float_as_uint(v) >> 31) != 0u;
@@ -57,16 +45,6 @@ CW_HD bool sign_bit(float v) {
 }
 CW_HD float max0(float x) { return x > 0.0f ? x : 0.0f; }                             // f32::max(0.0, x)
 CW_HD float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }      // f32::clamp(0.0, 1.0)
-CW_HD float min_rs(float a, float b) { return b < a ? b : a; }
-CW_HD float max_rs(float a, float b) { return b > a ? b : a; }
-// impact_math/src/random/splitmix.rs:4-10
-CW_HD unsigned long long splitmix(unsigned long long state) {
-    state += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = state;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 constexpr float EPS = 1e-8f;
 
 // Collidable::from_descriptor under the body's isometry, and the world box
@@ -325,12 +303,7 @@ __global__ __launch_bounds__(SCAN_ROUND) void k_cw_scan(const unsigned long long
     for (uint32_t r0 = 0; r0 < n_waves; r0 += SCAN_ROUND) {
         const uint32_t w = r0 + t;
         const uint32_t ch = w < n_waves ? (uint32_t)__popcll(mask_hit[w]) : 0u, cd = w < n_waves ? (uint32_t)__popcll(mask_def[w]) : 0u;
-        uint32_t ih = ch, id = cd;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t uh = (uint32_t)__shfl_up((int)ih, d, 64), ud = (uint32_t)__shfl_up((int)id, d, 64);
-            if (lane >= (uint32_t)d) ih += uh, id += ud;
-        }
+        const uint32_t ih = ivx_wave_incl_scan(ch), id = ivx_wave_incl_scan(cd);
         if (lane == 63u) wave_totals[0][wv] = ih, wave_totals[1][wv] = id;
         __syncthreads();
         uint32_t before_h = 0u, before_d = 0u, round_h = 0u, round_d = 0u;
@@ -365,16 +338,10 @@ __global__ __launch_bounds__(GROUP) void k_cw_emit(const uint2* __restrict__ pai
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-// world-owned state: device buffers that only grow, a pinned block the results of a call come back through
+// world-owned state: device buffers that only grow, a pinned block the results of a call come back through (device_common.hpp)
 struct CwState {
-    Buf local, world, scratch, contacts, deferred;
-    void* staging = nullptr;  // pinned
-    size_t staging_bytes = 0;
+    ivx_buf local, world, scratch, contacts, deferred;
+    ivx_staging staging;  // (no event: the call waits for the stream before it reads the block)
     bool has_collidables = false, synchronized = false;
     uint32_t n = 0;
     uint32_t need_dyn = 0, need_kin = 0;  // body counts the collidables' indices were checked against need at least
@@ -392,39 +359,6 @@ int state_of(ivx_world* w, CwState** out) {
     return IVX_OK;
 }
 
-// (a buffer that has to grow waits for the stream first: what is in flight may still read the old one)
-int grow(ivx_ctx* c, Buf* b, size_t bytes, size_t floor_bytes) {
-    if (b->bytes >= bytes) return IVX_OK;
-    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr, b->bytes = 0;
-    bytes = bytes + bytes / 2;
-    if (bytes < floor_bytes) bytes = floor_bytes;
-    IVX_HIP_CHECK(hipMalloc(&b->p, bytes));
-    b->bytes = bytes;
-    return IVX_OK;
-}
-
-int staging_for(CwState* st, size_t bytes) {
-    if (st->staging_bytes >= bytes) return IVX_OK;
-    if (st->staging) (void)hipHostFree(st->staging);
-    st->staging = nullptr, st->staging_bytes = 0;
-    bytes = bytes + bytes / 2;
-    if (bytes < (1u << 16)) bytes = 1u << 16;
-    IVX_HIP_CHECK(hipHostMalloc(&st->staging, bytes, hipHostMallocDefault));
-    st->staging_bytes = bytes;
-    return IVX_OK;
-}
-
-struct Layout {
-    size_t bytes = 0;
-    size_t take(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 255u) & ~(size_t)255u;
-        return at;
-    }
-};
-
 int synchronized_state(ivx_world* w, const char* who, CwState** out) {
     IVX_REQUIRE(w, IVX_ERR_INVALID, "%s: null world", who);
     CwState* st = static_cast<CwState*>(w->cw_state);
@@ -439,9 +373,8 @@ int synchronized_state(ivx_world* w, const char* who, CwState** out) {
 void ivx_cw_release(ivx_world* w) {
     if (!w || !w->cw_state) return;
     CwState* s = static_cast<CwState*>(w->cw_state);
-    for (Buf* b : {&s->local, &s->world, &s->scratch, &s->contacts, &s->deferred})
-        if (b->p) (void)hipFree(b->p);
-    if (s->staging) (void)hipHostFree(s->staging);
+    for (ivx_buf* b : {&s->local, &s->world, &s->scratch, &s->contacts, &s->deferred}) ivx_buf_free(b);
+    ivx_staging_release(&s->staging);
     delete s;
     w->cw_state = nullptr;
 }
@@ -491,8 +424,8 @@ int ivx_cw_set_collidables(ivx_world* w, const ivx_collidable* collidables, size
     st->has_collidables = false, st->synchronized = false, st->n = 0;  // (until this call's set stands)
     if (n) {
         IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));  // (a synchronize in flight reads the records this call replaces)
-        if (int rc = grow(w->ctx, &st->local, n * sizeof(ivx_collidable), 1u << 16)) return rc;
-        if (int rc = grow(w->ctx, &st->world, n * sizeof(ivx_collidable), 1u << 16)) return rc;
+        if (int rc = ivx_buf_grow(w->ctx, &st->local, n * sizeof(ivx_collidable), 1u << 16)) return rc;
+        if (int rc = ivx_buf_grow(w->ctx, &st->world, n * sizeof(ivx_collidable), 1u << 16)) return rc;
         IVX_HIP_CHECK(ivx_memcpy_sync(st->local.p, collidables, n * sizeof(ivx_collidable), hipMemcpyHostToDevice));
     }
     st->n = (uint32_t)n, st->need_dyn = need_dyn, st->need_kin = need_kin;
@@ -557,15 +490,15 @@ int ivx_cw_collide(ivx_world* w, uint32_t mode, ivx_contact* out, size_t cap, si
     if (int rc = ivx_bvol_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) return rc;  // (the call's first wait: the grand total)
     if (n_pairs == 0) return IVX_OK;
     const uint32_t np = (uint32_t)n_pairs, n_waves = (np + 63u) / 64u;
-    Layout l;
+    ivx_layout l;
     const size_t o_mh = l.take((size_t)n_waves * 8), o_md = l.take((size_t)n_waves * 8), o_oh = l.take((size_t)n_waves * 4), o_od = l.take((size_t)n_waves * 4), o_tot = l.take(8);
-    if (int rc = grow(c, &st->scratch, l.bytes, 1u << 16)) return rc;
-    if (int rc = grow(c, &st->contacts, n_pairs * sizeof(ivx_contact), 1u << 16)) return rc;  // (at most one contact per pair)
-    if (int rc = grow(c, &st->deferred, n_pairs * 8, 1u << 16)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 16)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->contacts, n_pairs * sizeof(ivx_contact), 1u << 16)) return rc;  // (at most one contact per pair)
+    if (int rc = ivx_buf_grow(c, &st->deferred, n_pairs * 8, 1u << 16)) return rc;
     const size_t copy_contacts = out ? (cap < n_pairs ? cap : n_pairs) : 0, copy_deferred = deferred_pairs ? (deferred_cap < n_pairs ? deferred_cap : n_pairs) : 0;
-    Layout h;
+    ivx_layout h;
     const size_t h_tot = h.take(8), h_contacts = h.take(copy_contacts * sizeof(ivx_contact)), h_deferred = h.take(copy_deferred * 8);
-    if (int rc = staging_for(st, h.bytes)) return rc;
+    if (int rc = ivx_staging_for(&st->staging, h.bytes)) return rc;
     char* s = static_cast<char*>(st->scratch.p);
     unsigned long long* d_mh = reinterpret_cast<unsigned long long*>(s + o_mh);
     unsigned long long* d_md = reinterpret_cast<unsigned long long*>(s + o_md);
@@ -582,7 +515,7 @@ int ivx_cw_collide(ivx_world* w, uint32_t mode, ivx_contact* out, size_t cap, si
                 (const uint32_t*)d_od, static_cast<ivx_contact*>(st->contacts.p), static_cast<uint2*>(st->deferred.p));
     IVX_HIP_CHECK(hipGetLastError());
     // the call's second wait: the two counts, and as much of the two lists as the caller's buffers could hold (what lies behind the counts is dropped)
-    char* hs = static_cast<char*>(st->staging);
+    char* hs = static_cast<char*>(st->staging.p);
     IVX_HIP_CHECK(ivx_memcpy_async(hs + h_tot, d_tot, 8, hipMemcpyDeviceToHost, c->stream));
     if (copy_contacts) IVX_HIP_CHECK(ivx_memcpy_async(hs + h_contacts, st->contacts.p, copy_contacts * sizeof(ivx_contact), hipMemcpyDeviceToHost, c->stream));
     if (copy_deferred) IVX_HIP_CHECK(ivx_memcpy_async(hs + h_deferred, st->deferred.p, copy_deferred * 8, hipMemcpyDeviceToHost, c->stream));

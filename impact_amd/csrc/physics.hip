@@ -30,25 +30,15 @@
 
 #include "ivx_internal.hpp"
 #include "physics_internal.hpp"
+#include "vec3.hpp"
 
 namespace {
 
-struct V3 {
-    float x, y, z;
-};
-struct Q4 {
-    float x, y, z, w;
-};
+using namespace ivx_vec;  // V3, Q4, mk, ld3, st3, the operators, dot, cross, qrot, max_rs
+
 struct M3 {
     V3 c0, c1, c2;
 };
-__device__ __forceinline__ V3 mk(float x, float y, float z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 ld3(const float* p) { return V3{p[0], p[1], p[2]}; }
-__device__ __forceinline__ void st3(float* p, V3 v) {
-    p[0] = v.x;
-    p[1] = v.y;
-    p[2] = v.z;
-}
 __device__ __forceinline__ Q4 ldq(const float* p) { return Q4{p[0], p[1], p[2], p[3]}; }
 __device__ __forceinline__ void stq(float* p, Q4 q) {
     p[0] = q.x;
@@ -62,12 +52,6 @@ __device__ __forceinline__ void stm(float* p, const M3& m) {
     st3(p + 3, m.c1);
     st3(p + 6, m.c2);
 }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
 __device__ __forceinline__ V3 div_elem(V3 a, float s) { return {a.x / s, a.y / s, a.z / s}; }
 __device__ __forceinline__ V3 div_recip(V3 a, float s) {
     const float r = 1.0f / s;
@@ -99,13 +83,6 @@ __device__ __forceinline__ Q4 qnormalize(Q4 q) {
     const float l = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
     return {q.x / l, q.y / l, q.z / l, q.w / l};
 }
-// glam Quat::mul_vec3a
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
-    const V3 b = mk(q.x, q.y, q.z);
-    const float b2 = dot(b, b);
-    return (v * (q.w * q.w - b2) + b * (dot(v, b) * 2.0f)) + cross(b, v) * (q.w * 2.0f);
-}
-__device__ __forceinline__ float max_rs(float a, float b) { return (b > a) ? b : a; }
 // f32::sin / f32::cos of the reference are libm's sinf / cosf, which are the correctly rounded values in all but rare cases; the device
 // library's single-precision versions are one ulp off now and then (found by a random contact graph whose 1-ulp orientation grew past the
 // 1e-5 bar in two frames). The double-precision functions rounded once agree with libm on every value the tests have met; it is two calls

@@ -13,6 +13,7 @@
 #include <new>
 
 #include "physics_internal.hpp"
+#include "vec3.hpp"
 
 namespace {
 
@@ -40,14 +41,7 @@ inline H3 operator*(H3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 inline float hdot(H3 a, H3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 inline H3 hcross(H3 a, H3 b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
 
-// impact_math/src/random/splitmix.rs:4-15
-inline uint64_t splitmix(uint64_t state) {
-    state += 0x9E3779B97F4A7C15ull;
-    uint64_t z = state;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+using ivx_vec::splitmix;
 inline uint64_t splitmix2(uint64_t a, uint64_t b) { return splitmix(a ^ splitmix(b)); }
 
 // objects_in_contact_are_interlocked (contact.rs:610-636)

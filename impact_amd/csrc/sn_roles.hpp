@@ -336,26 +336,6 @@ __device__ __forceinline__ void load_tile(const GridView& g, int ci, int cj, int
     }
 }
 
-// Ordered block-wide exclusive prefix of `val` in thread order; `total` = block sum (same in every thread).
-// (TRAILING = false: no barrier behind the read of the wave sums — for a caller that does not write them again before another barrier)
-template <bool TRAILING = true>
-__device__ __forceinline__ uint32_t block_prefix(uint32_t val, uint32_t* s_wsum, uint32_t tid, uint32_t& total) {
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    uint32_t incl = val;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t n = __shfl_up(incl, o, 64);
-        if (lane >= (uint32_t)o) incl += n;
-    }
-    if (lane == 63u) s_wsum[wave] = incl;
-    __syncthreads();
-    uint32_t w0 = s_wsum[0], w1 = s_wsum[1], w2 = s_wsum[2], w3 = s_wsum[3];
-    uint32_t wbase = wave == 0 ? 0u : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
-    total = w0 + w1 + w2 + w3;
-    if (TRAILING) __syncthreads();
-    return wbase + incl - val;
-}
-
 // Bit k of the results refers to the cube (i, j, k) of cube row cr = i*17 + j (k = 0..16):
 //   vbits: the cube holds a vertex (its 8 corner signs are mixed, surface_nets.rs:209-224)
 //   qx/qy/qz: it emits the quad of its X / Y / Z edge (maybe_make_surface_nets_quad, surface_nets.rs:251-334)
@@ -1369,7 +1349,7 @@ __device__ __forceinline__ void role_sn_emit(uint32_t bid, uint32_t nb, SnParams
             }
         }
         uint32_t total;
-        const uint32_t pre = block_prefix<false>((__popc(vb[0]) + __popc(vb[1])) | ((nq[0] + nq[1]) << 16), s_wsum, tid, total);  // (2)
+        const uint32_t pre = ivx_block_prefix<false>((__popc(vb[0]) + __popc(vb[1])) | ((nq[0] + nq[1]) << 16), s_wsum, tid, total);  // (2)
         uint32_t base = pre & 0xFFFFu, qb = pre >> 16;
         if (tid == 0) s_nq = total >> 16;
         for (int q = 0; q < 2; ++q) {
@@ -1677,7 +1657,7 @@ __device__ __forceinline__ void role_sn_emit_general(uint32_t bid, uint32_t nb, 
             }
         }
         uint32_t total;
-        uint32_t base = block_prefix(__popc(vb[0]) + __popc(vb[1]), s_wsum, tid, total);
+        uint32_t base = ivx_block_prefix(__popc(vb[0]) + __popc(vb[1]), s_wsum, tid, total);
         for (int q = 0; q < 2; ++q) {
             const int cr = r0 + q;
             if (cr < NCROWS) {
@@ -1805,7 +1785,7 @@ __device__ __forceinline__ void role_sn_emit_general(uint32_t bid, uint32_t nb, 
             qm = ((qx >> k) & 1u) | (((qy >> k) & 1u) << 1) | (((qz >> k) & 1u) << 2);
         }
         uint32_t total;
-        uint32_t slot = block_prefix(__popc(qm), s_wsum, tid, total);  // (ends with a barrier: the previous batch's list is consumed)
+        uint32_t slot = ivx_block_prefix(__popc(qm), s_wsum, tid, total);  // (ends with a barrier: the previous batch's list is consumed)
 #pragma unroll
         for (uint32_t axis = 0; axis < 3; ++axis)
             if ((qm >> axis) & 1u) s_quad[slot++] = (uint16_t)(cid | (axis << 13));

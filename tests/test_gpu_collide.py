@@ -119,6 +119,31 @@ def test_mutual_contacts(ctx, case):
     GB.close()
 
 
+def test_probes_and_mutual_contacts_of_boxes_of_many_chunks(ctx):
+    """the exclusive scan over the submeshes' probe counts takes 256 counts a round. A solid box of 7 x 7 x 7 chunks (112 voxels a side) with
+    probes built and a second copy overlapping it: only the 343 - 125 = 218 outer chunks have a submesh, which is still one round; the box of
+    8 x 8 x 8 chunks has 512 - 216 = 296 submeshes, and the probes of the last 40 take their offsets from the second round's carry. (The scan
+    over the mutual contacts' counts has one count per 256 probes: a second round there would take 65 536 probes.)"""
+    for side, n_submeshes in ((110.0, 218), (126.0, 296)):
+        A, GA = both(ctx, scenes.box_scene((side, side, side)))
+        B, GB = both(ctx, scenes.box_scene((side, side, side)))
+        pa, pb = probes_both(A, GA), probes_both(B, GB)
+        assert len(pa[1]) == n_submeshes
+        ca, cb = A.center_of_mass(), B.center_of_mass()
+        ax_b = np.array([0.3, 0.1, 1.0]) / np.linalg.norm([0.3, 0.1, 1.0])
+        qa = np.array([0.0, 0.0, 0.0, 1.0], dtype=f32)
+        qb = np.array([*(ax_b * np.sin(0.25)), np.cos(0.25)], dtype=f32)
+        ta = placed(ca, qa, [0.5, -0.25, 0.125])
+        tb = placed(cb, qb, [0.5 + 0.3 * side, -0.25 + 0.8 * side, 0.125])
+        resp = (0.3, 0.6, 0.45)
+        want, wi = oracle_contact_list(A, pa, ca, qa, ta, B, pb, cb, qb, tb, 11, 22, 0, 1, resp)
+        got = GA.mutual_contacts(qa, ta, ca, GB, qb, tb, cb, 11, 22, 0, 1, resp)
+        assert len(want) > 10 and set(wi[:, 0].tolist()) == {0, 1}
+        assert_contacts_equal(got, want)
+        GA.close()
+        GB.close()
+
+
 def test_mutual_contacts_of_many_pairs(ctx):
     """the pairs list (ivx_mutual_voxel_object_contacts_many) against the single-pair call: a row of five bodies of different shapes and extents,
     neighbours touching, one pair far apart, one body in three pairs; the manifolds must be the single-pair lists, byte for byte"""

@@ -150,6 +150,34 @@ def test_plane_against_rotated_voxel_box(ctx):
     g.close()
 
 
+def test_ground_plane_through_a_box_of_343_chunks(ctx):
+    """the exclusive scan over the chunks of the collidable's box takes 256 chunks a round: a solid box of 7 x 7 x 7 chunks (112 voxels a side)
+    against ground planes through it. A plane restricts the touched ranges along its normal: the level plane through the middle leaves
+    7 x 4 x 7 = 196 chunks (one round), the high one and the tilted one leave all 343 (two rounds), and the box's lower corner voxels, the only
+    ones a plane tests, sit in chunks 0, 6, 294 and 300 of that box: two contacts take their offsets from the second round's carry"""
+    o, g = both(ctx, scenes.box_scene((110.0, 110.0, 110.0)), 1.0)
+    assert tuple(o.info()["chunk_counts"]) == (7, 7, 7)
+    ident = (np.array([0.0, 0.0, 0.0, 1.0], dtype=np.float32), np.zeros(3, dtype=np.float32))
+    axis = np.array([0.2, 1.0, -0.4]) / np.linalg.norm([0.2, 1.0, -0.4])
+    turned = (np.array([*(axis * np.sin(0.3)), np.cos(0.3)], dtype=np.float32), np.array([0.5, 2.0, -1.0], dtype=np.float32))
+    resp = (0.1, 0.8, 0.6)
+    for (q, t), normal, disp, whole_box in ((ident, (0.0, 1.0, 0.0), 56.0, False), (ident, (0.0, 1.0, 0.0), 100.0, True), (ident, (0.3, 1.0, 0.2), None, True),
+                                            (turned, (0.1, 1.0, 0.05), 60.0, False)):
+        n = np.asarray(normal, dtype=np.float64)
+        n = (n / np.linalg.norm(n)).astype(np.float32)
+        if disp is None:
+            disp = float(n.astype(np.float64) @ np.array([56.0, 56.0, 56.0]))  # through the box's centre
+        want = oracle_plane_contact_list(o, q, t, n, disp, 5, 9, 0, 0x80000000, resp)
+        got = g.plane_contacts(q, t, n, disp, 5, 9, 0, 0x80000000, resp)
+        assert len(want) >= 2
+        if whole_box:
+            idx = np.asarray(o.plane_contacts(q, t, n, disp)[0]) // 16
+            in_box = (idx[:, 0] * 7 + idx[:, 1]) * 7 + idx[:, 2]
+            assert in_box.min() < 256 <= in_box.max()
+        assert_contacts_equal(got, want)
+    g.close()
+
+
 def test_voxel_box_dropped_on_the_ground_steps_like_the_oracle(ctx):
     """a voxel box (dynamic body) falls onto a static plane: corner-voxel contacts -> prepare -> solve (with positional correction) ->
     integrate, 80 steps against the oracle running the same chain"""

@@ -1,5 +1,6 @@
-// Host-side pieces the device subsystems (drag.hip, cull.hip, bvol.hip, narrow.hip) build their state from: device buffers that only grow, the
-// pinned staging block a call's one upload or download goes through, and the layout of the parts of one allocation.
+// Host-side pieces the device subsystems (drag.hip, cull.hip, bvol.hip, narrow.hip) and the host units of the C ABI build their state from:
+// device buffers that only grow, host-mapped blocks that only grow, the pinned staging block a call's one upload or download goes through, and
+// the layout of the parts of one allocation.
 #pragma once
 #include "ivx_internal.hpp"
 
@@ -19,6 +20,22 @@ static inline int ivx_buf_grow(ivx_ctx* c, ivx_buf* b, size_t bytes, size_t floo
 static inline void ivx_buf_free(ivx_buf* b) {
     if (b->p) (void)hipFree(b->p);
     b->p = nullptr, b->bytes = 0;
+}
+
+// `m` holds at least `bytes` afterwards. A block that has to grow does not keep its contents and is made `want` bytes (the owner's growth
+// rule, at least `bytes`); `wait` non-null: what is in flight on that stream may still use the old block and is waited for first.
+static inline void ivx_mapped_free(ivx_mapped* m) {
+    if (m->p) (void)hipHostFree(m->p);
+    *m = ivx_mapped();
+}
+static inline int ivx_mapped_grow(ivx_mapped* m, size_t bytes, size_t want, hipStream_t wait) {
+    if (m->bytes >= bytes) return IVX_OK;
+    if (wait) IVX_HIP_CHECK(ivx_stream_sync(wait));
+    ivx_mapped_free(m);
+    IVX_HIP_CHECK(hipHostMalloc(&m->p, want, hipHostMallocMapped));
+    IVX_HIP_CHECK(hipHostGetDevicePointer(&m->dev, m->p, 0));
+    m->bytes = want;
+    return IVX_OK;
 }
 
 // parts of one allocation, each on a 256-byte boundary: take all, then add the base

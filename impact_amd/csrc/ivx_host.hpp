@@ -1,0 +1,110 @@
+// What the host units of the C ABI (ivx_api.hip, voxel_collision_api.hip) share and nothing else links against: staged copies, the objects'
+// device scratch, the recorder phases of the many-object calls and the host mirrors of the reference's range allocators. Defined in ivx_api.hip
+// (the functions hidden: the library exports what it exported before).
+#pragma once
+#include <functional>
+#include <limits>
+#include <map>
+#include <unordered_map>
+#include <vector>
+
+#include "device_common.hpp"
+
+#pragma GCC visibility push(hidden)
+
+template <class T>
+int dev_alloc(T** p, size_t count) {
+    *p = nullptr;
+    if (count == 0) return IVX_OK;
+    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
+    return IVX_OK;
+}
+
+// Host<->device copies through the grid's pinned staging buffer: ONE stream-ordered copy and ONE wait (large ones: plain blocking copies)
+int d2h(ivx_grid* g, void* dst, const void* src, size_t bytes);
+int h2d(ivx_grid* g, void* dst, const void* src, size_t bytes);
+// the object's device scratch (ivx_grid::dev_scratch) holds at least `bytes`; a growth waits for the stream and keeps nothing
+int ensure_dev_scratch(ivx_grid* g, size_t bytes);
+
+// box sweep + region stages after an edit that changed voxels, enqueued and collected
+int rederive(ivx_grid* g);
+
+// many objects per call (many.hpp): the objects of one context, each listed once | `f(i)` for every object under the recorder, then the flush |
+// the drain after a failure half way
+int many_check(ivx_grid* const* grids, size_t n, const char* who);
+int many_phase(ivx_grid* const* grids, size_t n, const std::function<int(size_t)>& f);
+int many_fail(ivx_grid* const* grids, size_t n, int rc);
+
+static inline uint32_t linear_chunk(const ivx_grid* g, const uint32_t c[3]) { return (c[0] * g->cc[1] + c[1]) * g->cc[2] + c[2]; }
+
+// grow device arrays keeping what they hold: every array that has to grow gets its new block and its copy on the stream, then ONE wait by the
+// caller, then the old blocks go (a wait per array was most of what a growth cost)
+struct GrowKeep {
+    void** slot;
+    void* fresh;
+    uint32_t group;  // the mesh group the array belongs to (mesh_group_free); 0: none
+};
+template <class T>
+int grow_keep_enqueue(ivx_grid* g, T** buf, size_t old_count, size_t new_count, std::vector<GrowKeep>& pending, uint32_t group) {
+    T* fresh = nullptr;
+    int rc = dev_alloc(&fresh, new_count);
+    if (rc) return rc;
+    if (*buf && old_count) IVX_HIP_CHECK(ivx_memcpy_async(fresh, *buf, old_count * sizeof(T), hipMemcpyDeviceToDevice, g->ctx->stream));
+    pending.push_back(GrowKeep{reinterpret_cast<void**>(buf), fresh, group});
+    return IVX_OK;
+}
+
+#pragma GCC visibility pop
+
+// Host mirror of a RangeAllocator (impact_containers/src/range_allocator.rs)
+struct ivx_range_allocator {
+    std::map<size_t, size_t> free_ranges;  // start -> end; a second range with the same start is dropped, as BTreeSet::insert does
+    void free_range(size_t a, size_t b) {
+        if (a < b) free_ranges.emplace(a, b);
+    }
+    bool allocate(size_t len, size_t* start) {  // the smallest free range that fits, the first of equals
+        auto best = free_ranges.end();
+        size_t best_len = std::numeric_limits<size_t>::max();
+        for (auto it = free_ranges.begin(); it != free_ranges.end(); ++it) {
+            const size_t l = it->second - it->first;
+            if (l < best_len && l >= len) best = it, best_len = l;
+        }
+        if (best == free_ranges.end()) return false;
+        const size_t a = best->first, b = best->second;
+        free_ranges.erase(best);
+        if (a + len < b) free_ranges.emplace(a + len, b);
+        *start = a;
+        return true;
+    }
+    void merge_consecutive() {  // (in place: a range that starts where the one before it ends is folded into that one)
+        if (free_ranges.size() < 2) return;
+        auto prev = free_ranges.begin();
+        for (auto it = std::next(prev); it != free_ranges.end();) {
+            if (it->first == prev->second) {
+                prev->second = it->second;
+                it = free_ranges.erase(it);
+            } else {
+                prev = it;
+                ++it;
+            }
+        }
+    }
+};
+// Host mirror of the ChunkSubmeshManager (mesh.rs:699-849) with its two RangeAllocators: which slot of the submesh table a chunk owns and which
+// ranges of the vertex / index buffers are free. The mesh data stays in HBM. (The probes' sync reads which chunks have a submesh from it.)
+struct ivx_submesh_manager {
+    std::vector<ivx_submesh> table;                   // slot order = the reference's chunk_submeshes order
+    std::unordered_map<uint32_t, uint32_t> slot_of;   // linear chunk index -> slot
+    ivx_range_allocator vertices, indices;
+    size_t total_vertices = 0, total_indices = 0;     // buffer lengths (freed ranges inside them stay counted)
+    std::vector<ivx_submesh_data_ranges> updated;     // VoxelMeshModifications (mesh.rs:113-123) since the last report
+    bool chunks_were_removed = false;
+    uint64_t serial = 0;                              // the mesh_serial this state describes
+};
+// VoxelObjectCollisionProbes' bookkeeping (collidable.rs:97-101): chunk -> range of the point buffer, free ranges
+struct ivx_probe_manager {
+    std::unordered_map<uint32_t, std::pair<uint32_t, uint32_t>> range_of;  // linear chunk index -> [start, end)
+    ivx_range_allocator points;
+    size_t total = 0;  // length of the point buffer, freed ranges included
+    bool built = true;  // false right after a recompute: the map is filled from the device entries when somebody needs it
+};

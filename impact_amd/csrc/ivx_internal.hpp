@@ -62,6 +62,12 @@ struct ivx_buf {
     void* p = nullptr;
     size_t bytes = 0;
 };
+// a pinned host allocation the device reads and writes in place, that only grows (ivx_mapped_grow / ivx_mapped_free, device_common.hpp)
+struct ivx_mapped {
+    void* p = nullptr;    // the host's pointer
+    void* dev = nullptr;  // the device's address of the same memory
+    size_t bytes = 0;
+};
 
 struct ivx_ctx {
     int device;
@@ -70,11 +76,8 @@ struct ivx_ctx {
     int n_cu;  // compute units of the device
     // pinned, device-visible scratch of the many-object calls that bring lists back (ivx_voxel_object_contacts_many: per-object totals, then the
     // contacts themselves, written by the kernels straight into host memory); grown on demand, freed by ivx_shutdown
-    void* pinned_scratch;
-    void* pinned_scratch_dev;
-    size_t pinned_scratch_bytes;
-    void* dev_scratch;  // device scratch of the same calls (counts and offsets of every pair of ivx_mutual_voxel_object_contacts_many)
-    size_t dev_scratch_bytes;
+    ivx_mapped pinned_scratch;
+    ivx_buf dev_scratch;  // device scratch of the same calls (counts and offsets of every pair of ivx_mutual_voxel_object_contacts_many)
     hipStream_t aux_stream;  // made on first use (ivx_aux_stream): the sampler's pre-pass one step ahead (ivx_grid_set_sample_ahead)
     void* many_recorder;  // the launch recorder of ivx_many_begin / _flush and its staging ring (many.cpp); made on first use, freed by ivx_shutdown
     int many_error;       // a flush of recorded launches failed on this context (sticky until reported: ivx_many_error)

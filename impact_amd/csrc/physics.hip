@@ -34,7 +34,7 @@
 
 namespace {
 
-using namespace ivx_vec;  // V3, Q4, mk, ld3, st3, the operators, dot, cross, qrot, max_rs
+using namespace ivx_vec;  // V3, Q4, mk, ld3, st3, the operators, dot, cross, qrot, qmul, max_rs
 
 struct M3 {
     V3 c0, c1, c2;
@@ -75,10 +75,6 @@ __device__ __forceinline__ M3 rotated(const M3& m, Q4 q) {  // R M R^T (inertia.
     return mul(mul(r, m), transpose(r));
 }
 __device__ __forceinline__ Q4 conj(Q4 q) { return {-q.x, -q.y, -q.z, q.w}; }
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-    return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-            a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
 __device__ __forceinline__ Q4 qnormalize(Q4 q) {
     const float l = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
     return {q.x / l, q.y / l, q.z / l, q.w / l};

@@ -34,6 +34,11 @@ IVX_VEC_HD V3 qrot(const float q[4], V3 v) {
     const float b2 = dot(b, b);
     return (v * (q[3] * q[3] - b2) + b * (dot(v, b) * 2.0f)) + cross(b, v) * (q[3] * 2.0f);
 }
+// glam Quat::mul_quat (xyzw)
+IVX_VEC_HD Q4 qmul(Q4 a, Q4 b) {
+    return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
+            a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
+}
 // (the second operand wins only when strictly smaller / larger: the order of the operands matters for -0.0 and NaN)
 IVX_VEC_HD float min_rs(float a, float b) { return b < a ? b : a; }
 IVX_VEC_HD float max_rs(float a, float b) { return b > a ? b : a; }

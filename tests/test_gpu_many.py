@@ -543,3 +543,93 @@ def test_random_batches_of_contacts_pairs_and_probe_syncs(ctx, seed):
     assert pu.fuzzing() or (exercised[0] > 100 and exercised[1] > 0 and exercised[2] > 5), exercised  # (the committed seeds are ones that meet something)
     for g in objs + twins:
         g.close()
+
+
+def test_contacts_many_outgrows_the_pinned_block_between_its_phases():
+    """the FIRST batched contact call of a fresh context returns more contacts than the floor of the context's host-mapped block holds (1 MiB /
+    64 bytes = 16 384): the block is grown, and may move, between the count phase that wrote the totals into it and the emit phase. Four 32^3 boxes,
+    each wholly inside its sphere collidable — every surface voxel of a box in contact, 30^3 - 28^3 = 5 048 a box by the oracle's count (three
+    boxes stay under the floor) —: the very lists of the single-object calls, and the oracle's. (The mutual form shares that tail; a pair of
+    bodies this small yields a hundred contacts, so it is left to the sphere form.)"""
+    import test_gpu_contacts as tcon
+    from impact_amd.voxel import Context
+
+    own = Context(0)
+    try:
+        both_ = [tcon.both(own, scenes.box_scene(), 1.0) for _ in range(4)]
+        o, objs = both_[0][0], [b[1] for b in both_]
+        occ = np.array(o.info()["occupied_voxel_ranges"], dtype=np.float64)
+        centre, radius = (0.5 * (occ[:, 0] + occ[:, 1])).astype(np.float32), 40.0
+        ident, zero, resp = np.array([0, 0, 0, 1], dtype=np.float32), np.zeros(3, dtype=np.float32), (0.25, 0.6, 0.4)
+        qs = many.collidable_queries(4)
+        qs["mode"], qs["shape3"], qs["shape1"], qs["response"] = 0, centre, radius, resp
+        qs["collidable_id_a"], qs["collidable_id_b"], qs["body_a"], qs["body_b"] = 7, 99, 3, 0x80000000
+        got, off = many.voxel_object_contacts_many(objs, qs)
+        total = int(off[-1])
+        print(f"contacts of the first batched call: {total} (floor of the pinned block: 16384)")
+        assert total > 16384 and total == len(got)
+        o_want = tcon.oracle_contact_list(o, ident, zero, centre, radius, 7, 99, 3, 0x80000000, resp)
+        assert len(o_want) == 5048
+        for k, g in enumerate(objs):
+            want = g.sphere_contacts(ident, zero, centre, radius, 7, 99, 3, 0x80000000, resp, capacity=8192)
+            assert got[off[k]:off[k + 1]].tobytes() == want.tobytes(), f"box {k}"
+            tcon.assert_contacts_equal(got[off[k]:off[k + 1]], o_want)
+        for g in objs:
+            g.close()
+    finally:
+        own.close()
+
+
+def test_batched_contacts_find_nothing_then_something():
+    """on a fresh context a batched call whose every query misses — nothing to emit: all offsets zero, no second phase — and then one that hits,
+    for the collidable form and the pair form: the lists of the single-object calls, byte for byte. Misses of both kinds: the boxes do not meet
+    (nothing is launched for the query), and the boxes meet at a corner of a round body where there is no voxel (counted, total zero)."""
+    import test_gpu_collide as tc
+    from impact_amd.voxel import Context
+
+    own = Context(0)
+    try:
+        objs = [tc.both(own, scenes.sphere_scene(12.0), 1.0)[1] for _ in range(2)]
+        for g in objs:
+            g.collision_probes_recompute()
+        occ = np.array(objs[0].update_occupied_voxel_ranges(), dtype=np.float64)
+        centre, half = 0.5 * (occ[:, 0] + occ[:, 1]), 0.5 * (occ[:, 1] - occ[:, 0])
+        ident, zero, resp = np.array([0, 0, 0, 1], dtype=np.float32), np.zeros(3, dtype=np.float32), (0.25, 0.6, 0.4)
+        com = centre.astype(np.float32)
+
+        def collidables(c0, c1):
+            qs = many.collidable_queries(2)
+            qs["mode"], qs["shape1"], qs["response"] = 0, 3.0, resp
+            qs["shape3"][0], qs["shape3"][1] = c0, c1
+            qs["collidable_id_a"], qs["collidable_id_b"], qs["body_a"], qs["body_b"] = (40, 41), 7, (0, 1), 0x80000000
+            singles = [g.sphere_contacts(ident, zero, qs["shape3"][k], 3.0, 40 + k, 7, k, 0x80000000, resp) for k, g in enumerate(objs)]
+            return many.voxel_object_contacts_many(objs, qs), singles
+
+        corner = (centre + half + 1.0).astype(np.float32)  # the ball's box reaches two voxels into the occupied box at its corner: no voxel there
+        (got, off), singles = collidables((centre + [500.0, 0.0, 0.0]).astype(np.float32), corner)
+        assert len(got) == 0 and off.tolist() == [0, 0, 0] and all(len(s) == 0 for s in singles)
+        (got, off), singles = collidables((centre + [half[0] + 1.0, 0.0, 0.0]).astype(np.float32), (centre - [0.0, half[1] + 2.0, 0.0]).astype(np.float32))
+        assert len(singles[0]) > 0 and len(singles[1]) > 0 and int(off[-1]) == len(got)
+        for k, s in enumerate(singles):
+            assert got[off[k]:off[k + 1]].tobytes() == s.tobytes(), f"collidable of body {k}"
+
+        def pairs(*b_positions):
+            ps, singles = [], []
+            for k, at in enumerate(b_positions):
+                ta, tb = tc.placed(com, ident, [0.0, 0.0, 0.0]), tc.placed(com, ident, at)
+                ps.append(dict(a=objs[0], b=objs[1], rotation_a=ident, translation_a=ta, center_of_mass_a=com, rotation_b=ident, translation_b=tb,
+                               center_of_mass_b=com, collidable_id_a=100, collidable_id_b=101 + k, body_a=0, body_b=1, response=resp))
+                singles.append(objs[0].mutual_contacts(ident, ta, com, objs[1], ident, tb, com, 100, 101 + k, 0, 1, resp))
+            return many.mutual_voxel_object_contacts_many(many.mutual_queries(ps)), singles
+
+        d = 2.0 * float(half[0])
+        (got, off), singles = pairs([500.0, 0.0, 0.0], [0.8 * d, 0.8 * d, 0.0])  # apart | the boxes overlap at an edge, the balls are 1.13 diameters apart
+        assert len(got) == 0 and off.tolist() == [0, 0, 0] and all(len(s) == 0 for s in singles)
+        (got, off), singles = pairs([0.8 * d, 0.0, 0.0], [0.0, 0.0, -0.9 * d])
+        assert len(singles[0]) > 0 and len(singles[1]) > 0 and int(off[-1]) == len(got)
+        for k, s in enumerate(singles):
+            assert got[off[k]:off[k + 1]].tobytes() == s.tobytes(), f"pair {k}"
+        for g in objs:
+            g.close()
+    finally:
+        own.close()

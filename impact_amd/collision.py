@@ -48,7 +48,12 @@ def capsule(segment_start, segment_vector, radius, body, collidable_id, kind=cap
 
 
 def voxel_object(model_lower, model_upper, body, collidable_id, kind=capi.BV_DYNAMIC, response=(0.0, 0.0, 0.0), kinematic=False) -> np.ndarray:
-    """a voxel object's place in the broad phase (`bvol.grid_model_aabb` gives its model box); its pairs come back deferred"""
+    """a voxel object's place in the broad phase; its pairs come back deferred. The box is the object's model box IN THE BODY'S FRAME, whose origin
+    is the body's centre of mass and not the grid's origin: `bvol.grid_model_aabb` MINUS the origin offset (the local centre of mass, in float32),
+    and again after every edit that moves the centre of mass. A record holding the model box as it is puts the world box a centre of mass away
+    from the body. The reference derives the object's world -> object transform from the same offset, in float32 (collidable.rs:310-327):
+    t_w = rotate(q, -origin_offset) + p;  rotation = conj(q);  translation = -rotate(rotation, t_w) — the transform the deferred pairs' generators
+    take (INTEGRATION.md 2c has the table of which member is A)"""
     c = _collidable(capi.CW_VOXEL_OBJECT, body, collidable_id, kind, response, kinematic)
     c["a"], c["b"] = model_lower, model_upper
     return c

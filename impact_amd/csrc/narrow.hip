@@ -46,6 +46,8 @@ CW_HD bool sign_bit(float v) {
 CW_HD float max0(float x) { return x > 0.0f ? x : 0.0f; }                             // f32::max(0.0, x)
 CW_HD float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }      // f32::clamp(0.0, 1.0)
 constexpr float EPS = 1e-8f;
+constexpr float CW_BOX_PAD = 1.9073486328125e-6f;  // 2^-19
+CW_HD float max_abs(float u, float v) { return fabsf(v) > fabsf(u) ? fabsf(v) : fabsf(u); }
 
 // Collidable::from_descriptor under the body's isometry, and the world box
 CW_HD void cw_transform(const ivx_collidable& local, const float p[3], const float q[4], ivx_collidable* world, ivx_aabb* box) {
@@ -86,6 +88,12 @@ CW_HD void cw_transform(const ivx_collidable& local, const float p[3], const flo
             for (int k = 0; k < 4; ++k) s.rotation[k] = q[k];
             s.scaling = 1.0f;
             ivx_bv_world_aabb_of(m, s, &b);
+            // outward by more than the float32 derivation can have lost (header): the box must HOLD the object the generators see
+            const float reach = (max_abs(local.a[0], local.b[0]) + max_abs(local.a[1], local.b[1])) + max_abs(local.a[2], local.b[2]);
+            for (int k = 0; k < 3; ++k) {
+                const float pad = (reach + fabsf(p[k])) * CW_BOX_PAD;
+                b.lower[k] = b.lower[k] - pad, b.upper[k] = b.upper[k] + pad;
+            }
             for (int k = 0; k < 3; ++k) w.a[k] = b.lower[k], w.b[k] = b.upper[k];
             break;
         }

@@ -1082,7 +1082,11 @@ typedef struct {
  *   plane (plane.rs:197-203):  a' = qrot(q, a);  s' = dot(a', qrot(q, a s) + p);  box = (-FLT_MAX, +FLT_MAX) on every axis — the reference gives a
  *            plane no bounding volume; here it pairs with every box that has no NaN bound. PLANES BELONG AT THE END OF THE LIST: a block of 64
  *            consecutive objects that holds one has an unbounded block box and is never rejected as a whole by the pair pass.
- *   voxel object: (a', b') = ivx_bv_world_aabb of the model box (a, b) under (q, p, scaling 1) — also its box
+ *   voxel object: (lo, hi) = ivx_bv_world_aabb of the model box (a, b) under (q, p, scaling 1), then widened per axis k by
+ *            pad_k = (((m_0 + m_1) + m_2) + |p_k|) 2^-19, m_j = |b_j| > |a_j| ? |b_j| : |a_j|:  a' = lo - pad, b' = hi + pad — also its box. The float32
+ *            derivation alone can leave a corner of the rotated model box a few units in the last place OUTSIDE; the pad is several times the
+ *            largest such loss, so the box holds the exact image of the model box. (a, b) is the model box in the BODY's frame: for a voxel
+ *            object, ivx_grid_model_aabb minus the origin offset (the body frame's origin in model space, its centre of mass).
  *   Everything else of the record is copied. `box` may be NULL.
  * ivx_cw_contact — generate_contact_manifold (basic.rs:57-151) for one pair of WORLD-SPACE collidables A, B. *hit = 0: no contact (plane against
  *   plane always); 1: `out` holds it; 2: a member is a voxel object, nothing is tested. Where the reference answers CollidableOrder::Swapped —

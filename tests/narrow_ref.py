@@ -280,6 +280,10 @@ def transform(local, positions, orientations):
     boxes["lower"][pl], boxes["upper"][pl] = -FLT_MAX, FLT_MAX
     vo = np.nonzero(shape == VOXEL)[0]
     lo, hi = world_aabb_f32(a, b, q, p)
+    m = np.where(np.abs(b) > np.abs(a), np.abs(b), np.abs(a))  # widened by (((m_0 + m_1) + m_2) + |p_k|) 2^-19, the header's order
+    pad = (((m[:, 0] + m[:, 1]) + m[:, 2])[:, None] + np.abs(p)) * f32(2.0 ** -19)
+    lo, hi = lo - pad, hi + pad
+    assert lo.dtype == np.float32 and hi.dtype == np.float32
     world["a"][vo], world["b"][vo] = lo[vo], hi[vo]
     boxes["lower"][vo], boxes["upper"][vo] = lo[vo], hi[vo]
     return world, boxes

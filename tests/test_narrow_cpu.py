@@ -253,7 +253,7 @@ def test_transform_is_byte_equal_to_the_restatement_and_its_boxes_contain_the_sh
     for corner in range(8):
         pick = np.array([(corner >> 2) & 1, (corner >> 1) & 1, corner & 1], dtype=bool)
         c64 = np.einsum("nij,nj->ni", rot, np.where(pick, local["b"], local["a"]).astype(np.float64)) + p
-        assert (lo[vo] <= c64[vo] + slack).all() and (hi[vo] >= c64[vo] - slack).all()
+        assert (lo[vo] <= c64[vo]).all() and (hi[vo] >= c64[vo]).all()  # (no allowance: a voxel object's box is widened past its derivation's rounding)
     # a plane keeps its geometry: the transformed point n x displacement lies on the transformed plane
     tp = np.einsum("nij,nj->ni", rot, (local["a"] * local["s"][:, None]).astype(np.float64)) + p
     assert np.abs(nr.dot(want_world["a"].astype(np.float64), tp) - want_world["s"])[planes].max() <= slack

@@ -523,8 +523,8 @@ int ivx_grid_create(ivx_ctx* c, const uint32_t cc[3], float voxel_extent, uint32
 
 // Grids that come into being together (the fragments of an impact, fracturing.rs:1047-1189; docs/voxel_gpu_buffer_pooling.md:44-66): their
 // arenas from ONE device allocation and their host-mapped result blocks from ONE pinned allocation, both released with the last of them.
-// The chunk records and work counters start zeroed by ONE fill over the whole block. `ccs`: 3 chunk counts per grid.
-static int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, float voxel_extent, ivx_grid** out) {
+// The chunk records and work counters start zeroed by ONE fill over the whole block. `ccs`: 3 chunk counts per grid; `who`: the call, for messages.
+extern "C++" int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, float voxel_extent, ivx_grid** out, const char* who) {
     for (size_t i = 0; i < n; ++i) out[i] = nullptr;
     if (n == 0) return IVX_OK;
     IVX_HIP_CHECK(hipSetDevice(c->device));
@@ -549,7 +549,7 @@ static int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, float v
     blk->dev = blk->pinned = nullptr;
     blk->refs = 0;
     if (hipMalloc(&blk->dev, off[n]) != hipSuccess || hipHostMalloc(&blk->pinned, n * 256, hipHostMallocMapped) != hipSuccess) {
-        ivx_set_error("ivx_copy_polyhedra: allocation of %zu bytes for %zu grids failed", off[n], n);
+        ivx_set_error("%s: allocation of %zu bytes for %zu grids failed", who, off[n], n);
         blk->refs = 1;
         ivx_block_release(blk);
         return fail(IVX_ERR_HIP);
@@ -1170,7 +1170,7 @@ int ivx_region_labels_download(ivx_grid* g, uint32_t* labels, size_t n_voxels) {
     return d2h(g, labels, g->dev_scratch, g->n_vox * sizeof(uint32_t));
 }
 
-static int describe_regions_internal(ivx_grid* g, const float* d_dens, std::vector<ivx_region_desc>& out) {
+extern "C++" int describe_regions_internal(ivx_grid* g, const float* d_dens, std::vector<ivx_region_desc>& out) {
     const uint32_t n = g->region_count;
     out.assign(n, ivx_region_desc{});
     if (n == 0) return IVX_OK;
@@ -1226,505 +1226,6 @@ int ivx_regions_describe(ivx_grid* g, const float densities[256], ivx_region_des
     std::vector<ivx_region_desc> d;
     if ((rc = describe_regions_internal(g, d_dens, d))) return rc;
     for (uint32_t r = 0; r < n; ++r) out[r] = d[r];
-    return IVX_OK;
-}
-
-// Derived state + regions of an object whose voxels changed, through the fused step path (ivx_voxel_step_enqueue: five launches and the
-// results block instead of the stand-alone passes' ten launches and a blocking copy). `rederive_enqueue` only puts the work on the
-// stream — a caller with results of its own still in flight waits for both with the one `rederive_collect`.
-int ivx_voxel_step_enqueue(ivx_grid* g, uint32_t stages);
-int ivx_voxel_step_collect(ivx_grid* g, ivx_step_result* out);
-static int rederive_enqueue(ivx_grid* g) {
-    const uint32_t keep = g->stage_timing_off;
-    g->stage_timing_off = 0xFFFFFFFFu;  // (no event records around the slots: nobody reads this call's stage times)
-    const int rc = ivx_voxel_step_enqueue(g, IVX_STAGE_DERIVE | IVX_STAGE_REGIONS);
-    g->stage_timing_off = keep;
-    return rc;
-}
-static int rederive_collect(ivx_grid* g) {
-    ivx_step_result res;
-    const int rc = ivx_voxel_step_collect(g, &res);
-    if (rc) return rc;
-    g->mesh_valid = 0;
-    return IVX_OK;
-}
-extern "C++" int rederive(ivx_grid* g) {
-    const int rc = rederive_enqueue(g);
-    return rc ? rc : rederive_collect(g);
-}
-
-int ivx_split_off_smallest_region(ivx_grid* parent, ivx_grid** child, uint32_t origin_offset_in_parent[3], int* outcome, ivx_region_desc* moved) {
-    IVX_REQUIRE(parent && child && origin_offset_in_parent && outcome, IVX_ERR_INVALID, "ivx_split_off_smallest_region: null argument");
-    *child = nullptr;
-    *outcome = 0;
-    IVX_REQUIRE(parent->regions_valid, IVX_ERR_STATE, "ivx_split_off_smallest_region: call ivx_label_regions first");
-    IVX_REQUIRE(parent->x_off == 0 && parent->gx == parent->cc[0] && !parent->has_ghost[0] && !parent->has_ghost[1], IVX_ERR_STATE,
-                "ivx_split_off_smallest_region: not available on a slab of a decomposed grid");
-    if (parent->region_count < 2) return IVX_OK;
-    int rc;
-    if (!parent->has_dens) {
-        float ones[256];
-        for (float& x : ones) x = 1.0f;
-        if ((rc = h2d(parent, parent->dens_dev, ones, sizeof(ones)))) return rc;
-        memcpy(parent->dens_host, ones, sizeof(ones));
-        parent->has_dens = 1;
-    }
-    std::vector<ivx_region_desc> d;
-    if ((rc = describe_regions_internal(parent, parent->dens_dev, d))) return rc;
-    // the first two regions in scan order; the one with fewer non-uniform chunks goes, ties by chunk count,
-    // then the second (extraction.rs:255-271)
-    uint32_t pick;
-    if (d[0].non_uniform_chunk_count != d[1].non_uniform_chunk_count) pick = d[0].non_uniform_chunk_count < d[1].non_uniform_chunk_count ? 0u : 1u;
-    else pick = d[0].chunk_count < d[1].chunk_count ? 0u : 1u;
-    const ivx_region_desc& r = d[pick];
-    if (moved) *moved = r;
-    uint32_t lo[3], cc[3];
-    for (int q = 0; q < 3; ++q) {
-        lo[q] = r.lo[q] >> 4;
-        cc[q] = ((r.hi[q] - 1u) >> 4) - lo[q] + 1u;
-    }
-    const uint32_t uniform_count = r.chunk_count - r.non_uniform_chunk_count;
-    const bool discard = uniform_count == 0 && r.voxel_count < 8;  // NON_EMPTY_VOXEL_THRESHOLD (object.rs:203)
-    ivx_grid* c = nullptr;
-    if (!discard && (rc = ivx_grid_create(parent->ctx, cc, parent->extent, 0, 0, &c))) return rc;
-    if ((rc = ivx_launch_split_move(parent, c, lo, cc, pick))) {
-        ivx_grid_destroy(c);
-        return rc;
-    }
-    for (int q = 0; q < 3; ++q) origin_offset_in_parent[q] = lo[q] * 16u;
-    if (c && cc[0] <= 2 && cc[1] <= 2 && cc[2] <= 2 && uniform_count == 0 && cc[0] * cc[1] * cc[2] > 1 && r.hi[0] - r.lo[0] <= 14 &&
-        r.hi[1] - r.lo[1] <= 14 && r.hi[2] - r.lo[2] <= 14) {
-        uint32_t off[3];
-        for (int q = 0; q < 3; ++q) {
-            const uint32_t rel = r.lo[q] - lo[q] * 16u;
-            off[q] = rel > 0 ? rel - 1u : 0u;
-        }
-        const uint32_t one[3] = {1, 1, 1};
-        ivx_grid* single = nullptr;
-        if ((rc = ivx_grid_create(parent->ctx, one, parent->extent, 0, 0, &single))) {
-            ivx_grid_destroy(c);
-            return rc;
-        }
-        if ((rc = ivx_launch_split_repack(c, single, off))) {
-            ivx_grid_destroy(c);
-            ivx_grid_destroy(single);
-            return rc;
-        }
-        ivx_grid_destroy(c);
-        c = single;
-        for (int q = 0; q < 3; ++q) origin_offset_in_parent[q] += off[q];
-    }
-    if ((parent->occ_ref_valid = 0, rc = rederive(parent))) {
-        ivx_grid_destroy(c);
-        return rc;
-    }
-    if (c && (rc = rederive(c))) {
-        ivx_grid_destroy(c);
-        return rc;
-    }
-    *child = c;
-    *outcome = c ? 1 : 2;
-    return IVX_OK;
-}
-
-static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_ids, void* slab_record, uint32_t part = 3u);
-static int ivx_step_collect_launch(ivx_grid* g);
-// The reference's split-off LOOP in one call (interaction.rs:256: `while let Some(..) = find_two_disconnected_regions` ->
-// extract the smaller of the FIRST TWO regions in scan order, extraction.rs:255-271): the regions of the object are described once; what a
-// region is — voxels, box, chunk counts — does not change when another region leaves (regions share no voxel, and a chunk that holds two of
-// them stays NonUniform for the one that remains), nor does their scan order, so the loop's picks follow from the one description: the host
-// plays the loop over the descriptors, every region that goes is moved out by its own launch into a grid from one shared block, the parent
-// is re-derived ONCE and the children together (recorded, many.hpp). `children` / `origins3` / `outcomes` / `moved` in the order the loop
-// extracts them (outcome 1: a child object, 2: discarded as a crumb); *n_out = number of split-offs (regions - 1).
-int ivx_split_off_all(ivx_grid* parent, size_t cap, ivx_grid** children, uint32_t* origins3, int* outcomes, ivx_region_desc* moved, size_t* n_out) {
-    IVX_REQUIRE(parent && n_out && (cap == 0 || (children && origins3 && outcomes)), IVX_ERR_INVALID, "ivx_split_off_all: null argument");
-    *n_out = 0;
-    IVX_REQUIRE(parent->regions_valid, IVX_ERR_STATE, "ivx_split_off_all: call ivx_label_regions first");
-    IVX_REQUIRE(parent->x_off == 0 && parent->gx == parent->cc[0] && !parent->has_ghost[0] && !parent->has_ghost[1], IVX_ERR_STATE,
-                "ivx_split_off_all: not available on a slab of a decomposed grid");
-    if (parent->region_count < 2) return IVX_OK;
-    const size_t n = parent->region_count - 1u;
-    *n_out = n;
-    IVX_REQUIRE(n <= cap, IVX_ERR_CAPACITY, "ivx_split_off_all: %zu split-offs exceed capacity %zu", n, cap);
-    int rc;
-    hipStream_t s = parent->ctx->stream;
-    float ones[256];
-    for (float& x : ones) x = 1.0f;
-    if (!parent->has_dens) {
-        if ((rc = h2d(parent, parent->dens_dev, ones, sizeof(ones)))) return rc;
-        memcpy(parent->dens_host, ones, sizeof(ones));
-        parent->has_dens = 1;
-    }
-    std::vector<ivx_region_desc> d;
-    if ((rc = describe_regions_internal(parent, parent->dens_dev, d))) return rc;
-    // the loop over the descriptors: `front` is the first region still there, `second` the next one
-    std::vector<uint32_t> order;
-    order.reserve(n);
-    {
-        uint32_t front = 0;
-        for (uint32_t second = 1; second < (uint32_t)d.size(); ++second) {
-            const ivx_region_desc &a = d[front], &b = d[second];
-            bool take_first;
-            if (a.non_uniform_chunk_count != b.non_uniform_chunk_count) take_first = a.non_uniform_chunk_count < b.non_uniform_chunk_count;
-            else take_first = a.chunk_count < b.chunk_count;
-            if (take_first) {
-                order.push_back(front);
-                front = second;
-            } else {
-                order.push_back(second);
-            }
-        }
-    }
-    // the children's boxes and grids (crumbs get none: their voxels are just emptied)
-    std::vector<uint32_t> ccs, los;
-    std::vector<size_t> slot(n, (size_t)-1);
-    std::vector<char> repack(n, 0);
-    for (size_t k = 0; k < n; ++k) {
-        const ivx_region_desc& r = d[order[k]];
-        if (moved) moved[k] = r;
-        children[k] = nullptr;
-        const uint32_t uniform_count = r.chunk_count - r.non_uniform_chunk_count;
-        uint32_t lo[3], cc[3];
-        for (int q = 0; q < 3; ++q) {
-            lo[q] = r.lo[q] >> 4;
-            cc[q] = ((r.hi[q] - 1u) >> 4) - lo[q] + 1u;
-            origins3[3 * k + q] = lo[q] * 16u;
-        }
-        const bool discard = uniform_count == 0 && r.voxel_count < 8;  // NON_EMPTY_VOXEL_THRESHOLD (object.rs:203)
-        outcomes[k] = discard ? 2 : 1;
-        if (!discard) {
-            slot[k] = ccs.size() / 3;
-            repack[k] = cc[0] <= 2 && cc[1] <= 2 && cc[2] <= 2 && uniform_count == 0 && cc[0] * cc[1] * cc[2] > 1 && r.hi[0] - r.lo[0] <= 14 && r.hi[1] - r.lo[1] <= 14 &&
-                        r.hi[2] - r.lo[2] <= 14;
-        }
-        for (int q = 0; q < 3; ++q) {
-            if (!discard) ccs.push_back(cc[q]);
-            los.push_back(lo[q]);
-        }
-    }
-    const size_t n_kids = ccs.size() / 3;
-    std::vector<ivx_grid*> kids(n_kids, nullptr);
-    if ((rc = grid_create_pooled(parent->ctx, ccs.data(), n_kids, parent->extent, kids.data()))) return rc;
-    auto fail = [&](int code) {
-        (void)ivx_stream_sync(s);
-        for (ivx_grid*& c : kids)
-            if (c) {
-                c->pending_stages = 0, c->gather_launched = 0;
-                ivx_grid_destroy(c);
-                c = nullptr;
-            }
-        for (size_t k = 0; k < n; ++k) children[k] = nullptr;
-        parent->regions_valid = 0;  // (voxels may have left: the caller derives the object again)
-        return code;
-    };
-    // every region that goes, by its own launch (they read the labelling the parent has now; none of them changes it)
-    for (size_t k = 0; k < n; ++k) {
-        ivx_grid* c = slot[k] == (size_t)-1 ? nullptr : kids[slot[k]];
-        uint32_t cc[3];
-        if (c) memcpy(cc, c->cc, sizeof(cc));
-        else {
-            const ivx_region_desc& r = d[order[k]];
-            for (int q = 0; q < 3; ++q) cc[q] = ((r.hi[q] - 1u) >> 4) - los[3 * k + q] + 1u;
-        }
-        if ((rc = ivx_launch_split_move(parent, c, &los[3 * k], cc, order[k]))) return fail(rc);
-    }
-    // small children into one chunk (complete_extracted_voxel_object, extraction.rs:1902-2142)
-    for (size_t k = 0; k < n; ++k) {
-        if (!repack[k]) continue;
-        ivx_grid*& c = kids[slot[k]];
-        const ivx_region_desc& r = d[order[k]];
-        uint32_t off[3];
-        for (int q = 0; q < 3; ++q) {
-            const uint32_t rel = r.lo[q] - los[3 * k + q] * 16u;
-            off[q] = rel > 0 ? rel - 1u : 0u;
-        }
-        const uint32_t one[3] = {1, 1, 1};
-        ivx_grid* single = nullptr;
-        if ((rc = ivx_grid_create(parent->ctx, one, parent->extent, 0, 0, &single))) return fail(rc);
-        if ((rc = ivx_launch_split_repack(c, single, off))) {
-            ivx_grid_destroy(single);
-            return fail(rc);
-        }
-        ivx_grid_destroy(c);  // (waits for the stream: the repack has read its source)
-        c = single;
-        for (int q = 0; q < 3; ++q) origins3[3 * k + q] += off[q];
-    }
-    // derived state and regions: the parent and every child, recorded and issued together; one wait
-    parent->occ_ref_valid = 0;
-    std::vector<ivx_grid*> all(kids);
-    all.push_back(parent);
-    auto enqueue_one = [&](size_t i) -> int {
-        ivx_grid* g = all[i];
-        if (g != parent && !g->arena_block) return IVX_OK;  // (a repacked child: own allocation, zeroed at creation)
-        if (g != parent && !ivx_many_zero(g->ctx, g, g->work_counts, 8 * sizeof(uint32_t))) IVX_HIP_CHECK(ivx_memset_async(g->work_counts, 0, 8 * sizeof(uint32_t), s));
-        return IVX_OK;
-    };
-    auto derive_one = [&](size_t i) -> int {
-        int r = enqueue_one(i);
-        if (r) return r;
-        if ((r = rederive_enqueue(all[i]))) return r;
-        return ivx_step_collect_launch(all[i]);
-    };
-    if (ivx_many_recording()) {
-        (void)ivx_many_break();
-        for (size_t i = 0; i < all.size(); ++i)
-            if ((rc = derive_one(i))) return fail(rc);
-    } else {
-        if ((rc = ivx_many_begin(parent->ctx))) return fail(rc);
-        int first = IVX_OK;
-        for (size_t i = 0; i < all.size() && !first; ++i) {
-            ivx_many_object((uint32_t)i);
-            first = derive_one(i);
-        }
-        rc = ivx_many_flush(parent->ctx);
-        if (first || rc) return fail(first ? first : rc);
-    }
-    for (ivx_grid* g : all)
-        if ((rc = rederive_collect(g))) return fail(rc);
-    for (size_t k = 0; k < n; ++k)
-        if (slot[k] != (size_t)-1) children[k] = kids[slot[k]];
-    return IVX_OK;
-}
-
-// complete_extracted_voxel_object (extraction.rs:1901-2123) for a freshly filled child grid: discard rule, single-chunk
-// repack, derived state. On return *pc is the final child (or nullptr when discarded).
-static int complete_extracted(ivx_grid* parent, ivx_grid** pc, uint32_t origin[3]) {
-    ivx_grid* c = *pc;
-    int rc;
-    std::vector<ivx_chunk_info> info(c->n_chunks);
-    if ((rc = d2h(c, info.data(), c->info, sizeof(ivx_chunk_info) * c->n_chunks))) return rc;
-    uint32_t uniform_count = 0;
-    for (const ivx_chunk_info& i : info) uniform_count += i.gen_kind == KIND_UNIFORM;
-    // non-empty voxel count and tight voxel box of the child: derive (flags + per-chunk boxes), unit-density mass
-    if ((rc = ivx_launch_derive(c, 0))) return rc;
-    uint32_t* d_occ = c->rscalar + 16;
-    if ((rc = ivx_launch_occupied(c, d_occ))) return rc;
-    uint32_t occ[12], occ_raw[12];
-    if ((rc = d2h(c, occ_raw, d_occ, sizeof(occ_raw)))) return rc;
-    ivx_occupied_from_raw(c, occ_raw, occ);
-    float ones[256];
-    for (float& x : ones) x = 1.0f;
-    if ((rc = h2d(c, c->dens_dev, ones, sizeof(ones)))) return rc;
-    memcpy(c->dens_host, ones, sizeof(ones));
-    c->has_dens = 1;
-    double* out_dev = c->partials + c->partial_blocks * 10;
-    if ((rc = ivx_launch_inertia(c, c->dens_dev, out_dev, 0))) return rc;
-    double m0 = 0.0;
-    if ((rc = d2h(c, &m0, out_dev, sizeof(double)))) return rc;
-    const double e = (double)c->extent;
-    const unsigned long long non_empty = (unsigned long long)(m0 / (e * e * e) + 0.5);
-    if (uniform_count == 0 && non_empty < 8) {  // NON_EMPTY_VOXEL_THRESHOLD (object.rs:203)
-        ivx_grid_destroy(c);
-        *pc = nullptr;
-        return IVX_OK;
-    }
-    if (c->cc[0] <= 2 && c->cc[1] <= 2 && c->cc[2] <= 2 && uniform_count == 0 && c->n_chunks > 1 && occ[1] != 0 && occ[7] - occ[6] <= 14 &&
-        occ[9] - occ[8] <= 14 && occ[11] - occ[10] <= 14) {
-        uint32_t off[3];
-        for (int q = 0; q < 3; ++q) off[q] = occ[6 + 2 * q] > 0 ? occ[6 + 2 * q] - 1u : 0u;
-        const uint32_t one[3] = {1, 1, 1};
-        ivx_grid* single = nullptr;
-        if ((rc = ivx_grid_create(parent->ctx, one, parent->extent, 0, 0, &single))) return rc;
-        if ((rc = ivx_launch_split_repack(c, single, off))) {
-            ivx_grid_destroy(single);
-            return rc;
-        }
-        ivx_grid_destroy(c);
-        c = single;
-        *pc = c;
-        for (int q = 0; q < 3; ++q) origin[q] += off[q];
-    }
-    return rederive(c);
-}
-
-int ivx_clip_polyhedron(ivx_grid* parent, const float* planes4, size_t n_planes, const float aabb[6], int copy, ivx_grid** child,
-                        uint32_t origin_offset_in_parent[3], int* outcome) {
-    IVX_REQUIRE(parent && planes4 && aabb && child && origin_offset_in_parent && outcome, IVX_ERR_INVALID, "ivx_clip_polyhedron: null argument");
-    *child = nullptr;
-    *outcome = 0;
-    IVX_REQUIRE(n_planes >= 1 && n_planes <= 64, IVX_ERR_CAPACITY, "ivx_clip_polyhedron: 1..64 planes supported, got %zu", n_planes);
-    IVX_REQUIRE(parent->regions_valid, IVX_ERR_STATE, "ivx_clip_polyhedron: the object needs its derived state (ivx_derive_state + ivx_label_regions)");
-    IVX_REQUIRE(parent->x_off == 0 && parent->gx == parent->cc[0] && !parent->has_ghost[0] && !parent->has_ghost[1], IVX_ERR_STATE,
-                "ivx_clip_polyhedron: not available on a slab of a decomposed grid");
-    int rc;
-    // voxel_ranges_in_object_touching_aab (object/intersection.rs:693-782) of the AABB expanded by 2.54
-    uint32_t* d_occ = parent->rscalar + 16;
-    if ((rc = ivx_launch_occupied(parent, d_occ))) return rc;
-    uint32_t occ[12], occ_raw[12];
-    if ((rc = d2h(parent, occ_raw, d_occ, sizeof(occ_raw)))) return rc;
-    ivx_occupied_from_raw(parent, occ_raw, occ);
-    if (occ[1] == 0) return IVX_OK;
-    uint32_t lo[3], cc[3];
-    for (int q = 0; q < 3; ++q) {
-        const float l = aabb[q] - 2.54f, h = aabb[3 + q] + 2.54f;
-        const float fl = floorf(l);
-        const long s = (long)(fl > 0.0f ? fl : 0.0f), e = (long)ceilf(h);
-        const long vlo = std::max<long>((long)occ[6 + 2 * q], s), vhi = std::min<long>((long)occ[7 + 2 * q], std::max<long>(e, 0));
-        if (vlo >= vhi) return IVX_OK;
-        lo[q] = (uint32_t)(vlo / 16);
-        cc[q] = (uint32_t)((vhi + 15) / 16) - lo[q];
-    }
-    ivx_grid* c = nullptr;
-    if ((rc = ivx_grid_create(parent->ctx, cc, parent->extent, 0, 0, &c))) return rc;
-    if ((rc = ivx_launch_clip(parent, c, lo, cc, planes4, (uint32_t)n_planes, copy ? 0 : 1))) {
-        ivx_grid_destroy(c);
-        return rc;
-    }
-    for (int q = 0; q < 3; ++q) origin_offset_in_parent[q] = lo[q] * 16u;
-    if (!copy && (parent->occ_ref_valid = 0, rc = rederive(parent))) {
-        ivx_grid_destroy(c);
-        return rc;
-    }
-    if ((rc = complete_extracted(parent, &c, origin_offset_in_parent))) {
-        if (c) ivx_grid_destroy(c);
-        return rc;
-    }
-    *child = c;
-    *outcome = c ? 1 : 2;
-    return IVX_OK;
-}
-
-// Batched polyhedron COPY: every fragment of one impact in one call (FracturingProcess::execute_in_parallel, fracturing.rs:1047-1189, runs
-// copy_polyhedron_with_property_computer, extraction.rs:1301-1768, for all Voronoi cells of an impact over a thread pool; the object itself
-// is not changed). The looped form pays per fragment: an occupied-range reduction with a host read, the child's record download, three more
-// host reads for its voxel count / box / regions. Here the parent's ranges are reduced once, all clip kernels and all children's derive /
-// range / voxel-count passes are enqueued back to back and read with ONE wait, the discard / repack decisions are taken on the host, then
-// all region passes follow with a second wait. Per fragment the results are those of ivx_clip_polyhedron(copy = 1).
-int ivx_copy_polyhedra(ivx_grid* parent, const float* planes4, const uint32_t* plane_counts, const float* aabbs6, size_t n_sets, ivx_grid** children,
-                       uint32_t* origins3, int* outcomes) {
-    IVX_REQUIRE(parent && planes4 && plane_counts && aabbs6 && children && origins3 && outcomes, IVX_ERR_INVALID, "ivx_copy_polyhedra: null argument");
-    IVX_REQUIRE(parent->regions_valid, IVX_ERR_STATE, "ivx_copy_polyhedra: the object needs its derived state (ivx_derive_state + ivx_label_regions)");
-    IVX_REQUIRE(parent->x_off == 0 && parent->gx == parent->cc[0] && !parent->has_ghost[0] && !parent->has_ghost[1], IVX_ERR_STATE,
-                "ivx_copy_polyhedra: not available on a slab of a decomposed grid");
-    for (size_t f = 0; f < n_sets; ++f) {
-        children[f] = nullptr;
-        outcomes[f] = 0;
-        IVX_REQUIRE(plane_counts[f] >= 1 && plane_counts[f] <= 64, IVX_ERR_CAPACITY, "ivx_copy_polyhedra: 1..64 planes per polyhedron, set %zu has %u", f, plane_counts[f]);
-    }
-    if (n_sets == 0) return IVX_OK;
-    int rc;
-    hipStream_t s = parent->ctx->stream;
-    uint32_t* d_occ = parent->rscalar + 16;
-    if ((rc = ivx_launch_occupied(parent, d_occ))) return rc;
-    uint32_t occ[12], occ_raw[12];
-    if ((rc = d2h(parent, occ_raw, d_occ, sizeof(occ_raw)))) return rc;
-    ivx_occupied_from_raw(parent, occ_raw, occ);
-    if (occ[1] == 0) return IVX_OK;
-    // 1. the children's chunk boxes; their grids from ONE device block and ONE pinned block (grid_create_pooled)
-    std::vector<uint32_t> live, ccs, los;
-    size_t plane_off = 0;
-    std::vector<size_t> plane_offs(n_sets);
-    for (size_t f = 0; f < n_sets; plane_off += plane_counts[f], ++f) {
-        plane_offs[f] = plane_off;
-        const float* aabb = aabbs6 + 6 * f;
-        uint32_t lo[3], cc[3];
-        bool hit = true;
-        for (int q = 0; q < 3 && hit; ++q) {
-            const float l = aabb[q] - 2.54f, h = aabb[3 + q] + 2.54f;
-            const float fl = floorf(l);
-            const long st = (long)(fl > 0.0f ? fl : 0.0f), e = (long)ceilf(h);
-            const long vlo = std::max<long>((long)occ[6 + 2 * q], st), vhi = std::min<long>((long)occ[7 + 2 * q], std::max<long>(e, 0));
-            if (vlo >= vhi) hit = false;
-            else {
-                lo[q] = (uint32_t)(vlo / 16);
-                cc[q] = (uint32_t)((vhi + 15) / 16) - lo[q];
-            }
-        }
-        if (!hit) continue;
-        live.push_back((uint32_t)f);
-        for (int q = 0; q < 3; ++q) ccs.push_back(cc[q]), los.push_back(lo[q]), origins3[3 * f + q] = lo[q] * 16u;
-    }
-    const size_t n_live = live.size();
-    if (n_live == 0) return IVX_OK;
-    std::vector<ivx_grid*> kids(n_live, nullptr);
-    if ((rc = grid_create_pooled(parent->ctx, ccs.data(), n_live, parent->extent, kids.data()))) return rc;
-    auto fail = [&](int code) {
-        (void)ivx_stream_sync(s);
-        for (ivx_grid*& c : kids)
-            if (c) {
-                c->pending_stages = 0, c->gather_launched = 0;
-                ivx_grid_destroy(c);
-                c = nullptr;
-            }
-        for (size_t f = 0; f < n_sets; ++f) children[f] = nullptr, outcomes[f] = 0;
-        return code;
-    };
-    if ((rc = ivx_ensure_dense(parent))) return fail(rc);  // (what the clips read; ahead of the recording: it may launch)
-    // 2. per child, RECORDED (many.hpp) and issued as one launch per chain position for all of them: the clip, then a step of the child without
-    // the sample and remesh stages — derived state, regions, occupied ranges, unit-density mass (= voxel count) — and the gather of its small
-    // results into its host-mapped block. One wait for all.
-    float ones[256];
-    for (float& x : ones) x = 1.0f;
-    const uint32_t child_stages = IVX_STAGE_DERIVE | IVX_STAGE_REGIONS | IVX_STAGE_OCCUPIED | IVX_STAGE_INERTIA;
-    auto enqueue_child = [&](size_t i) -> int {
-        ivx_grid* c = kids[i];
-        const size_t f = live[i];
-        int r;
-        if (!ivx_many_zero(c->ctx, c, c->work_counts, 8 * sizeof(uint32_t))) IVX_HIP_CHECK(ivx_memset_async(c->work_counts, 0, 8 * sizeof(uint32_t), s));
-        if ((r = ivx_launch_clip(parent, c, &los[3 * i], &ccs[3 * i], planes4 + 4 * plane_offs[f], plane_counts[f], 0))) return r;
-        if (!ivx_many_upload(c->ctx, c, c->dens_dev, ones, sizeof(ones))) IVX_HIP_CHECK(ivx_memcpy_async(c->dens_dev, ones, sizeof(ones), hipMemcpyHostToDevice, s));
-        memcpy(c->dens_host, ones, sizeof(ones));
-        c->has_dens = 1;
-        const uint32_t keep = c->stage_timing_off;
-        c->stage_timing_off = 0xFFFFFFFFu;  // (no event records: they would cut the merged launches between every two children)
-        r = step_enqueue(c, child_stages, nullptr, nullptr);
-        c->stage_timing_off = keep;
-        if (r) return r;
-        return ivx_step_collect_launch(c);
-    };
-    if (ivx_many_recording()) {  // (inside somebody else's bracket: in order on the stream, unmerged)
-        (void)ivx_many_break();
-        for (size_t i = 0; i < n_live; ++i)
-            if ((rc = enqueue_child(i))) return fail(rc);
-    } else {
-        if ((rc = ivx_many_begin(parent->ctx))) return fail(rc);
-        int first = IVX_OK;
-        for (size_t i = 0; i < n_live && !first; ++i) {
-            ivx_many_object((uint32_t)i);
-            first = enqueue_child(i);
-        }
-        rc = ivx_many_flush(parent->ctx);
-        if (first || rc) return fail(first ? first : rc);
-    }
-    std::vector<ivx_step_result> res(n_live);
-    for (size_t i = 0; i < n_live; ++i)
-        if ((rc = ivx_voxel_step_collect(kids[i], &res[i]))) return fail(rc);
-    // 3. discard crumbs, repack small children into one chunk (complete_extracted_voxel_object, extraction.rs:1902-2142)
-    for (size_t i = 0; i < n_live; ++i) {
-        ivx_grid* c = kids[i];
-        const size_t f = live[i];
-        const uint32_t* cocc = res[i].occupied;
-        const double e = (double)c->extent;
-        const unsigned long long non_empty = (unsigned long long)(res[i].moments.m64[0] / (e * e * e) + 0.5);
-        // (a chunk filled with one type — gen_kind Uniform — holds 4096 voxels and spans 16 along every axis: neither test below can pass with
-        // one, which is what the reference's `uniform_chunk_count == 0` conditions say)
-        if (non_empty < 8) {  // NON_EMPTY_VOXEL_THRESHOLD (object.rs:203)
-            ivx_grid_destroy(c);
-            kids[i] = nullptr;
-            outcomes[f] = 2;
-            continue;
-        }
-        if (c->cc[0] <= 2 && c->cc[1] <= 2 && c->cc[2] <= 2 && c->n_chunks > 1 && cocc[1] != 0 && cocc[7] - cocc[6] <= 14 && cocc[9] - cocc[8] <= 14 &&
-            cocc[11] - cocc[10] <= 14) {
-            uint32_t off[3];
-            for (int q = 0; q < 3; ++q) off[q] = cocc[6 + 2 * q] > 0 ? cocc[6 + 2 * q] - 1u : 0u;
-            const uint32_t one[3] = {1, 1, 1};
-            ivx_grid* single = nullptr;
-            if ((rc = ivx_grid_create(parent->ctx, one, parent->extent, 0, 0, &single))) return fail(rc);
-            if ((rc = ivx_launch_split_repack(c, single, off))) {
-                ivx_grid_destroy(single);
-                return fail(rc);
-            }
-            ivx_grid_destroy(c);  // (waits for the stream: the repack has read its source)
-            c = kids[i] = single;
-            for (int q = 0; q < 3; ++q) origins3[3 * f + q] += off[q];
-            ivx_step_result again;
-            if ((rc = ivx_grid_set_densities(single, ones)) || (rc = ivx_voxel_step(single, child_stages, &again))) return fail(rc);
-        }
-        c->mesh_valid = 0;
-        children[f] = c;
-        outcomes[f] = 1;
-    }
     return IVX_OK;
 }
 
@@ -1981,16 +1482,11 @@ static int absorb_enqueue(ivx_grid* g, const char* who, int capsule, const float
         *reinterpret_cast<volatile uint32_t*>(static_cast<char*>(e->pinned) + e->off_bell) = 0u;
         e->early_armed = 1;
     }
-    {
-        const uint32_t keep = g->stage_timing_off;
-        g->stage_timing_off = 0xFFFFFFFFu;       // (no event records around the slots: nobody reads this call's stage times)
-        g->preset_fresh |= IVX_SCRATCH_REGIONS;  // (the region scalars were zeroed by the edit kernel, before the box sweep listed its multi-region chunks)
-        g->regions_labelled_locally = 1;         // (... and the sweep labelled the box: no stand-alone local pass in front of the resolve)
-        rc = ivx_voxel_step_enqueue(g, IVX_STAGE_REGIONS);
-        g->regions_labelled_locally = 0;
-        g->stage_timing_off = keep;
-        if (rc) return rc;
-    }
+    g->preset_fresh |= IVX_SCRATCH_REGIONS;  // (the region scalars were zeroed by the edit kernel, before the box sweep listed its multi-region chunks)
+    g->regions_labelled_locally = 1;         // (... and the sweep labelled the box: no stand-alone local pass in front of the resolve)
+    rc = step_enqueue_untimed(g, IVX_STAGE_REGIONS);  // (nobody reads this call's stage times)
+    g->regions_labelled_locally = 0;
+    if (rc) return rc;
     if (e->staged) {
         g->gather_copy_src = reinterpret_cast<const uint32_t*>(base);
         g->gather_copy_dst = static_cast<uint32_t*>(e->pinned_dev);
@@ -2217,7 +1713,7 @@ static int ensure_pairs(ivx_grid* g);
 // slab's record ride in the phase's own launches instead of taking two more
 // `part` (slab protocol, ivx_voxel_step_enqueue_part): bit 0 = the call's sample and derive sweeps, bit 1 = everything behind them; the two
 // halves of ONE call enqueued apart, so that the slab's face planes can be packed and sent between them.
-static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_ids, void* slab_record, uint32_t part) {
+static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_ids, void* slab_record, uint32_t part = 3u) {
     IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_voxel_step_enqueue: null grid");
     const bool front = (part & 1u) != 0u, back = (part & 2u) != 0u;
     ivx_many_other_context other_(g->ctx);
@@ -2359,6 +1855,15 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
 }
 
 int ivx_voxel_step_enqueue(ivx_grid* g, uint32_t stages) { return step_enqueue(g, stages, nullptr, nullptr); }
+// ... without event records around the stage slots, whatever ivx_grid_set_stage_timing has asked for: for callers whose stage times nobody reads,
+// and for recorded steps — an event is a stream operation of its own and would end the merging after every object
+extern "C++" int step_enqueue_untimed(ivx_grid* g, uint32_t stages) {
+    const uint32_t keep = g->stage_timing_off;
+    g->stage_timing_off = 0xFFFFFFFFu;
+    const int rc = step_enqueue(g, stages, nullptr, nullptr);
+    g->stage_timing_off = keep;
+    return rc;
+}
 }  // extern "C"
 // (slab_comm.cpp) one call's launches in two parts: 1 = its sample and derive sweeps, 2 = what follows them
 int ivx_voxel_step_enqueue_part(ivx_grid* g, uint32_t stages, uint32_t part) { return step_enqueue(g, stages, nullptr, nullptr, part); }
@@ -2414,7 +1919,7 @@ static uint64_t collect_spin_ns() {
 
 // the launch half of ivx_voxel_step_collect: the gather of the step's results (and whatever rides on it) goes on the stream — or into the
 // batch being recorded —, the wait is left to the collect
-static int ivx_step_collect_launch(ivx_grid* g) {
+extern "C++" int ivx_step_collect_launch(ivx_grid* g) {
     if (g->results_in_block || g->gather_launched) return IVX_OK;
     if (!g->result_host) {
         IVX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->result_host), 64 * sizeof(uint32_t), hipHostMallocMapped));
@@ -2712,16 +2217,8 @@ int ivx_voxel_step_many(ivx_grid* const* grids, size_t n, uint32_t stages, ivx_s
     int rc = many_check(grids, n, "ivx_voxel_step_many");
     if (rc) return rc;
     IVX_REQUIRE(out, IVX_ERR_INVALID, "ivx_voxel_step_many: null result array");
-    // (no event records around the stage slots: an event is a stream operation of its own and would end the merging after every object;
-    // `stage_ms` of a merged step is zero — the launches are shared, their times are not an object's)
-    if ((rc = many_phase(grids, n, [&](size_t i) {
-             const uint32_t keep = grids[i]->stage_timing_off;
-             grids[i]->stage_timing_off = 0xFFFFFFFFu;
-             const int r = step_enqueue(grids[i], stages, nullptr, nullptr);
-             grids[i]->stage_timing_off = keep;
-             return r;
-         })))
-        return many_fail(grids, n, rc);
+    // (`stage_ms` of a merged step is zero — the launches are shared, their times are not an object's)
+    if ((rc = many_phase(grids, n, [&](size_t i) { return step_enqueue_untimed(grids[i], stages); }))) return many_fail(grids, n, rc);
     if ((rc = many_phase(grids, n, [&](size_t i) { return ivx_step_collect_launch(grids[i]); }))) return many_fail(grids, n, rc);
     for (size_t i = 0; i < n; ++i) {
         grids[i]->defer_mesh_growth = 1;

@@ -1,6 +1,7 @@
-// What the host units of the C ABI (ivx_api.hip, voxel_collision_api.hip) share and nothing else links against: staged copies, the objects'
-// device scratch, the recorder phases of the many-object calls and the host mirrors of the reference's range allocators. Defined in ivx_api.hip
-// (the functions hidden: the library exports what it exported before).
+// What the host units of the C ABI (ivx_api.hip, voxel_collision_api.hip, extraction_api.hip) share and nothing else links against: staged
+// copies, the objects' device scratch, the recorder phases of the many-object calls, what the extraction calls need of the grid life cycle, the
+// regions and the step, and the host mirrors of the reference's range allocators. Defined in ivx_api.hip unless said otherwise (the functions
+// hidden: the library exports what it exported before).
 #pragma once
 #include <functional>
 #include <limits>
@@ -26,8 +27,32 @@ int h2d(ivx_grid* g, void* dst, const void* src, size_t bytes);
 // the object's device scratch (ivx_grid::dev_scratch) holds at least `bytes`; a growth waits for the stream and keeps nothing
 int ensure_dev_scratch(ivx_grid* g, size_t bytes);
 
-// box sweep + region stages after an edit that changed voxels, enqueued and collected
+// box sweep + region stages after an edit that changed voxels, enqueued and collected (extraction_api.hip): both halves, and the two apart for a
+// caller that has results of its own in flight behind the same doorbell
 int rederive(ivx_grid* g);
+int rederive_enqueue(ivx_grid* g);
+int rederive_collect(ivx_grid* g);
+
+// for extraction_api.hip: grids that come into being together, from one device block and one pinned block (`who`: the call, for messages) | the
+// descriptors of all regions of a labelled object | a step's launches without event records around the stage slots | the launch half of
+// ivx_voxel_step_collect
+int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, float voxel_extent, ivx_grid** out, const char* who);
+int describe_regions_internal(ivx_grid* g, const float* d_dens, std::vector<ivx_region_desc>& out);
+int step_enqueue_untimed(ivx_grid* g, uint32_t stages);
+int ivx_step_collect_launch(ivx_grid* g);
+
+// What the collision and extraction calls ask of an object: derived state current, (needs_probes) probes picked from the current mesh, not a
+// slab of a decomposed grid. `item` non-null names the object or pair of a batched call in the message ("object 3: ...").
+inline int require_whole_object(const ivx_grid* g, const char* who, bool needs_probes, const char* item = nullptr, size_t index = 0) {
+    const char* missing = nullptr;
+    if (!g->regions_valid) missing = "derived state must be current (ivx_derive_state + ivx_label_regions)";
+    else if (needs_probes && !(g->mesh_valid && g->probes_serial == g->mesh_serial)) missing = "collision probes must be current (ivx_collision_probes_recompute)";
+    else if (!(g->x_off == 0 && g->gx == g->cc[0] && !g->has_ghost[0] && !g->has_ghost[1])) missing = "not available on a slab of a decomposed grid";
+    if (!missing) return IVX_OK;
+    if (item) ivx_set_error("%s: %s %zu: %s", who, item, index, missing);
+    else ivx_set_error("%s: %s", who, missing);
+    return IVX_ERR_STATE;
+}
 
 // many objects per call (many.hpp): the objects of one context, each listed once | `f(i)` for every object under the recorder, then the flush |
 // the drain after a failure half way

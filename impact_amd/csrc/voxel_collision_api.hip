@@ -257,19 +257,6 @@ bool host_intersection_ranges(const ivx_grid* a, const uint32_t occ_a[12], const
     return true;
 }
 
-// What the calls here ask of an object: derived state current, (needs_probes) probes picked from the current mesh, not a slab of a decomposed
-// grid. `item` non-null names the object or pair of a batched call in the message ("object 3: ...").
-int require_whole_object(const ivx_grid* g, const char* who, bool needs_probes, const char* item = nullptr, size_t index = 0) {
-    const char* missing = nullptr;
-    if (!g->regions_valid) missing = "derived state must be current (ivx_derive_state + ivx_label_regions)";
-    else if (needs_probes && !(g->mesh_valid && g->probes_serial == g->mesh_serial)) missing = "collision probes must be current (ivx_collision_probes_recompute)";
-    else if (!(g->x_off == 0 && g->gx == g->cc[0] && !g->has_ghost[0] && !g->has_ghost[1])) missing = "not available on a slab of a decomposed grid";
-    if (!missing) return IVX_OK;
-    if (item) ivx_set_error("%s: %s %zu: %s", who, item, index, missing);
-    else ivx_set_error("%s: %s", who, missing);
-    return IVX_ERR_STATE;
-}
-
 // the end of the single calls: the total, then that many contacts, each a copy and a wait
 int contacts_download(ivx_grid* g, const char* who, const uint32_t* d_total, const ivx_contact* d_out, ivx_contact* out, size_t cap, size_t* n_out) {
     uint32_t total = 0;

@@ -11,6 +11,7 @@ static __device__ uint32_t ivx_dbg_derive_skip = 0u;
 #define IVX_DBG_KEEP(bit) true
 #endif
 #include "ivx_internal.hpp"
+#include "device_common.hpp"
 
 #define NODE_NONE 0xFFFFFFFFu
 
@@ -486,7 +487,8 @@ __device__ __forceinline__ void ccl_exact_chunk(CclShared& sh, uint32_t tid, uin
 // the node of a run is the voxel index of its first voxel, links go through LDS atomicMin (root = smallest index).
 // `m`: the thread's non-empty row mask (ignored when the chunk is Void or was generated Uniform). Writes the label plane
 // (NonUniform chunks only: compact planes) and the first slot of the region table; returns the region counts for the
-// caller to put into the chunk record (same values in every thread).
+// caller to put into the chunk record (same values in every thread). `POL`: the store policy of the label plane (device_common.hpp).
+template <int POL = IVX_ST_PLAIN>
 __device__ __forceinline__ void ccl_local_chunk(CclShared& sh, uint32_t tid, uint32_t chunk, uint32_t kind, uint32_t gen, uint32_t m_in,
                                                 uint8_t* __restrict__ labels, uint32_t* __restrict__ rparent, uint32_t* __restrict__ rscalar,
                                                 uint32_t* __restrict__ multi_list, uint32_t& rc_out, uint32_t& brc_out) {
@@ -556,7 +558,7 @@ __device__ __forceinline__ void ccl_local_chunk(CclShared& sh, uint32_t tid, uin
     if (!any || all_full) {
         // no voxels, or one solid region touching every face
         const uint32_t lab = any ? 0u : 0xFFFFFFFFu;
-        if (kind == KIND_NONUNIFORM && IVX_DBG_KEEP(8u)) *reinterpret_cast<uint4*>(labels + base) = make_uint4(lab, lab, lab, lab);  // else: compact planes
+        if (kind == KIND_NONUNIFORM && IVX_DBG_KEEP(8u)) ivx_st16<POL>(labels + base, make_uint4(lab, lab, lab, lab));  // else: compact planes
         // only slots below region_count are ever read (flatten / assign / find walk valid nodes only)
         if (tid == 0) rp[0] = any ? chunk * 256u : NODE_NONE;
         rc_out = any ? 1u : 0u;
@@ -612,7 +614,7 @@ __device__ __forceinline__ void ccl_local_chunk(CclShared& sh, uint32_t tid, uin
 #pragma unroll
         for (int k = 0; k < 16; ++k)
             if (!((m >> k) & 1u)) w[k >> 2] |= 0xFFu << (8 * (k & 3));
-        if (IVX_DBG_KEEP(8u)) *reinterpret_cast<uint4*>(labels + base) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (IVX_DBG_KEEP(8u)) ivx_st16<POL>(labels + base, make_uint4(w[0], w[1], w[2], w[3]));
         if (tid == 0) rp[0] = chunk * 256u;
         rc_out = 1u;
         brc_out = touches ? 1u : 0u;

@@ -18,6 +18,7 @@
 //
 // Traffic: reads 1 B/voxel (sdf sign) + six neighbour faces, writes 1 B/voxel (flags). Emptiness of the
 // 16 voxels of a row is a 16-bit mask; the 18x18 halo of masks sits in LDS.
+#include "device_common.hpp"
 #include "chunk_passes.hpp"
 #include "table_roles.hpp"
 #include "many.hpp"
@@ -27,6 +28,12 @@
 // (stores leave the L2 on this part), per lane and chunk: with all of the sweep's own store groups switched off the headline launch still wrote
 // 52 of its 91 MB (tools/derive_budget.sh). Measured (tools/derive_waves.sh, profiles/round5): headline 39.5 us / 103.7 MB written at seven,
 // 37.6 us / 45.6 MB at six, 38.3 us / 32.8 MB at five; all-surface 188 us / 378 MB, 181 us / 302 MB, 187 us / 270 MB. Six it is.
+// Store policy of the sweep's flags and label planes (device_common.hpp, store forms): whole lines that nobody reads in this launch, written
+// through as they are made — about 1 us off the launch on the headline (profiles/round9/README.md). The sdf / type planes of a chunk demoted
+// in this pass and the per-chunk words (record, list entry, touch byte, region slot) are plain stores: no other form gained anything.
+#ifndef IVX_POL_SWEEP_PLANES
+#define IVX_POL_SWEEP_PLANES IVX_ST_WT
+#endif
 #ifndef IVX_DERIVE_WAVES
 #define IVX_DERIVE_WAVES 6
 #endif
@@ -546,7 +553,7 @@ __device__ __forceinline__ void derive_body(const DeriveArgs& a_, uint32_t bid_,
     // the planes of a Uniform chunk that was demoted before hold its voxels already; its record no longer has the type
     const uint32_t utype = own_uniform ? (own_info.kind == KIND_NONUNIFORM ? (type0 & 0xFFu) : (uint32_t)own_info.uniform_type) : 0u;
     if (kind == KIND_NONUNIFORM) {
-        if (IVX_DBG_KEEP(1u)) *reinterpret_cast<uint4*>(flags_out + base + (size_t)tid * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (IVX_DBG_KEEP(1u)) ivx_st16<IVX_POL_SWEEP_PLANES>(flags_out + base + (size_t)tid * 16, make_uint4(w[0], w[1], w[2], w[3]));
         if (own_uniform && own_info.kind != KIND_NONUNIFORM && IVX_DBG_KEEP(2u)) {
             // convert_to_non_uniform_if_uniform (object.rs:2530-2550): the demoted chunk gets its 4096 voxels
             const uint32_t t4 = utype * 0x01010101u;
@@ -566,7 +573,7 @@ __device__ __forceinline__ void derive_body(const DeriveArgs& a_, uint32_t bid_,
     IVX_T(g, li, 3);  // flags written
     // ---- fused passes over the same chunk (uniform branches: `parts` and `kind` are the same for the whole workgroup)
     uint32_t rc = own_info.region_count, brc = own_info.boundary_region_count;
-    if (fz.parts & IVX_PART_REGIONS) ccl_local_chunk(s_ccl, tid, chunk, kind, gen, m, fz.labels, fz.rparent, fz.rscalar, fz.multi_list, rc, brc);
+    if (fz.parts & IVX_PART_REGIONS) ccl_local_chunk<IVX_POL_SWEEP_PLANES>(s_ccl, tid, chunk, kind, gen, m, fz.labels, fz.rparent, fz.rscalar, fz.multi_list, rc, brc);
     IVX_T(g, li, 4);  // regions labelled
     if ((fz.parts & IVX_PART_MOMENTS) && kind == KIND_NONUNIFORM && IVX_DBG_KEEP(16u)) {
         // (a chunk demoted in this pass has no type plane yet: its voxels all have the record's type)
@@ -932,7 +939,7 @@ __device__ __forceinline__ void derive_wave_body(const DeriveArgs& a_) {
                 w[2 * h] = lo, w[2 * h + 1] = hi;
             }
         }
-        if (IVX_DBG_KEEP(1u)) *reinterpret_cast<uint4*>(flags_out + base + (size_t)r * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (IVX_DBG_KEEP(1u)) ivx_st16<IVX_POL_SWEEP_PLANES>(flags_out + base + (size_t)r * 16, make_uint4(w[0], w[1], w[2], w[3]));
         if (fresh && IVX_DBG_KEEP(2u)) {
             const uint32_t t4 = utype * 0x01010101u;
             *reinterpret_cast<uint4*>(sdf_rw + base + (size_t)r * 16) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
@@ -1002,7 +1009,7 @@ __device__ __forceinline__ void derive_wave_body(const DeriveArgs& a_) {
             if (kind == KIND_NONUNIFORM && IVX_DBG_KEEP(8u)) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    *reinterpret_cast<uint4*>(fz.labels + base + (size_t)((4u * la + q) * 16u + j) * 16) = make_uint4(lab, lab, lab, lab);
+                    ivx_st16<IVX_POL_SWEEP_PLANES>(fz.labels + base + (size_t)((4u * la + q) * 16u + j) * 16, make_uint4(lab, lab, lab, lab));
             }
             if (lane == 0u) rp[0] = any ? chunk * 256u : NODE_NONE;
             rc = any ? 1u : 0u;
@@ -1014,7 +1021,7 @@ __device__ __forceinline__ void derive_wave_body(const DeriveArgs& a_) {
 #pragma unroll
                 for (int k = 0; k < 16; ++k)
                     if (!((R[q] >> k) & 1u)) w[k >> 2] |= 0xFFu << (8 * (k & 3));
-                if (IVX_DBG_KEEP(8u)) *reinterpret_cast<uint4*>(fz.labels + base + (size_t)((4u * la + q) * 16u + j) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+                if (IVX_DBG_KEEP(8u)) ivx_st16<IVX_POL_SWEEP_PLANES>(fz.labels + base + (size_t)((4u * la + q) * 16u + j) * 16, make_uint4(w[0], w[1], w[2], w[3]));
             }
             if (lane == 0u) rp[0] = chunk * 256u;
             rc = 1u;

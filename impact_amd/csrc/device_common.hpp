@@ -75,3 +75,72 @@ static inline void ivx_staging_release(ivx_staging* st) {
     if (st->staged) (void)hipEventDestroy(st->staged);
     *st = ivx_staging();
 }
+
+// ---- store forms of the device code -------------------------------------------------------------------------------------------------------
+// What a store says about the line it writes (gfx950; MI355X_MICROARCH.md, visibility): a PLAIN store leaves it dirty in the XCD's L2 until
+// something writes it back — at the latest the end of the launch, when the chip waits for every dirty line of every L2 —; NT marks it as
+// streaming but still leaves it in the L2 ("nt is not write-through"); WT (sc1) writes it through as it is made and drops it from the L2, so
+// a reader on the same XCD fetches it from the memory side again; WT_NT is both. A kernel's output stream takes ONE policy, a -D macro at its
+// store site (tools/build_variant.sh builds the variants side by side); the values stored are the same under every policy.
+//
+// Forms. Plain and NT are the compiler's own stores. WT of 8 bytes or fewer is the relaxed agent-scope atomic store (global_store ... sc1,
+// counted by the compiler's waits like any store). WT of 16 bytes has no builtin on a global address: it is the instruction itself, which
+// costs no scalar registers (a buffer resource is four per plane; the evaluator has none to spare) but is NOT counted by the compiler's
+// s_waitcnt — use it only for bytes that nobody reads again in the same launch. (`s_nop 1`: the data registers of a store wider than 64 bits
+// may not be overwritten in the two states after it.) The buffer form, for code that holds a resource anyway, is counted; its offset is 32 bits
+// and a store beyond the resource's range is dropped, so the host sizes the resource and keeps planes that do not fit it on the global forms.
+#define IVX_ST_PLAIN 0
+#define IVX_ST_NT 1
+#define IVX_ST_WT 2
+#define IVX_ST_WT_NT 3
+typedef unsigned int ivx_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int ivx_u32x2 __attribute__((ext_vector_type(2)));
+
+template <int POL>
+__device__ __forceinline__ void ivx_st16(void* p, uint4 v) {
+    ivx_u32x4 x;
+    x.x = v.x, x.y = v.y, x.z = v.z, x.w = v.w;
+    if constexpr (POL == IVX_ST_PLAIN) *reinterpret_cast<uint4*>(p) = v;
+    else if constexpr (POL == IVX_ST_NT) __builtin_nontemporal_store(x, reinterpret_cast<ivx_u32x4*>(p));
+    else if constexpr (POL == IVX_ST_WT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+    else asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+}
+template <int POL>
+__device__ __forceinline__ void ivx_st8(void* p, uint2 v) {
+    ivx_u32x2 x;
+    x.x = v.x, x.y = v.y;
+    const unsigned long long u = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+    if constexpr (POL == IVX_ST_PLAIN) *reinterpret_cast<uint2*>(p) = v;
+    else if constexpr (POL == IVX_ST_NT) __builtin_nontemporal_store(x, reinterpret_cast<ivx_u32x2*>(p));
+    else if constexpr (POL == IVX_ST_WT) __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(p), "v"(x) : "memory");
+}
+template <int POL>
+__device__ __forceinline__ void ivx_st4(void* p, uint32_t v) {
+    if constexpr (POL == IVX_ST_PLAIN) *reinterpret_cast<uint32_t*>(p) = v;
+    else if constexpr (POL == IVX_ST_NT) __builtin_nontemporal_store(v, reinterpret_cast<uint32_t*>(p));
+    else if constexpr (POL == IVX_ST_WT) __hip_atomic_store(reinterpret_cast<uint32_t*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else asm volatile("global_store_dword %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
+}
+template <int POL>
+__device__ __forceinline__ void ivx_st4(float* p, float v) { ivx_st4<POL>(static_cast<void*>(p), __float_as_uint(v)); }
+template <int POL>
+__device__ __forceinline__ void ivx_st4(uint32_t* p, uint32_t v) { ivx_st4<POL>(static_cast<void*>(p), v); }
+template <int POL>
+__device__ __forceinline__ void ivx_st2(void* p, uint16_t v) {
+    if constexpr (POL == IVX_ST_PLAIN) *reinterpret_cast<uint16_t*>(p) = v;
+    else if constexpr (POL == IVX_ST_NT) __builtin_nontemporal_store(v, reinterpret_cast<uint16_t*>(p));
+    else if constexpr (POL == IVX_ST_WT) __hip_atomic_store(reinterpret_cast<uint16_t*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else asm volatile("global_store_short %0, %1, off sc1 nt" ::"v"(p), "v"((uint32_t)v) : "memory");
+}
+// the buffer form: `aux` 2 = nt, 16 = sc1
+template <int POL>
+__device__ __forceinline__ void ivx_st16_buf(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, ivx_u32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)byte_off, 0, (POL & 1 ? 2 : 0) | (POL & 2 ? 16 : 0));
+}
+// (the solver's hand-off store, physics.hip: write-through, so that another workgroup anywhere on the chip reads it back with an sc1 load)
+__device__ __forceinline__ void st16_sc1(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, float4 f) {
+    ivx_u32x4 v;
+    v.x = __float_as_uint(f.x), v.y = __float_as_uint(f.y), v.z = __float_as_uint(f.z), v.w = __float_as_uint(f.w);
+    ivx_st16_buf<IVX_ST_WT>(rs, byte_off, v);
+}

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "ivx_internal.hpp"
+#include "device_common.hpp"
 #include "physics_internal.hpp"
 #include "vec3.hpp"
 
@@ -581,11 +582,7 @@ __device__ __forceinline__ float4 ld16_sc1(__amdgpu_buffer_rsrc_t rs, uint32_t b
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 16);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
-__device__ __forceinline__ void st16_sc1(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, float4 f) {
-    u32x4 v;
-    v.x = __float_as_uint(f.x), v.y = __float_as_uint(f.y), v.z = __float_as_uint(f.z), v.w = __float_as_uint(f.w);
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)byte_off, 0, 16);
-}
+// (st16_sc1, the write-through store that goes with it: device_common.hpp)
 // The hand-off store of the multi-workgroup solve. A write-through (sc1) store is what another workgroup ANYWHERE on the chip can read back with
 // an sc1 load — but it also drops the line from the XCD's L2, so the reader's load goes to the memory side: ~2 us of every level. When all
 // working workgroups sit on ONE XCD (k_solve_mg places them so and CHECKS it, `one_xcd`), their common L2 is the point of coherence: a plain

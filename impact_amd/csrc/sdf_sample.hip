@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "ivx_internal.hpp"
+#include "device_common.hpp"
 #include "noise.hpp"
 #include "table_roles.hpp"
 
@@ -184,6 +185,14 @@ struct SampleParams {
     uint32_t voxel_type;
 };
 
+// Store policy of the evaluator's planes (device_common.hpp, store forms): 16 bytes per thread, whole 128-byte lines per wave, read by nobody
+// in this launch — written through as they are made, 1.1-1.4 us off the launch and about 1 us off its start-to-start distance on the headline
+// (profiles/round9/README.md). The sign rows, the k-face bytes and the record, which k_chunk_pre and the sweep read in the very next
+// launches, gained nothing from any other form than the plain one they have.
+#ifndef IVX_POL_EVAL_PLANES
+#define IVX_POL_EVAL_PLANES IVX_ST_WT
+#endif
+
 // the low bytes of 16 ints as 16 bytes: three byte permutes per word (v_perm_b32 selector bytes: 0-3 = second operand's, 4-7 = first's)
 __device__ __forceinline__ uint4 pack16(const int* v) {
     uint32_t w[4];
@@ -235,8 +244,8 @@ __device__ __forceinline__ void classify_and_store(int* sd, uint4 types, bool ty
     if (kind == KIND_NONUNIFORM || !compact) {  // Void / Uniform chunks are their 8-byte record (compact planes)
         size_t base = (size_t)chunk * IVX_CHUNK_VOXELS + (size_t)tid * 16;
         const uint4 packed = pack16(sd);
-        *reinterpret_cast<uint4*>(sdf_out + base) = packed;
-        *reinterpret_cast<uint4*>(type_out + base) = types;
+        ivx_st16<IVX_POL_EVAL_PLANES>(sdf_out + base, packed);
+        ivx_st16<IVX_POL_EVAL_PLANES>(type_out + base, types);
         if (signs_out && kind == KIND_NONUNIFORM) {
             // What the derive sweep and the mesher need of this chunk besides its planes, while the row is in registers: the row's 16-bit
             // "distance negative" mask (GridView::signs) and its bytes on the two k faces (GridView::kface). With them in place the sweep

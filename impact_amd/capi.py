@@ -208,6 +208,10 @@ COLLIDABLE_DTYPE = np.dtype([("shape", "<u4"), ("kind", "<u4"), ("body", "<u4"),
 CW_SPHERE, CW_PLANE, CW_CAPSULE, CW_VOXEL_OBJECT = 0, 1, 2, 3
 CW_PTR_WORLD_COLLIDABLES, CW_PTR_CONTACTS, CW_PTR_DEFERRED_PAIRS = 0, 1, 2
 assert COLLIDABLE_DTYPE.itemsize == 64
+# motion drivers of kinematic bodies (csrc/motion.hip): `ivx_motion_driver`; `p` holds the reference's setup struct of that kind
+MOTION_DRIVER_DTYPE = np.dtype([("kind", "<u4"), ("body", "<u4"), ("p", "<f4", (14,))])
+MD_CIRCULAR, MD_CONSTANT_ACCELERATION, MD_HARMONIC, MD_ORBITAL, MD_CONSTANT_ROTATION = 0, 1, 2, 3, 4
+assert MOTION_DRIVER_DTYPE.itemsize == 64
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -238,6 +242,7 @@ EXPORTED_SYMBOLS = [
     "ivx_bv_world_aabb", "ivx_bv_frustum_query", "ivx_grid_model_aabb", "ivx_bv_set", "ivx_bv_set_grids", "ivx_bv_download", "ivx_bv_pairs", "ivx_bv_queries",
     "ivx_bv_device_ptr",
     "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
+    "ivx_world_set_motion_drivers", "ivx_world_set_time", "ivx_world_time", "ivx_world_apply_motion", "ivx_md_eval", "ivx_md_apply_host",
 ]
 
 
@@ -269,7 +274,7 @@ def extra_struct_sizes():
         "ivx_cull_object": (CULL_OBJECT_DTYPE, 8), "ivx_draw_args": (DRAW_ARGS_DTYPE, 16), "ivx_draw_indexed_args": (DRAW_INDEXED_ARGS_DTYPE, 20),
         "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
         "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128),
-        "ivx_collidable": (COLLIDABLE_DTYPE, 64),
+        "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
     }
 
 
@@ -463,6 +468,12 @@ def lib():
         "ivx_cw_download": (i32, [vp, vp, sz]),
         "ivx_cw_collide": (i32, [vp, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]),
         "ivx_cw_device_ptr": (vp, [vp, i32]),
+        "ivx_world_set_motion_drivers": (i32, [vp, vp, sz]),
+        "ivx_world_set_time": (i32, [vp, f32]),
+        "ivx_world_time": (i32, [vp, C.POINTER(f32)]),
+        "ivx_world_apply_motion": (i32, [vp, f32]),
+        "ivx_md_eval": (i32, [vp, f32, vp]),
+        "ivx_md_apply_host": (i32, [vp, sz, vp, sz, f32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -76,16 +76,8 @@ __device__ __forceinline__ M3 rotated(const M3& m, Q4 q) {  // R M R^T (inertia.
     return mul(mul(r, m), transpose(r));
 }
 __device__ __forceinline__ Q4 conj(Q4 q) { return {-q.x, -q.y, -q.z, q.w}; }
-__device__ __forceinline__ Q4 qnormalize(Q4 q) {
-    const float l = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-    return {q.x / l, q.y / l, q.z / l, q.w / l};
-}
-// f32::sin / f32::cos of the reference are libm's sinf / cosf, which are the correctly rounded values in all but rare cases; the device
-// library's single-precision versions are one ulp off now and then (found by a random contact graph whose 1-ulp orientation grew past the
-// 1e-5 bar in two frames). The double-precision functions rounded once agree with libm on every value the tests have met; it is two calls
-// per body and step.
-__device__ __forceinline__ float sin_rn(float x) { return (float)sin((double)x); }
-__device__ __forceinline__ float cos_rn(float x) { return (float)cos((double)x); }
+using ivx_phys::advance_orientation;  // (with sin_rn / cos_rn inside it: physics_internal.hpp, shared with the motion drivers)
+using ivx_phys::qnormalize;
 
 // AngularVelocity::from_vector (quantities.rs:160-172): unit axis + speed, zero at or below f32::EPSILON
 struct AngVel {
@@ -227,10 +219,7 @@ __device__ __forceinline__ void post_solve_body(uint32_t i, uint32_t n_dyn, uint
         if (advance) {
             st3(b.position, ld3(b.position) + body_velocity(b) * dt);
             const AngVel av = body_angular_velocity(b);
-            const float angle = av.speed * dt;
-            const float s = sin_rn(0.5f * angle), co = cos_rn(0.5f * angle);
-            const V3 im = av.axis * s;
-            stq(b.orientation, qnormalize(qmul(Q4{im.x, im.y, im.z, co}, ldq(b.orientation))));
+            stq(b.orientation, advance_orientation(ldq(b.orientation), av.axis, av.speed, dt));
         }
         dyn[i] = b;
     } else if (advance || (write_back && touched[i])) {
@@ -251,10 +240,7 @@ __device__ __forceinline__ void post_solve_body(uint32_t i, uint32_t n_dyn, uint
             return;
         }
         st3(k.position, ld3(k.position) + ld3(k.velocity) * dt);
-        const float angle = k.angular_speed * dt;
-        const float s = sin_rn(0.5f * angle), co = cos_rn(0.5f * angle);
-        const V3 im = ld3(k.angular_axis) * s;
-        stq(k.orientation, qnormalize(qmul(Q4{im.x, im.y, im.z, co}, ldq(k.orientation))));
+        stq(k.orientation, advance_orientation(ldq(k.orientation), ld3(k.angular_axis), k.angular_speed, dt));
         kin[i - n_dyn] = k;
     }
 }

@@ -623,6 +623,7 @@ void ivx_world_destroy(ivx_world* w) {
         (void)hipStreamDestroy(w->side_stream);
     }
     ivx_cw_release(w);
+    ivx_md_release(w);
     if (w->stage_sched) (void)hipHostFree(w->stage_sched);  // pinned staging of the general path's uploads
     if (w->stage_sched_ev_ready) (void)hipEventDestroy(w->stage_sched_ev);
     if (w->stage_contacts) (void)hipHostFree(w->stage_contacts);  // pinned staging of the set_contacts fast path
@@ -1049,16 +1050,28 @@ static int world_step_enqueue(ivx_world* w, float dt, bool timed) {
     return IVX_OK;
 }
 
+// The tail of perform_physics_step (lib.rs:86-100): the clock moves on (new_simulation_time, host-side only) and the motion drivers, if the
+// world has a set, are applied at the new time — one launch behind the advance of configurations. (stage_ms does not cover it.)
+static int world_step_finish(ivx_world* w, float dt, const char* who) {
+    w->time = w->time + dt;
+    return w->md_state ? ivx_launch_motion_apply(w, w->time, who) : IVX_OK;
+}
+
 int ivx_world_step_enqueue(ivx_world* w, float dt) {
     IVX_REQUIRE(w, IVX_ERR_INVALID, "ivx_world_step_enqueue: null world");
     if (int rc = ivx_world_check_solve(w, "ivx_world_step_enqueue")) return rc;  // (an earlier step's flag, if it is up by now)
-    return world_step_enqueue(w, dt, false);
+    if (w->md_state)
+        if (int rc = ivx_motion_ready(w, "ivx_world_step_enqueue")) return rc;
+    if (int rc = world_step_enqueue(w, dt, false)) return rc;
+    return world_step_finish(w, dt, "ivx_world_step_enqueue");
 }
 
 int ivx_world_step(ivx_world* w, float dt, ivx_physics_result* out) {
     IVX_REQUIRE(w, IVX_ERR_INVALID, "ivx_world_step: null world");
-    int rc = world_step_enqueue(w, dt, out != nullptr);
+    int rc = w->md_state ? ivx_motion_ready(w, "ivx_world_step") : IVX_OK;
     if (rc) return rc;
+    if ((rc = world_step_enqueue(w, dt, out != nullptr))) return rc;
+    if ((rc = world_step_finish(w, dt, "ivx_world_step"))) return rc;
     IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));
     if ((rc = ivx_world_check_solve(w, "ivx_world_step"))) return rc;
     if (out) {

@@ -5,6 +5,34 @@
 #include <vector>
 
 #include "ivx_internal.hpp"
+#include "vec3.hpp"
+
+// Arithmetic the step's advance of configurations (physics.hip, post_solve_body) and the constant-rotation motion driver (motion.hip) share,
+// host and device: one text, so the two cannot drift apart.
+namespace ivx_phys {
+using ivx_vec::Q4;
+using ivx_vec::V3;
+#define IVX_PHYS_HD __host__ __device__ __forceinline__
+// f32::sin / f32::cos of the reference are libm's sinf / cosf, which are the correctly rounded values in all but rare cases; the device
+// library's single-precision versions are one ulp off now and then (found by a random contact graph whose 1-ulp orientation grew past the
+// 1e-5 bar in two frames). The double-precision functions rounded once agree with libm on every value the tests have met; it is two calls
+// per body and step.
+IVX_PHYS_HD float sin_rn(float x) { return (float)sin((double)x); }
+IVX_PHYS_HD float cos_rn(float x) { return (float)cos((double)x); }
+IVX_PHYS_HD float tan_rn(float x) { return (float)tan((double)x); }
+IVX_PHYS_HD Q4 qnormalize(Q4 q) {
+    const float l = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
+    return {q.x / l, q.y / l, q.z / l, q.w / l};
+}
+// advance_orientation (rigid_body.rs:1020-1034): the rotation by angular speed x duration about the unit axis, applied on the left, re-normalised
+IVX_PHYS_HD Q4 advance_orientation(Q4 q, V3 axis, float speed, float duration) {
+    const float angle = speed * duration;
+    const float s = sin_rn(0.5f * angle), co = cos_rn(0.5f * angle);
+    const V3 im = ivx_vec::operator*(axis, s);
+    return qnormalize(ivx_vec::qmul(Q4{im.x, im.y, im.z, co}, q));
+}
+#undef IVX_PHYS_HD
+}  // namespace ivx_phys
 
 // ConstrainedBody (impact_physics/src/constraint.rs:137-150), 96 bytes. Dynamic bodies first (same index as
 // in the rigid-body array), kinematic bodies after them.
@@ -166,10 +194,15 @@ struct ivx_world {
     int cs_feasible[2];
     uint32_t forms_built;
     std::vector<uint32_t> chain_bodies, prev_chain_start, prev_chain_bodies;  // body pair per chain; last frame's chains (an unchanged contact structure keeps its schedule)
+    float time;      // the simulation clock (ivx_world_set_time / ivx_world_time): every step adds its dt; host-side only
+    void* md_state;  // motion drivers (motion.hip): the sorted driver set, the compact list of driven bodies and their offsets; made by ivx_world_set_motion_drivers, freed by ivx_md_release
     void* cw_state;  // primitive collidables (narrow.hip): local and world-space records, wave masks and offsets, contact and deferred buffers; made on first use, freed by ivx_cw_release
 };
 
 void ivx_cw_release(ivx_world* w);  // narrow.hip (ivx_world_destroy)
+void ivx_md_release(ivx_world* w);  // motion.hip (ivx_world_destroy)
+int ivx_motion_ready(ivx_world* w, const char* who);  // motion.hip: IVX_ERR_STATE when the driver set refers to more kinematic bodies than the world holds (checked before a step launches anything)
+int ivx_launch_motion_apply(ivx_world* w, float time, const char* who);  // motion.hip: nothing without a driver set
 int ivx_launch_phys_prepare_bodies(ivx_world* w);
 int ivx_launch_phys_prepare_contacts(ivx_world* w, const int32_t* d_prev_slot);
 int ivx_launch_phys_mark_joint_bodies(ivx_world* w);

@@ -474,6 +474,55 @@ private:
     Context* ctx_;
 };
 
+// ---- motion drivers of kinematic bodies (impact_physics/src/driven_motion/): the reference's setup structs in their #[repr(C)] layouts ------
+// (all fields are f32: a record's parameters are the struct's bytes). `driver(kinematic_body_index)` gives the record ivx_world_set_motion_drivers takes.
+namespace detail {
+template <class T>
+ivx_motion_driver motion_driver(uint32_t kind, uint32_t body, const T& setup) {
+    static_assert(sizeof(T) <= sizeof(ivx_motion_driver::p) && sizeof(T) % sizeof(float) == 0, "a setup struct fits the record's parameters");
+    ivx_motion_driver d{};
+    d.kind = kind, d.body = body;
+    const float* f = reinterpret_cast<const float*>(&setup);
+    for (size_t i = 0; i < sizeof(T) / sizeof(float); ++i) d.p[i] = f[i];
+    return d;
+}
+}  // namespace detail
+struct CircularTrajectory {  // circular.rs:52-68
+    float initial_time;
+    float orientation[4];  // x, y, z, w
+    float center_position[3];
+    float radius, period;
+    ivx_motion_driver driver(uint32_t body) const { return detail::motion_driver(IVX_MD_CIRCULAR, body, *this); }
+};
+struct ConstantAccelerationTrajectory {  // constant_acceleration.rs:52-61
+    float initial_time;
+    float initial_position[3], initial_velocity[3], acceleration[3];
+    ivx_motion_driver driver(uint32_t body) const { return detail::motion_driver(IVX_MD_CONSTANT_ACCELERATION, body, *this); }
+};
+struct HarmonicOscillatorTrajectory {  // harmonic_oscillation.rs:55-64
+    float center_time;
+    float center_position[3], direction[3];
+    float amplitude, period;
+    ivx_motion_driver driver(uint32_t body) const { return detail::motion_driver(IVX_MD_HARMONIC, body, *this); }
+};
+struct OrbitalTrajectory {  // orbit.rs:52-70
+    float periapsis_time;
+    float orientation[4];  // x, y, z, w
+    float focal_position[3];
+    float semi_major_axis, eccentricity, period;
+    ivx_motion_driver driver(uint32_t body) const { return detail::motion_driver(IVX_MD_ORBITAL, body, *this); }
+};
+struct ConstantRotation {  // constant_rotation.rs:51-59; AngularVelocityC = unit axis + angular speed
+    float initial_time;
+    float initial_orientation[4];  // x, y, z, w
+    float axis_of_rotation[3];
+    float angular_speed;
+    ivx_motion_driver driver(uint32_t body) const { return detail::motion_driver(IVX_MD_CONSTANT_ROTATION, body, *this); }
+};
+static_assert(sizeof(CircularTrajectory) == 40 && sizeof(ConstantAccelerationTrajectory) == 40 && sizeof(HarmonicOscillatorTrajectory) == 36 &&
+                  sizeof(OrbitalTrajectory) == 44 && sizeof(ConstantRotation) == 36 && sizeof(ivx_motion_driver) == 64,
+              "motion driver layouts");
+
 // ---- rigid bodies + constraint solver (impact_physics/src/lib.rs:31-110) --------------------------------------------------------------
 class PhysicsWorld {
 public:
@@ -498,6 +547,20 @@ public:
         std::vector<ivx_rigid_body> d(n_dyn_);
         check(ivx_world_get_bodies(w_, d.data(), nullptr));
         return d;
+    }
+    std::vector<ivx_kinematic_body> kinematic_bodies() {
+        std::vector<ivx_kinematic_body> k(n_kin_);
+        check(ivx_world_get_bodies(w_, nullptr, k.data()));
+        return k;
+    }
+    // MotionDriverManager: the set replaces the one before (empty: none); with a set every step ends by applying it at the new simulation time
+    void set_motion_drivers(const std::vector<ivx_motion_driver>& drivers) { check(ivx_world_set_motion_drivers(w_, drivers.data(), drivers.size())); }
+    void apply_motion(float simulation_time) { check(ivx_world_apply_motion(w_, simulation_time)); }
+    void set_simulation_time(float t) { check(ivx_world_set_time(w_, t)); }
+    float simulation_time() {
+        float t = 0.0f;
+        check(ivx_world_time(w_, &t));
+        return t;
     }
 
 private:

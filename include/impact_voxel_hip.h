@@ -733,9 +733,10 @@ int ivx_world_set_contacts(ivx_world*, const ivx_contact*, size_t n, size_t* n_p
  * velocities are written back after the solve — which is all this entry point makes happen. Stays in force until replaced; call it after
  * ivx_world_set_bodies. */
 int ivx_world_set_spherical_joints(ivx_world*, const uint32_t* body_pairs, size_t n_joints);
-/* perform_physics_step (src/lib.rs:31-110) without force generators / motion drivers: prepare constraints ->
+/* perform_physics_step (src/lib.rs:31-110) without force generators: prepare constraints ->
  * advance momenta -> synchronise velocities, warm start, n_iterations sweeps, positional correction,
- * write back -> advance configurations. The stages are also exposed one by one. */
+ * write back -> advance configurations -> motion drivers at the new simulation time (when a set is installed,
+ * ivx_world_set_motion_drivers). The stages are also exposed one by one. */
 int ivx_world_step(ivx_world*, float dt, ivx_physics_result* out);
 /* the same step, only enqueued on the context's stream (no wait, no result): lets the rigid-body step of a frame run
  * behind the voxel step of the same frame with a single wait for both (ivx_voxel_step_collect / ivx_synchronize);
@@ -1136,6 +1137,76 @@ int ivx_cw_download(ivx_world*, ivx_collidable* world_space, size_t cap);
 int ivx_cw_collide(ivx_world*, uint32_t mode, ivx_contact* out, size_t cap, size_t* n_out, uint32_t* deferred_pairs, size_t deferred_cap, size_t* n_deferred);
 /* IVX_CW_PTR_*: the world collidables, the contacts and the deferred pairs of the last calls; world-owned and grow-only, NULL before they exist */
 void* ivx_cw_device_ptr(ivx_world*, int which);
+
+/* ---- motion drivers of kinematic bodies (impact_physics/src/driven_motion.rs and the files under driven_motion/; csrc/motion.hip) -----------
+ * A kinematic body whose state is a function of the simulation time. One record per driver, 64 bytes: `body` indexes the world's kinematic
+ * bodies (WITHOUT the IVX_KINEMATIC_BODY bit), `p` holds the reference's setup struct of that kind, field by field in its #[repr(C)] order:
+ *   IVX_MD_CIRCULAR              CircularTrajectory            p[0] initial_time, p[1..4] orientation xyzw, p[5..7] center_position, p[8] radius, p[9] period
+ *   IVX_MD_CONSTANT_ACCELERATION ConstantAccelerationTrajectory p[0] initial_time, p[1..3] initial_position, p[4..6] initial_velocity, p[7..9] acceleration
+ *   IVX_MD_HARMONIC              HarmonicOscillatorTrajectory  p[0] center_time, p[1..3] center_position, p[4..6] direction, p[7] amplitude, p[8] period
+ *   IVX_MD_ORBITAL               OrbitalTrajectory             p[0] periapsis_time, p[1..4] orientation xyzw, p[5..7] focal_position, p[8] semi_major_axis,
+ *                                                              p[9] eccentricity, p[10] period
+ *   IVX_MD_CONSTANT_ROTATION     ConstantRotation              p[0] initial_time, p[1..4] initial_orientation xyzw, p[5..7] unit axis, p[8] angular speed
+ * The rest of `p` is ignored.
+ *
+ * Arithmetic: float32, uncontracted, in the reference's operation order (TWO_PI = 6.2831855f, PI = 3.1415927f; `%` is fmodf: the result has the
+ * dividend's sign; sin, cos and tan are the double-precision functions rounded once; rotate_point / rotate_vector are glam's mul_vec3a):
+ *   circular (circular.rs:134-194)    w = TWO_PI / period;  angle = (w * (t - initial_time)) % TWO_PI;  s, c = sin, cos(angle)
+ *       position = center + rotate(q, (radius * c, radius * s, 0));  v = radius * w;  velocity = rotate(q, (-v * s, v * c, 0))
+ *   constant acceleration (constant_acceleration.rs:143-157)    dt = t - initial_time
+ *       position = (p0 + dt * v0) + (0.5 * (dt * dt)) * a;  velocity = v0 + dt * a
+ *   harmonic (harmonic_oscillation.rs:139-159)    dt = t - center_time;  w = TWO_PI / period
+ *       position = center + (amplitude * sin(w * dt)) * direction;  velocity = ((amplitude * w) * cos(w * dt)) * direction
+ *   orbital (orbit.rs:149-365)    n = TWO_PI / period;  M = (n * (t - periapsis_time)) % TWO_PI
+ *       E: Newton from E = M, E' = E - ((E - e * sin E) - M) / (1 - e * cos E), until |E' - E| <= 1e-4 or 100 iterations
+ *       f2 = (1 + e) / (1 - e);  f = sqrt(f2);  th = tan(0.5 * E);  th2 = th * th;  tv2 = f2 * th2;  k = 1 / (1 + tv2)
+ *       cos_v = (1 - tv2) * k;  dv_dE = (f * (1 + th2)) * k;  r = (a * (1 - e * e)) / (1 + e * cos_v)
+ *       sin_v = sqrt(1 - cos_v * cos_v), negated unless E <= PI  (a time before periapsis_time has M < 0 and so E < PI: it takes the
+ *       positive root, as in the reference)
+ *       position = focus + rotate(q, (r * cos_v, r * sin_v, 0));  dv = (n * dv_dE) / (1 - e * cos E)
+ *       vr = ((((dv * e) * a) * (1 - e * e)) * sin_v) / ((1 + e * cos_v) * (1 + e * cos_v));  vt = r * dv
+ *       velocity = rotate(q, (vr * cos_v - vt * sin_v, vr * sin_v + vt * cos_v, 0))
+ *   constant rotation (constant_rotation.rs:111-120)    orientation = advance_orientation(q0, axis, speed, t - initial_time), the very code of the
+ *       step's advance of configurations (rigid_body.rs:1013-1034);  angular velocity = (axis, speed) as given
+ *
+ * Composition (MotionDriverManager::apply_motion, driven_motion.rs:50-82), the same code on the device and in ivx_md_apply_host:
+ *   - a body with at least one trajectory driver (the first four kinds) has position and velocity reset to +0.0, then the contributions are
+ *     added in the order circular, constant acceleration, harmonic, orbital and, within a kind, in the order of the caller's list. (The
+ *     reference walks the drivers of a kind in the order of a hash map, which nothing pins; the list order is this library's choice.) The sum
+ *     starts from the reset zero, so a lone -0.0 component comes out +0.0, as in the reference.
+ *   - constant rotations come last; each sets orientation and angular velocity, the last one in list order wins.
+ *   - a body with rotation drivers only keeps the position and velocity it has; one with trajectory drivers only keeps its orientation and
+ *     angular velocity. Bodies without a driver are not written. */
+#define IVX_MD_CIRCULAR 0u
+#define IVX_MD_CONSTANT_ACCELERATION 1u
+#define IVX_MD_HARMONIC 2u
+#define IVX_MD_ORBITAL 3u
+#define IVX_MD_CONSTANT_ROTATION 4u
+typedef struct {
+    uint32_t kind; /* IVX_MD_* */
+    uint32_t body; /* index into the kinematic bodies */
+    float p[14];
+} ivx_motion_driver;
+/* The world's driver set, resident until replaced (n == 0 removes it); call it after ivx_world_set_bodies. The set is stored sorted stably by
+ * (body, kind, list index) with a compact list of the driven bodies, and uploaded once. IVX_ERR_INVALID, with a message that names the driver
+ * (the set then stays as it was), for what the reference asserts when it applies a driver: a radius or semi-major axis that is not > 0, a period
+ * with |period| <= FLT_EPSILON (circular, harmonic, orbital), an eccentricity outside [0, 1); and for an unknown kind or body >= the world's
+ * kinematic bodies. With a set installed every ivx_world_step / ivx_world_step_enqueue ends by applying it at the new time (below): one launch
+ * behind the advance of configurations on the same stream, a lane per driven body; nothing waits. A world without a set launches what it
+ * launched before. If the world's bodies are replaced by fewer kinematic bodies than the set refers to, the next apply is IVX_ERR_STATE. */
+int ivx_world_set_motion_drivers(ivx_world*, const ivx_motion_driver*, size_t n);
+/* The world's simulation clock: 0 at creation; every ivx_world_step and ivx_world_step_enqueue sets time = time + dt in float32
+ * (perform_physics_step's new_simulation_time, src/lib.rs:86-100). Host-side only. */
+int ivx_world_set_time(ivx_world*, float time);
+int ivx_world_time(ivx_world*, float* out);
+/* MotionDriverManager::apply_motion at `time` on its own, like the other stages: enqueued, does not touch the clock. No set installed: nothing. */
+int ivx_world_apply_motion(ivx_world*, float time);
+/* One driver at `time`, the function the kernel runs, on the host (tests). Trajectory kinds: out[0..2] position, out[3..5] velocity, the rest 0;
+ * constant rotation: out[0..3] orientation xyzw, out[4..6] axis, out[7] angular speed, the rest 0. Validates like ivx_world_set_motion_drivers
+ * (the body index is not looked at). */
+int ivx_md_eval(const ivx_motion_driver*, float time, float out[10]);
+/* The composition above over host arrays, the code the kernel runs (tests). Validates like ivx_world_set_motion_drivers against n_kinematic. */
+int ivx_md_apply_host(const ivx_motion_driver*, size_t n, ivx_kinematic_body* bodies, size_t n_kinematic, float time);
 
 #ifdef __cplusplus
 }

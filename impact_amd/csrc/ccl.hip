@@ -167,7 +167,9 @@ __global__ __launch_bounds__(256) void k_step_record(const uint32_t* __restrict_
                                                      const uint2* __restrict__ pairs, const uint32_t* __restrict__ mesh_totals,
                                                      const double* __restrict__ moments, uint32_t x_off, uint32_t max_pairs,
                                                      unsigned long long* __restrict__ rec, const uint32_t* __restrict__ work_count,
-                                                     const uint32_t* __restrict__ eval_count, uint32_t* __restrict__ host_block) {
+                                                     const uint32_t* __restrict__ eval_count, uint32_t* __restrict__ host_block,
+                                                     unsigned long long* tick) {
+    ivx_stage_stamp(tick);  // (a step that ends in its record has no gather: this launch closes its last timed slot)
     role_step_record(rscalar, pair_count, pairs, mesh_totals, moments, x_off, max_pairs, rec);
     // (with `host_block`: the step's small results where ivx_voxel_step_collect looks for them, so that it needs no launch of its own)
     if (host_block && threadIdx.x < 64u) role_result_gather(rscalar, mesh_totals, moments, work_count, eval_count, host_block, false, 0u);
@@ -412,7 +414,7 @@ int ivx_launch_step_record(ivx_grid* g, const uint32_t* d_pair_count, const void
     IVX_KLAUNCH(k_step_record, dim3(1), dim3(256), 0, g->ctx->stream, g->rscalar, d_pair_count, static_cast<const uint2*>(d_pairs),
                        g->chunk_offsets + 2 * (size_t)g->n_chunks, g->partials + g->partial_blocks * 10, g->x_off, max_pairs,
                        static_cast<unsigned long long*>(d_record), ivx_wc(g), g->samp_len ? g->samp_len + g->n_chunks : nullptr,
-                       with_results ? g->result_host_dev : nullptr);
+                       with_results ? g->result_host_dev : nullptr, ivx_take_tick(g));
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }

@@ -84,6 +84,7 @@ struct ChunkPreArgs {
     // (slab protocol, the sweep split around the arrival of the ghost layers) 1: a Uniform chunk of a face plane that only the ghost layer's
     // record can settle is left PENDING (class 2: neither settled nor listed) for k_face_settle, which runs behind the wait
     uint32_t defer_ghost, pad_;
+    unsigned long long* tick;  // stage stamp (ivx_stage_stamp): the clock word this launch writes on entry, or null
 };
 // the record of a chunk that needs no sweep: Void, or Uniform among Uniform neighbours
 __device__ __forceinline__ void chunk_settle(const GridView& g, const ChunkPreArgs& a, uint32_t chunk, const ivx_chunk_info& own) {
@@ -163,7 +164,10 @@ __device__ __forceinline__ void chunk_pre_body(const ChunkPreArgs& a, uint32_t b
         active_list[off] = chunk;
     }
 }
-__global__ __launch_bounds__(256) void k_chunk_pre(ChunkPreArgs a) { chunk_pre_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void k_chunk_pre(ChunkPreArgs a) {
+    ivx_stage_stamp(a.tick);
+    chunk_pre_body(a, blockIdx.x, gridDim.x);
+}
 IVX_MANY_TWIN(k_chunk_pre_many, ChunkPreArgs, chunk_pre_body, __launch_bounds__(256))
 IVX_MANY_LAUNCHER(many_chunk_pre, k_chunk_pre_many, ChunkPreArgs, 256)
 
@@ -306,6 +310,7 @@ struct DeriveArgs {
     DeriveFused fz;
     uint32_t signs_type, x_part;  // (x_part: IVX_XPART_*, the slab protocol's split around the arrival of the ghost layers)
     DeriveBox box;
+    unsigned long long* tick;  // stage stamp (ivx_stage_stamp): the clock word this launch writes on entry, or null
 };
 template <bool SIGNS>
 __device__ __forceinline__ void derive_body(const DeriveArgs& a_, uint32_t bid_, uint32_t nb_) {
@@ -626,6 +631,7 @@ __device__ __forceinline__ void derive_body(const DeriveArgs& a_, uint32_t bid_,
 }
 template <bool SIGNS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVES, 8))) void k_derive(DeriveArgs a) {
+    ivx_stage_stamp(a.tick);
     derive_body<SIGNS>(a, blockIdx.x, gridDim.x);
 }
 IVX_MANY_TWIN(k_derive_planes_many, DeriveArgs, derive_body<false>, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVES, 8))))
@@ -1087,7 +1093,10 @@ __device__ __forceinline__ void derive_wave_body(const DeriveArgs& a_) {
     ivx_wave_lds_sync();  // this chunk's LDS reads are over before the next chunk's stores
     }
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVE_WAVES, 8))) void k_derive_wave(DeriveArgs a) { derive_wave_body(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVE_WAVES, 8))) void k_derive_wave(DeriveArgs a) {
+    ivx_stage_stamp(a.tick);
+    derive_wave_body(a);
+}
 
 // The active list anew from the chunk records alone (after a box sweep changed kinds: ivx_ensure_active_list): k_chunk_pre's rule for what is
 // settled — Void, or generated Uniform among six chunks generated Uniform —, entries with the kinds and the exposure bit the derive sweep would
@@ -1313,8 +1322,10 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
         // not look at the ghost layers' chunk records — a Uniform chunk of a face plane that only such a record can settle is left pending)
         if (g->ghost_event && g->ghost_split && ivx_has_interior_planes(g)) pa.defer_ghost = 1u;
         const uint32_t blocks = (g->n_chunks + 255u) / 256u;
+        pa.tick = ivx_take_tick(g);
         if (!ivx_many_try(g->ctx, g, IVX_MK_CHUNK_PRE, blocks, pa)) IVX_KLAUNCH(k_chunk_pre, dim3(blocks), dim3(256), 0, g->ctx->stream, pa);
         face_settle = pa;
+        face_settle.tick = nullptr;
     }
     g->scratch_dirty &= ~preset_groups;
     if (roll) g->scratch_dirty &= ~IVX_SCRATCH_EVAL;
@@ -1345,6 +1356,7 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
     }
     auto sweep = [&](uint32_t x_part) {
         da.x_part = x_part;
+        da.tick = ivx_take_tick(g);
         if (g->signs_current) {
             if (ivx_many_try(g->ctx, g, IVX_MK_DERIVE_SIGNS, derive_grid, da)) return;
             if (x_part == IVX_XPART_ALL && v.ghost_sdf[0] == nullptr && v.ghost_sdf[1] == nullptr)

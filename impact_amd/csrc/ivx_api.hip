@@ -384,6 +384,17 @@ int ivx_init(int device_id, void* stream, ivx_ctx** out) {
     IVX_REQUIRE(c, IVX_ERR_CAPACITY, "ivx_init: out of host memory");
     c->device = device_id;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    {
+        // the rate of the clock the kernels' stage stamps read (ivx_stage_stamp); 100 MHz on this part, assumed — and said — when the query fails
+        int khz = 0;
+        const hipError_t ce = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id);
+        if (ce != hipSuccess || khz <= 0) {
+            ivx_set_error("ivx_init: the wall clock rate of device %d could not be queried (%s); stage times from clock stamps assume 100 MHz", device_id,
+                          ce == hipSuccess ? "0 kHz reported" : hipGetErrorString(ce));
+            khz = 100000;
+        }
+        c->wall_clock_khz = (double)khz;
+    }
     if (stream) {
         c->stream = static_cast<hipStream_t>(stream);
         c->own_stream = false;
@@ -601,6 +612,8 @@ void ivx_grid_destroy(ivx_grid* g) {
         if (p) (void)hipFree(p);
     if (g->host_scratch) (void)hipHostFree(g->host_scratch);
     if (g->result_host) (void)hipHostFree(g->result_host);
+    if (g->tick_dev) (void)hipFree(g->tick_dev);  // (the stage stamps' words: two small allocations of their own, made on first use)
+    if (g->tick_host) (void)hipHostFree(g->tick_host);
     if (g->ev_ready)
         for (int i = 0; i < 2 * IVX_N_TIMED_STAGES; ++i) (void)hipEventDestroy(g->ev[i]);
     delete g;
@@ -1706,8 +1719,41 @@ int ivx_grid_set_densities(ivx_grid* g, const float densities[256]) {
 // Timed slots of a step (ivx_step_result::stage_ms): 0 sample (k_sdf_super, k_sdf_prepass, k_sdf_eval), 1 derive (k_chunk_pre, k_derive:
 // flags, chunk state, chunk-local regions, chunk moments), 2 k_step_post1 (mesher count | region merge by columns | occupied slots
 // | moment partial sums), 3 k_step_post2 (exact local numbering -> multi-region merge | mesher scan | moments and occupied ranges
-// final), 4 k_step_emit (region forest flatten | mesher emit), 5 k_step_assign (component ids); 6..9 unused. Stage timing costs two
-// event records per slot on the stream; ivx_grid_set_stage_timing(g, 0) turns it off.
+// final), 4 k_step_emit (region forest flatten | mesher emit), 5 k_step_assign (component ids); 6..9 unused.
+//
+// How a timed slot is measured. On the step's fused path — a whole call (`part` 3) outside the slab protocol's remesh phase, on a grid
+// the fused assign reaches, with the derive stage in it or nothing left for the stand-alone per-chunk kernels, not recorded into a batch —
+// a slot costs the queue nothing: block 0 of the slot's first launch writes the device's constant-rate clock to a word on entry
+// (ivx_stage_stamp), block 0 of the first launch enqueued BEHIND the slot writes the closing word, and the slot's time is the distance of
+// the two: start to start, the launch boundary behind the slot included. Adjacent timed slots share the word between them. The closing word
+// of a call's last slot goes to whatever stamping launch this grid makes next — the next call's first kernel, or k_step_gather (a launch
+// of another object enqueued in between, the bench's k_free_step, falls into that boundary). The gather copies the words to host-mapped
+// memory ahead of the doorbell and zeroes them. Every other call keeps two event records per slot, 2-3 us each on the queue — which is
+// what the 6 us boundaries on either side of a timed k_step_emit were (profiles/stage_stamps) —, and IVX_STAGE_TIMING_EVENTS=1 (read once)
+// forces that path everywhere. One call never mixes the two clocks. ivx_grid_set_stage_timing(g, 0) turns timing off.
+static const bool g_stage_timing_events = [] {
+    const char* e = getenv("IVX_STAGE_TIMING_EVENTS");
+    return e && atoi(e) == 1;
+}();
+static int ensure_stage_events(ivx_grid* g) {
+    if (g->ev_ready) return IVX_OK;
+    for (int i = 0; i < 2 * IVX_N_TIMED_STAGES; ++i) IVX_HIP_CHECK(hipEventCreate(&g->ev[i]));
+    g->ev_ready = 1;
+    return IVX_OK;
+}
+static int ensure_stage_ticks(ivx_grid* g) {
+    if (g->tick_dev && g->tick_host) return IVX_OK;
+    if (!g->tick_dev) {
+        IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->tick_dev), IVX_TICK_WORDS * sizeof(unsigned long long)));
+        IVX_HIP_CHECK(hipMemset(g->tick_dev, 0, IVX_TICK_WORDS * sizeof(unsigned long long)));
+    }
+    if (!g->tick_host) {
+        IVX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->tick_host), IVX_TICK_WORDS * sizeof(unsigned long long), hipHostMallocMapped));
+        memset(g->tick_host, 0, IVX_TICK_WORDS * sizeof(unsigned long long));
+        IVX_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g->tick_host_dev), g->tick_host, 0));
+    }
+    return IVX_OK;
+}
 static int ensure_pairs(ivx_grid* g);
 // `slab_nbr_ids` / `slab_record`: the slab protocol's remesh phase (ivx_slab_remesh_enqueue) — the pass over the neighbour's face ids and the
 // slab's record ride in the phase's own launches instead of taking two more
@@ -1724,10 +1770,6 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
     // stages enqueued after a record change the step's results: the block the record role wrote is stale (this call sets the flag again
     // further down when it carries the slab record itself)
     g->results_in_block = 0;
-    if (!g->ev_ready) {
-        for (int i = 0; i < 2 * IVX_N_TIMED_STAGES; ++i) IVX_HIP_CHECK(hipEventCreate(&g->ev[i]));
-        g->ev_ready = 1;
-    }
     if (!g->result_host) {
         IVX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->result_host), 64 * sizeof(uint32_t), hipHostMallocMapped));
         memset(g->result_host, 0, 64 * sizeof(uint32_t));
@@ -1759,28 +1801,61 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
         else if ((rc = ivx_launch_step_preset(g, need & ~fresh))) return rc;
         g->preset_fresh = ahead;
     }
-    // a slot's duration runs from the stop event of the slot enqueued just before it, when there is one
-    const uint32_t timing = ~g->stage_timing_off;  // slots with event records
-    hipEvent_t* last_stop = nullptr;
-#define T0(i)                                                      \
-    if (!((timing >> (i)) & 1u)) last_stop = nullptr;              \
-    else {                                                         \
-        if (last_stop) g->ev_start_ref[i] = last_stop;             \
-        else {                                                     \
-            IVX_HIP_CHECK(ivx_event_record(g->ev[2 * (i)], s));      \
-            g->ev_start_ref[i] = &g->ev[2 * (i)];                  \
-        }                                                          \
-    }
-#define T1(i)                                                      \
-    if ((timing >> (i)) & 1u) {                                    \
-        IVX_HIP_CHECK(ivx_event_record(g->ev[2 * (i) + 1], s));      \
-        last_stop = &g->ev[2 * (i) + 1];                           \
-        g->timed_mask |= 1u << (i);                                \
-    }
     // derive runs the chunk-local region labelling and the chunk moments in the same sweep when those stages are part of this call
     const uint32_t fused_parts = (stages & IVX_STAGE_DERIVE) ? (((stages & IVX_STAGE_REGIONS) ? IVX_PART_REGIONS : 0u) |
                                                                  ((stages & IVX_STAGE_INERTIA) ? IVX_PART_MOMENTS : 0u))
                                                               : 0u;
+    const uint32_t post = back ? stages & (IVX_STAGE_OCCUPIED | IVX_STAGE_REGIONS | IVX_STAGE_REMESH | IVX_STAGE_INERTIA) : 0u;
+    // (a call without the derive stage: stand-alone per-chunk kernels, which carry no stamp, run ahead of k_step_post1)
+    const bool standalone_first = ((post & IVX_STAGE_REGIONS) && !(fused_parts & IVX_PART_REGIONS) && !g->regions_labelled_locally) ||
+                                  ((post & IVX_STAGE_INERTIA) && !(fused_parts & IVX_PART_MOMENTS));
+    const uint32_t timing = ~g->stage_timing_off;  // timed slots
+    // stamps or events, for the whole call (see above); a call takes at most a word per slot and one more
+    const bool stamps = timing != 0u && !g_stage_timing_events && !g->stage_events_only && part == 3u && !slab_record && ivx_step_assign_fits(g) && !standalone_first &&
+                        !ivx_many_recording() && g->tick_used + IVX_N_TIMED_STAGES + 1u <= IVX_TICK_WORDS;
+    if (stamps && (rc = ensure_stage_ticks(g))) return rc;
+    if (timing != 0u && !stamps && (rc = ensure_stage_events(g))) return rc;
+    // events: a slot's duration runs from the stop event of the slot enqueued just before it, when there is one
+    hipEvent_t* last_stop = nullptr;
+    // stamps: the word the open slot starts at, and whether the slot armed it itself (else it is the closing word of the slot before, still pending)
+    int slot_word = -1;
+    bool slot_fresh = false;
+#define T0(i)                                                                            \
+    if (!((timing >> (i)) & 1u)) last_stop = nullptr;                                    \
+    else if (stamps) {                                                                   \
+        slot_fresh = g->tick_next == nullptr;                                            \
+        if (slot_fresh) {                                                                \
+            g->tick_host[g->tick_used] = 0ull;                                           \
+            g->tick_next = g->tick_dev + g->tick_used++;                                 \
+        }                                                                                \
+        slot_word = (int)(g->tick_next - g->tick_dev);                                   \
+    } else {                                                                             \
+        if (last_stop) g->ev_start_ref[i] = last_stop;                                   \
+        else {                                                                           \
+            IVX_HIP_CHECK(ivx_event_record(g->ev[2 * (i)], s));                          \
+            g->ev_start_ref[i] = &g->ev[2 * (i)];                                        \
+        }                                                                                \
+    }
+    // (stamps: a word that nobody took means the slot launched nothing — it reports 0, and a word it armed itself is given back)
+#define T1(i)                                                                            \
+    if ((timing >> (i)) & 1u) {                                                          \
+        if (stamps) {                                                                    \
+            g->stamp_mask |= 1u << (i), g->timed_mask &= ~(1u << (i));                   \
+            if (g->tick_next == g->tick_dev + slot_word) {                               \
+                g->tick_start_ref[i] = g->tick_end_ref[i] = -1;                          \
+                if (slot_fresh) g->tick_next = nullptr, --g->tick_used;                  \
+            } else {                                                                     \
+                g->tick_start_ref[i] = (int8_t)slot_word;                                \
+                g->tick_end_ref[i] = (int8_t)g->tick_used;                               \
+                g->tick_host[g->tick_used] = 0ull;                                       \
+                g->tick_next = g->tick_dev + g->tick_used++;                             \
+            }                                                                            \
+        } else {                                                                         \
+            IVX_HIP_CHECK(ivx_event_record(g->ev[2 * (i) + 1], s));                      \
+            last_stop = &g->ev[2 * (i) + 1];                                             \
+            g->timed_mask |= 1u << (i), g->stamp_mask &= ~(1u << (i));                   \
+        }                                                                                \
+    }
     if (front && (stages & IVX_STAGE_SAMPLE)) {
         T0(0);
         if ((rc = ivx_launch_sdf_sample(g, g->prog_nodes, g->prog_n, g->prog_stack, g->prog_shape, g->prog_center, g->prog_type, preset_in_sample, true,
@@ -1799,7 +1874,6 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
         T1(1);
         if (g->eval_len_pending == 1) g->eval_len_pending = 2;
     }
-    const uint32_t post = back ? stages & (IVX_STAGE_OCCUPIED | IVX_STAGE_REGIONS | IVX_STAGE_REMESH | IVX_STAGE_INERTIA) : 0u;
     if (post) {
         // stages that were not swept inside k_derive get their stand-alone per-chunk kernels first (a call without the derive stage)
         if ((stages & IVX_STAGE_REGIONS) && !(fused_parts & IVX_PART_REGIONS)) {
@@ -1906,6 +1980,15 @@ int ivx_grid_set_stage_timing(ivx_grid* g, uint32_t slot_mask) {
     return IVX_OK;
 }
 
+// Developer aid: the raw clock stamps behind the last collected step's stage_ms, start then end per slot (0: the slot was not stamped — not
+// timed, without a launch, or timed by events), and the clock's rate in kHz.
+int ivx_debug_stage_ticks(ivx_grid* g, unsigned long long ticks[2 * IVX_N_TIMED_STAGES], double* clock_khz) {
+    IVX_REQUIRE(g && ticks, IVX_ERR_INVALID, "ivx_debug_stage_ticks: null argument");
+    memcpy(ticks, g->tick_last, sizeof(g->tick_last));
+    if (clock_khz) *clock_khz = g->ctx->wall_clock_khz;
+    return IVX_OK;
+}
+
 // How long ivx_voxel_step_collect polls the doorbell before it falls back to hipStreamSynchronize (IVX_COLLECT_SPIN_US, default 2000;
 // 0 = never poll).
 static uint64_t collect_spin_ns() {
@@ -1991,6 +2074,12 @@ int ivx_voxel_step_collect(ivx_grid* g, ivx_step_result* out) {
             }
         }
     }
+    if (have_results && g->stamp_mask && g->tick_dev) {
+        // (stamped slots of a step that ended in ivx_step_record_enqueue instead of the gather — the slab protocol driven from outside the
+        // library: the stream has been waited for, the words are fetched and cleared here)
+        IVX_HIP_CHECK(ivx_memcpy_sync(g->tick_host, g->tick_dev, IVX_TICK_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        IVX_HIP_CHECK(hipMemset(g->tick_dev, 0, IVX_TICK_WORDS * sizeof(unsigned long long)));
+    }
     const uint32_t* sc = g->result_host;
     if (sc[31]) g->last_active = sc[31];
     if (g->eval_len_pending == 2 && g->samp_len) {  // a sample stage and a derive sweep behind it have run under the resident program
@@ -2041,12 +2130,23 @@ int ivx_voxel_step_collect(ivx_grid* g, ivx_step_result* out) {
     out->mesh = g->mesh_counts;
     for (int i = 0; i < IVX_N_TIMED_STAGES; ++i) {
         float ms = 0.0f;
-        if ((g->timed_mask >> i) & 1u)
+        g->tick_last[2 * i] = g->tick_last[2 * i + 1] = 0ull;
+        if ((g->stamp_mask >> i) & 1u) {  // clock stamps (step_enqueue): start to start, in ticks of the device's constant-rate clock
+            if (g->tick_start_ref[i] >= 0 && g->tick_end_ref[i] >= 0) {
+                const unsigned long long t0 = g->tick_host[g->tick_start_ref[i]], t1 = g->tick_host[g->tick_end_ref[i]];
+                g->tick_last[2 * i] = t0, g->tick_last[2 * i + 1] = t1;
+                if (t0 != 0ull && t1 > t0) ms = (float)((double)(t1 - t0) / g->ctx->wall_clock_khz);
+            }
+        } else if ((g->timed_mask >> i) & 1u) {
             if (hipEventElapsedTime(&ms, *g->ev_start_ref[i], g->ev[2 * i + 1]) != hipSuccess) ms = 0.0f;
+        }
         out->stage_ms[i] = ms;
     }
     g->pending_stages = 0;
     g->timed_mask = 0;
+    g->stamp_mask = 0;
+    g->tick_used = 0;
+    g->tick_next = nullptr;
     return IVX_OK;
 }
 

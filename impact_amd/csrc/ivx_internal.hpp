@@ -74,6 +74,7 @@ struct ivx_ctx {
     hipStream_t stream;
     bool own_stream;
     int n_cu;  // compute units of the device
+    double wall_clock_khz;  // rate of the constant clock the kernels' stage stamps read (wall_clock64), queried by ivx_init
     // pinned, device-visible scratch of the many-object calls that bring lists back (ivx_voxel_object_contacts_many: per-object totals, then the
     // contacts themselves, written by the kernels straight into host memory); grown on demand, freed by ivx_shutdown
     ivx_mapped pinned_scratch;
@@ -238,6 +239,17 @@ struct ivx_grid {
     hipEvent_t* ev_start_ref[IVX_N_TIMED_STAGES];  // the event a stage's duration starts from (the previous stage's stop when adjacent)
     uint32_t pending_stages;  // stages enqueued since the last collect
     uint32_t timed_mask;      // timed stages whose events were recorded since the last collect
+    // Stage stamps (step_enqueue, ivx_api.hip): on the step's fused path a timed slot is the distance between two clock words that block 0 of
+    // two launches writes on entry (ivx_stage_stamp), not a pair of event records. Words are handed out in stream order since the last collect.
+    unsigned long long* tick_dev;    // [IVX_TICK_WORDS] device words the launches stamp; k_step_gather copies them out and zeroes them
+    unsigned long long* tick_host;   // [IVX_TICK_WORDS] host-mapped copy, written by the gather ahead of the doorbell
+    unsigned long long* tick_host_dev;
+    unsigned long long* tick_next;   // the word the next stamping launch on this grid writes (ivx_take_tick), or null
+    uint32_t tick_used;              // words handed out since the last collect
+    int stage_events_only;           // this grid's timed slots always take event records (a slab of the slab protocol, ivx_slab_create)
+    uint32_t stamp_mask;             // timed slots whose words were armed since the last collect (their times come from tick_host)
+    int8_t tick_start_ref[IVX_N_TIMED_STAGES], tick_end_ref[IVX_N_TIMED_STAGES];  // word indices of a stamped slot's two ends (-1: the slot had no launch)
+    unsigned long long tick_last[2 * IVX_N_TIMED_STAGES];  // the last collect's raw stamps, start then end per slot (ivx_debug_stage_ticks)
     uint32_t* pairs_dev;      // [4 + 128 + 2 * IVX_MAX_FACE_PAIRS]: count, seen table, (own, neighbour) component pairs across the upper x face
     unsigned long long* record_head_copy;  // (in-process slab transport) where the record role also puts the record's first `record_head_words` words:
     uint32_t record_head_words;            // this slab's place in the gathered block — the gather of the heads is then no copy at all
@@ -290,6 +302,15 @@ struct ivx_mutual_pass {
 };
 
 void ivx_set_error(const char* fmt, ...);
+#define IVX_TICK_WORDS 32
+// The clock word the launch being made stamps: the grid's pending one, handed out once. A launch that is only recorded into a batch of
+// several objects (its twin does not stamp) leaves the word to the next launch made directly.
+static inline unsigned long long* ivx_take_tick(ivx_grid* g) {
+    if (!g->tick_next || ivx_many_recording()) return nullptr;
+    unsigned long long* t = g->tick_next;
+    g->tick_next = nullptr;
+    return t;
+}
 void ivx_cull_release(ivx_ctx* c);  // cull.hip (ivx_shutdown)
 void ivx_bvol_release(ivx_ctx* c);  // bvol.hip (ivx_shutdown)
 // the occupied ranges the object holds (ivx_grid::occ_ref), refreshed first when something invalidated them; IVX_ERR_STATE when the grid has none yet
@@ -398,6 +419,12 @@ __device__ __forceinline__ Total ivx_scan_rounds(const uint32_t* counts, uint32_
         __syncthreads();
     }
     return carry;
+}
+
+// Stage stamp: thread 0 of block 0 writes the constant-rate clock to `tick` on entry (null: no stamp) — one ordinary store by one lane.
+// The launches that can open or close a timed slot of a step carry the address in their arguments (step_enqueue, ivx_api.hip).
+__device__ __forceinline__ void ivx_stage_stamp(unsigned long long* tick) {
+    if (tick && blockIdx.x == 0u && threadIdx.x == 0u) *tick = wall_clock64();
 }
 
 // Workgroup timeline probes for the list-driven kernels: IVX_T(g, entry, slot) stores the 100 MHz wall clock of wave 0.

@@ -183,6 +183,7 @@ struct SampleParams {
     float shifted_center[3];
     uint32_t n_nodes, stack_size;
     uint32_t voxel_type;
+    unsigned long long* tick;  // stage stamp (ivx_stage_stamp): the clock word this launch writes on entry, or null
 };
 
 // Store policy of the evaluator's planes (device_common.hpp, store forms): 16 bytes per thread, whole 128-byte lines per wave, read by nobody
@@ -484,6 +485,7 @@ __device__ __forceinline__ uint2 super_skip_of(const ivx_sdf_processed_node* nod
 __global__ __launch_bounds__(64) void k_sdf_super(SampleParams p, const ivx_sdf_processed_node* __restrict__ nodes, uint32_t* __restrict__ super_mask,
                                                   uint2* __restrict__ super_skip, uint32_t words, uint32_t sy, uint32_t sz, ivx_roles::PresetArgs preset) {
     extern __shared__ uint32_t s_mask[];  // [words]
+    ivx_stage_stamp(p.tick);
     const uint32_t sb = blockIdx.x, lane = threadIdx.x;
     ivx_roles::role_preset(preset, sb * 64u + lane);  // the step's first kernel also presets the scratch words of the step's stages
     const uint32_t sk = sb % sz, sj = (sb / sz) % sy, si = sb / (sz * sy);
@@ -527,6 +529,7 @@ __global__ __launch_bounds__(PRE_T * PRE_WAVES) void k_sdf_prepass(SampleParams 
                                                        uint32_t sy, uint32_t sz, uint32_t n_sb, uint32_t fused_super, uint32_t ahead, ivx_roles::PresetArgs preset) {
     // (with `fused_super` this is the step's first kernel and hosts the presets of the later stages' scratch words; the sampler's own
     // counters are never among them: other blocks of this launch are adding to those)
+    ivx_stage_stamp(p.tick);
     ivx_roles::role_preset(preset, blockIdx.x * (uint32_t)(PRE_T * PRE_WAVES) + threadIdx.x);
     __shared__ uint32_t s_mask_all[SUPER_MAX_WORDS];  // fused_super: the super-block's far bit of every node of the program
     __shared__ uint2 s_skip[NODE_TILE];
@@ -1319,6 +1322,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_EVAL_WA
                                                   uint16_t* __restrict__ signs_out, uint8_t* __restrict__ kface_out,
                                                   const ivx_chunk_info* __restrict__ shadow, uint32_t n_chunks, ivx_roles::PresetArgs preset) {
     extern __shared__ float stack[];  // [stack_size][16][256]
+    ivx_stage_stamp(p.tick);
     constexpr bool TRIM = MODE == 1;
     const uint32_t tid = threadIdx.x;
     const uint32_t ti = tid >> 4, tj = tid & 15u;
@@ -1756,6 +1760,7 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
     }
     p.n_nodes = n_nodes;
     p.stack_size = stack_size;
+    p.tick = nullptr;  // (set for the stage's first launch alone, below)
 #ifdef IVX_WG_TRACE
     p.trace = reinterpret_cast<unsigned long long*>(g->chunk_moments);
 #endif
@@ -1835,9 +1840,11 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
                 g->samp_super_words = need;
             }
             super_skip = reinterpret_cast<uint2*>(g->samp_super + (((size_t)sx * sy * sz * words + 1u) & ~(size_t)1u));
+            p.tick = ivx_take_tick(g);
             IVX_KLAUNCH(k_sdf_super, dim3(sx * sy * sz), dim3(64), words * sizeof(uint32_t), g->ctx->stream, p, d_nodes, g->samp_super, super_skip, words, sy, sz,
                                ivx_preset_args(g, super_presets));
         }
+        p.tick = ivx_take_tick(g);
         if (noise)
             IVX_KLAUNCH(k_sdf_prepass<true>, dim3(sx * sy * sz), dim3(PRE_T * PRE_WAVES), 0, g->ctx->stream, p, d_nodes, g->samp_len, ops, eval_count, eval_list,
                                g->n_chunks, g->info, g->samp_super, super_skip, words, sy, sz, sx * sy * sz, fused_super ? 1u : 0u, 0u, ivx_preset_args(g, prepass_presets));
@@ -1870,6 +1877,7 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
             // one level + 64 words of scratch: 16 640 bytes = 13 LDS granules, eight workgroups per CU (the waves a SIMD holds)
             const uint32_t scratch_off = IVX_CHUNK_VOXELS;
             const ivx_chunk_info* sh = take_shadow();
+            p.tick = ivx_take_tick(g);
             IVX_KLAUNCH(k_sdf_eval<2>, dim3(fit(g->eval_len[0])), dim3(256), (size_t)(scratch_off + 64u) * sizeof(float), g->ctx->stream, p, eval_count + 0, list0,
                                eval_count + 3, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
                                sh, g->n_chunks, sh ? first_presets : no_presets);
@@ -1878,6 +1886,7 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
             // two levels, the second one 15 rows long + 64 words of scratch: 32 000 bytes = 25 LDS granules, five workgroups per CU
             const uint32_t scratch_off = IVX_CHUNK_VOXELS + 15u * 256u;
             const ivx_chunk_info* sh = take_shadow();
+            p.tick = ivx_take_tick(g);
             if (merge01)
                 IVX_KLAUNCH(k_sdf_eval<1>, dim3(fit(g->eval_len[0] + g->eval_len[1])), dim3(256), (size_t)(scratch_off + 64u) * sizeof(float), g->ctx->stream, p, eval_count + 0, list0,
                                    eval_count + 3, eval_count + 1, list1, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
@@ -1893,6 +1902,7 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
             const uint32_t lv = stack_size ? stack_size : 1u;
             const uint32_t scratch_off = lv * IVX_CHUNK_VOXELS - 16u;
             const ivx_chunk_info* sh = take_shadow();
+            p.tick = ivx_take_tick(g);
             if (noise)
                 IVX_KLAUNCH((k_sdf_eval<0, true>), dim3(fit(g->eval_len[2])), dim3(256), (size_t)lv * IVX_CHUNK_VOXELS * sizeof(float), g->ctx->stream, p, eval_count + 2,
                                    eval_list + 2 * (size_t)g->n_chunks, nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info,
@@ -1956,6 +1966,7 @@ int ivx_sampler_launch_ahead(ivx_grid* g, bool behind_stream) {
     }
     p.n_nodes = g->prog_n;
     p.stack_size = g->prog_stack;
+    p.tick = nullptr;  // (a launch on the second stream is no part of a timed slot)
 #ifdef IVX_WG_TRACE
     p.trace = reinterpret_cast<unsigned long long*>(g->chunk_moments);
 #endif

@@ -95,6 +95,12 @@ struct StepArgs {
     const uint32_t* copy_src;
     uint32_t* copy_dst;
     uint32_t copy_words;
+    // stage stamps (ivx_stage_stamp): the clock word this launch writes on entry, or null; k_step_gather also copies the grid's `n_ticks` words
+    // to host-mapped memory ahead of the doorbell and zeroes them for the next step
+    uint32_t n_ticks;
+    unsigned long long* tick;
+    unsigned long long* ticks_dev;
+    unsigned long long* ticks_host;
 };
 
 __device__ __forceinline__ sn::SnParams sn_params(const StepArgs& a) {
@@ -159,7 +165,10 @@ __device__ __forceinline__ void step_post1_body(const StepArgs& a, uint32_t b, u
 #ifndef IVX_POST1_WAVES
 #define IVX_POST1_WAVES 6
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_POST1_WAVES, 8))) void k_step_post1(StepArgs a) { step_post1_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_POST1_WAVES, 8))) void k_step_post1(StepArgs a) {
+    ivx_stage_stamp(a.tick);
+    step_post1_body(a, blockIdx.x, gridDim.x);
+}
 IVX_MANY_TWIN(k_step_post1_many, StepArgs, step_post1_body, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_POST1_WAVES, 8))))
 
 // roles: 5 (the launch's FIRST blocks) exact numbering of the multi-region chunks, 0 region merge of multi-region chunks, 1 mesher scan,
@@ -223,7 +232,10 @@ __device__ __forceinline__ void step_post2_body(const StepArgs& a, uint32_t b, u
         role_face_pairs(b, a.g, a.fp_side, a.labels, a.rcompid, a.fp_nbr, a.fp_count, a.fp_pairs, a.fp_cap, a.fp_seen, s_seen);
     }
 }
-__global__ __launch_bounds__(256) void k_step_post2(StepArgs a) { step_post2_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void k_step_post2(StepArgs a) {
+    ivx_stage_stamp(a.tick);
+    step_post2_body(a, blockIdx.x, gridDim.x);
+}
 IVX_MANY_TWIN(k_step_post2_many, StepArgs, step_post2_body, __launch_bounds__(256))
 
 // roles: 0 flatten the region forest, 1 mesher emit, 2 the slab protocol's record
@@ -251,7 +263,10 @@ __device__ __forceinline__ void step_emit_body(const StepArgs& a, uint32_t b, ui
     }
 }
 template <bool ST>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST ? IVX_EMIT_ST_PER_CU : 4, ST ? IVX_EMIT_ST_PER_CU : 4))) void k_step_emit(StepArgs a) { step_emit_body<ST>(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST ? IVX_EMIT_ST_PER_CU : 4, ST ? IVX_EMIT_ST_PER_CU : 4))) void k_step_emit(StepArgs a) {
+    ivx_stage_stamp(a.tick);
+    step_emit_body<ST>(a, blockIdx.x, gridDim.x);
+}
 IVX_MANY_TWIN(k_step_emit_many, StepArgs, step_emit_body<false>, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
 
 // roles: 0 component ids, 1 the mesher's general pass over the chunks the main pass (k_step_emit) handed on — the launch after the main pass
@@ -264,11 +279,23 @@ __device__ __forceinline__ void step_assign_body(const StepArgs& a, uint32_t b, 
     sn::role_sn_emit_general<false>(b - a.nb[0], a.nb[1], sn_params(a), a.positions, a.normals, a.indices, a.imats, a.vmats, a.submeshes,
                                     a.offsets + 2 * (size_t)a.n_chunks + 2, a.emit_items, a.vcap, a.icap, a.scap, nullptr, a.hard_count, a.hard_list);
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_step_assign(StepArgs a) { step_assign_body(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_step_assign(StepArgs a) {
+    ivx_stage_stamp(a.tick);
+    step_assign_body(a, blockIdx.x, gridDim.x);
+}
 IVX_MANY_TWIN(k_step_assign_many, StepArgs, step_assign_body, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
 
 // the results as a launch of their own (one block), ordered after everything enqueued so far
 __device__ __forceinline__ void step_gather_body(const StepArgs& a, uint32_t, uint32_t) {
+    // (stage stamps: this launch closes the call's last timed slot; its own word travels in a register, the others were written by earlier launches)
+    if (a.ticks_dev) {
+        const unsigned long long now = wall_clock64();
+        if (threadIdx.x < a.n_ticks) {
+            unsigned long long* w = a.ticks_dev + threadIdx.x;
+            a.ticks_host[threadIdx.x] = w == a.tick ? now : *w;
+            *w = 0ull;
+        }
+    }
     role_result_gather(a.rscalar, a.offsets + 2 * (size_t)a.n_chunks, a.moments_out, a.work_count, a.eval_count, a.host_block, false, 0u);
     // (the edit path's small results, into pinned host memory: eight loads in flight per lane — one wave copying word by word spent 6 us on 3 KB)
     for (uint32_t i0 = threadIdx.x; i0 < a.copy_words; i0 += 512u) {
@@ -394,6 +421,7 @@ int ivx_launch_step_post1(ivx_grid* g, uint32_t stages) {
             ai.nb[1] = ai.nb[3] = ai.nb[4] = ai.nb[5] = 0;
             ai.x_part = IVX_XPART_INTERIOR;
             a.x_part = IVX_XPART_FACES;
+            ai.tick = ivx_take_tick(g);
             if (!ivx_many_try(g->ctx, g, IVX_MK_POST1, ai.nb[0], ai)) IVX_KLAUNCH(k_step_post1, dim3(ai.nb[0]), dim3(256), 0, g->ctx->stream, ai);
         }
         (void)ivx_many_break();
@@ -403,6 +431,7 @@ int ivx_launch_step_post1(ivx_grid* g, uint32_t stages) {
     }
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[3] + a.nb[4] + a.nb[5];
     if (total == 0) return IVX_OK;
+    a.tick = ivx_take_tick(g);
     if (!ivx_many_try(g->ctx, g, IVX_MK_POST1, total, a)) IVX_KLAUNCH(k_step_post1, dim3(total), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -446,6 +475,7 @@ int ivx_launch_step_post2(ivx_grid* g, uint32_t stages, const uint16_t* face_pai
     if (stages & IVX_STAGE_OCCUPIED) a.nb[3] = 1;
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[2] + a.nb[3] + a.nb[4] + a.nb[5];
     if (total == 0) return IVX_OK;
+    a.tick = ivx_take_tick(g);
     if (!ivx_many_try(g->ctx, g, IVX_MK_POST2, total, a)) IVX_KLAUNCH(k_step_post2, dim3(total), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -472,6 +502,7 @@ int ivx_launch_step_emit(ivx_grid* g, uint32_t stages, bool general_in_assign, v
     }
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[2];
     if (total == 0) return IVX_OK;
+    a.tick = ivx_take_tick(g);
     if (single_type) IVX_KLAUNCH(k_step_emit<true>, dim3(total), dim3(256), 0, g->ctx->stream, a);
     else if (!ivx_many_try(g->ctx, g, IVX_MK_EMIT, total, a)) IVX_KLAUNCH(k_step_emit<false>, dim3(total), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
@@ -489,6 +520,7 @@ int ivx_launch_step_assign(ivx_grid* g, bool with_mesher_general, bool with_ccl)
     a.nb[0] = with_ccl ? (g->n_chunks + 255u) / 256u : 0u;
     a.nb[1] = with_mesher_general ? sn::ivx_emit_general_grid(g, g->n_chunks) : 0u;
     if (a.nb[0] + a.nb[1] == 0u) return IVX_OK;
+    a.tick = ivx_take_tick(g);
     if (!ivx_many_try(g->ctx, g, IVX_MK_ASSIGN, a.nb[0] + a.nb[1], a)) IVX_KLAUNCH(k_step_assign, dim3(a.nb[0] + a.nb[1]), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -499,6 +531,11 @@ int ivx_launch_step_gather(ivx_grid* g) {
     a.seq = ++g->result_seq;
     a.copy_src = g->gather_copy_src, a.copy_dst = g->gather_copy_dst, a.copy_words = g->gather_copy_words;  // (consumed by this launch)
     g->gather_copy_words = 0;
+    if (g->tick_used) {  // (stamped slots since the last collect: their words go out with the results; a word still pending is this launch's)
+        a.ticks_dev = g->tick_dev, a.ticks_host = g->tick_host_dev, a.n_ticks = g->tick_used;
+        a.tick = g->tick_next;
+        g->tick_next = nullptr;
+    }
     if (!ivx_many_try(g->ctx, g, IVX_MK_GATHER, 1u, a)) IVX_KLAUNCH(k_step_gather, dim3(1), dim3(64), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;

@@ -245,8 +245,15 @@ class VoxelObject:
         check(capi.lib().ivx_grid_set_sample_ahead(self.h, 1 if on else 0))
 
     def set_stage_timing(self, slot_mask: int = 0xFFFFFFFF):
-        """which timed slots of a step get event records (`ivx_grid_set_stage_timing`): all by default, 0 = none"""
+        """which timed slots of a step are timed (`ivx_grid_set_stage_timing`): all by default, 0 = none"""
         check(capi.lib().ivx_grid_set_stage_timing(self.h, int(slot_mask) & 0xFFFFFFFF))
+
+    def stage_ticks(self):
+        """(`ivx_debug_stage_ticks`) the raw clock stamps of the last collected step, [slot, (start, end)], 0 = not stamped; the clock's rate in kHz"""
+        out = np.zeros((capi.N_TIMED_STAGES, 2), dtype=np.uint64)
+        khz = np.zeros(1, dtype=np.float64)
+        check(capi.lib().ivx_debug_stage_ticks(self.h, ptr(out), ptr(khz)))
+        return out, float(khz[0])
 
     def stage_counters(self):
         out = np.zeros(4, dtype=np.uint32)

@@ -381,9 +381,20 @@ int ivx_voxel_step(ivx_grid*, uint32_t stages, ivx_step_result* out);
  * grows them and repeats the emit pass. */
 int ivx_voxel_step_enqueue(ivx_grid*, uint32_t stages);
 int ivx_voxel_step_collect(ivx_grid*, ivx_step_result* out);
-/* Stage timing (ivx_step_result::stage_ms) costs event records on the stream (about 2 us each on the GPU's queue): slot_mask bit i = time
- * slot i. Default: every slot. 0 turns timing off (stage_ms reads 0); a single bit times one slot with two records per step. */
+/* Stage timing (ivx_step_result::stage_ms): slot_mask bit i = time slot i. Default: every slot. 0 turns timing off (stage_ms reads 0).
+ * A whole step on the fused path (ivx_voxel_step / _enqueue outside the slab protocol, on a grid of at most 524 288 chunks, with the derive
+ * stage in the call or nothing left for the stand-alone per-chunk kernels) costs the queue nothing for it: the first workgroup of the
+ * slot's first launch and of the first launch enqueued behind the slot write the device's constant-rate clock, and stage_ms[i] is the
+ * distance of the two — START TO START, the launch boundary behind the slot included; the last slot of a call ends where the next launch
+ * of this grid starts, which is the step's result gather unless another call was enqueued first (a launch of another object in between
+ * falls into that boundary). A slot without a launch reads 0. Every other path — the slab protocol's phases, calls enqueued in parts,
+ * larger grids, calls that run the stand-alone region / moment kernels — brackets a slot with two event records on the stream, about
+ * 2-3 us each on the GPU's queue, and stage_ms[i] is the distance of those (the boundary in FRONT of the slot included). One call never
+ * mixes the two. IVX_STAGE_TIMING_EVENTS=1 in the environment (read when the library is loaded) forces the event records everywhere. */
 int ivx_grid_set_stage_timing(ivx_grid*, uint32_t slot_mask);
+/* Developer aid: the raw clock stamps behind the last collected step's stage_ms, ticks[2 * i] = start and ticks[2 * i + 1] = end of slot i
+ * (0: not stamped — not timed, no launch, or timed by events); *clock_khz (may be null) = the clock's rate. */
+int ivx_debug_stage_ticks(ivx_grid*, unsigned long long ticks[2 * IVX_N_TIMED_STAGES], double* clock_khz);
 /* Sample-ahead, for callers that sample the resident program step after step (the voxel generator of a streamed or re-generated object,
  * generation.rs:293-371 per chunk — the bench's headline step): with `on`, a sample stage also enqueues the NEXT sample stage's interval
  * pre-pass — it reads nothing but the program and the grid's geometry — on the context's second stream behind its own evaluator, and the next

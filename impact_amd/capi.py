@@ -212,6 +212,11 @@ assert COLLIDABLE_DTYPE.itemsize == 64
 MOTION_DRIVER_DTYPE = np.dtype([("kind", "<u4"), ("body", "<u4"), ("p", "<f4", (14,))])
 MD_CIRCULAR, MD_CONSTANT_ACCELERATION, MD_HARMONIC, MD_ORBITAL, MD_CONSTANT_ROTATION = 0, 1, 2, 3, 4
 assert MOTION_DRIVER_DTYPE.itemsize == 64
+# force generators of dynamic bodies (csrc/forces.hip): `ivx_force_generator`; `body_b` is the second body of a spring
+FORCE_GENERATOR_DTYPE = np.dtype([("kind", "<u4"), ("body", "<u4"), ("body_b", "<u4"), ("p", "<f4", (13,))])
+(FG_CONSTANT_ACCELERATION, FG_LOCAL_FORCE, FG_SPRING_DYNAMIC_DYNAMIC, FG_SPRING_DYNAMIC_KINEMATIC, FG_ALIGNMENT_FIXED,
+ FG_ALIGNMENT_GRAVITY) = 0, 1, 2, 3, 4, 5
+assert FORCE_GENERATOR_DTYPE.itemsize == 64
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -243,6 +248,7 @@ EXPORTED_SYMBOLS = [
     "ivx_bv_device_ptr",
     "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
     "ivx_world_set_motion_drivers", "ivx_world_set_time", "ivx_world_time", "ivx_world_apply_motion", "ivx_md_eval", "ivx_md_apply_host",
+    "ivx_world_set_force_generators", "ivx_world_set_dynamic_gravity", "ivx_world_apply_forces", "ivx_world_gravity_loads", "ivx_fg_apply_host",
 ]
 
 
@@ -275,6 +281,7 @@ def extra_struct_sizes():
         "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
         "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128),
         "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
+        "ivx_force_generator": (FORCE_GENERATOR_DTYPE, 64),
     }
 
 
@@ -475,6 +482,11 @@ def lib():
         "ivx_world_apply_motion": (i32, [vp, f32]),
         "ivx_md_eval": (i32, [vp, f32, vp]),
         "ivx_md_apply_host": (i32, [vp, sz, vp, sz, f32]),
+        "ivx_world_set_force_generators": (i32, [vp, vp, sz]),
+        "ivx_world_set_dynamic_gravity": (i32, [vp, vp, sz, f32]),
+        "ivx_world_apply_forces": (i32, [vp]),
+        "ivx_world_gravity_loads": (i32, [vp, vp, sz]),
+        "ivx_fg_apply_host": (i32, [vp, sz, vp, sz, f32, vp, sz, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -624,6 +624,7 @@ void ivx_world_destroy(ivx_world* w) {
     }
     ivx_cw_release(w);
     ivx_md_release(w);
+    ivx_fg_release(w);
     if (w->stage_sched) (void)hipHostFree(w->stage_sched);  // pinned staging of the general path's uploads
     if (w->stage_sched_ev_ready) (void)hipEventDestroy(w->stage_sched_ev);
     if (w->stage_contacts) (void)hipHostFree(w->stage_contacts);  // pinned staging of the set_contacts fast path
@@ -1050,25 +1051,33 @@ static int world_step_enqueue(ivx_world* w, float dt, bool timed) {
     return IVX_OK;
 }
 
-// The tail of perform_physics_step (lib.rs:86-100): the clock moves on (new_simulation_time, host-side only) and the motion drivers, if the
-// world has a set, are applied at the new time — one launch behind the advance of configurations. (stage_ms does not cover it.)
+// The tail of perform_physics_step (lib.rs:86-108): the clock moves on (new_simulation_time, host-side only) and the motion drivers, if the
+// world has a set, are applied at the new time — one launch behind the advance of configurations; then the force generators and the gravity
+// field, if the world has either, so that a spring sees a driven kinematic body at the new time. (stage_ms does not cover the tail.)
 static int world_step_finish(ivx_world* w, float dt, const char* who) {
     w->time = w->time + dt;
-    return w->md_state ? ivx_launch_motion_apply(w, w->time, who) : IVX_OK;
+    if (w->md_state)
+        if (int rc = ivx_launch_motion_apply(w, w->time, who)) return rc;
+    return w->fg_state ? ivx_launch_forces_apply(w, who) : IVX_OK;
+}
+// what the tail refuses, asked before the step launches anything
+static int world_step_tail_ready(ivx_world* w, const char* who) {
+    if (w->md_state)
+        if (int rc = ivx_motion_ready(w, who)) return rc;
+    return w->fg_state ? ivx_forces_ready(w, who) : IVX_OK;
 }
 
 int ivx_world_step_enqueue(ivx_world* w, float dt) {
     IVX_REQUIRE(w, IVX_ERR_INVALID, "ivx_world_step_enqueue: null world");
     if (int rc = ivx_world_check_solve(w, "ivx_world_step_enqueue")) return rc;  // (an earlier step's flag, if it is up by now)
-    if (w->md_state)
-        if (int rc = ivx_motion_ready(w, "ivx_world_step_enqueue")) return rc;
+    if (int rc = world_step_tail_ready(w, "ivx_world_step_enqueue")) return rc;
     if (int rc = world_step_enqueue(w, dt, false)) return rc;
     return world_step_finish(w, dt, "ivx_world_step_enqueue");
 }
 
 int ivx_world_step(ivx_world* w, float dt, ivx_physics_result* out) {
     IVX_REQUIRE(w, IVX_ERR_INVALID, "ivx_world_step: null world");
-    int rc = w->md_state ? ivx_motion_ready(w, "ivx_world_step") : IVX_OK;
+    int rc = world_step_tail_ready(w, "ivx_world_step");
     if (rc) return rc;
     if ((rc = world_step_enqueue(w, dt, out != nullptr))) return rc;
     if ((rc = world_step_finish(w, dt, "ivx_world_step"))) return rc;

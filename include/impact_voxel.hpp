@@ -523,6 +523,92 @@ static_assert(sizeof(CircularTrajectory) == 40 && sizeof(ConstantAccelerationTra
                   sizeof(OrbitalTrajectory) == 44 && sizeof(ConstantRotation) == 36 && sizeof(ivx_motion_driver) == 64,
               "motion driver layouts");
 
+// ---- force generators of dynamic bodies (impact_physics/src/force/): the reference's setup structs ------------------------------------------
+// `record(dynamic_body_index, ..)` gives the record ivx_world_set_force_generators takes. Entity ids and AnchorManager bookkeeping stay with the
+// caller: a body is given by its index, an anchor as that index plus the body-space point.
+namespace detail {
+inline ivx_force_generator force_generator(uint32_t kind, uint32_t body, uint32_t body_b) {
+    ivx_force_generator g{};
+    g.kind = kind, g.body = body, g.body_b = body_b;
+    return g;
+}
+inline void put3(float* p, const float v[3]) { p[0] = v[0], p[1] = v[1], p[2] = v[2]; }
+}  // namespace detail
+struct ConstantAcceleration {  // constant_acceleration.rs:52-103
+    float acceleration[3];
+    static constexpr float EARTH_DOWNWARD_ACCELERATION = 9.81f;
+    static ConstantAcceleration downward(float acceleration) { return ConstantAcceleration{{0.0f, -acceleration, 0.0f}}; }
+    static ConstantAcceleration earth() { return downward(EARTH_DOWNWARD_ACCELERATION); }
+    ivx_force_generator record(uint32_t body) const {
+        ivx_force_generator g = detail::force_generator(IVX_FG_CONSTANT_ACCELERATION, body, 0);
+        detail::put3(g.p, acceleration);
+        return g;
+    }
+};
+struct LocalForce {  // local_force.rs:29-34
+    float force[3];  // body frame
+    float point[3];  // body frame
+    ivx_force_generator record(uint32_t body) const {
+        ivx_force_generator g = detail::force_generator(IVX_FG_LOCAL_FORCE, body, 0);
+        detail::put3(g.p, force), detail::put3(g.p + 3, point);
+        return g;
+    }
+};
+struct Spring {  // spring_force.rs:125-138, 285-313
+    float stiffness, damping, rest_length, slack_length;
+    static Spring standard(float stiffness, float damping, float rest_length) { return Spring{stiffness, damping, rest_length, 0.0f}; }
+    static Spring elastic_band(float stiffness, float damping, float slack_length) { return Spring{stiffness, damping, slack_length, slack_length}; }
+};
+namespace detail {
+inline ivx_force_generator spring_generator(uint32_t kind, uint32_t body_1, uint32_t body_2, const float point_1[3], const float point_2[3], const Spring& s) {
+    ivx_force_generator g = force_generator(kind, body_1, body_2);
+    put3(g.p, point_1), put3(g.p + 3, point_2);
+    g.p[6] = s.stiffness, g.p[7] = s.damping, g.p[8] = s.rest_length, g.p[9] = s.slack_length;
+    return g;
+}
+}  // namespace detail
+struct DynamicDynamicSpringForceProperties {  // spring_force.rs:83-102 (the two entities are the two body indices of record())
+    float attachment_point_1[3], attachment_point_2[3];  // each in its body's frame
+    Spring spring;
+    ivx_force_generator record(uint32_t dynamic_body_1, uint32_t dynamic_body_2) const {
+        return detail::spring_generator(IVX_FG_SPRING_DYNAMIC_DYNAMIC, dynamic_body_1, dynamic_body_2, attachment_point_1, attachment_point_2, spring);
+    }
+};
+struct DynamicKinematicSpringForceProperties {  // spring_force.rs:104-123; the second body is kinematic (its index WITHOUT IVX_KINEMATIC_BODY)
+    float attachment_point_1[3], attachment_point_2[3];
+    Spring spring;
+    ivx_force_generator record(uint32_t dynamic_body_1, uint32_t kinematic_body_2) const {
+        return detail::spring_generator(IVX_FG_SPRING_DYNAMIC_KINEMATIC, dynamic_body_1, kinematic_body_2, attachment_point_1, attachment_point_2, spring);
+    }
+};
+struct FixedDirectionAlignmentTorque {  // alignment_torque.rs:64-84
+    float axis_to_align[3];        // body frame, unit
+    float alignment_direction[3];  // world, unit
+    float settling_time, spin_damping, precession_damping;
+    ivx_force_generator record(uint32_t body) const {
+        ivx_force_generator g = detail::force_generator(IVX_FG_ALIGNMENT_FIXED, body, 0);
+        detail::put3(g.p, axis_to_align), detail::put3(g.p + 3, alignment_direction);
+        g.p[6] = settling_time, g.p[7] = spin_damping, g.p[8] = precession_damping;
+        return g;
+    }
+};
+struct GravityAlignmentTorque {  // alignment_torque.rs:86-105: towards the gravitational force on the body (it must be in the gravity field)
+    float axis_to_align[3];
+    float settling_time, spin_damping, precession_damping;
+    ivx_force_generator record(uint32_t body) const {
+        ivx_force_generator g = detail::force_generator(IVX_FG_ALIGNMENT_GRAVITY, body, 0);
+        detail::put3(g.p, axis_to_align);
+        g.p[6] = settling_time, g.p[7] = spin_damping, g.p[8] = precession_damping;
+        return g;
+    }
+};
+struct DynamicGravityConfig {  // dynamic_gravity.rs:36-46, 170-176
+    float gravitational_constant = 1.0f;
+};
+static_assert(sizeof(ivx_force_generator) == 64 && sizeof(Spring) == 16 && sizeof(LocalForce) == 24 && sizeof(FixedDirectionAlignmentTorque) == 36 &&
+                  sizeof(GravityAlignmentTorque) == 24,
+              "force generator layouts");
+
 // ---- rigid bodies + constraint solver (impact_physics/src/lib.rs:31-110) --------------------------------------------------------------
 class PhysicsWorld {
 public:
@@ -562,10 +648,23 @@ public:
         check(ivx_world_time(w_, &t));
         return t;
     }
+    // ForceGeneratorManager: each set replaces the one before (empty: none); with either installed every step ends with the force stage, which
+    // resets the totals of all dynamic bodies first (apply_forces primes them before the first step)
+    void set_force_generators(const std::vector<ivx_force_generator>& generators) { check(ivx_world_set_force_generators(w_, generators.data(), generators.size())); }
+    void set_dynamic_gravity(const std::vector<uint32_t>& dynamic_bodies, const DynamicGravityConfig& config = {}) {
+        n_gravity_ = dynamic_bodies.size();
+        check(ivx_world_set_dynamic_gravity(w_, dynamic_bodies.data(), dynamic_bodies.size(), config.gravitational_constant));
+    }
+    void apply_forces() { check(ivx_world_apply_forces(w_)); }
+    std::vector<float> gravity_loads() {  // force and torque, 6 floats per field member in field order
+        std::vector<float> loads(6 * n_gravity_);
+        check(ivx_world_gravity_loads(w_, loads.data(), n_gravity_));
+        return loads;
+    }
 
 private:
     ivx_world* w_ = nullptr;
-    size_t n_dyn_ = 0, n_kin_ = 0;
+    size_t n_dyn_ = 0, n_kin_ = 0, n_gravity_ = 0;
 };
 
 }  // namespace impact_voxel

@@ -744,10 +744,12 @@ int ivx_world_set_contacts(ivx_world*, const ivx_contact*, size_t n, size_t* n_p
  * velocities are written back after the solve — which is all this entry point makes happen. Stays in force until replaced; call it after
  * ivx_world_set_bodies. */
 int ivx_world_set_spherical_joints(ivx_world*, const uint32_t* body_pairs, size_t n_joints);
-/* perform_physics_step (src/lib.rs:31-110) without force generators: prepare constraints ->
+/* perform_physics_step (src/lib.rs:31-110): prepare constraints ->
  * advance momenta -> synchronise velocities, warm start, n_iterations sweeps, positional correction,
  * write back -> advance configurations -> motion drivers at the new simulation time (when a set is installed,
- * ivx_world_set_motion_drivers). The stages are also exposed one by one. */
+ * ivx_world_set_motion_drivers) -> force generators and dynamic gravity (when either is installed,
+ * ivx_world_set_force_generators / ivx_world_set_dynamic_gravity; detailed drag is not part of that stage).
+ * A world with neither keeps the total_force / total_torque the host gave its bodies. The stages are also exposed one by one. */
 int ivx_world_step(ivx_world*, float dt, ivx_physics_result* out);
 /* the same step, only enqueued on the context's stream (no wait, no result): lets the rigid-body step of a frame run
  * behind the voxel step of the same frame with a single wait for both (ivx_voxel_step_collect / ivx_synchronize);
@@ -1218,6 +1220,92 @@ int ivx_world_apply_motion(ivx_world*, float time);
 int ivx_md_eval(const ivx_motion_driver*, float time, float out[10]);
 /* The composition above over host arrays, the code the kernel runs (tests). Validates like ivx_world_set_motion_drivers against n_kinematic. */
 int ivx_md_apply_host(const ivx_motion_driver*, size_t n, ivx_kinematic_body* bodies, size_t n_kinematic, float time);
+
+/* ---- force generators and dynamic gravity (impact_physics/src/force.rs and the files under force/; csrc/forces.hip) ---------------------------
+ * ForceGeneratorManager::apply_forces_and_torques (force.rs:130-159) as the last stage of the step. One record per generator, 64 bytes: `body`
+ * indexes the world's dynamic bodies; `body_b` is the second body of a spring — a dynamic index, or for the dynamic-kinematic spring a
+ * kinematic index WITHOUT the IVX_KINEMATIC_BODY bit — and is ignored by the other kinds. An anchor is given resolved, as body index plus
+ * body-space point; AnchorManager stays the host's business. `p`:
+ *   IVX_FG_CONSTANT_ACCELERATION    constant_acceleration.rs:96-102   p[0..2] acceleration (world)
+ *   IVX_FG_LOCAL_FORCE              local_force.rs:37-62              p[0..2] force (body frame), p[3..5] point (body frame)
+ *   IVX_FG_SPRING_DYNAMIC_DYNAMIC   spring_force.rs:140-189, 317-331  p[0..2] attachment point 1, p[3..5] attachment point 2 (each in its body's frame),
+ *                                                                     p[6] stiffness, p[7] damping, p[8] rest_length, p[9] slack_length
+ *   IVX_FG_SPRING_DYNAMIC_KINEMATIC spring_force.rs:191-243           as above; body_b kinematic
+ *   IVX_FG_ALIGNMENT_FIXED          alignment_torque.rs:107-241       p[0..2] axis_to_align (body frame, unit), p[3..5] alignment_direction (world, unit),
+ *                                                                     p[6] settling_time, p[7] spin_damping, p[8] precession_damping
+ *   IVX_FG_ALIGNMENT_GRAVITY        the same, AlignmentDirection::GravityForce   p[0..2] axis_to_align, p[6..8] as above
+ * The rest of `p` is ignored.
+ *
+ * Arithmetic: float32, uncontracted, in the reference's operation order (EPSILON = f32::EPSILON; dot(a, b) = (ax bx + ay by) + az bz;
+ * rotate(q, v) is glam's mul_vec3a; M v = (c0 vx + c1 vy) + c2 vz over the columns; rotated(M, q) = (R M) R^T with R = Mat3A::from_quat(q);
+ * v / s on a Vec3A divides each component, on impact_math's vectors it multiplies by 1 / s — noted as `*recip` below):
+ *   angular velocity of a dynamic body:  w0 = rotated(inv_inertia, q) L;  |w0|^2 > EPSILON^2 ? (w0 / |w0|) * |w0| : 0
+ *   apply_force(f, at):  total_force += f;  total_torque += (at - position) x f
+ *   constant acceleration    total_force += acceleration * mass
+ *   local force              apply_force(rotate(q, force), position + rotate(q, point))
+ *   spring (both kinds)      a1 = position_1 + rotate(q_1, point_1);  a2 likewise;  d = a2 - a1;  no force unless dot(d, d) > EPSILON^2
+ *       length = sqrt(dot(d, d));  dir = d / length
+ *       rate = 0 when |damping| <= EPSILON, else dot(v2, dir) - dot(v1, dir) with v = velocity + w x (a - position): for a dynamic body
+ *       velocity = momentum *recip mass and w as above, for a kinematic body its velocity and axis * speed
+ *       scalar = length <= slack_length ? 0 : (-stiffness) * (length - rest_length) + (-damping) * rate;  force_on_2 = scalar * dir
+ *       body 1: apply_force(-force_on_2, a1);  body 2, if dynamic: apply_force(force_on_2, a2)
+ *   gravity pair (i the lower rank; dynamic_gravity.rs:188-231, EPS = 1e-6; I = rotated(inertia, q))    r = p_j - p_i;  r2 = dot(r, r);  r1 = sqrt(r2)
+ *       r3 = r2 * r1;  r5 = r3 * r2;  mono = (((G * m_i) * m_j) / (r3 + EPS)) * r;  qs = (1.5 * G) / (r5 + EPS)
+ *       a = m_j * (I_i r);  b = m_i * (I_j r);  s = a + b;  trace = (xx + yy) + zz
+ *       quad = qs * (((m_j * trace_i + m_i * trace_j) - (5 * dot(r, s)) / (r2 + EPS)) * r + 2 * s);  force_i = mono + quad
+ *       torque_i = (2 * qs) * (r x a);  torque_j = (2 * qs) * (r x b)
+ *       load_i.force += force_i, load_i.torque += torque_i;  load_j.force -= force_i, load_j.torque += torque_j
+ *   alignment torque    direction = alignment_direction, or for the gravity kind load.force *recip |load.force| — nothing when the body is not in
+ *       the field or when dot(load.force, load.force) <= 1e-9^2
+ *       axis = rotate(q, axis_to_align);  c = direction x axis;  rot = dot(c, c) > 1e-8^2 ? c / sqrt(dot(c, c)) : orthogonal(axis), glam's
+ *       any_orthonormal_vector: sign = copysign(1, z); a = -1 / (sign + z); (x * y * a, sign + y * y * a, -y)
+ *       s_rot = dot(w, rot);  w_rot = s_rot * rot;  s_ax = dot(w, axis);  w_ax = s_ax * axis;  w_prec = (w - w_rot) - w_ax
+ *       angle = acos(clamp(dot(direction, axis), -1, 1)), the double-precision function rounded once
+ *       tc = 0.25 * settling_time;  nf = 1 / tc;  acc = (-(nf * nf)) * angle - (2 * nf) * s_rot
+ *       alpha = (acc * rot - (spin_damping / settling_time) * w_ax) - (precession_damping / settling_time) * w_prec
+ *       total_torque += rotated(inertia, q) alpha + w x L
+ *
+ * Composition, the same code on the device and in ivx_fg_apply_host:
+ *   - total_force and total_torque of ALL dynamic bodies are reset to +0.0;
+ *   - the contributions are added in the reference's phase order: constant accelerations, local forces, dynamic-dynamic springs, dynamic-kinematic
+ *     springs, [detailed drag: not part of this stage; ivx_drag_force_and_torque stays a host path], dynamic gravity, alignment torques (both
+ *     kinds are one phase, as they are one registry);
+ *   - inside a phase the order is that of the caller's list. (The reference walks a hash map there, which nothing pins; the list order is this
+ *     library's choice, as for the motion drivers.)
+ *   - dynamic gravity: the field is the caller's list of dynamic bodies (KeyIndexMapper order). Per body the reference's double loop adds the pairs
+ *     in ascending partner rank; that order is kept. A field of fewer than two bodies gives zero loads.
+ * Every body's sums are made by one lane in that order; there are no float atomics, so two runs leave the same bytes. */
+#define IVX_FG_CONSTANT_ACCELERATION 0u
+#define IVX_FG_LOCAL_FORCE 1u
+#define IVX_FG_SPRING_DYNAMIC_DYNAMIC 2u
+#define IVX_FG_SPRING_DYNAMIC_KINEMATIC 3u
+#define IVX_FG_ALIGNMENT_FIXED 4u
+#define IVX_FG_ALIGNMENT_GRAVITY 5u
+typedef struct {
+    uint32_t kind;   /* IVX_FG_* */
+    uint32_t body;   /* index into the dynamic bodies */
+    uint32_t body_b; /* springs: the second body (see above) */
+    float p[13];
+} ivx_force_generator;
+/* The world's generator set, resident until replaced (n == 0 removes it); call it after ivx_world_set_bodies. IVX_ERR_INVALID, with a message that
+ * names the generator (the set in force then stays): an unknown kind, a body index past the world's bodies, a dynamic-dynamic spring with
+ * body == body_b (the reference's assert_ne!), a settling_time that is not > 0. With a set or a field installed every ivx_world_step /
+ * ivx_world_step_enqueue ends with the force stage, behind the motion drivers on the same stream; nothing waits. Host-set totals are therefore
+ * overwritten by the end of the first step (ivx_world_apply_forces primes them before it). A world with neither launches exactly what it launched
+ * before and keeps host-set totals. If the world's bodies are later replaced by fewer than the sets refer to, the next apply or step is
+ * IVX_ERR_STATE, before anything is launched; any other number of bodies gets a new plan at the next apply. */
+int ivx_world_set_force_generators(ivx_world*, const ivx_force_generator*, size_t n);
+/* DynamicGravityManager: the field's members in order and the gravitational constant (n == 0 removes the field; setting it again changes the
+ * constant). IVX_ERR_INVALID: a body index out of range, a body listed twice (the reference panics in include_body). */
+int ivx_world_set_dynamic_gravity(ivx_world*, const uint32_t* dynamic_bodies, size_t n, float gravitational_constant);
+/* The stage on its own, enqueued on the context's stream: nothing when neither set is installed. */
+int ivx_world_apply_forces(ivx_world*);
+/* get_load_on_body for every field member in field order, as of the last apply (zero before the first one after a set call): 6 floats per member,
+ * force then torque; `cap` counts members. Waits for the stream. Without a field nothing is written. */
+int ivx_world_gravity_loads(ivx_world*, float* force3_torque3, size_t cap);
+/* The stage over host arrays, the code the kernels run (tests). Validates like the two set calls. gravity_loads6 (6 floats per field member) may be NULL. */
+int ivx_fg_apply_host(const ivx_force_generator*, size_t n, const uint32_t* gravity_bodies, size_t n_gravity, float gravitational_constant, ivx_rigid_body* dynamic,
+                      size_t n_dynamic, const ivx_kinematic_body* kinematic, size_t n_kinematic, float* gravity_loads6);
 
 #ifdef __cplusplus
 }

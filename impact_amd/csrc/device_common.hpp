@@ -38,12 +38,13 @@ static inline int ivx_mapped_grow(ivx_mapped* m, size_t bytes, size_t want, hipS
     return IVX_OK;
 }
 
-// parts of one allocation, each on a 256-byte boundary: take all, then add the base
+// parts of one allocation, each on a 256-byte boundary (or another power of two: `align`): take all, then add the base
 struct ivx_layout {
     size_t bytes = 0;
+    size_t align = 256;
     size_t take(size_t n) {
         const size_t at = bytes;
-        bytes += (n + 255u) & ~(size_t)255u;
+        bytes += (n + align - 1) & ~(align - 1);
         return at;
     }
 };

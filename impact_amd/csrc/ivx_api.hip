@@ -8,15 +8,9 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
-#include <limits>
-#include <map>
-#include <unordered_map>
 #include <new>
-#include <vector>
-
 #include <type_traits>
-
-#include <dlfcn.h>
+#include <vector>
 
 #include "ivx_host.hpp"
 
@@ -90,7 +84,6 @@ int ensure_dev_scratch(ivx_grid* g, size_t bytes) {
     return IVX_OK;
 }
 
-namespace {
 // Shared allocations (ivx_block, ivx_internal.hpp): released by the last grid that holds a part.
 void block_release(ivx_block* b) {
     if (!b || --b->refs > 0) return;
@@ -98,144 +91,8 @@ void block_release(ivx_block* b) {
     if (b->pinned) (void)hipHostFree(b->pinned);
     delete b;
 }
-// the mesh arrays of a group (1: positions, normals, vertex scratch; 2: indices, index materials; 4: submeshes) given up: freed, or — parts of a
-// shared block — just let go, the block with its last part
-void mesh_group_free(ivx_grid* g, uint32_t group) {
-    const bool pooled = (g->mesh_pooled & group) != 0u;
-    auto drop = [&](auto*& p) {
-        if (p && !pooled) (void)hipFree(p);
-        p = nullptr;
-    };
-    if (group == 1u) drop(g->positions), drop(g->normals), drop(g->vertex_materials);
-    if (group == 2u) drop(g->indices), drop(g->index_materials);
-    if (group == 4u) drop(g->submeshes);
-    if (pooled) {
-        g->mesh_pooled &= ~group;
-        if (!g->mesh_pooled) {
-            block_release(g->mesh_block);
-            g->mesh_block = nullptr;
-        }
-    }
-}
-// Mesh arrays for several grids from ONE device allocation (the fragments of an impact meet their first mesh together): capacities
-// `vcaps` / `icaps` / `scaps` per grid; whatever the grids held before is given up. Every array starts on a 256-byte boundary.
-int mesh_pool_assign(ivx_grid* const* grids, size_t n, const size_t* vcaps, const size_t* icaps, const size_t* scaps) {
-    if (n == 0) return IVX_OK;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t total = 0;
-    for (size_t i = 0; i < n; ++i) total += 2 * up(vcaps[i] * 12) + up(vcaps[i] * 16) + up(icaps[i] * 4) + up(icaps[i] * 8) + up(scaps[i] * sizeof(ivx_submesh));
-    ivx_block* blk = new (std::nothrow) ivx_block();
-    IVX_REQUIRE(blk, IVX_ERR_CAPACITY, "mesh buffers: out of host memory");
-    blk->dev = blk->pinned = nullptr;
-    blk->refs = 0;
-    if (hipMalloc(&blk->dev, total) != hipSuccess) {
-        delete blk;
-        ivx_set_error("mesh buffers: device allocation of %zu bytes for %zu objects failed", total, n);
-        return IVX_ERR_HIP;
-    }
-    char* b = static_cast<char*>(blk->dev);
-    for (size_t i = 0; i < n; ++i) {
-        ivx_grid* g = grids[i];
-        mesh_group_free(g, 1u), mesh_group_free(g, 2u), mesh_group_free(g, 4u);
-        auto take = [&](auto*& p, size_t bytes) {
-            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(b);
-            b += up(bytes);
-        };
-        take(g->positions, vcaps[i] * 12), take(g->normals, vcaps[i] * 12), take(g->vertex_materials, vcaps[i] * 16);
-        take(g->indices, icaps[i] * 4), take(g->index_materials, icaps[i] * 8), take(g->submeshes, scaps[i] * sizeof(ivx_submesh));
-        g->vcap = vcaps[i], g->icap = icaps[i], g->scap = scaps[i];
-        g->mesh_block = blk;
-        g->mesh_pooled = 7u;
-        g->mesh_generation += 1;
-        blk->refs += 1;
-    }
-    return IVX_OK;
-}
 
-// Developer experiment (IVX_MESH_ARENA=<mode>, IVX_MESH_PHASE=<bytes>): the mesher's four output arrays (+ the vertex scratch) carved from ONE
-// allocation at chosen relative offsets — array k starts `k * phase` bytes past its 2 MiB-aligned place. mode 1: hipMalloc; 2: one physically
-// contiguous block (hipExtMallocWithFlags(hipDeviceMallocContiguous)). What the mesher's run-to-run modes do NOT depend on.
-static int mesh_arena_mode() {
-    static const int m = [] {
-        const char* e = getenv("IVX_MESH_ARENA");
-        return e ? atoi(e) : 0;
-    }();
-    return m;
-}
-static int ensure_mesh_block(ivx_grid* g, size_t nv, size_t ni) {
-    if (nv <= g->vcap && ni <= g->icap) return IVX_OK;
-    IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
-    static const size_t phase = [] {
-        const char* e = getenv("IVX_MESH_PHASE");
-        return (size_t)(e ? strtoull(e, nullptr, 0) : 0ull);
-    }();
-    const size_t vcap = std::max(2 * nv + 4096, g->vcap * 2), icap = std::max(2 * ni + 24576, g->icap * 2);
-    const size_t sizes[5] = {vcap * 12, vcap * 12, icap * 4, icap * 8, vcap * 16};
-    size_t off[5], total = 0;
-    for (int k = 0; k < 5; ++k) {
-        total = (total + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
-        off[k] = total + (size_t)k * phase;
-        total = off[k] + sizes[k];
-    }
-    mesh_group_free(g, 1u), mesh_group_free(g, 2u);
-    g->vcap = g->icap = 0;
-    ivx_block* blk = new (std::nothrow) ivx_block();
-    IVX_REQUIRE(blk, IVX_ERR_CAPACITY, "mesh buffers: out of host memory");
-    blk->dev = blk->pinned = nullptr;
-    blk->refs = 1;
-    if ((mesh_arena_mode() == 2 ? hipExtMallocWithFlags(&blk->dev, total, hipDeviceMallocContiguous) : hipMalloc(&blk->dev, total)) != hipSuccess) {
-        delete blk;
-        ivx_set_error("mesh buffers: device allocation of %zu bytes failed", total);
-        return IVX_ERR_HIP;
-    }
-    char* b = static_cast<char*>(blk->dev);
-    g->positions = reinterpret_cast<float*>(b + off[0]);
-    g->normals = reinterpret_cast<float*>(b + off[1]);
-    g->indices = reinterpret_cast<uint32_t*>(b + off[2]);
-    g->index_materials = reinterpret_cast<uint8_t*>(b + off[3]);
-    g->vertex_materials = reinterpret_cast<uint8_t*>(b + off[4]);
-    g->vcap = vcap, g->icap = icap;
-    if (g->mesh_block) block_release(g->mesh_block);  // (only the submeshes of an earlier shared block can still be there: they move out below)
-    g->mesh_block = blk;
-    g->mesh_pooled = 3u;
-    g->mesh_generation += 1;
-    return IVX_OK;
-}
-
-int ensure_mesh_capacity(ivx_grid* g, size_t nv, size_t ni, size_t ns) {
-    if (mesh_arena_mode())
-        if (int rc = ensure_mesh_block(g, nv, ni)) return rc;
-    if (nv > g->vcap || ni > g->icap || ns > g->scap) g->mesh_generation += 1;
-    if (nv > g->vcap) {
-        size_t cap = std::max(2 * nv + 4096, g->vcap * 2);  // (slack: under the reference's range allocator an edited mesh's buffers grow — a re-meshed chunk that needs a little more than it had goes to the end — by about as much again before freed ranges start to be reused; 2 x 48 B per vertex is nothing next to 288 GB)
-        mesh_group_free(g, 1u);
-        g->vcap = 0;
-        int rc;
-        if ((rc = dev_alloc(&g->positions, cap * 3))) return rc;
-        if ((rc = dev_alloc(&g->normals, cap * 3))) return rc;
-        if ((rc = dev_alloc(&g->vertex_materials, cap * 16))) return rc;
-        g->vcap = cap;
-    }
-    if (ni > g->icap) {
-        size_t cap = std::max(2 * ni + 24576, g->icap * 2);
-        mesh_group_free(g, 2u);
-        g->icap = 0;
-        int rc;
-        if ((rc = dev_alloc(&g->indices, cap))) return rc;
-        if ((rc = dev_alloc(&g->index_materials, cap * 8))) return rc;
-        g->icap = cap;
-    }
-    if (ns > g->scap) {
-        size_t cap = std::max(2 * ns + 64, g->scap * 2);
-        mesh_group_free(g, 4u);
-        g->scap = 0;
-        int rc;
-        if ((rc = dev_alloc(&g->submeshes, cap))) return rc;
-        g->scap = cap;
-    }
-    return IVX_OK;
-}
-
+namespace {
 __global__ __launch_bounds__(256) void k_halo_pack(GridView g, uint32_t side, int8_t* __restrict__ out_sdf, uint8_t* __restrict__ out_type,
                                                    ivx_chunk_info* __restrict__ out_info) {
     const uint32_t col = blockIdx.x;  // cj*cz + ck
@@ -263,19 +120,6 @@ int ivx_launch_halo_pack(ivx_grid* g, int side, void* buf) {
     return IVX_OK;
 }
 
-// what the incremental remesh needs to know about the listed chunks: vertex count, index count, kind | flags << 8
-__global__ __launch_bounds__(256) void k_chunk_mesh_needs(uint32_t n, const uint32_t* __restrict__ list, const uint32_t* __restrict__ counts,
-                                                          const ivx_chunk_info* __restrict__ info, uint32_t* __restrict__ out) {
-    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
-    if (e >= n) return;
-    const uint32_t c = list[e];
-    out[3 * e] = counts[2 * (size_t)c];
-    out[3 * e + 1] = counts[2 * (size_t)c + 1];
-    out[3 * e + 2] = (uint32_t)info[c].kind | ((uint32_t)info[c].flags << 8);
-}
-
-// ---- incremental remesh (row a7: VoxelObjectMesh::sync_with_voxel_object, mesh.rs:355-456) ---------------------------------------------
-// (the host mirror of the ChunkSubmeshManager and its RangeAllocators: ivx_submesh_manager, ivx_host.hpp)
 // the occupied ranges in the reference's sense (see ivx_grid::occ_ref): cached, recomputed only when something invalidated them
 static int reference_occupied(ivx_grid* g, uint32_t occ[12]) {
     if (!g->occ_ref_valid) {
@@ -295,69 +139,6 @@ int ivx_reference_occupied(ivx_grid* g, const char* who, uint32_t occ[12]) {
     IVX_REQUIRE(g->occ_ref_valid || g->bbox_valid, IVX_ERR_STATE, "%s: the object holds no occupied ranges yet (call ivx_derive_state or a step first)", who);
     return reference_occupied(g, occ);
 }
-
-void ivx_submesh_manager_free(ivx_submesh_manager* m) { delete m; }
-void ivx_probe_manager_free(ivx_probe_manager* m) { delete m; }
-
-namespace {
-void manager_remove(ivx_grid* g, ivx_submesh_manager* m, uint32_t chunk) {  // remove_chunk_if_present (mesh.rs:811-824)
-    auto it = m->slot_of.find(chunk);
-    if (it == m->slot_of.end()) return;
-    const uint32_t slot = it->second;
-    m->slot_of.erase(it);
-    const ivx_submesh gone = m->table[slot];
-    if (slot + 1 != m->table.size()) {
-        m->table[slot] = m->table.back();
-        m->slot_of[linear_chunk(g, m->table[slot].chunk_indices)] = slot;
-    }
-    m->table.pop_back();
-    m->chunks_were_removed = true;
-    m->vertices.free_range(gone.vertex_offset, (size_t)gone.vertex_offset + gone.vertex_count);
-    m->indices.free_range(gone.index_offset, (size_t)gone.index_offset + gone.index_count);
-}
-// grow the mesh buffers keeping what they hold (the full remesh may simply reallocate, a sync may not): grow_keep_enqueue, ivx_host.hpp
-int ensure_mesh_capacity_keep(ivx_grid* g, size_t nv, size_t ni, size_t ns) {
-    int rc;
-    if (!(nv > g->vcap || ni > g->icap || ns > g->scap)) return IVX_OK;
-    g->mesh_generation += 1;
-    // (growth by copy costs allocations, device copies and a wait — the price of hundreds of small objects' syncs when each of them outgrows
-    // its buffers by a few vertices per frame: double, and never by less than a few thousand elements; memory is not what this part is short of)
-    std::vector<GrowKeep> pending;
-    struct FreeOnError {  // (a failed allocation further down must not leak the blocks made so far)
-        std::vector<GrowKeep>& p;
-        bool armed = true;
-        ~FreeOnError() {
-            if (armed)
-                for (GrowKeep& k : p) (void)hipFree(k.fresh);
-        }
-    } guard{pending};
-    size_t vcap = g->vcap, icap = g->icap, scap = g->scap;
-    if (nv > g->vcap) {
-        vcap = std::max(nv + nv / 2 + 4096, 2 * g->vcap);
-        if ((rc = grow_keep_enqueue(g, &g->positions, g->vcap * 3, vcap * 3, pending, 1u))) return rc;
-        if ((rc = grow_keep_enqueue(g, &g->normals, g->vcap * 3, vcap * 3, pending, 1u))) return rc;
-        if ((rc = grow_keep_enqueue(g, &g->vertex_materials, (size_t)0, vcap * 16, pending, 1u))) return rc;  // scratch of the emit kernel
-    }
-    if (ni > g->icap) {
-        icap = std::max(ni + ni / 2 + 24576, 2 * g->icap);
-        if ((rc = grow_keep_enqueue(g, &g->indices, g->icap, icap, pending, 2u))) return rc;
-        if ((rc = grow_keep_enqueue(g, &g->index_materials, g->icap * 8, icap * 8, pending, 2u))) return rc;
-    }
-    if (ns > g->scap) {
-        scap = std::max(ns + ns / 2 + 64, 2 * g->scap);
-        if ((rc = grow_keep_enqueue(g, &g->submeshes, g->scap, scap, pending, 4u))) return rc;
-    }
-    IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
-    guard.armed = false;
-    uint32_t groups = 0;
-    for (GrowKeep& k : pending) groups |= k.group;
-    for (uint32_t grp = 1u; grp <= 4u; grp <<= 1)
-        if (groups & grp) mesh_group_free(g, grp);  // (the old arrays: freed, or let go of as parts of a shared block)
-    for (GrowKeep& k : pending) *k.slot = k.fresh;
-    g->vcap = vcap, g->icap = icap, g->scap = scap;
-    return IVX_OK;
-}
-}  // namespace
 
 extern "C" {
 
@@ -506,8 +287,6 @@ static int grid_new(ivx_ctx* c, const uint32_t cc[3], float voxel_extent, uint32
     return IVX_OK;
 }
 
-static void ivx_block_release(ivx_block* b) { block_release(b); }
-
 int ivx_grid_create(ivx_ctx* c, const uint32_t cc[3], float voxel_extent, uint32_t x_chunk_offset, uint32_t global_x_chunks, ivx_grid** out) {
     ivx_grid* g = nullptr;
     int rc = grid_new(c, cc, voxel_extent, x_chunk_offset, global_x_chunks, &g);
@@ -562,14 +341,14 @@ extern "C++" int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, f
     if (hipMalloc(&blk->dev, off[n]) != hipSuccess || hipHostMalloc(&blk->pinned, n * 256, hipHostMallocMapped) != hipSuccess) {
         ivx_set_error("%s: allocation of %zu bytes for %zu grids failed", who, off[n], n);
         blk->refs = 1;
-        ivx_block_release(blk);
+        block_release(blk);
         return fail(IVX_ERR_HIP);
     }
     memset(blk->pinned, 0, n * 256);
     void* pinned_dev = nullptr;
     if (hipHostGetDevicePointer(&pinned_dev, blk->pinned, 0) != hipSuccess) {
         blk->refs = 1;
-        ivx_block_release(blk);
+        block_release(blk);
         return fail(IVX_ERR_HIP);
     }
     for (size_t i = 0; i < n; ++i) {
@@ -599,11 +378,11 @@ void ivx_grid_destroy(ivx_grid* g) {
     if (g->dens_call) (void)hipFree(g->dens_call);
     mesh_group_free(g, 1u), mesh_group_free(g, 2u), mesh_group_free(g, 4u);  // (allocations of their own, or parts of a shared block)
     if (g->arena_block) {  // (the arena is a part of a block shared with the grids that came into being with this one)
-        ivx_block_release(g->arena_block);
+        block_release(g->arena_block);
         g->arena = nullptr;
     }
     if (g->host_block) {
-        ivx_block_release(g->host_block);
+        block_release(g->host_block);
         g->result_host = nullptr;
     }
     void* ptrs[] = {g->arena, g->positions, g->normals, g->indices, g->index_materials, g->vertex_materials, g->submeshes, g->dev_scratch, g->prog_nodes,
@@ -756,376 +535,6 @@ int ivx_occupied_ranges(ivx_grid* g, uint32_t out[12]) {
     ivx_occupied_from_raw(g, raw, out);
     memcpy(g->occ_ref, out, sizeof(g->occ_ref));  // VoxelObject::update_occupied_ranges: this is what the object holds from now on
     g->occ_ref_valid = 1;
-    return IVX_OK;
-}
-
-int ivx_remesh(ivx_grid* g, ivx_mesh_counts* out) {
-    IVX_REQUIRE(g && out, IVX_ERR_INVALID, "ivx_remesh: null argument");
-    int rc;
-    if ((rc = ivx_launch_sn_count(g))) return rc;
-    if ((rc = ivx_launch_sn_scan(g))) return rc;
-    uint32_t totals[3];
-    if ((rc = d2h(g, totals, g->chunk_offsets + 2 * (size_t)g->n_chunks, sizeof(totals)))) return rc;
-    if ((rc = ensure_mesh_capacity(g, totals[0], totals[1], totals[2]))) return rc;
-    if (totals[1] > 0 && (rc = ivx_launch_sn_emit(g))) return rc;
-    g->mesh_counts.n_vertices = totals[0];
-    g->mesh_counts.n_indices = totals[1];
-    g->mesh_counts.n_submeshes = totals[2];
-    g->mesh_counts.reserved = 0;
-    g->mesh_valid = 1;
-    g->mesh_built = 1;
-    g->mesh_serial += 1;
-    *out = g->mesh_counts;
-    IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
-    return IVX_OK;
-}
-
-static void ivx_edit_state_free(struct ivx_edit_state* e);
-struct ivx_edit_state;
-static ivx_edit_state* edit_state(ivx_grid* g);
-static bool edit_needs_lookup(ivx_grid* g, uint32_t chunk, uint32_t out3[3]);
-static int edit_sync_upload(ivx_grid* g, const void* src, size_t bytes, void* d_dst);
-static void edit_sync_mark(ivx_grid* g, int pending);
-static int edit_sync_pending(ivx_grid* g);
-static bool edit_sync_drained_take(ivx_grid* g);  // (and clears it)
-
-// VoxelObjectMesh::sync_with_voxel_object (mesh.rs:355-456) in two halves. ENQUEUE: the sizes the invalidated chunks' meshes need come from the
-// last edit's result block when the set is that edit's (ivx_absorb_collect: no count pass, no read-back) — else from a count over just these
-// chunks and one read-back —; the host mirror of the ChunkSubmeshManager places them; records and slots go up from pinned memory and the
-// emit pass for the listed chunks follows on the stream. COLLECT: the wait. (Round 3 counted the whole object, read the sizes back, uploaded
-// through a blocking copy and waited again: two round trips and ~25 us of counting for ~100 chunks.)
-// what the edit in flight invalidates and what those meshes need, from the records its count role delivers early (ivx_edit_state::early_*):
-// waits for the role's bell — a third of the way down the edit's chain —, not for the edit
-static int edit_early_needs(ivx_grid* g, const char* who, std::vector<uint32_t>& list);
-static int edit_sync_stage(ivx_grid* g, const void* src, size_t bytes, void** dev_view);
-static int edit_sync_stage_done(ivx_grid* g);
-static int mesh_sync_enqueue(ivx_grid* g, const uint8_t* invalidated_chunks, const char* who) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "%s: null argument", who);
-    ivx_many_other_context other_(g->ctx);
-    IVX_REQUIRE(!edit_sync_pending(g), IVX_ERR_STATE, "%s: a sync of this object is in flight (ivx_mesh_sync_collect first)", who);
-    IVX_REQUIRE(g->mesh_built, IVX_ERR_STATE, "ivx_mesh_sync: there is no mesh to synchronise (call ivx_remesh first)");
-    IVX_REQUIRE(g->regions_valid, IVX_ERR_STATE, "ivx_mesh_sync: derived state must be current (the edit ops leave it so)");
-    IVX_REQUIRE(g->x_off == 0 && g->gx == g->cc[0] && !g->has_ghost[0] && !g->has_ghost[1], IVX_ERR_STATE,
-                "ivx_mesh_sync: not available on a slab of a decomposed grid");
-    int rc;
-    static const bool trace_ = getenv("IVX_MANY_TRACE") != nullptr;
-    static thread_local double acc_[6];
-    static thread_local int calls_ = 0;
-    auto tp_ = std::chrono::steady_clock::now();
-    auto lap_ = [&](int slot) {
-        if (!trace_) return;
-        const auto t = std::chrono::steady_clock::now();
-        acc_[slot] += 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(t - tp_).count();
-        tp_ = t;
-    };
-    if (!g->submesh_manager) g->submesh_manager = new (std::nothrow) ivx_submesh_manager();
-    IVX_REQUIRE(g->submesh_manager, IVX_ERR_HIP, "ivx_mesh_sync: out of host memory");
-    ivx_submesh_manager* m = g->submesh_manager;
-    if (m->serial != g->mesh_serial) {  // the mesh was rebuilt in full since: push_chunk for every submesh, no free ranges (mesh.rs:731-749)
-        m->table.assign(g->mesh_counts.n_submeshes, ivx_submesh{});
-        if ((rc = d2h(g, m->table.data(), g->submeshes, m->table.size() * sizeof(ivx_submesh)))) return rc;
-        m->slot_of.clear();
-        for (uint32_t s = 0; s < m->table.size(); ++s) m->slot_of[linear_chunk(g, m->table[s].chunk_indices)] = s;
-        m->vertices.free_ranges.clear();
-        m->indices.free_ranges.clear();
-        m->total_vertices = g->mesh_counts.n_vertices;
-        m->total_indices = g->mesh_counts.n_indices;
-        m->updated.clear();  // (recreate -> ChunkSubmeshManager::clear, mesh.rs:843-851)
-        m->chunks_were_removed = false;
-        m->serial = g->mesh_serial;
-    }
-    lap_(0);
-    // what the invalidated chunks' meshes need now and their records (exposure, obscuredness flags)
-    // (the call's work lists live on across calls: with a hundred objects per frame their allocations were a third of the host's time here)
-    static thread_local std::vector<uint32_t> list, needs, dirty_slots, rec_chunk, slots;
-    static thread_local std::vector<char> stage;
-    list.clear();
-    if (!invalidated_chunks) {  // the set of the edit in flight
-        if ((rc = edit_early_needs(g, who, list))) return rc;
-    } else {   // chunk-linear order (the reference walks a hash set: unpinned); eight flags a look — nearly all of them are zero
-        uint32_t c = 0;
-        for (; c + 8u <= g->n_chunks; c += 8u) {
-            uint64_t w;
-            memcpy(&w, invalidated_chunks + c, 8);
-            if (!w) continue;
-            for (uint32_t b = 0; b < 8u; ++b)
-                if (invalidated_chunks[c + b]) list.push_back(c + b);
-        }
-        for (; c < g->n_chunks; ++c)
-            if (invalidated_chunks[c]) list.push_back(c);
-    }
-    needs.assign(3 * list.size(), 0u);
-    bool cached = g->needs_current != 0;
-    for (size_t e = 0; e < list.size() && cached; ++e) cached = edit_needs_lookup(g, list[e], &needs[3 * e]);
-    if (!list.empty() && !cached) {
-        const size_t off_out = (list.size() * 4 + 15) & ~(size_t)15;
-        if ((rc = ensure_dev_scratch(g, off_out + list.size() * 16))) return rc;
-        char* base = static_cast<char*>(g->dev_scratch);
-        if ((rc = edit_sync_upload(g, list.data(), list.size() * 4, base))) return rc;
-        if ((rc = ivx_launch_list_mesh_needs(g, (uint32_t)list.size(), reinterpret_cast<const uint32_t*>(base), reinterpret_cast<uint32_t*>(base + off_out)))) return rc;
-        std::vector<uint32_t> raw(4 * list.size());
-        if ((rc = d2h(g, raw.data(), base + off_out, raw.size() * 4))) return rc;
-        for (size_t e = 0; e < list.size(); ++e) needs[3 * e] = raw[4 * e + 1], needs[3 * e + 1] = raw[4 * e + 2], needs[3 * e + 2] = raw[4 * e] & 0xFFFFu;
-    }
-    lap_(1);
-    dirty_slots.clear();  // slots of the device table that a removal rewrote (the emit pass writes the others)
-    const size_t table_before = m->table.size();
-    struct Rec {
-        uint32_t chunk, voff, ioff, packed;
-    };
-    static thread_local std::vector<Rec> recs;
-    recs.clear();
-    rec_chunk.clear();
-    for (size_t e = 0; e < list.size(); ++e) {
-        const uint32_t c = list[e];
-        const uint32_t nv = needs[3 * e], ni = needs[3 * e + 1], kind = needs[3 * e + 2] & 0xFFu, flags = (needs[3 * e + 2] >> 8) & 0xFFu;
-        const bool exposed = kind == KIND_NONUNIFORM && (flags & CF_FULLY_OBSCURED) != CF_FULLY_OBSCURED;
-        if (!exposed || ni == 0) {  // no longer exposed, or an empty mesh (mesh.rs:375-379, 447-451)
-            auto gone = m->slot_of.find(c);
-            if (gone != m->slot_of.end()) dirty_slots.push_back(gone->second);  // (the last entry moves here)
-            manager_remove(g, m, c);
-            continue;
-        }
-        // write_chunk (mesh.rs:751-809)
-        auto it = m->slot_of.find(c);
-        if (it != m->slot_of.end()) {
-            const ivx_submesh& old = m->table[it->second];
-            m->vertices.free_range(old.vertex_offset, (size_t)old.vertex_offset + old.vertex_count);
-            m->indices.free_range(old.index_offset, (size_t)old.index_offset + old.index_count);
-        }
-        size_t v0, i0;
-        if (!m->vertices.allocate(nv, &v0)) v0 = m->total_vertices, m->total_vertices += nv;
-        if (!m->indices.allocate(ni, &i0)) i0 = m->total_indices, m->total_indices += ni;
-        IVX_REQUIRE(m->total_vertices < 0xFFFFFFFFull && m->total_indices < 0xFFFFFFFFull, IVX_ERR_CAPACITY, "ivx_mesh_sync: mesh buffers exceed 2^32 elements");
-        ivx_submesh sm;
-        memset(&sm, 0, sizeof(sm));
-        sm.chunk_indices[0] = c / (g->cc[1] * g->cc[2]);
-        sm.chunk_indices[1] = (c / g->cc[2]) % g->cc[1];
-        sm.chunk_indices[2] = c % g->cc[2];
-        sm.index_offset = (uint32_t)i0;
-        sm.index_count = ni;
-        sm.vertex_offset = (uint32_t)v0;
-        sm.vertex_count = nv;
-        for (int a = 0; a < 2; ++a)  // ChunkSubmesh::new (mesh.rs:611-635): bits X_DN 0, Y_DN 1, Z_DN 2, X_UP 3, Y_UP 4, Z_UP 5
-            for (int b = 0; b < 2; ++b)
-                for (int d = 0; d < 2; ++d)
-                    sm.is_obscured_from_direction[a][b][d] =
-                        (((flags >> (3 * a)) & 1u) && ((flags >> (3 * b + 1)) & 1u) && ((flags >> (3 * d + 2)) & 1u)) ? 1u : 0u;
-        if (it != m->slot_of.end()) {
-            m->table[it->second] = sm;
-        } else {
-            m->slot_of[c] = (uint32_t)m->table.size();
-            m->table.push_back(sm);
-        }
-        m->updated.push_back(ivx_submesh_data_ranges{(uint32_t)v0, (uint32_t)(v0 + nv), (uint32_t)i0, (uint32_t)(i0 + ni)});
-        recs.push_back(Rec{c, (uint32_t)v0, (uint32_t)i0, nv | ((ni / 6u) << 16)});
-        rec_chunk.push_back(c);
-    }
-    lap_(2);
-    m->vertices.merge_consecutive();  // perform_maintainance
-    m->indices.merge_consecutive();
-    if ((rc = ensure_mesh_capacity_keep(g, m->total_vertices, m->total_indices, m->table.size()))) return rc;
-    lap_(3);
-    // the device table: the emit pass writes the re-meshed chunks' entries; entries a removal moved are patched from the host mirror — by the
-    // emit pass's first workgroup when there is one (they ride in its upload), else by a small copy each
-    size_t n_patch = 0;
-    for (uint32_t slot : dirty_slots) n_patch += slot < m->table.size() ? 1u : 0u;
-    if (!recs.empty()) {
-        // (slots are final only now: a removal after a write may have moved the written entry)
-        slots.resize(recs.size());
-        for (size_t r = 0; r < recs.size(); ++r) slots[r] = m->slot_of.at(rec_chunk[r]);
-        const size_t off_slots = 16 + recs.size() * sizeof(Rec), off_pslots = off_slots + recs.size() * 4;
-        const size_t off_pent = (off_pslots + n_patch * 4 + 15) & ~(size_t)15, total = off_pent + n_patch * sizeof(ivx_submesh);
-        if ((rc = ensure_dev_scratch(g, total))) return rc;
-        stage.assign(total, 0);
-        const uint32_t n = (uint32_t)recs.size();
-        memcpy(stage.data(), &n, 4);
-        memcpy(stage.data() + 16, recs.data(), recs.size() * sizeof(Rec));
-        memcpy(stage.data() + off_slots, slots.data(), slots.size() * 4);
-        size_t e = 0;
-        for (uint32_t slot : dirty_slots)
-            if (slot < m->table.size()) {
-                memcpy(stage.data() + off_pslots + 4 * e, &slot, 4);
-                memcpy(stage.data() + off_pent + e * sizeof(ivx_submesh), &m->table[slot], sizeof(ivx_submesh));
-                e += 1;
-            }
-        // (records, slots and patches are a few KB the passes only read: from host-mapped memory in place — a copy ahead of the passes is a
-        // stream operation of 4 us and a gap; a recorded batch carries them in its one staging copy instead)
-        char* base = static_cast<char*>(g->dev_scratch);
-        void* view = nullptr;
-        if ((rc = edit_sync_stage(g, stage.data(), total, &view))) return rc;
-        if (view) base = static_cast<char*>(view);
-        else if ((rc = edit_sync_upload(g, stage.data(), total, base))) return rc;
-        if ((rc = ivx_launch_sn_emit_list(g, n, reinterpret_cast<const uint32_t*>(base), base + 16, reinterpret_cast<const uint32_t*>(base + off_slots), (uint32_t)n_patch,
-                                          base + off_pent, reinterpret_cast<const uint32_t*>(base + off_pslots))))
-            return rc;
-        if (view && (rc = edit_sync_stage_done(g))) return rc;
-    }
-    lap_(4);
-    (void)table_before;
-    if (recs.empty())
-        for (uint32_t slot : dirty_slots)
-            if (slot < m->table.size() && !ivx_many_upload(g->ctx, g, g->submeshes + slot, &m->table[slot], sizeof(ivx_submesh)))
-                IVX_HIP_CHECK(ivx_memcpy_async(g->submeshes + slot, &m->table[slot], sizeof(ivx_submesh), hipMemcpyHostToDevice, g->ctx->stream));
-    g->mesh_counts.n_vertices = (uint32_t)m->total_vertices;
-    g->mesh_counts.n_indices = (uint32_t)m->total_indices;
-    g->mesh_counts.n_submeshes = (uint32_t)m->table.size();
-    g->mesh_serial += 1;  // collision probes picked from the old mesh are stale
-    m->serial = g->mesh_serial;
-    edit_sync_mark(g, 1);
-    (void)edit_sync_drained_take(g);
-    lap_(5);
-    static const int period_ = trace_ && atoi(getenv("IVX_MANY_TRACE")) > 1 ? atoi(getenv("IVX_MANY_TRACE")) : 81;
-    if (trace_ && ++calls_ % period_ == 0) {
-        fprintf(stderr, "[ivx many]   sync enqueue laps (us per period): setup %.1f list+needs %.1f allocator %.1f capacity %.1f upload+emit %.1f tail %.1f\n", acc_[0], acc_[1], acc_[2],
-                acc_[3], acc_[4], acc_[5]);
-        for (double& a : acc_) a = 0.0;
-    }
-    return IVX_OK;
-}
-
-static int mesh_sync_collect(ivx_grid* g, ivx_mesh_counts* out, const char* who, bool stream_is_drained = false) {
-    IVX_REQUIRE(g && out, IVX_ERR_INVALID, "%s: null argument", who);
-    IVX_REQUIRE(edit_sync_pending(g), IVX_ERR_STATE, "%s: no sync of this object is in flight", who);
-    edit_sync_mark(g, 0);
-    if (edit_sync_drained_take(g)) stream_is_drained = true;  // (the edit's collect waited behind this sync's launches)
-    if (!stream_is_drained) IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
-    g->mesh_valid = 1;
-    *out = g->mesh_counts;
-    return IVX_OK;
-}
-
-int ivx_mesh_sync_enqueue(ivx_grid* g, const uint8_t* invalidated_chunks) { return mesh_sync_enqueue(g, invalidated_chunks, "ivx_mesh_sync_enqueue"); }
-int ivx_grid_set_early_mesh_needs(ivx_grid* g, int on) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_grid_set_early_mesh_needs: null grid");
-    g->early_needs_on = on ? 1 : 0;
-    return IVX_OK;
-}
-int ivx_mesh_sync_collect(ivx_grid* g, ivx_mesh_counts* out) { return mesh_sync_collect(g, out, "ivx_mesh_sync_collect"); }
-int ivx_mesh_sync(ivx_grid* g, const uint8_t* invalidated_chunks, ivx_mesh_counts* out) {
-    IVX_REQUIRE(out, IVX_ERR_INVALID, "ivx_mesh_sync: null argument");
-    const int rc = mesh_sync_enqueue(g, invalidated_chunks, "ivx_mesh_sync");
-    return rc ? rc : mesh_sync_collect(g, out, "ivx_mesh_sync");
-}
-
-int ivx_mesh_modifications(ivx_grid* g, ivx_submesh_data_ranges* out, size_t cap, size_t* n_out, int* chunks_were_removed) {
-    IVX_REQUIRE(g && n_out && chunks_were_removed && (out || cap == 0), IVX_ERR_INVALID, "ivx_mesh_modifications: null argument");
-    const ivx_submesh_manager* m = g->submesh_manager;
-    const bool current = m && m->serial == g->mesh_serial;  // (a full remesh since the last sync: nothing pending, the whole mesh is new)
-    *n_out = current ? m->updated.size() : 0;
-    *chunks_were_removed = current && m->chunks_were_removed ? 1 : 0;
-    IVX_REQUIRE(*n_out <= cap || !out, IVX_ERR_CAPACITY, "ivx_mesh_modifications: %zu ranges exceed the capacity %zu", *n_out, cap);
-    if (out && *n_out) memcpy(out, m->updated.data(), *n_out * sizeof(ivx_submesh_data_ranges));
-    return IVX_OK;
-}
-
-int ivx_mesh_report_synchronized(ivx_grid* g) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_mesh_report_synchronized: null grid");
-    if (g->submesh_manager) {
-        g->submesh_manager->updated.clear();
-        g->submesh_manager->chunks_were_removed = false;
-    }
-    return IVX_OK;
-}
-
-int ivx_mesh_download(ivx_grid* g, float* positions, float* normals, uint32_t* indices, uint8_t* index_materials, ivx_submesh* submeshes) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_mesh_download: null grid");
-    IVX_REQUIRE(g->mesh_valid, IVX_ERR_STATE, "ivx_mesh_download: call ivx_remesh first");
-    const size_t nv = g->mesh_counts.n_vertices, ni = g->mesh_counts.n_indices, ns = g->mesh_counts.n_submeshes;
-    int rc;
-    if (positions && (rc = d2h(g, positions, g->positions, nv * 12))) return rc;
-    if (normals && (rc = d2h(g, normals, g->normals, nv * 12))) return rc;
-    if (indices && (rc = d2h(g, indices, g->indices, ni * 4))) return rc;
-    if (index_materials && (rc = d2h(g, index_materials, g->index_materials, ni * 8))) return rc;
-    if (submeshes && (rc = d2h(g, submeshes, g->submeshes, ns * sizeof(ivx_submesh)))) return rc;
-    return IVX_OK;
-}
-
-void* ivx_mesh_device_ptr(ivx_grid* g, int which) {
-    if (!g || !g->mesh_valid) return nullptr;
-    switch (which) {
-        case 0: return g->positions;
-        case 1: return g->normals;
-        case 2: return g->indices;
-        case 3: return g->index_materials;
-        case 4: return g->submeshes;
-        default: return nullptr;
-    }
-}
-
-// §8f-4: handles of a mesh buffer another process or another API can import (gpu_resource.rs:498-530, 729-907 fill wgpu buffers from these
-// arrays; mesh.rs:94-123). The buffers are plain hipMalloc allocations of their own, so the IPC handle names exactly the buffer.
-int ivx_mesh_export(ivx_grid* g, int which, ivx_mesh_export_info* out) {
-    IVX_REQUIRE(g && out && which >= 0 && which <= 4, IVX_ERR_INVALID, "ivx_mesh_export: bad argument");
-    IVX_REQUIRE(g->mesh_valid || g->mesh_built, IVX_ERR_STATE, "ivx_mesh_export: the grid has no mesh");
-    memset(out, 0, sizeof(*out));
-    out->dmabuf_fd = -1;
-    void* p = nullptr;
-    size_t elem = 0, count = 0, cap = 0;
-    switch (which) {
-        case 0: p = g->positions, elem = 12, count = g->mesh_counts.n_vertices, cap = g->vcap; break;
-        case 1: p = g->normals, elem = 12, count = g->mesh_counts.n_vertices, cap = g->vcap; break;
-        case 2: p = g->indices, elem = 4, count = g->mesh_counts.n_indices, cap = g->icap; break;
-        case 3: p = g->index_materials, elem = 8, count = g->mesh_counts.n_indices, cap = g->icap; break;
-        default: p = g->submeshes, elem = sizeof(ivx_submesh), count = g->mesh_counts.n_submeshes, cap = g->scap; break;
-    }
-    if (g->submesh_manager) {  // after an incremental sync the live ranges are scattered over the buffers: everything up to the capacity may be in use
-        count = cap;
-    }
-    IVX_REQUIRE(p && cap, IVX_ERR_STATE, "ivx_mesh_export: the buffer is empty");
-    out->bytes = (uint64_t)count * elem;
-    out->capacity_bytes = (uint64_t)cap * elem;
-    out->element_bytes = (uint32_t)elem;
-    out->generation = g->mesh_generation;
-    out->device_ptr = (uint64_t)(uintptr_t)p;
-    hipIpcMemHandle_t h;
-    static_assert(sizeof(h) == sizeof(out->ipc_handle), "hipIpcMemHandle_t is 64 bytes");
-    IVX_HIP_CHECK(hipIpcGetMemHandle(&h, p));
-    memcpy(out->ipc_handle, &h, sizeof(h));
-    // a dma-buf file descriptor for APIs that import those (Vulkan VK_EXT_external_memory_dma_buf under wgpu): optional, -1 where the
-    // runtime cannot make one; the caller owns the descriptor (close it)
-    int fd = -1;
-    const size_t page = 4096;
-    // The HSA runtime's export names the offset of the range inside the dma-buf object (the HIP call drops it): taken from there when the
-    // symbol is in the process (it is wherever libamdhip64 is: libhsa-runtime64 is its dependency), page-aligned range around the buffer.
-    typedef int (*export_fn)(const void*, size_t, int*, uint64_t*);
-    static export_fn hsa_export = reinterpret_cast<export_fn>(dlsym(RTLD_DEFAULT, "hsa_amd_portable_export_dmabuf"));
-    const uintptr_t lo = (uintptr_t)p & ~(uintptr_t)(page - 1), hi = ((uintptr_t)p + (size_t)out->capacity_bytes + page - 1) & ~(uintptr_t)(page - 1);
-    uint64_t off = 0;
-    if (hsa_export && hsa_export(reinterpret_cast<const void*>(lo), hi - lo, &fd, &off) == 0 && fd >= 0) {
-        out->dmabuf_fd = fd;
-        out->dmabuf_offset = off + ((uintptr_t)p - lo);
-        out->dmabuf_bytes = hi - lo;
-    } else if (hipMemGetHandleForAddressRange(&fd, reinterpret_cast<void*>(lo), hi - lo, hipMemRangeHandleTypeDmaBufFd, 0) == hipSuccess && fd >= 0) {
-        out->dmabuf_fd = fd;
-        out->dmabuf_offset = (uintptr_t)p - lo;  // (the range's own start: this call does not say where the range lies in the object)
-        out->dmabuf_bytes = hi - lo;
-    } else {
-        const hipError_t e = hipGetLastError();
-        ivx_set_error("ivx_mesh_export: no dma-buf descriptor for the buffer (%s); the hipIpc handle is valid", hipGetErrorString(e));
-    }
-    return IVX_OK;
-}
-
-// the importing side for a HIP process: the 64-byte handle of ivx_mesh_export -> a device pointer in THIS process (no context needed beyond
-// the device being usable); ivx_mesh_import_close gives it back
-int ivx_mesh_import_open(const uint8_t ipc_handle[64], int device, void** device_ptr) {
-    IVX_REQUIRE(ipc_handle && device_ptr, IVX_ERR_INVALID, "ivx_mesh_import_open: null argument");
-    IVX_HIP_CHECK(hipSetDevice(device));
-    hipIpcMemHandle_t h;
-    memcpy(&h, ipc_handle, sizeof(h));
-    IVX_HIP_CHECK(hipIpcOpenMemHandle(device_ptr, h, hipIpcMemLazyEnablePeerAccess));
-    return IVX_OK;
-}
-int ivx_mesh_import_close(void* device_ptr) {
-    IVX_REQUIRE(device_ptr, IVX_ERR_INVALID, "ivx_mesh_import_close: null argument");
-    IVX_HIP_CHECK(hipIpcCloseMemHandle(device_ptr));
-    return IVX_OK;
-}
-
-int ivx_mesh_generation(ivx_grid* g, uint64_t* generation) {
-    IVX_REQUIRE(g && generation, IVX_ERR_INVALID, "ivx_mesh_generation: null argument");
-    *generation = g->mesh_generation;
     return IVX_OK;
 }
 
@@ -1306,83 +715,24 @@ struct ivx_edit_state {
     int early_armed = 0, early_taken = 0;
     uint32_t early_seq = 0;
     size_t off_early = 0, off_bell = 0;
-    // the sync in flight
-    int sync_pending = 0;
-    ivx_mapped pinned_up;  // (host-mapped: the sync's kernels read their small lists in place)
-    int sync_drained = 0;  // an edit's collect has waited for a doorbell that was rung behind this sync's launches: nothing left to wait for
-    hipEvent_t up_done = nullptr;  // the last upload from pinned_up has been read
-    int up_busy = 0;
 };
 static void ivx_edit_state_free(ivx_edit_state* e) {
     if (!e) return;
     if (e->pinned) (void)hipHostFree(e->pinned);
     if (e->d_results) (void)hipFree(e->d_results);
-    ivx_mapped_free(&e->pinned_up);
-    if (e->up_done) (void)hipEventDestroy(e->up_done);
     delete e;
 }
 static ivx_edit_state* edit_state(ivx_grid* g) {
     if (!g->edit) g->edit = new (std::nothrow) ivx_edit_state();
     return g->edit;
 }
-static bool edit_needs_lookup(ivx_grid* g, uint32_t chunk, uint32_t out3[3]) {
+extern "C++" bool edit_needs_lookup(ivx_grid* g, uint32_t chunk, uint32_t out3[3]) {
     if (!g->edit) return false;
     const auto& v = g->edit->needs;
     const auto it = std::lower_bound(v.begin(), v.end(), chunk, [](const std::array<uint32_t, 4>& a, uint32_t c) { return a[0] < c; });
     if (it == v.end() || (*it)[0] != chunk) return false;
     out3[0] = (*it)[1], out3[1] = (*it)[2], out3[2] = (*it)[3];
     return true;
-}
-static void edit_sync_mark(ivx_grid* g, int pending) {
-    if (ivx_edit_state* e = edit_state(g)) e->sync_pending = pending;
-}
-static int edit_sync_pending(ivx_grid* g) { return g->edit ? g->edit->sync_pending : 0; }
-static bool edit_sync_drained_take(ivx_grid* g) {
-    if (!g->edit) return false;
-    const bool d = g->edit->sync_drained != 0;
-    g->edit->sync_drained = 0;
-    return d;
-}
-// the sync's own host-mapped block, free (the event behind the last upload from it has passed) and at least `bytes`
-static int edit_sync_block(ivx_grid* g, size_t bytes, ivx_edit_state** out) {
-    ivx_edit_state* e = *out = edit_state(g);
-    IVX_REQUIRE(e, IVX_ERR_CAPACITY, "ivx_mesh_sync: out of host memory");
-    if (!e->up_done) IVX_HIP_CHECK(hipEventCreateWithFlags(&e->up_done, hipEventDisableTiming));
-    if (e->up_busy) {
-        IVX_HIP_CHECK(hipEventSynchronize(e->up_done));
-        e->up_busy = 0;
-    }
-    return ivx_mapped_grow(&e->pinned_up, bytes, std::max<size_t>(bytes, 1 << 16), nullptr);
-}
-// host -> device from that block, asynchronously (the block is free again once the event behind the copy has passed)
-static int edit_sync_upload(ivx_grid* g, const void* src, size_t bytes, void* d_dst) {
-    if (ivx_many_upload(g->ctx, g, d_dst, src, (bytes + 3) & ~(size_t)3)) return IVX_OK;  // (a batch is being recorded: the words ride in its staging copy)
-    ivx_edit_state* e;
-    int rc = edit_sync_block(g, bytes, &e);
-    if (rc) return rc;
-    memcpy(e->pinned_up.p, src, bytes);
-    IVX_HIP_CHECK(ivx_memcpy_async(d_dst, e->pinned_up.p, bytes, hipMemcpyHostToDevice, g->ctx->stream));
-    IVX_HIP_CHECK(ivx_event_record(e->up_done, g->ctx->stream));
-    e->up_busy = 1;
-    return IVX_OK;
-}
-// The sync's small lists where its kernels can read them WITHOUT a copy on the stream: into the block, *dev_view = the device's address
-// of it. Null view: a batch is being recorded (the caller uploads as before). edit_sync_stage_done goes behind the last reader's launch.
-static int edit_sync_stage(ivx_grid* g, const void* src, size_t bytes, void** dev_view) {
-    *dev_view = nullptr;
-    if (ivx_many_recording()) return IVX_OK;
-    ivx_edit_state* e;
-    int rc = edit_sync_block(g, bytes, &e);
-    if (rc) return rc;
-    memcpy(e->pinned_up.p, src, bytes);
-    *dev_view = e->pinned_up.dev;
-    return IVX_OK;
-}
-static int edit_sync_stage_done(ivx_grid* g) {
-    // (no event behind the readers: the block is next written by the object's next sync, which cannot be enqueued before this one's collect has
-    // waited for them — an event record here is a stream operation between the sync's launches and whatever follows them)
-    (void)g;
-    return IVX_OK;
 }
 
 static int absorb_enqueue(ivx_grid* g, const char* who, int capsule, const float center[3], const float seg[3], float influence_radius, float shape_radius,
@@ -1522,7 +872,7 @@ static int absorb_collect(ivx_grid* g, const char* who, ivx_absorb_result* out, 
     if (e->nothing) return IVX_OK;
     int rc;
     if ((rc = rederive_collect(g))) return rc;  // (the doorbell behind everything enqueued: one wait)
-    if (e->sync_pending) e->sync_drained = 1;   // (... a sync enqueued while this edit was in flight included)
+    mesh_sync_stream_drained(g);                // (... a sync enqueued while this edit was in flight included)
     std::vector<char> hostbuf;
     const char* hb;
     if (e->staged) {
@@ -1568,7 +918,9 @@ static int absorb_collect(ivx_grid* g, const char* who, ivx_absorb_result* out, 
     return IVX_OK;
 }
 
-static int edit_early_needs(ivx_grid* g, const char* who, std::vector<uint32_t>& list) {
+// what the edit in flight invalidates and what those meshes need, from the records its count role delivers early (ivx_edit_state::early_*):
+// waits for the role's bell — a third of the way down the edit's chain —, not for the edit
+extern "C++" int edit_early_needs(ivx_grid* g, const char* who, std::vector<uint32_t>& list) {
     ivx_edit_state* e = g->edit;
     IVX_REQUIRE(e && e->pending, IVX_ERR_STATE, "%s: a null set stands for the chunks of an edit in flight, and none is", who);
     if (e->nothing) return IVX_OK;
@@ -2101,27 +1453,17 @@ int ivx_voxel_step_collect(ivx_grid* g, ivx_step_result* out) {
     }
     if (stages & IVX_STAGE_REMESH) {
         const uint32_t totals[3] = {sc[28], sc[29], sc[30]};
-        bool grown_later = false;
-        if (totals[0] > g->vcap || totals[1] > g->icap || totals[2] > g->scap) {
-            if (g->defer_mesh_growth) {
-                grown_later = true;  // (ivx_voxel_step_many: the buffers of all objects that outgrew theirs from one allocation, their emit passes as one launch)
-            } else {
-                int rc;
-                if ((rc = ensure_mesh_capacity(g, totals[0], totals[1], totals[2]))) return rc;
-                if ((rc = ivx_launch_sn_emit(g))) return rc;
-                IVX_HIP_CHECK(ivx_stream_sync(s));
-            }
+        const bool outgrown = totals[0] > g->vcap || totals[1] > g->icap || totals[2] > g->scap;
+        // (ivx_voxel_step_many: the buffers of all objects that outgrew theirs from one allocation, their emit passes as one launch)
+        g->mesh_growth_pending = outgrown && g->defer_mesh_growth ? 1 : 0;
+        if (outgrown && !g->mesh_growth_pending) {
+            int rc;
+            if ((rc = ensure_mesh_capacity(g, totals[0], totals[1], totals[2]))) return rc;
+            if ((rc = ivx_launch_sn_emit(g))) return rc;
+            IVX_HIP_CHECK(ivx_stream_sync(s));
         }
-        g->mesh_counts.n_vertices = totals[0];
-        g->mesh_counts.n_indices = totals[1];
-        g->mesh_counts.n_submeshes = totals[2];
-        g->mesh_counts.reserved = 0;
-        g->mesh_growth_pending = grown_later ? 1 : 0;
-        if (!grown_later) {
-            g->mesh_valid = 1;
-            g->mesh_built = 1;
-            g->mesh_serial += 1;
-        }
+        if (g->mesh_growth_pending) mesh_set_counts(g, totals);  // (valid, built and serial wait for the emit that ivx_voxel_step_many runs again)
+        else mesh_adopt_full(g, totals);
     }
     if (stages & IVX_STAGE_INERTIA) {
         memcpy(out->moments.m64, sc + 32, 10 * sizeof(double));
@@ -2273,15 +1615,12 @@ extern "C++" int many_fail(ivx_grid* const* grids, size_t n, int rc) {
             ivx_absorb_result tmp;
             (void)absorb_collect(g, "ivx_*_many (drain)", &tmp, nullptr, nullptr);
         }
-        if (g->edit && g->edit->sync_pending) {
-            ivx_mesh_counts mc;
-            (void)mesh_sync_collect(g, &mc, "ivx_*_many (drain)", true);
-        }
+        mesh_sync_abandon(g);
         if (g->pending_stages || g->gather_launched) {
             ivx_step_result tmp;
             (void)ivx_voxel_step_collect(g, &tmp);
         }
-        if (g->edit) g->edit->pending = 0, g->edit->sync_pending = 0;
+        if (g->edit) g->edit->pending = 0;
         g->pending_stages = 0;
         g->gather_launched = 0;
         g->results_in_block = 0;
@@ -2339,11 +1678,10 @@ int ivx_voxel_step_many(ivx_grid* const* grids, size_t n, uint32_t stages, ivx_s
         caps.resize(3 * m);
         for (size_t k = 0; k < m; ++k) {
             const ivx_mesh_counts& mc = grow[k]->mesh_counts;
-            caps[k] = std::max<size_t>(2 * (size_t)mc.n_vertices + 4096, grow[k]->vcap * 2);
-            caps[m + k] = std::max<size_t>(2 * (size_t)mc.n_indices + 24576, grow[k]->icap * 2);
-            caps[2 * m + k] = std::max<size_t>(2 * (size_t)mc.n_submeshes + 64, grow[k]->scap * 2);
+            const size_t need[3] = {mc.n_vertices, mc.n_indices, mc.n_submeshes}, have[3] = {grow[k]->vcap, grow[k]->icap, grow[k]->scap};
+            mesh_grown_capacities(need, have, false, &caps[3 * k]);
         }
-        if ((rc = mesh_pool_assign(grow.data(), m, caps.data(), caps.data() + m, caps.data() + 2 * m))) return many_fail(grids, n, rc);
+        if ((rc = mesh_pool_assign(grow.data(), m, caps.data()))) return many_fail(grids, n, rc);
         if ((rc = many_phase(grow.data(), m, [&](size_t k) -> int {
                  ivx_grid* g = grow[k];
                  if (!ivx_many_zero(g->ctx, g, ivx_sn_hard_count(g), IVX_SN_TAIL_WORDS * sizeof(uint32_t)))
@@ -2355,31 +1693,13 @@ int ivx_voxel_step_many(ivx_grid* const* grids, size_t n, uint32_t stages, ivx_s
             return many_fail(grids, n, rc);
         IVX_HIP_CHECK(ivx_stream_sync(grids[0]->ctx->stream));
         for (ivx_grid* g : grow) {
+            const uint32_t totals[3] = {g->mesh_counts.n_vertices, g->mesh_counts.n_indices, g->mesh_counts.n_submeshes};
             g->mesh_growth_pending = 0;
-            g->mesh_valid = 1;
-            g->mesh_built = 1;
-            g->mesh_serial += 1;
+            mesh_adopt_full(g, totals);
         }
     }
     return IVX_OK;
 }
-
-// developer aid: IVX_MANY_TRACE=1 prints the host time of every phase of the many-object calls
-static bool many_trace() {
-    static const bool on = getenv("IVX_MANY_TRACE") != nullptr;
-    return on;
-}
-struct ManyClock {
-    const char* what;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    explicit ManyClock(const char* w) : what(w) {}
-    void lap(const char* phase) {
-        if (!many_trace()) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[ivx many] %s %s: %.1f us\n", what, phase, 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count());
-        t0 = t1;
-    }
-};
 
 // one absorber per object: spheres (segments3 == NULL) or capsules (segment vectors, 3 floats per object)
 static int absorb_many(ivx_grid* const* grids, size_t n, const char* who, const float* points3, const float* segments3, const float* influence_radii,
@@ -2430,21 +1750,6 @@ int ivx_absorb_capsule_many(ivx_grid* const* grids, size_t n, const float* segme
                             const float* capsule_radii, const float densities[256], ivx_absorb_result* out, uint8_t* const* invalidated_chunks) {
     IVX_REQUIRE(n == 0 || segment_vectors3, IVX_ERR_INVALID, "ivx_absorb_capsule_many: null argument");
     return absorb_many(grids, n, "ivx_absorb_capsule_many", segment_starts3, segment_vectors3, influence_radii, capsule_radii, densities, out, invalidated_chunks);
-}
-
-int ivx_mesh_sync_many(ivx_grid* const* grids, size_t n, const uint8_t* const* invalidated_chunks, ivx_mesh_counts* out) {
-    if (n == 0) return IVX_OK;  // (a manager without voxel objects)
-    int rc = many_check(grids, n, "ivx_mesh_sync_many");
-    if (rc) return rc;
-    IVX_REQUIRE(invalidated_chunks && out, IVX_ERR_INVALID, "ivx_mesh_sync_many: null argument");
-    ManyClock clk("sync");
-    if ((rc = many_phase(grids, n, [&](size_t i) { return mesh_sync_enqueue(grids[i], invalidated_chunks[i], "ivx_mesh_sync_many"); }))) return many_fail(grids, n, rc);
-    clk.lap("enqueue + flush");
-    IVX_HIP_CHECK(ivx_stream_sync(grids[0]->ctx->stream));  // (one wait for all)
-    clk.lap("wait");
-    for (size_t i = 0; i < n; ++i)
-        if ((rc = mesh_sync_collect(grids[i], &out[i], "ivx_mesh_sync_many", true))) return many_fail(grids, n, rc);
-    return IVX_OK;
 }
 
 int ivx_halo_clear(ivx_grid* g, int side) {

@@ -1,8 +1,9 @@
-// What the host units of the C ABI (ivx_api.hip, voxel_collision_api.hip, extraction_api.hip) share and nothing else links against: staged
-// copies, the objects' device scratch, the recorder phases of the many-object calls, what the extraction calls need of the grid life cycle, the
-// regions and the step, and the host mirrors of the reference's range allocators. Defined in ivx_api.hip unless said otherwise (the functions
-// hidden: the library exports what it exported before).
+// What the host units of the C ABI (ivx_api.hip, voxel_collision_api.hip, extraction_api.hip, mesh_api.hip) share and nothing else links
+// against: staged copies, the objects' device scratch, the recorder phases of the many-object calls, what the extraction calls need of the grid
+// life cycle, the regions and the step, what crosses between the mesh unit and the edit and step paths, and the host mirrors of the reference's
+// range allocators. Defined in ivx_api.hip unless said otherwise (the functions hidden: the library exports what it exported before).
 #pragma once
+#include <chrono>
 #include <functional>
 #include <limits>
 #include <map>
@@ -26,6 +27,8 @@ int d2h(ivx_grid* g, void* dst, const void* src, size_t bytes);
 int h2d(ivx_grid* g, void* dst, const void* src, size_t bytes);
 // the object's device scratch (ivx_grid::dev_scratch) holds at least `bytes`; a growth waits for the stream and keeps nothing
 int ensure_dev_scratch(ivx_grid* g, size_t bytes);
+// a shared allocation (ivx_block, ivx_internal.hpp) let go of by one holder: freed with the last
+void block_release(ivx_block* b);
 
 // box sweep + region stages after an edit that changed voxels, enqueued and collected (extraction_api.hip): both halves, and the two apart for a
 // caller that has results of its own in flight behind the same doorbell
@@ -60,6 +63,46 @@ int many_check(ivx_grid* const* grids, size_t n, const char* who);
 int many_phase(ivx_grid* const* grids, size_t n, const std::function<int(size_t)>& f);
 int many_fail(ivx_grid* const* grids, size_t n, int rc);
 
+// developer aid: IVX_MANY_TRACE=1 prints the host time of every phase of the many-object calls (and, summed over a period, of a sync's enqueue)
+inline bool many_trace() {
+    static const bool on = getenv("IVX_MANY_TRACE") != nullptr;
+    return on;
+}
+struct ManyClock {
+    const char* what;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit ManyClock(const char* w) : what(w) {}
+    double lap_us() {  // since the lap before
+        const auto t1 = std::chrono::steady_clock::now();
+        const double us = 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
+        t0 = t1;
+        return us;
+    }
+    void lap(const char* phase) {
+        if (many_trace()) fprintf(stderr, "[ivx many] %s %s: %.1f us\n", what, phase, lap_us());
+    }
+};
+
+// ---- the mesh unit (mesh_api.hip) and the edit and step paths (ivx_api.hip) --------------------------------------------------------------
+// mesh -> edit: what the mesh of `chunk` needs (vertices, indices, kind | flags << 8) when the last edit counted it | the chunks the edit in
+// flight invalidates, from the records its count role delivers early (waits for the role's bell, not for the edit)
+bool edit_needs_lookup(ivx_grid* g, uint32_t chunk, uint32_t out3[3]);
+int edit_early_needs(ivx_grid* g, const char* who, std::vector<uint32_t>& list);
+// edit / many -> mesh: the stream was drained behind the launches of the sync in flight, if there is one (its collect has nothing to wait for)
+// | the sync in flight, if there is one, is given up: collected without a wait, its counts discarded (many_fail, after its own drain)
+void mesh_sync_stream_drained(ivx_grid* g);
+void mesh_sync_abandon(ivx_grid* g);
+// step / many -> mesh. Capacities a growth gives for the needed counts (vertices, indices, submeshes): max(2 n + slack, 2 cap) when the mesh is
+// rebuilt, max(n + n / 2 + slack, 2 cap) when it keeps what it holds; the slack 4096, 24576, 64. The caller takes those of the groups that grow.
+void mesh_grown_capacities(const size_t need[3], const size_t cap[3], bool keep, size_t out[3]);
+// ... room for a mesh rebuilt in full (contents are not kept) | the mesh arrays of several grids from ONE device allocation, `caps3`: the three
+// capacities per grid | "a full mesh of these totals now stands here" | the arrays of a group given up (ivx_grid_destroy)
+int ensure_mesh_capacity(ivx_grid* g, size_t nv, size_t ni, size_t ns);
+int mesh_pool_assign(ivx_grid* const* grids, size_t n, const size_t* caps3);
+void mesh_adopt_full(ivx_grid* g, const uint32_t totals[3]);
+void mesh_group_free(ivx_grid* g, uint32_t group);
+static inline void mesh_set_counts(ivx_grid* g, const uint32_t totals[3]) { g->mesh_counts = ivx_mesh_counts{totals[0], totals[1], totals[2], 0}; }
+
 static inline uint32_t linear_chunk(const ivx_grid* g, const uint32_t c[3]) { return (c[0] * g->cc[1] + c[1]) * g->cc[2] + c[2]; }
 
 // grow device arrays keeping what they hold: every array that has to grow gets its new block and its copy on the stream, then ONE wait by the
@@ -67,7 +110,7 @@ static inline uint32_t linear_chunk(const ivx_grid* g, const uint32_t c[3]) { re
 struct GrowKeep {
     void** slot;
     void* fresh;
-    uint32_t group;  // the mesh group the array belongs to (mesh_group_free); 0: none
+    uint32_t group;  // the mesh group the array belongs to (mesh_group_free, mesh_api.hip); 0: none
 };
 template <class T>
 int grow_keep_enqueue(ivx_grid* g, T** buf, size_t old_count, size_t new_count, std::vector<GrowKeep>& pending, uint32_t group) {
@@ -125,6 +168,12 @@ struct ivx_submesh_manager {
     std::vector<ivx_submesh_data_ranges> updated;     // VoxelMeshModifications (mesh.rs:113-123) since the last report
     bool chunks_were_removed = false;
     uint64_t serial = 0;                              // the mesh_serial this state describes
+    // the sync in flight (no manager: none)
+    int sync_pending = 0;
+    int sync_drained = 0;          // an edit's collect has waited for a doorbell that was rung behind this sync's launches: nothing left to wait for
+    ivx_mapped pinned_up;          // (host-mapped: the sync's kernels read their small lists in place)
+    hipEvent_t up_done = nullptr;  // the last upload from pinned_up has been read
+    int up_busy = 0;
 };
 // VoxelObjectCollisionProbes' bookkeeping (collidable.rs:97-101): chunk -> range of the point buffer, free ranges
 struct ivx_probe_manager {

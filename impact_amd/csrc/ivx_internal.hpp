@@ -88,7 +88,7 @@ struct ivx_ctx {
 };
 
 // A device allocation (and / or a pinned host allocation) shared by several grids that came into being together — the fragments of an impact
-// (fracturing.rs:1047-1189; docs/voxel_gpu_buffer_pooling.md:44-66: arenas, objects hold a part) —, freed by the last holder (ivx_block_release, ivx_api.hip).
+// (fracturing.rs:1047-1189; docs/voxel_gpu_buffer_pooling.md:44-66: arenas, objects hold a part) —, freed by the last holder (block_release, ivx_api.hip).
 struct ivx_block {
     void* dev;
     void* pinned;
@@ -177,7 +177,7 @@ struct ivx_grid {
     // a derive sweep of its own rebuilds it first (ivx_ensure_active_list)
     int active_list_stale;
     int regions_labelled_locally;  // (set around the resolve stage of an edit: the box sweep has labelled the chunk-local regions)
-    struct ivx_edit_state* edit;   // host state of the edit path (ivx_absorb_*_enqueue / _collect, ivx_mesh_sync_enqueue / _collect)
+    struct ivx_edit_state* edit;   // host state of the edit path (ivx_absorb_*_enqueue / _collect)
     // handed to the next k_step_post1 / k_step_gather launch and consumed by it (the edit path's riders on the step's launches)
     uint32_t post1_needs_box[12];         // touched box lo, cc; grown box lo, cc
     const uint32_t* post1_needs_touched;
@@ -284,8 +284,8 @@ struct ivx_grid {
     int occ_ref_valid;
     int bbox_valid;  // the per-chunk boxes the occupied ranges are reduced from exist (written by the derive sweep; the sampler uses the buffer as scratch)
     int mesh_built;  // the mesh buffers hold a mesh of this grid, current (mesh_valid) or made stale by an edit — what ivx_mesh_sync patches
-    struct ivx_submesh_manager* submesh_manager;
-    struct ivx_probe_manager* probe_manager;  // host mirror of the probes' chunk -> point range map and range allocator  // host mirror of the ChunkSubmeshManager, built by the first ivx_mesh_sync after a full remesh
+    struct ivx_submesh_manager* submesh_manager;  // host mirror of the ChunkSubmeshManager, built by the first ivx_mesh_sync after a full remesh; the state of a sync in flight
+    struct ivx_probe_manager* probe_manager;      // host mirror of the probes' chunk -> point range map and range allocator
 };
 
 // host-side description of one pass of the mutual contact generation (see collide.hip)
@@ -593,8 +593,8 @@ int ivx_launch_step_record(ivx_grid* g, const uint32_t* d_pair_count, const void
 int ivx_launch_split_move(ivx_grid* parent, ivx_grid* child, const uint32_t lo[3], const uint32_t cc[3], uint32_t target);
 int ivx_launch_clip(ivx_grid* parent, ivx_grid* child, const uint32_t lo[3], const uint32_t cc[3], const float* planes4, uint32_t n_planes, int extract);
 int ivx_launch_split_repack(ivx_grid* src, ivx_grid* dst, const uint32_t off[3]);
-void ivx_submesh_manager_free(struct ivx_submesh_manager* m);
-void ivx_probe_manager_free(struct ivx_probe_manager* m);
+void ivx_submesh_manager_free(struct ivx_submesh_manager* m);  // mesh_api.hip
+void ivx_probe_manager_free(struct ivx_probe_manager* m);      // voxel_collision_api.hip
 int ivx_launch_sn_emit_list(ivx_grid* g, uint32_t n_records, const uint32_t* d_count, const void* d_records, const uint32_t* d_slots, uint32_t n_patch = 0,
                             const void* d_patch_entries = nullptr, const uint32_t* d_patch_slots = nullptr);
 int ivx_launch_probe_select(ivx_grid* g, uint32_t n_sub, uint32_t log2_bs, uint32_t* d_corner_list, uint32_t* d_sel, uint32_t* d_counts, uint32_t* d_offsets,

@@ -424,6 +424,7 @@ int ivx_capsule_voxel_object_contacts(ivx_grid* g, const float rotation_xyzw[4],
 }
 
 // ---- collision probes + mutual contacts (second part) ---------------------------------------------------------
+void ivx_probe_manager_free(ivx_probe_manager* m) { delete m; }  // (ivx_grid_destroy)
 // determine_log2_block_size_for_object (collidable.rs:451-471)
 static uint32_t probe_log2_block_size(const uint32_t occ[12]) {
     uint32_t min_extent = 0xFFFFFFFFu;

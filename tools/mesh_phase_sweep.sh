@@ -1,6 +1,6 @@
 #!/bin/bash
 # developer experiment: the all-surface step's mesher launch with the mesh arrays carved from one block at different relative offsets
-# (IVX_MESH_ARENA / IVX_MESH_PHASE, ivx_api.hip ensure_mesh_block), three fresh processes per setting. usage (GPU box): tools/mesh_phase_sweep.sh <tag>
+# (IVX_MESH_ARENA / IVX_MESH_PHASE, mesh_api.hip ensure_mesh_block), three fresh processes per setting. usage (GPU box): tools/mesh_phase_sweep.sh <tag>
 tag=${1:-phase}
 out=$PWD/gpurun_out/$tag
 mkdir -p "$out"

@@ -6,8 +6,10 @@ import numpy as np
 import pytest
 
 import parity_util as pu
+import sampler_census as sc
+from impact_amd import capi
 from impact_amd.sdf_graph import SDFGraph, SDFNode
-from impact_amd.voxel import SDFVoxelGenerator
+from impact_amd.voxel import SDFVoxelGenerator, VoxelObject
 from test_gpu_parity import full_pipeline
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +64,82 @@ def test_random_sdf_program(ctx, seed):
     del o
     _, obj = full_pipeline(ctx, g, extent)
     obj.close()
+
+
+# Seeds whose programs are KNOWN to reach the pre-pass's rules (a census of seeds 1000..1299 at voxel extent 1.0, tests/sampler_census.py;
+# 1122, 1191, 1193, 1221 and 1245 of that range have a degenerate root domain), all on grids of at most 336 chunks. What a seed witnesses:
+#   P  chunks on the `poisoned` fallback (a saturation-class drop, then a combination behind the 14-position test: the full program)
+#   S  OP_SKIP ops (a first operand dropped as a mirror image or by its saturation class)
+#   O  OP_COMBINE_OUTSIDE ops (a combination behind the 14-position test)
+#   1  a non-empty two-level list          2  a non-empty general list (programs of stack size >= 3)
+#   M  one-level and two-level lists both non-empty: the second step takes both in one launch (`merge01`)
+# 1039 and 1160 have stack size 2: their poisoned chunks run the full program in the two-level class, the others' in the general class.
+WITNESSED = {1024: "PSO12M", 1039: "PO1", 1041: "PSO12M", 1042: "PSO12M", 1072: "PSO12M", 1092: "PSO12M", 1093: "PSO12M", 1141: "PSO12M", 1160: "PS1M",
+             1169: "PSO12M", 1195: "PSO12M", 1254: "PSO12M", 1259: "PSO12M", 1260: "PSO12M", 1261: "PSO12M", 1263: "PSO12M", 1268: "PSO12M", 1272: "PSO12M"}
+assert all(sum(1 for w in WITNESSED.values() if k in w) >= 8 for k in "PSO12M")
+
+
+def witnessed_program(seed):
+    """(graph, generator at voxel extent 1.0) of a seed of the table"""
+    rng = np.random.default_rng(seed)
+    g = SDFGraph()
+    random_tree(g, rng, int(rng.integers(1, 5)))
+    return g, SDFVoxelGenerator(1.0, g, 0)
+
+
+def resident_object(ctx, gen, ahead=False):
+    obj = VoxelObject(ctx, gen.chunk_counts(), 1.0)
+    obj.set_sdf_program(gen)
+    obj.set_densities(np.ones(256, dtype=np.float32))
+    obj.set_sample_ahead(ahead)
+    return obj
+
+
+def witnesses_of(cen):
+    found = ""
+    found += "P" if cen.poisoned_chunks else ""
+    found += "S" if cen.op_total(sc.OP_SKIP) else ""
+    found += "O" if cen.op_total(sc.OP_COMBINE_OUTSIDE) else ""
+    found += "1" if cen.lists[1] else ""
+    found += "2" if cen.lists[2] else ""
+    found += "M" if cen.lists[0] and cen.lists[1] else ""
+    return found
+
+
+@pytest.mark.parametrize("seed", pu.fuzz_seeds(list(WITNESSED)))
+def test_witnessed_seed_stepped_twice(ctx, seed):
+    """a resident program stepped twice through every stage, each step against the oracle: the second runs with the remembered list
+    lengths, the class gating and, where two classes have work, the merged launch"""
+    g, gen = witnessed_program(seed)
+    if min(gen.chunk_counts()) == 0 or int(np.prod(gen.chunk_counts())) > 2000:
+        assert pu.fuzzing()  # (no committed seed is a degenerate or an oversized one)
+        return
+    o = pu.oracle_from_graph(g)
+    o.update_occupied_voxel_ranges()
+    o.compute_all_derived_state()
+    obj = resident_object(ctx, gen)
+    for i in range(2):
+        r = obj.step(capi.STAGE_ALL)
+        p = pu.step_parity(o, obj, r)
+        assert p["equal"], (i, p)
+    obj.close()
+
+
+def test_witnessed_seeds_still_witness(ctx):
+    """the census again on every seed of the table: a change to the pruning must not quietly turn them into trivial programs"""
+    if pu.fuzzing():
+        pytest.skip("holds for the committed seeds")
+    for seed, want in WITNESSED.items():
+        _, gen = witnessed_program(seed)
+        assert 0 < int(np.prod(gen.chunk_counts())) <= 2000
+        assert len(gen.sdf_generator.nodes) <= sc.OP_CAP  # (an OP_OVERFLOW chunk of such a program is a poisoned one)
+        obj = resident_object(ctx, gen)
+        obj.step(capi.STAGE_ALL)
+        cen = sc.census(obj, len(gen.sdf_generator.nodes))
+        assert sum(cen.lists) == obj.stage_counters()["evaluated_chunks"]
+        obj.close()
+        found = witnesses_of(cen)
+        assert all(k in found for k in want), (seed, want, found)
 
 
 def _far_first_operand_scene(s_outer, s_inner, op, smooth_top):

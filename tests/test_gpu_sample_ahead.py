@@ -1,6 +1,16 @@
 """Sample-ahead (`ivx_grid_set_sample_ahead`): the next sample stage's interval pre-pass rides on the context's second stream behind this
 stage's evaluator, into a second set of the sampler's buffers, and the records it settles wait in a shadow array until the next evaluator
-launch commits them. Whatever order the steps come in, what a step leaves on the device must be what the oracle computes."""
+launch commits them. Whatever order the steps come in, what a step leaves on the device must be what the oracle computes.
+
+A step of an unchanged program rewrites bytes that are resident already: a consumed pre-pass that handed the evaluator an empty list, or
+shadow records that were never committed, would go unseen. So the tests overwrite the planes with junk between sampled steps
+(`clobber`): `ivx_grid_upload_dense` also re-classifies every chunk — all of them come out NonUniform — so the next step has to restore
+the bytes of the evaluated chunks AND the records of the chunks its pre-pass settled (Void / Uniform, parked in the shadow array)."""
+import os
+import subprocess
+import sys
+import tempfile
+
 import numpy as np
 import pytest
 
@@ -10,6 +20,16 @@ from impact_amd.sdf_graph import SDFGraph, SDFNode
 from impact_amd.voxel import SDFVoxelGenerator, VoxelObject
 
 pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def clobber(obj):
+    """0x55 into every byte of the sdf and type planes; every chunk record becomes NonUniform (k_classify)"""
+    n = obj.n_voxels
+    junk_sdf, junk_typ = np.full(n, 0x55, np.int8), np.full(n, 0x55, np.uint8)
+    capi.check(capi.lib().ivx_grid_upload_dense(obj.h, junk_sdf.ctypes.data, junk_typ.ctypes.data, n))
+    info = obj.download(sdf=False, types=False, flags=False, labels=False)[4]
+    assert np.all(info["kind"] == 2) and np.all(info["gen_kind"] == 2)  # (nothing of the step before is left in the records either)
 
 
 def resident_object(ctx, graph, ahead):
@@ -52,6 +72,8 @@ def test_steps_with_the_pre_pass_a_step_ahead_are_the_same_steps(ctx):
         assert ra["mesh"] == rb["mesh"] and ra["region_count"] == rb["region_count"]
         np.testing.assert_array_equal(np.asarray(ra["occupied"]), np.asarray(rb["occupied"]))
         np.testing.assert_array_equal(np.asarray(ra["moments"]["m64"]), np.asarray(rb["moments"]["m64"]))
+        if i < 4:  # (the counters below are the last step's)
+            clobber(a)
     assert a.stage_counters()["evaluated_chunks"] == b.stage_counters()["evaluated_chunks"]
     a.close()
     b.close()
@@ -74,17 +96,21 @@ def test_other_steps_in_between_and_a_new_program(ctx):
     assert pu.step_parity(o1, obj, r)["equal"]
     obj.step(capi.STAGE_DERIVE | capi.STAGE_REGIONS)
     obj.step(capi.STAGE_REMESH)
+    clobber(obj)
     r = obj.step(capi.STAGE_ALL)
     assert pu.step_parity(o1, obj, r)["equal"]
     obj.set_sdf_program(gen2)
     for _ in range(2):
+        clobber(obj)
         r = obj.step(capi.STAGE_ALL)
         assert pu.step_parity(o2, obj, r)["equal"]
     obj.set_sdf_program(gen1)
     for _ in range(2):
+        clobber(obj)
         r = obj.step(capi.STAGE_ALL)
         assert pu.step_parity(o1, obj, r)["equal"]
     obj.set_sample_ahead(False)  # (drops the pre-pass under way)
+    clobber(obj)
     r = obj.step(capi.STAGE_ALL)
     assert pu.step_parity(o1, obj, r)["equal"]
     obj.close()
@@ -143,4 +169,126 @@ def test_random_programs_with_the_pre_pass_a_step_ahead(ctx, seed):
         r = obj.step(capi.STAGE_ALL)
         p = pu.step_parity(o, obj, r)
         assert p["equal"], (i, p)
+        clobber(obj)
     obj.close()
+
+
+def test_two_programs_alternated_every_step(ctx):
+    """two programs of equal chunk counts, the resident one swapped before every step for ten steps: every pre-pass under way was made for
+    the other program and must be dropped, and nothing of the step before may stand in for this step's work (planes clobbered)"""
+    g1, g2 = craters(3), craters(1)
+    gens = (SDFVoxelGenerator(1.0, g1, 0), SDFVoxelGenerator(1.0, g2, 0))
+    assert gens[0].chunk_counts() == gens[1].chunk_counts()
+    os_ = (oracle_of(g1), oracle_of(g2))
+    obj = VoxelObject(ctx, gens[0].chunk_counts(), 1.0)
+    obj.set_densities(np.ones(256, dtype=np.float32))
+    obj.set_sample_ahead(True)
+    for i in range(10):
+        obj.set_sdf_program(gens[i % 2])
+        r = obj.step(capi.STAGE_ALL)
+        p = pu.step_parity(os_[i % 2], obj, r)
+        assert p["equal"], (i, p)
+        clobber(obj)
+    obj.close()
+
+
+def test_steps_enqueued_without_a_collect_in_between(ctx):
+    """three whole steps enqueued back to back, one collect: from the second on the caller has not collected what it enqueued before, so the
+    pre-pass ahead takes its place in the stream's order behind the step's last big launch; then a collected step"""
+    graph = scenes.asteroid_scene(1.0)
+    o = oracle_of(graph)
+    _, obj = resident_object(ctx, graph, True)
+    r = obj.step(capi.STAGE_ALL)
+    assert pu.step_parity(o, obj, r)["equal"]
+    clobber(obj)
+    for _ in range(3):
+        obj.step_enqueue(capi.STAGE_ALL)
+    r = obj.step_collect().copy()
+    p = pu.step_parity(o, obj, r)
+    assert p["equal"], p
+    clobber(obj)
+    r = obj.step(capi.STAGE_ALL)
+    p = pu.step_parity(o, obj, r)
+    assert p["equal"], p
+    obj.close()
+
+
+def _poisoned_seeds():
+    from test_gpu_random_sdf import WITNESSED
+
+    return [s for s, w in WITNESSED.items() if "P" in w][:6]
+
+
+@pytest.mark.parametrize("seed", _poisoned_seeds())
+def test_poisoned_chunks_with_the_pre_pass_a_step_ahead(ctx, seed):
+    """witnessed seeds with chunks on the `poisoned` fallback: from the second step on their OP_OVERFLOW lengths come out of the second set of
+    the sampler's buffers"""
+    import sampler_census as sc
+    from test_gpu_random_sdf import witnessed_program
+
+    g, gen = witnessed_program(seed)
+    o = oracle_of(g)
+    obj = VoxelObject(ctx, gen.chunk_counts(), 1.0)
+    obj.set_sdf_program(gen)
+    obj.set_densities(np.ones(256, dtype=np.float32))
+    obj.set_sample_ahead(True)
+    poisoned = []
+    for i in range(3):
+        r = obj.step(capi.STAGE_ALL)
+        poisoned.append(sc.census(obj, len(gen.sdf_generator.nodes)).poisoned_chunks)
+        p = pu.step_parity(o, obj, r)
+        assert p["equal"], (i, p)
+        clobber(obj)
+    assert poisoned[0] > 0 and poisoned == [poisoned[0]] * 3, poisoned  # (both sets of buffers carried them)
+    obj.close()
+
+
+# ---- the ahead pre-pass's block loop: fewer blocks than super-blocks (IVX_AHEAD_BLOCKS is read once, on first use: a child process) ----
+def ahead_blocks_graph():
+    """6 x 7 x 5 chunks: 2 x 2 x 2 super-blocks, the upper ones ragged"""
+    g = SDFGraph()
+    acc = g.add_node(SDFNode.new_box([64.0, 78.0, 62.0]))
+    for i in range(4):
+        s = g.add_node(SDFNode.new_sphere(14.0 + 2.0 * i))
+        t = g.add_node(SDFNode.new_translation(s, (30.0 - 18.0 * i, -36.0 + 24.0 * i, 28.0 - 16.0 * i)))
+        acc = g.add_node(SDFNode.new_subtraction(acc, t, 2.0) if i % 2 == 0 else SDFNode.new_union(acc, t, 3.0))
+    return g
+
+
+def ahead_blocks_steps(ctx):
+    """three steps with sample-ahead on and the planes clobbered in between: what the last one left (planes, records, step record)"""
+    graph = ahead_blocks_graph()
+    gen, obj = resident_object(ctx, graph, True)
+    for i in range(3):
+        if i:
+            clobber(obj)
+        r = obj.step(capi.STAGE_ALL)
+    sdf, typ, flg, lab, info = obj.download()
+    out = {"sdf": sdf, "type": typ, "flags": flg, "labels": lab, "info": info.view(np.uint8),
+           "counts": np.array([int(r["mesh"]["n_vertices"]), int(r["mesh"]["n_indices"]), int(r["region_count"]), obj.stage_counters()["evaluated_chunks"]], dtype=np.int64),
+           "moments": np.asarray(r["moments"]["m64"], dtype=np.float64).view(np.uint64)}
+    obj.close()
+    return graph, gen, out
+
+
+def test_ahead_pre_pass_walks_the_super_blocks_in_turn(ctx):
+    """IVX_AHEAD_BLOCKS=1: one block walks all eight super-blocks through the loop's barrier; =3: three blocks, two or three rounds each.
+    The bytes are those of the same steps in this process (a block per super-block), which are the oracle's."""
+    graph, gen, want = ahead_blocks_steps(ctx)
+    cc = gen.chunk_counts()
+    assert all(c % 4 != 0 and c > 4 for c in cc), cc
+    o = oracle_of(graph)
+    o_sdf, o_typ, o_flg, o_lab, o_info = o.export_dense()
+    np.testing.assert_array_equal(want["sdf"], o_sdf)
+    np.testing.assert_array_equal(want["flags"], o_flg)
+    np.testing.assert_array_equal(want["info"].view(capi.CHUNK_INFO_DTYPE)["kind"], o_info["kind"])
+    for blocks in ("1", "3"):
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "steps.npz")
+            p = subprocess.run([sys.executable, os.path.join(HERE, "sample_ahead_worker.py"), out], env=dict(os.environ, IVX_AHEAD_BLOCKS=blocks),
+                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+            assert p.returncode == 0, p.stdout[-3000:]
+            got = dict(np.load(out))
+        assert sorted(got) == sorted(want)
+        for k in want:
+            np.testing.assert_array_equal(got[k], want[k], err_msg=f"IVX_AHEAD_BLOCKS={blocks}: {k}")

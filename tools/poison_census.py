@@ -2,7 +2,6 @@
 """Developer tool: how often the sampler's pre-pass falls back to the full program because a saturation-class drop was followed by a
 combination behind the 14-position test (`poisoned`, sdf_sample.hip) — over the random SDF programs of tests/test_gpu_random_sdf.py.
 usage: poison_census.py [first seed] [one past the last]"""
-import ctypes as C
 import os
 import sys
 
@@ -14,13 +13,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from impact_amd import capi  # noqa: E402
 from impact_amd.sdf_graph import SDFGraph  # noqa: E402
 from impact_amd.voxel import Context, SDFVoxelGenerator, VoxelObject  # noqa: E402
+import sampler_census as sc  # noqa: E402
 from test_gpu_random_sdf import random_tree  # noqa: E402
 
 a, b = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (1000, 1300)
 ctx = Context(0)
-lib = capi.lib()
-lib.ivx_grid_device_ptr.restype = C.c_void_p
-hip = C.CDLL("libamdhip64.so")
 tot_chunks = tot_over = progs_with = progs = 0
 for seed in range(a, b):
     rng = np.random.default_rng(seed)
@@ -35,10 +32,8 @@ for seed in range(a, b):
     obj.set_densities(np.ones(256, dtype=np.float32))
     obj.step(capi.STAGE_SAMPLE)
     n = obj.n_chunks
-    lens = np.zeros(n, dtype=np.uint32)
-    hip.hipDeviceSynchronize()
-    assert hip.hipMemcpy(lens.ctypes.data_as(C.c_void_p), C.c_void_p(lib.ivx_grid_device_ptr(obj.h, 7)), lens.nbytes, 2) == 0
-    over = int(np.count_nonzero(lens == 0xFFFFFFFF))
+    # (the sample stage alone: the list counters are still live; these programs have fewer nodes than OP_CAP, so a chunk on the full program is a poisoned one)
+    over = sc.census(obj, len(gen.sdf_generator.nodes), rolled=False).overflow_chunks
     progs += 1
     tot_chunks += n
     tot_over += over

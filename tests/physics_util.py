@@ -24,6 +24,26 @@ def assert_bodies_close(gpu_dyn, orc_dyn, rtol=RTOL, what=""):
         np.testing.assert_array_equal(gpu_dyn[f], orc_dyn[f], err_msg=f)
 
 
+def body_state_error(got, want):
+    """the figure `assert_bodies_close` bounds: the largest error of a state field, relative to the body's vector norm floored as there;
+    `got` maps field names to arrays of any float type (a float64 restatement keeps its precision)"""
+    worst = 0.0
+    for f in STATE_FIELDS:
+        g = np.asarray(got[f], dtype=np.float64)
+        o = want[f].astype(np.float64)
+        scale = np.maximum(np.linalg.norm(o, axis=1, keepdims=True), max(float(np.abs(o).max()), 1e-30) * 1e-2)
+        worst = max(worst, float((np.abs(g - o) / scale).max()))
+    return worst
+
+
+def impulse_error(got, want):
+    """the figure `compare_contact_state` bounds: the largest error of an accumulated impulse, relative to the largest impulse"""
+    if len(want) == 0:
+        return 0.0
+    w = np.asarray(want, dtype=np.float64)
+    return float(np.abs(np.asarray(got, dtype=np.float64) - w).max() / max(float(np.abs(w).max()), 1e-30))
+
+
 def make_pair(ctx, dyn, kin=None, config=(8, 0.4, 3, 0.2)):
     w = PhysicsWorld(ctx, ConstraintSolverConfig(*config))
     w.set_bodies(dyn, kin)
@@ -52,6 +72,22 @@ def static_plane():
     k["orientation"] = (0, 0, 0, 1)
     k["angular_axis"] = (0, 1, 0)
     return k
+
+
+def anisotropic_body(rng, position, velocity=(0.0, 0.0, 0.0), mass=None, spin=1.0):
+    """a body whose rotation matters to every contact: full symmetric positive definite inertia in the body frame (A A^T + 0.5 * 1, condition
+    number between 2 and 30), a random unit orientation, an angular velocity of `spin` times 0.5..1.5 rad/s about a random axis"""
+    while True:
+        a = rng.normal(0.0, 0.5, (3, 3))
+        inertia = a @ a.T + 0.5 * np.eye(3)
+        if 2.0 <= np.linalg.cond(inertia) <= 30.0:
+            break
+    q = rng.normal(size=4)
+    q /= np.linalg.norm(q)
+    axis = rng.normal(size=3)
+    omega = axis / np.linalg.norm(axis) * rng.uniform(0.5, 1.5) * spin
+    m = float(rng.uniform(0.5, 3.0)) if mass is None else float(mass)
+    return ol.rigid_body_new(m, inertia, position, q, velocity, omega)
 
 
 def smoke_check(ctx):

@@ -397,8 +397,8 @@ int ivx_launch_face_ids(ivx_grid* g, int side, uint16_t* d_out) {
 
 int ivx_launch_face_pairs(ivx_grid* g, int side, const uint16_t* d_nbr, uint32_t* d_count, void* d_pairs, uint32_t cap, uint32_t* d_seen) {
     GridView v = ivx_view(g);
-    if (d_seen == d_count + 4) {  // count and seen-table are neighbours (the enqueue path): one fill, unless the pack kernel before cleared them
-        if (!(g->pairs_zeroed && d_count == g->pairs_dev)) IVX_HIP_CHECK(ivx_memset_async(d_count, 0, (4 + 128) * sizeof(uint32_t), g->ctx->stream));
+    if (d_seen == d_count + IVX_PAIRS_COUNTERS) {  // count and seen-table are neighbours (the enqueue path): one fill, unless the pack kernel before cleared them
+        if (!(g->pairs_zeroed && d_count == g->pairs_dev)) IVX_HIP_CHECK(ivx_memset_async(d_count, 0, IVX_PAIRS_HEAD_WORDS * sizeof(uint32_t), g->ctx->stream));
         g->pairs_zeroed = 0;
     } else {
         IVX_HIP_CHECK(ivx_memset_async(d_count, 0, sizeof(uint32_t), g->ctx->stream));
@@ -414,7 +414,7 @@ int ivx_launch_step_record(ivx_grid* g, const uint32_t* d_pair_count, const void
     IVX_KLAUNCH(k_step_record, dim3(1), dim3(256), 0, g->ctx->stream, g->rscalar, d_pair_count, static_cast<const uint2*>(d_pairs),
                        g->chunk_offsets + 2 * (size_t)g->n_chunks, g->partials + g->partial_blocks * 10, g->x_off, max_pairs,
                        static_cast<unsigned long long*>(d_record), ivx_wc(g), g->samp_len ? g->samp_len + g->n_chunks : nullptr,
-                       with_results ? g->result_host_dev : nullptr, ivx_take_tick(g));
+                       with_results ? g->result_host_dev : nullptr, g->timing.take(ivx_many_recording()));
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }

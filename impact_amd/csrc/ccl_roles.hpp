@@ -344,7 +344,7 @@ __device__ __forceinline__ void role_face_pairs(uint32_t bid, const GridView& g,
 // Everything the other ranks need from this slab after a step, as one fixed-size record of 64-bit words written on the
 // device so that it can go straight into an all-gather (impact_amd/distributed.py): [0] components, [1] pairs across the
 // upper face, [2..14) occupied ranges (public layout, global coordinates), [14..17) mesh totals, [18..28) moments (f64
-// bit patterns), [28..28+2*max_pairs) the pairs.
+// bit patterns), then from IVX_RECORD_HEAD_WORDS the 2*max_pairs words of the pairs.
 __device__ __forceinline__ void role_step_record(const uint32_t* __restrict__ rscalar, const uint32_t* __restrict__ pair_count,
                                                  const uint2* __restrict__ pairs, const uint32_t* __restrict__ mesh_totals,
                                                  const double* __restrict__ moments, uint32_t x_off, uint32_t max_pairs,
@@ -372,8 +372,8 @@ __device__ __forceinline__ void role_step_record(const uint32_t* __restrict__ rs
     }
     if (tid < 10) rec[18 + tid] = (unsigned long long)__double_as_longlong(moments[tid]);
     for (uint32_t i = tid; i < min(np, max_pairs); i += 256u) {
-        rec[28 + 2 * i] = pairs[i].x;
-        rec[29 + 2 * i] = pairs[i].y;
+        rec[IVX_RECORD_HEAD_WORDS + 2 * i] = pairs[i].x;
+        rec[IVX_RECORD_HEAD_WORDS + 1 + 2 * i] = pairs[i].y;
     }
 }
 

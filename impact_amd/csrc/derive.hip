@@ -1322,7 +1322,7 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
         // not look at the ghost layers' chunk records — a Uniform chunk of a face plane that only such a record can settle is left pending)
         if (g->ghost_event && g->ghost_split && ivx_has_interior_planes(g)) pa.defer_ghost = 1u;
         const uint32_t blocks = (g->n_chunks + 255u) / 256u;
-        pa.tick = ivx_take_tick(g);
+        pa.tick = g->timing.take(ivx_many_recording());
         if (!ivx_many_try(g->ctx, g, IVX_MK_CHUNK_PRE, blocks, pa)) IVX_KLAUNCH(k_chunk_pre, dim3(blocks), dim3(256), 0, g->ctx->stream, pa);
         face_settle = pa;
         face_settle.tick = nullptr;
@@ -1356,7 +1356,7 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
     }
     auto sweep = [&](uint32_t x_part) {
         da.x_part = x_part;
-        da.tick = ivx_take_tick(g);
+        da.tick = g->timing.take(ivx_many_recording());
         if (g->signs_current) {
             if (ivx_many_try(g->ctx, g, IVX_MK_DERIVE_SIGNS, derive_grid, da)) return;
             if (x_part == IVX_XPART_ALL && v.ghost_sdf[0] == nullptr && v.ghost_sdf[1] == nullptr)

@@ -5,7 +5,6 @@
 #include <array>
 #include <functional>
 #include <cmath>
-#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <new>
@@ -338,13 +337,13 @@ extern "C++" int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, f
     if (!blk) return fail(IVX_ERR_CAPACITY);
     blk->dev = blk->pinned = nullptr;
     blk->refs = 0;
-    if (hipMalloc(&blk->dev, off[n]) != hipSuccess || hipHostMalloc(&blk->pinned, n * 256, hipHostMallocMapped) != hipSuccess) {
+    if (hipMalloc(&blk->dev, off[n]) != hipSuccess || hipHostMalloc(&blk->pinned, n * IVX_RB_STRIDE_BYTES, hipHostMallocMapped) != hipSuccess) {
         ivx_set_error("%s: allocation of %zu bytes for %zu grids failed", who, off[n], n);
         blk->refs = 1;
         block_release(blk);
         return fail(IVX_ERR_HIP);
     }
-    memset(blk->pinned, 0, n * 256);
+    memset(blk->pinned, 0, n * IVX_RB_STRIDE_BYTES);
     void* pinned_dev = nullptr;
     if (hipHostGetDevicePointer(&pinned_dev, blk->pinned, 0) != hipSuccess) {
         blk->refs = 1;
@@ -356,8 +355,8 @@ extern "C++" int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, f
         g->arena = static_cast<char*>(blk->dev) + off[i];
         (void)grid_carve(g, g->arena);
         g->arena_block = blk;
-        g->result_host = reinterpret_cast<uint32_t*>(static_cast<char*>(blk->pinned) + i * 256);
-        g->result_host_dev = reinterpret_cast<uint32_t*>(static_cast<char*>(pinned_dev) + i * 256);
+        g->result_host = reinterpret_cast<uint32_t*>(static_cast<char*>(blk->pinned) + i * IVX_RB_STRIDE_BYTES);
+        g->result_host_dev = reinterpret_cast<uint32_t*>(static_cast<char*>(pinned_dev) + i * IVX_RB_STRIDE_BYTES);
         g->host_block = blk;
         blk->refs += 2;
     }
@@ -391,10 +390,7 @@ void ivx_grid_destroy(ivx_grid* g) {
         if (p) (void)hipFree(p);
     if (g->host_scratch) (void)hipHostFree(g->host_scratch);
     if (g->result_host) (void)hipHostFree(g->result_host);
-    if (g->tick_dev) (void)hipFree(g->tick_dev);  // (the stage stamps' words: two small allocations of their own, made on first use)
-    if (g->tick_host) (void)hipHostFree(g->tick_host);
-    if (g->ev_ready)
-        for (int i = 0; i < 2 * IVX_N_TIMED_STAGES; ++i) (void)hipEventDestroy(g->ev[i]);
+    stage_clock_free(g);
     delete g;
 }
 
@@ -405,11 +401,7 @@ int ivx_grid_upload_dense(ivx_grid* g, const int8_t* sdf, const uint8_t* type, s
     if ((rc = h2d(g, g->sdf, sdf, g->n_vox))) return rc;
     if ((rc = h2d(g, g->type, type, g->n_vox))) return rc;
     if ((rc = ivx_launch_classify(g))) return rc;
-    g->mesh_valid = 0;
-    g->mesh_built = 0;
-    g->occ_ref_valid = 0;
-    g->bbox_valid = 0;
-    g->regions_valid = 0;
+    ivx_voxels_replaced(g);
     IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
     return IVX_OK;
 }
@@ -505,11 +497,7 @@ int ivx_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* nodes, size_t n_no
     rc = ivx_launch_sdf_sample(g, static_cast<const ivx_sdf_processed_node*>(g->dev_scratch), (uint32_t)n_nodes, (uint32_t)max_depth, grid_shape,
                                shifted_grid_center, voxel_type, 0u, false, ivx_sdf_has_noise(nodes, n_nodes));
     if (rc) return rc;
-    g->mesh_valid = 0;
-    g->mesh_built = 0;
-    g->occ_ref_valid = 0;
-    g->bbox_valid = 0;
-    g->regions_valid = 0;
+    ivx_voxels_replaced(g);
     IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
     return IVX_OK;
 }
@@ -527,15 +515,8 @@ int ivx_derive_state(ivx_grid* g) {
 int ivx_occupied_ranges(ivx_grid* g, uint32_t out[12]) {
     IVX_REQUIRE(g && out, IVX_ERR_INVALID, "ivx_occupied_ranges: null argument");
     IVX_REQUIRE(g->bbox_valid, IVX_ERR_STATE, "ivx_occupied_ranges: the chunk boxes come from the derive sweep (call ivx_derive_state first)");
-    uint32_t* d = g->rscalar + 16;
-    int rc;
-    if ((rc = ivx_launch_occupied(g, d))) return rc;
-    uint32_t raw[12];
-    if ((rc = d2h(g, raw, d, 12 * sizeof(uint32_t)))) return rc;
-    ivx_occupied_from_raw(g, raw, out);
-    memcpy(g->occ_ref, out, sizeof(g->occ_ref));  // VoxelObject::update_occupied_ranges: this is what the object holds from now on
-    g->occ_ref_valid = 1;
-    return IVX_OK;
+    g->occ_ref_valid = 0;  // VoxelObject::update_occupied_ranges: reduced anew, and this is what the object holds from now on
+    return reference_occupied(g, out);
 }
 
 // a density table for ONE call: the resident copy when it is the resident table (ivx_grid_set_densities), else a copy of its own behind the
@@ -572,13 +553,13 @@ int ivx_label_regions(ivx_grid* g, uint32_t* region_count) {
     if ((rc = ivx_launch_ccl_local(g, 0))) return rc;
     if ((rc = ivx_launch_ccl_merge(g))) return rc;
     if ((rc = ivx_launch_ccl_resolve(g))) return rc;
-    uint32_t sc[2];
+    uint32_t sc[IVX_RB_FLAGS + 1];  // (the region scalars: the head of what a step's result block holds)
     if ((rc = d2h(g, sc, g->rscalar, sizeof(sc)))) return rc;
-    IVX_REQUIRE((sc[1] & 1u) == 0, IVX_ERR_CAPACITY,
+    IVX_REQUIRE((sc[IVX_RB_FLAGS] & IVX_RB_FLAG_LOCAL_REGIONS) == 0, IVX_ERR_CAPACITY,
                 "ivx_label_regions: a chunk has more than 254 local regions (the reference's CHUNK_MAX_REGIONS limit, split_detection.rs:145-157)");
-    g->region_count = sc[0];
+    g->region_count = sc[IVX_RB_REGION_TOTAL];
     g->regions_valid = 1;
-    *region_count = sc[0];
+    *region_count = sc[IVX_RB_REGION_TOTAL];
     return IVX_OK;
 }
 
@@ -860,6 +841,24 @@ static int absorb_enqueue(ivx_grid* g, const char* who, int capsule, const float
     return IVX_OK;
 }
 
+// The records of the edit's count role — a uint4 per chunk of the grown box: bit 31 | kind | flags << 8, vertices, indices, chunk — become
+// e->needs, ascending by chunk; with `invalidated_chunks`, the chunks they name are marked there.
+static void edit_take_needs(ivx_grid* g, const uint32_t* needs, uint8_t* invalidated_chunks) {
+    ivx_edit_state* e = g->edit;
+    const size_t grown = (size_t)e->bcc[0] * e->bcc[1] * e->bcc[2];
+    e->needs.clear();
+    for (size_t b = 0; b < grown; ++b) {
+        const uint32_t w = needs[4 * b];
+        if (!(w & 0x80000000u)) continue;
+        const uint32_t c = needs[4 * b + 3];
+        if (invalidated_chunks) invalidated_chunks[c] = 1;
+        e->needs.push_back({c, needs[4 * b + 1], needs[4 * b + 2], w & 0xFFFFu});
+    }
+    if (!std::is_sorted(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; }))
+        std::sort(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; });
+    g->needs_current = 1;
+}
+
 static int absorb_collect(ivx_grid* g, const char* who, ivx_absorb_result* out, uint32_t* emptied_by_type, uint8_t* invalidated_chunks) {
     IVX_REQUIRE(g && out, IVX_ERR_INVALID, "%s: null argument", who);
     ivx_many_other_context other_(g->ctx);
@@ -903,18 +902,7 @@ static int absorb_collect(ivx_grid* g, const char* who, ivx_absorb_result* out, 
     // handle_chunk_voxels_modified (intersection.rs:560-598): the touched chunk, and a neighbour when the touched voxel range of the chunk
     // comes within two voxels of the face they share — decided on the device per chunk of the grown box, with what its mesh needs now
     const uint32_t* needs = reinterpret_cast<const uint32_t*>(e->early_armed ? static_cast<const char*>(e->pinned) + e->off_early : hb + e->off_needs);
-    const size_t grown = (size_t)e->bcc[0] * e->bcc[1] * e->bcc[2];
-    e->needs.clear();  // (an early sync may have filled them from the same records)
-    for (size_t b = 0; b < grown; ++b) {
-        const uint32_t w = needs[4 * b];
-        if (!(w & 0x80000000u)) continue;
-        const uint32_t c = needs[4 * b + 3];
-        if (invalidated_chunks) invalidated_chunks[c] = 1;
-        e->needs.push_back({c, needs[4 * b + 1], needs[4 * b + 2], w & 0xFFFFu});
-    }
-    if (!std::is_sorted(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; }))
-        std::sort(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; });
-    g->needs_current = 1;
+    edit_take_needs(g, needs, invalidated_chunks);  // (an early sync may have taken them from the same records)
     return IVX_OK;
 }
 
@@ -929,32 +917,12 @@ extern "C++" int edit_early_needs(ivx_grid* g, const char* who, std::vector<uint
                 "host-mapped block): collect it and pass its set",
                 who);
     if (!e->early_taken) {
-        const volatile uint32_t* bell = reinterpret_cast<const volatile uint32_t*>(static_cast<const char*>(e->pinned) + e->off_bell);
         (void)ivx_many_break();
         bool rung = false;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t it = 0;; ++it) {
-            if (*bell == e->early_seq) {
-                rung = true;
-                break;
-            }
-            __builtin_ia32_pause();
-            if ((it & 255u) == 255u && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > 2000) break;
-        }
-        if (!rung) IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
-        std::atomic_thread_fence(std::memory_order_acquire);
-        IVX_REQUIRE(*bell == e->early_seq, IVX_ERR_HIP, "%s: the edit's mesh needs never arrived", who);
-        const uint32_t* needs = reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->pinned) + e->off_early);
-        const size_t grown = (size_t)e->bcc[0] * e->bcc[1] * e->bcc[2];
-        e->needs.clear();
-        for (size_t b = 0; b < grown; ++b) {
-            const uint32_t w = needs[4 * b];
-            if (!(w & 0x80000000u)) continue;
-            e->needs.push_back({needs[4 * b + 3], needs[4 * b + 1], needs[4 * b + 2], w & 0xFFFFu});
-        }
-        if (!std::is_sorted(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; }))
-            std::sort(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; });
-        g->needs_current = 1;
+        const int rc = doorbell_wait(reinterpret_cast<const volatile uint32_t*>(static_cast<const char*>(e->pinned) + e->off_bell), e->early_seq, 2000000u, g->ctx->stream, &rung);
+        if (rc) return rc;
+        IVX_REQUIRE(rung, IVX_ERR_HIP, "%s: the edit's mesh needs never arrived", who);
+        edit_take_needs(g, reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->pinned) + e->off_early), nullptr);
         e->early_taken = 1;
     }
     for (const auto& n : e->needs) list.push_back(n[0]);
@@ -1068,437 +1036,6 @@ int ivx_grid_set_densities(ivx_grid* g, const float densities[256]) {
     return IVX_OK;
 }
 
-// Timed slots of a step (ivx_step_result::stage_ms): 0 sample (k_sdf_super, k_sdf_prepass, k_sdf_eval), 1 derive (k_chunk_pre, k_derive:
-// flags, chunk state, chunk-local regions, chunk moments), 2 k_step_post1 (mesher count | region merge by columns | occupied slots
-// | moment partial sums), 3 k_step_post2 (exact local numbering -> multi-region merge | mesher scan | moments and occupied ranges
-// final), 4 k_step_emit (region forest flatten | mesher emit), 5 k_step_assign (component ids); 6..9 unused.
-//
-// How a timed slot is measured. On the step's fused path — a whole call (`part` 3) outside the slab protocol's remesh phase, on a grid
-// the fused assign reaches, with the derive stage in it or nothing left for the stand-alone per-chunk kernels, not recorded into a batch —
-// a slot costs the queue nothing: block 0 of the slot's first launch writes the device's constant-rate clock to a word on entry
-// (ivx_stage_stamp), block 0 of the first launch enqueued BEHIND the slot writes the closing word, and the slot's time is the distance of
-// the two: start to start, the launch boundary behind the slot included. Adjacent timed slots share the word between them. The closing word
-// of a call's last slot goes to whatever stamping launch this grid makes next — the next call's first kernel, or k_step_gather (a launch
-// of another object enqueued in between, the bench's k_free_step, falls into that boundary). The gather copies the words to host-mapped
-// memory ahead of the doorbell and zeroes them. Every other call keeps two event records per slot, 2-3 us each on the queue — which is
-// what the 6 us boundaries on either side of a timed k_step_emit were (profiles/stage_stamps) —, and IVX_STAGE_TIMING_EVENTS=1 (read once)
-// forces that path everywhere. One call never mixes the two clocks. ivx_grid_set_stage_timing(g, 0) turns timing off.
-static const bool g_stage_timing_events = [] {
-    const char* e = getenv("IVX_STAGE_TIMING_EVENTS");
-    return e && atoi(e) == 1;
-}();
-static int ensure_stage_events(ivx_grid* g) {
-    if (g->ev_ready) return IVX_OK;
-    for (int i = 0; i < 2 * IVX_N_TIMED_STAGES; ++i) IVX_HIP_CHECK(hipEventCreate(&g->ev[i]));
-    g->ev_ready = 1;
-    return IVX_OK;
-}
-static int ensure_stage_ticks(ivx_grid* g) {
-    if (g->tick_dev && g->tick_host) return IVX_OK;
-    if (!g->tick_dev) {
-        IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->tick_dev), IVX_TICK_WORDS * sizeof(unsigned long long)));
-        IVX_HIP_CHECK(hipMemset(g->tick_dev, 0, IVX_TICK_WORDS * sizeof(unsigned long long)));
-    }
-    if (!g->tick_host) {
-        IVX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->tick_host), IVX_TICK_WORDS * sizeof(unsigned long long), hipHostMallocMapped));
-        memset(g->tick_host, 0, IVX_TICK_WORDS * sizeof(unsigned long long));
-        IVX_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g->tick_host_dev), g->tick_host, 0));
-    }
-    return IVX_OK;
-}
-static int ensure_pairs(ivx_grid* g);
-// `slab_nbr_ids` / `slab_record`: the slab protocol's remesh phase (ivx_slab_remesh_enqueue) — the pass over the neighbour's face ids and the
-// slab's record ride in the phase's own launches instead of taking two more
-// `part` (slab protocol, ivx_voxel_step_enqueue_part): bit 0 = the call's sample and derive sweeps, bit 1 = everything behind them; the two
-// halves of ONE call enqueued apart, so that the slab's face planes can be packed and sent between them.
-static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_ids, void* slab_record, uint32_t part = 3u) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_voxel_step_enqueue: null grid");
-    const bool front = (part & 1u) != 0u, back = (part & 2u) != 0u;
-    ivx_many_other_context other_(g->ctx);
-    IVX_REQUIRE(!(stages & IVX_STAGE_SAMPLE) || g->prog_n > 0, IVX_ERR_STATE, "ivx_voxel_step: no SDF program resident (ivx_grid_set_sdf_program)");
-    IVX_REQUIRE(!(stages & IVX_STAGE_INERTIA) || g->has_dens, IVX_ERR_STATE, "ivx_voxel_step: no densities resident (ivx_grid_set_densities)");
-    hipStream_t s = g->ctx->stream;
-    g->ahead_unordered_ok = g->pending_stages == 0;  // (sample-ahead: whatever was enqueued before has been collected)
-    // stages enqueued after a record change the step's results: the block the record role wrote is stale (this call sets the flag again
-    // further down when it carries the slab record itself)
-    g->results_in_block = 0;
-    if (!g->result_host) {
-        IVX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->result_host), 64 * sizeof(uint32_t), hipHostMallocMapped));
-        memset(g->result_host, 0, 64 * sizeof(uint32_t));
-        IVX_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g->result_host_dev), g->result_host, 0));
-    }
-    int rc;
-    if (stages & IVX_STAGE_SAMPLE)
-        if ((rc = ivx_sampler_buffers(g))) return rc;
-    // Scratch word groups the stages of this call start from. They are preset by the call's first kernel (k_sdf_super or
-    // k_chunk_pre host that role); a call that starts with neither gets a preset launch of its own. Only the requested stages'
-    // groups are touched: a phase of the multi-GPU protocol must not wipe what an earlier phase of the same step left.
-    uint32_t preset_in_sample = 0, preset_in_derive = 0;
-    if (front) {  // (the second half of a call enqueued in two parts finds its groups preset by the first half's kernels)
-        uint32_t need = 0;
-        if (stages & IVX_STAGE_SAMPLE) need |= IVX_SCRATCH_EVAL;
-        if (stages & IVX_STAGE_REGIONS) need |= IVX_SCRATCH_REGIONS;
-        if (stages & IVX_STAGE_REMESH) need |= IVX_SCRATCH_SN;
-        // (ivx_step_preset_ahead: groups of the NEXT call, preset by this call's first kernel so that a call without one of its own — the
-        // remesh phase of the slab protocol — needs no preset launch)
-        const uint32_t fresh = g->preset_fresh;
-        g->preset_fresh = 0;
-        uint32_t ahead = 0;
-        if (stages & (IVX_STAGE_SAMPLE | IVX_STAGE_DERIVE)) {
-            ahead = g->preset_ahead & ~need;
-            g->preset_ahead = 0;
-        }
-        if (stages & IVX_STAGE_SAMPLE) preset_in_sample = need | ahead;
-        else if (stages & IVX_STAGE_DERIVE) preset_in_derive = need | ahead;
-        else if ((rc = ivx_launch_step_preset(g, need & ~fresh))) return rc;
-        g->preset_fresh = ahead;
-    }
-    // derive runs the chunk-local region labelling and the chunk moments in the same sweep when those stages are part of this call
-    const uint32_t fused_parts = (stages & IVX_STAGE_DERIVE) ? (((stages & IVX_STAGE_REGIONS) ? IVX_PART_REGIONS : 0u) |
-                                                                 ((stages & IVX_STAGE_INERTIA) ? IVX_PART_MOMENTS : 0u))
-                                                              : 0u;
-    const uint32_t post = back ? stages & (IVX_STAGE_OCCUPIED | IVX_STAGE_REGIONS | IVX_STAGE_REMESH | IVX_STAGE_INERTIA) : 0u;
-    // (a call without the derive stage: stand-alone per-chunk kernels, which carry no stamp, run ahead of k_step_post1)
-    const bool standalone_first = ((post & IVX_STAGE_REGIONS) && !(fused_parts & IVX_PART_REGIONS) && !g->regions_labelled_locally) ||
-                                  ((post & IVX_STAGE_INERTIA) && !(fused_parts & IVX_PART_MOMENTS));
-    const uint32_t timing = ~g->stage_timing_off;  // timed slots
-    // stamps or events, for the whole call (see above); a call takes at most a word per slot and one more
-    const bool stamps = timing != 0u && !g_stage_timing_events && !g->stage_events_only && part == 3u && !slab_record && ivx_step_assign_fits(g) && !standalone_first &&
-                        !ivx_many_recording() && g->tick_used + IVX_N_TIMED_STAGES + 1u <= IVX_TICK_WORDS;
-    if (stamps && (rc = ensure_stage_ticks(g))) return rc;
-    if (timing != 0u && !stamps && (rc = ensure_stage_events(g))) return rc;
-    // events: a slot's duration runs from the stop event of the slot enqueued just before it, when there is one
-    hipEvent_t* last_stop = nullptr;
-    // stamps: the word the open slot starts at, and whether the slot armed it itself (else it is the closing word of the slot before, still pending)
-    int slot_word = -1;
-    bool slot_fresh = false;
-#define T0(i)                                                                            \
-    if (!((timing >> (i)) & 1u)) last_stop = nullptr;                                    \
-    else if (stamps) {                                                                   \
-        slot_fresh = g->tick_next == nullptr;                                            \
-        if (slot_fresh) {                                                                \
-            g->tick_host[g->tick_used] = 0ull;                                           \
-            g->tick_next = g->tick_dev + g->tick_used++;                                 \
-        }                                                                                \
-        slot_word = (int)(g->tick_next - g->tick_dev);                                   \
-    } else {                                                                             \
-        if (last_stop) g->ev_start_ref[i] = last_stop;                                   \
-        else {                                                                           \
-            IVX_HIP_CHECK(ivx_event_record(g->ev[2 * (i)], s));                          \
-            g->ev_start_ref[i] = &g->ev[2 * (i)];                                        \
-        }                                                                                \
-    }
-    // (stamps: a word that nobody took means the slot launched nothing — it reports 0, and a word it armed itself is given back)
-#define T1(i)                                                                            \
-    if ((timing >> (i)) & 1u) {                                                          \
-        if (stamps) {                                                                    \
-            g->stamp_mask |= 1u << (i), g->timed_mask &= ~(1u << (i));                   \
-            if (g->tick_next == g->tick_dev + slot_word) {                               \
-                g->tick_start_ref[i] = g->tick_end_ref[i] = -1;                          \
-                if (slot_fresh) g->tick_next = nullptr, --g->tick_used;                  \
-            } else {                                                                     \
-                g->tick_start_ref[i] = (int8_t)slot_word;                                \
-                g->tick_end_ref[i] = (int8_t)g->tick_used;                               \
-                g->tick_host[g->tick_used] = 0ull;                                       \
-                g->tick_next = g->tick_dev + g->tick_used++;                             \
-            }                                                                            \
-        } else {                                                                         \
-            IVX_HIP_CHECK(ivx_event_record(g->ev[2 * (i) + 1], s));                      \
-            last_stop = &g->ev[2 * (i) + 1];                                             \
-            g->timed_mask |= 1u << (i), g->stamp_mask &= ~(1u << (i));                   \
-        }                                                                                \
-    }
-    if (front && (stages & IVX_STAGE_SAMPLE)) {
-        T0(0);
-        if ((rc = ivx_launch_sdf_sample(g, g->prog_nodes, g->prog_n, g->prog_stack, g->prog_shape, g->prog_center, g->prog_type, preset_in_sample, true,
-                                        g->prog_noise != 0))) return rc;
-        T1(0);
-        g->eval_len_pending = 1;  // (the list lengths reach the result block once a derive sweep has rolled the counters over)
-        g->occ_ref_valid = 0;
-        g->bbox_valid = 0;
-        g->mesh_valid = 0;
-        g->mesh_built = 0;  // a newly sampled object: whatever mesh the buffers hold is not a stale version of this one
-        g->regions_valid = 0;
-    }
-    if (front && (stages & IVX_STAGE_DERIVE)) {
-        T0(1);
-        if ((rc = ivx_launch_derive(g, fused_parts, preset_in_derive))) return rc;
-        T1(1);
-        if (g->eval_len_pending == 1) g->eval_len_pending = 2;
-    }
-    if (post) {
-        // stages that were not swept inside k_derive get their stand-alone per-chunk kernels first (a call without the derive stage)
-        if ((stages & IVX_STAGE_REGIONS) && !(fused_parts & IVX_PART_REGIONS)) {
-            // (level 1 over the active list; the exact numbering of multi-region chunks leads k_step_post2 below, so
-            // only the list-driven labelling kernel is launched here: ivx_launch_ccl_local would run both)
-            if (!g->regions_labelled_locally && (rc = ivx_launch_ccl_local_only(g))) return rc;
-        }
-        if ((stages & IVX_STAGE_INERTIA) && !(fused_parts & IVX_PART_MOMENTS))
-            if ((rc = ivx_launch_inertia_dense(g))) return rc;
-        const bool fused_assign = ivx_step_assign_fits(g);
-        T0(2);
-        if ((rc = ivx_launch_step_post1(g, post))) return rc;
-        T1(2);
-        T0(3);
-        if (slab_record) {
-            if ((rc = ensure_pairs(g))) return rc;
-            if (slab_nbr_ids && !g->pairs_zeroed) IVX_HIP_CHECK(ivx_memset_async(g->pairs_dev, 0, (4 + 128) * sizeof(uint32_t), s));
-            g->pairs_zeroed = 0;
-        }
-        if ((rc = ivx_launch_step_post2(g, post, slab_nbr_ids))) return rc;
-        T1(3);
-        // no host round trip for the mesh sizes: the emit pass writes into the buffers of the previous step and skips what
-        // does not fit; ivx_voxel_step_collect grows the buffers and repeats the pass in that (rare) case
-        if (post & (IVX_STAGE_REGIONS | IVX_STAGE_REMESH)) {
-            T0(4);
-            if (fused_assign) {
-                if ((rc = ivx_launch_step_emit(g, post, (post & IVX_STAGE_REGIONS) != 0, slab_record, slab_nbr_ids != nullptr))) return rc;
-                if (slab_record) g->results_in_block = 1;
-            } else {  // more than 524 288 chunks: the region resolve takes its stand-alone path
-                if ((post & IVX_STAGE_REMESH) && (rc = ivx_launch_step_emit(g, IVX_STAGE_REMESH))) return rc;
-                if ((post & IVX_STAGE_REGIONS) && (rc = ivx_launch_ccl_resolve(g))) return rc;
-            }
-            T1(4);
-        }
-        // (sample-ahead: the next sample stage's pre-pass goes behind the step's last big launch, beside the small ones that follow)
-        if (!g->ahead_unordered_ok && (rc = ivx_sampler_launch_ahead(g, true))) return rc;
-        if ((post & IVX_STAGE_REGIONS) && fused_assign) {
-            T0(5);
-            if ((rc = ivx_launch_step_assign(g, (post & IVX_STAGE_REMESH) != 0))) return rc;
-            T1(5);
-        }
-        if (post & IVX_STAGE_REMESH) {
-            g->mesh_valid = 0;
-            g->scratch_dirty |= IVX_SCRATCH_SN;
-        }
-        if (post & IVX_STAGE_REGIONS) g->scratch_dirty |= IVX_SCRATCH_REGIONS;
-    }
-#undef T0
-#undef T1
-    if (back && (rc = ivx_sampler_launch_ahead(g, !g->ahead_unordered_ok))) return rc;  // (a call without the stages behind the derive sweep)
-    g->pending_stages |= stages;
-    return IVX_OK;
-}
-
-int ivx_voxel_step_enqueue(ivx_grid* g, uint32_t stages) { return step_enqueue(g, stages, nullptr, nullptr); }
-// ... without event records around the stage slots, whatever ivx_grid_set_stage_timing has asked for: for callers whose stage times nobody reads,
-// and for recorded steps — an event is a stream operation of its own and would end the merging after every object
-extern "C++" int step_enqueue_untimed(ivx_grid* g, uint32_t stages) {
-    const uint32_t keep = g->stage_timing_off;
-    g->stage_timing_off = 0xFFFFFFFFu;
-    const int rc = step_enqueue(g, stages, nullptr, nullptr);
-    g->stage_timing_off = keep;
-    return rc;
-}
-}  // extern "C"
-// (slab_comm.cpp) one call's launches in two parts: 1 = its sample and derive sweeps, 2 = what follows them
-int ivx_voxel_step_enqueue_part(ivx_grid* g, uint32_t stages, uint32_t part) { return step_enqueue(g, stages, nullptr, nullptr, part); }
-extern "C" {
-
-// The remesh phase of the slab protocol in the step's own launches: count | — then scan | the component pairs across the upper x face (from
-// `neighbour_face_ids`, the ids behind the neighbour's face planes of the second exchange; null for the last slab) — then emit | the slab's
-// record into `device_record` and the step's small results into the grid's host-mapped block — then the mesher's general pass. Four launches
-// where face pairs, the remesh stage and the record took six; ivx_voxel_step_collect then has its results without a launch of its own (the
-// caller waits for the stream first: the slab protocol's doorbell).
-int ivx_slab_remesh_enqueue(ivx_grid* g, const void* neighbour_face_ids, void* device_record) {
-    IVX_REQUIRE(g && device_record, IVX_ERR_INVALID, "ivx_slab_remesh_enqueue: null argument");
-    if (!ivx_step_assign_fits(g)) {  // (grids beyond the fused launches' reach: the separate passes)
-        int rc;
-        if (neighbour_face_ids && (rc = ivx_region_face_pairs_enqueue(g, 1, neighbour_face_ids))) return rc;
-        if ((rc = step_enqueue(g, IVX_STAGE_REMESH, nullptr, nullptr))) return rc;
-        if ((rc = ivx_step_record_enqueue(g, device_record))) return rc;
-        if (g->record_head_copy)
-            IVX_HIP_CHECK(ivx_memcpy_async(g->record_head_copy, device_record, (size_t)g->record_head_words * 8, hipMemcpyDeviceToDevice, g->ctx->stream));
-        return IVX_OK;
-    }
-    g->pairs_enqueued = 0;
-    return step_enqueue(g, IVX_STAGE_REMESH, static_cast<const uint16_t*>(neighbour_face_ids), device_record);
-}
-
-// Sample-ahead: with `on`, every sample stage under the resident program also enqueues the NEXT sample stage's pre-pass — on the context's
-// second stream, behind its own evaluator —, and the next sample stage starts at its evaluator. For callers that sample the same program
-// step after step (the bench's headline step); the results are the same bytes either way. Off (the default): the pre-pass is the stage's
-// first kernel. Turning it off drops a pre-pass that is under way.
-int ivx_grid_set_sample_ahead(ivx_grid* g, int on) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_grid_set_sample_ahead: null grid");
-    g->ahead_on = on ? 1 : 0;
-    if (!on) return ivx_sampler_ahead_cancel(g);
-    return IVX_OK;
-}
-
-int ivx_grid_set_stage_timing(ivx_grid* g, uint32_t slot_mask) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_grid_set_stage_timing: null grid");
-    g->stage_timing_off = ~slot_mask;
-    return IVX_OK;
-}
-
-// Developer aid: the raw clock stamps behind the last collected step's stage_ms, start then end per slot (0: the slot was not stamped — not
-// timed, without a launch, or timed by events), and the clock's rate in kHz.
-int ivx_debug_stage_ticks(ivx_grid* g, unsigned long long ticks[2 * IVX_N_TIMED_STAGES], double* clock_khz) {
-    IVX_REQUIRE(g && ticks, IVX_ERR_INVALID, "ivx_debug_stage_ticks: null argument");
-    memcpy(ticks, g->tick_last, sizeof(g->tick_last));
-    if (clock_khz) *clock_khz = g->ctx->wall_clock_khz;
-    return IVX_OK;
-}
-
-// How long ivx_voxel_step_collect polls the doorbell before it falls back to hipStreamSynchronize (IVX_COLLECT_SPIN_US, default 2000;
-// 0 = never poll).
-static uint64_t collect_spin_ns() {
-    static const uint64_t ns = [] {
-        const char* e = getenv("IVX_COLLECT_SPIN_US");
-        const long us = e ? strtol(e, nullptr, 10) : 2000;
-        return (uint64_t)(us < 0 ? 0 : us) * 1000ull;
-    }();
-    return ns;
-}
-
-// the launch half of ivx_voxel_step_collect: the gather of the step's results (and whatever rides on it) goes on the stream — or into the
-// batch being recorded —, the wait is left to the collect
-extern "C++" int ivx_step_collect_launch(ivx_grid* g) {
-    if (g->results_in_block || g->gather_launched) return IVX_OK;
-    if (!g->result_host) {
-        IVX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->result_host), 64 * sizeof(uint32_t), hipHostMallocMapped));
-        memset(g->result_host, 0, 64 * sizeof(uint32_t));
-        IVX_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g->result_host_dev), g->result_host, 0));
-    }
-    g->gather_flush_id = ivx_many_flush_count();
-    const int rc = ivx_launch_step_gather(g);
-    if (!rc) g->gather_launched = 1;
-    return rc;
-}
-
-int ivx_voxel_step_collect(ivx_grid* g, ivx_step_result* out) {
-    IVX_REQUIRE(g && out, IVX_ERR_INVALID, "ivx_voxel_step_collect: null argument");
-    ivx_many_other_context other_(g->ctx);
-    hipStream_t s = g->ctx->stream;
-    memset(out, 0, sizeof(*out));
-    const uint32_t stages = g->pending_stages;
-    // the small results of every stage (region scalars + occupied minima/maxima, mesh totals, moments) arrive in one
-    // host-mapped block written by a last tiny kernel: one wait, no copies
-    if (!g->result_host) {
-        IVX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->result_host), 64 * sizeof(uint32_t), hipHostMallocMapped));
-        memset(g->result_host, 0, 64 * sizeof(uint32_t));
-        IVX_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g->result_host_dev), g->result_host, 0));
-    }
-    const bool have_results = g->results_in_block != 0;  // (ivx_slab_remesh_enqueue: the block is written, the caller has waited for the stream)
-    g->results_in_block = 0;
-    if (!have_results) {
-        if (!g->gather_launched) {  // (else ivx_step_collect_launch has put it on the stream: the many-object calls launch all objects' gathers as one)
-            int rc = ivx_launch_step_gather(g);
-            if (rc) return rc;
-            (void)ivx_many_break();
-        }
-        // (a gather that was only recorded has to be on the stream before anybody polls its doorbell: flushed now unless a flush has gone by since)
-        if (g->gather_launched && ivx_many_recording() && g->gather_flush_id == ivx_many_flush_count()) (void)ivx_many_break();
-        g->gather_launched = 0;
-    } else if (hipStreamQuery(s) != hipSuccess) {
-        IVX_HIP_CHECK(ivx_stream_sync(s));
-    }
-    // A short step is over before the runtime's blocking wait has gone to sleep and been woken again: poll the doorbell word the
-    // gather kernel writes last (in-order stream: everything enqueued before it is complete too) for a bounded time first.
-    if (!have_results) {
-        const volatile uint32_t* bell = g->result_host + 63;
-        const uint32_t want = g->result_seq;
-        const uint64_t budget_ns = collect_spin_ns();
-        bool rung = false;
-        if (budget_ns) {
-            const auto t0 = std::chrono::steady_clock::now();
-            for (uint32_t it = 0;; ++it) {
-                if (*bell == want) {
-                    rung = true;
-                    break;
-                }
-                __builtin_ia32_pause();
-                if ((it & 255u) == 255u && (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count() > budget_ns) break;
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        if (!rung) {
-            IVX_HIP_CHECK(ivx_stream_sync(s));
-            // the stream is empty and the doorbell has not rung: the gather never reached the stream (a flush of recorded launches failed and
-            // dropped it, many.hpp) — what the block holds is an earlier step's
-            std::atomic_thread_fence(std::memory_order_acquire);
-            if (*bell != want) {
-                const int dropped = ivx_many_error(g->ctx, true);
-                g->pending_stages = 0;
-                ivx_set_error("ivx_voxel_step_collect: the step's results never arrived (%s)", dropped ? "a flush of recorded launches failed" : "the gather did not run");
-                return IVX_ERR_HIP;
-            }
-        }
-    }
-    if (have_results && g->stamp_mask && g->tick_dev) {
-        // (stamped slots of a step that ended in ivx_step_record_enqueue instead of the gather — the slab protocol driven from outside the
-        // library: the stream has been waited for, the words are fetched and cleared here)
-        IVX_HIP_CHECK(ivx_memcpy_sync(g->tick_host, g->tick_dev, IVX_TICK_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        IVX_HIP_CHECK(hipMemset(g->tick_dev, 0, IVX_TICK_WORDS * sizeof(unsigned long long)));
-    }
-    const uint32_t* sc = g->result_host;
-    if (sc[31]) g->last_active = sc[31];
-    if (g->eval_len_pending == 2 && g->samp_len) {  // a sample stage and a derive sweep behind it have run under the resident program
-        for (int c = 0; c < 3; ++c) g->eval_len[c] = sc[52 + c];
-        g->eval_len_valid = 1;
-    }
-    g->eval_len_pending = 0;
-    if (stages & IVX_STAGE_REGIONS) {
-        IVX_REQUIRE((sc[1] & 1u) == 0, IVX_ERR_CAPACITY, "ivx_voxel_step: a chunk has more than 254 local regions");
-        IVX_REQUIRE((sc[1] & 8u) == 0, IVX_ERR_HIP, "ivx_voxel_step: the region merge gave up waiting for the numbering of the multi-region chunks (k_step_post2)");
-        g->region_count = sc[0];
-        g->regions_valid = 1;
-        out->region_count = sc[0];
-    }
-    if (stages & IVX_STAGE_OCCUPIED) {
-        ivx_occupied_from_raw(g, sc + 16, out->occupied);
-        memcpy(g->occ_ref, out->occupied, sizeof(g->occ_ref));
-        g->occ_ref_valid = 1;
-    }
-    if (stages & IVX_STAGE_REMESH) {
-        const uint32_t totals[3] = {sc[28], sc[29], sc[30]};
-        const bool outgrown = totals[0] > g->vcap || totals[1] > g->icap || totals[2] > g->scap;
-        // (ivx_voxel_step_many: the buffers of all objects that outgrew theirs from one allocation, their emit passes as one launch)
-        g->mesh_growth_pending = outgrown && g->defer_mesh_growth ? 1 : 0;
-        if (outgrown && !g->mesh_growth_pending) {
-            int rc;
-            if ((rc = ensure_mesh_capacity(g, totals[0], totals[1], totals[2]))) return rc;
-            if ((rc = ivx_launch_sn_emit(g))) return rc;
-            IVX_HIP_CHECK(ivx_stream_sync(s));
-        }
-        if (g->mesh_growth_pending) mesh_set_counts(g, totals);  // (valid, built and serial wait for the emit that ivx_voxel_step_many runs again)
-        else mesh_adopt_full(g, totals);
-    }
-    if (stages & IVX_STAGE_INERTIA) {
-        memcpy(out->moments.m64, sc + 32, 10 * sizeof(double));
-        for (int i = 0; i < 10; ++i) out->moments.m32[i] = (float)out->moments.m64[i];
-    }
-    out->mesh = g->mesh_counts;
-    for (int i = 0; i < IVX_N_TIMED_STAGES; ++i) {
-        float ms = 0.0f;
-        g->tick_last[2 * i] = g->tick_last[2 * i + 1] = 0ull;
-        if ((g->stamp_mask >> i) & 1u) {  // clock stamps (step_enqueue): start to start, in ticks of the device's constant-rate clock
-            if (g->tick_start_ref[i] >= 0 && g->tick_end_ref[i] >= 0) {
-                const unsigned long long t0 = g->tick_host[g->tick_start_ref[i]], t1 = g->tick_host[g->tick_end_ref[i]];
-                g->tick_last[2 * i] = t0, g->tick_last[2 * i + 1] = t1;
-                if (t0 != 0ull && t1 > t0) ms = (float)((double)(t1 - t0) / g->ctx->wall_clock_khz);
-            }
-        } else if ((g->timed_mask >> i) & 1u) {
-            if (hipEventElapsedTime(&ms, *g->ev_start_ref[i], g->ev[2 * i + 1]) != hipSuccess) ms = 0.0f;
-        }
-        out->stage_ms[i] = ms;
-    }
-    g->pending_stages = 0;
-    g->timed_mask = 0;
-    g->stamp_mask = 0;
-    g->tick_used = 0;
-    g->tick_next = nullptr;
-    return IVX_OK;
-}
-
-int ivx_voxel_step(ivx_grid* g, uint32_t stages, ivx_step_result* out) {
-    IVX_REQUIRE(g && out, IVX_ERR_INVALID, "ivx_voxel_step: null argument");
-    int rc = ivx_voxel_step_enqueue(g, stages);
-    if (rc) return rc;
-    return ivx_voxel_step_collect(g, out);
-}
-
 size_t ivx_halo_bytes(ivx_grid* g) {
     if (!g) return 0;
     const size_t cols = (size_t)g->cc[1] * g->cc[2];
@@ -1550,37 +1087,6 @@ int ivx_halo_pack_both_enqueue(ivx_grid* g, void* lower_buf, void* upper_buf, in
 int ivx_region_face_labels_enqueue(ivx_grid* g, int side, void* device_buf) {
     IVX_REQUIRE(g && device_buf && (side == 0 || side == 1), IVX_ERR_INVALID, "ivx_region_face_labels_enqueue: bad argument");
     return ivx_launch_face_ids(g, side, static_cast<uint16_t*>(device_buf));
-}
-
-static int ensure_pairs(ivx_grid* g) {
-    if (g->pairs_dev) return IVX_OK;
-    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->pairs_dev), sizeof(uint32_t) * (4 + 128 + 2 * (size_t)IVX_MAX_FACE_PAIRS)));
-    IVX_HIP_CHECK(ivx_memset_async(g->pairs_dev, 0, sizeof(uint32_t) * (4 + 128), g->ctx->stream));
-    return IVX_OK;
-}
-
-int ivx_region_face_pairs_enqueue(ivx_grid* g, int side, const void* neighbour_face_labels) {
-    IVX_REQUIRE(g && neighbour_face_labels && (side == 0 || side == 1), IVX_ERR_INVALID, "ivx_region_face_pairs_enqueue: bad argument");
-    int rc = ensure_pairs(g);
-    if (rc) return rc;
-    rc = ivx_launch_face_pairs(g, side, static_cast<const uint16_t*>(neighbour_face_labels), g->pairs_dev, g->pairs_dev + 4 + 128, IVX_MAX_FACE_PAIRS,
-                               g->pairs_dev + 4);
-    if (rc) return rc;
-    g->pairs_enqueued = 1;
-    return IVX_OK;
-}
-
-size_t ivx_step_record_words(void) { return 28 + 2 * (size_t)IVX_MAX_FACE_PAIRS; }
-
-int ivx_step_record_enqueue(ivx_grid* g, void* device_record) {
-    IVX_REQUIRE(g && device_record, IVX_ERR_INVALID, "ivx_step_record_enqueue: null argument");
-    int rc = ensure_pairs(g);
-    if (rc) return rc;
-    // (no face-pair pass since the last record: the record lists none — a null count, not a fill of the counter)
-    rc = ivx_launch_step_record(g, g->pairs_enqueued ? g->pairs_dev : nullptr, g->pairs_dev + 4 + 128, IVX_MAX_FACE_PAIRS, device_record, g->result_host_dev != nullptr);
-    if (!rc && g->result_host_dev) g->results_in_block = 1;
-    g->pairs_enqueued = 0;
-    return rc;
 }
 
 // ---- many objects per call (many.hpp) ---------------------------------------------------------------------------------------------------
@@ -1644,61 +1150,10 @@ extern "C++" int many_phase(ivx_grid* const* grids, size_t n, const std::functio
     }
     const auto t1 = std::chrono::steady_clock::now();
     rc = ivx_many_flush(c);
-    static const bool trace_phase_ = getenv("IVX_MANY_TRACE") != nullptr;
-    if (trace_phase_)
+    if (many_trace())
         fprintf(stderr, "[ivx many]   phase: objects %.1f us, flush %.1f us\n", 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count(),
                 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t1).count());
     return first ? first : rc;
-}
-
-int ivx_voxel_step_many(ivx_grid* const* grids, size_t n, uint32_t stages, ivx_step_result* out) {
-    if (n == 0) return IVX_OK;  // (a manager without voxel objects)
-    int rc = many_check(grids, n, "ivx_voxel_step_many");
-    if (rc) return rc;
-    IVX_REQUIRE(out, IVX_ERR_INVALID, "ivx_voxel_step_many: null result array");
-    // (`stage_ms` of a merged step is zero — the launches are shared, their times are not an object's)
-    if ((rc = many_phase(grids, n, [&](size_t i) { return step_enqueue_untimed(grids[i], stages); }))) return many_fail(grids, n, rc);
-    if ((rc = many_phase(grids, n, [&](size_t i) { return ivx_step_collect_launch(grids[i]); }))) return many_fail(grids, n, rc);
-    for (size_t i = 0; i < n; ++i) {
-        grids[i]->defer_mesh_growth = 1;
-        rc = ivx_voxel_step_collect(grids[i], &out[i]);
-        grids[i]->defer_mesh_growth = 0;
-        if (rc) return many_fail(grids, n, rc);
-    }
-    // Objects whose meshes outgrew their buffers (all of them, when the fragments of an impact are stepped for the first time): the new buffers
-    // of all from ONE allocation at twice what each needs (docs/voxel_gpu_buffer_pooling.md:44-66), their emit passes again as one launch
-    // each, one wait — where the single-object collect pays six allocations, a launch and a wait per object.
-    static thread_local std::vector<ivx_grid*> grow;
-    static thread_local std::vector<size_t> caps;
-    grow.clear(), caps.clear();
-    for (size_t i = 0; i < n; ++i)
-        if (grids[i]->mesh_growth_pending) grow.push_back(grids[i]);
-    if (!grow.empty()) {
-        const size_t m = grow.size();
-        caps.resize(3 * m);
-        for (size_t k = 0; k < m; ++k) {
-            const ivx_mesh_counts& mc = grow[k]->mesh_counts;
-            const size_t need[3] = {mc.n_vertices, mc.n_indices, mc.n_submeshes}, have[3] = {grow[k]->vcap, grow[k]->icap, grow[k]->scap};
-            mesh_grown_capacities(need, have, false, &caps[3 * k]);
-        }
-        if ((rc = mesh_pool_assign(grow.data(), m, caps.data()))) return many_fail(grids, n, rc);
-        if ((rc = many_phase(grow.data(), m, [&](size_t k) -> int {
-                 ivx_grid* g = grow[k];
-                 if (!ivx_many_zero(g->ctx, g, ivx_sn_hard_count(g), IVX_SN_TAIL_WORDS * sizeof(uint32_t)))
-                     IVX_HIP_CHECK(ivx_memset_async(ivx_sn_hard_count(g), 0, IVX_SN_TAIL_WORDS * sizeof(uint32_t), g->ctx->stream));
-                 int r = ivx_launch_step_emit(g, IVX_STAGE_REMESH, true, nullptr, false);
-                 if (r) return r;
-                 return ivx_launch_step_assign(g, true, false);
-             })))
-            return many_fail(grids, n, rc);
-        IVX_HIP_CHECK(ivx_stream_sync(grids[0]->ctx->stream));
-        for (ivx_grid* g : grow) {
-            const uint32_t totals[3] = {g->mesh_counts.n_vertices, g->mesh_counts.n_indices, g->mesh_counts.n_submeshes};
-            g->mesh_growth_pending = 0;
-            mesh_adopt_full(g, totals);
-        }
-    }
-    return IVX_OK;
 }
 
 // one absorber per object: spheres (segments3 == NULL) or capsules (segment vectors, 3 floats per object)

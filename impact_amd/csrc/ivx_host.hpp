@@ -1,8 +1,10 @@
-// What the host units of the C ABI (ivx_api.hip, voxel_collision_api.hip, extraction_api.hip, mesh_api.hip) share and nothing else links
-// against: staged copies, the objects' device scratch, the recorder phases of the many-object calls, what the extraction calls need of the grid
-// life cycle, the regions and the step, what crosses between the mesh unit and the edit and step paths, and the host mirrors of the reference's
-// range allocators. Defined in ivx_api.hip unless said otherwise (the functions hidden: the library exports what it exported before).
+// What the host units of the C ABI (ivx_api.hip, step_api.hip, voxel_collision_api.hip, extraction_api.hip, mesh_api.hip) share and nothing else
+// links against: staged copies, the objects' device scratch, the bounded wait for a doorbell, the recorder phases of the many-object calls, what
+// the extraction calls need of the grid life cycle, the regions and the step, what crosses between the mesh unit and the edit and step paths,
+// and the host mirrors of the reference's range allocators. Defined in ivx_api.hip unless said otherwise (the functions hidden: the library
+// exports what it exported before).
 #pragma once
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <limits>
@@ -30,6 +32,24 @@ int ensure_dev_scratch(ivx_grid* g, size_t bytes);
 // a shared allocation (ivx_block, ivx_internal.hpp) let go of by one holder: freed with the last
 void block_release(ivx_block* b);
 
+// A doorbell: a word of host-mapped memory that a kernel writes last (in-order stream: everything enqueued before it is complete too). A short
+// chain is over before the runtime's blocking wait has gone to sleep and been woken again: the word is polled for at most `budget_ns` (0: never),
+// then the stream is waited for. `rung`: the bell holds `want` (false behind a drained stream: its kernel never ran).
+inline int doorbell_wait(const volatile uint32_t* bell, uint32_t want, uint64_t budget_ns, hipStream_t s, bool* rung) {
+    *rung = false;
+    if (budget_ns) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t it = 0; !(*rung = *bell == want); ++it) {
+            __builtin_ia32_pause();
+            if ((it & 255u) == 255u && (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count() > budget_ns) break;
+        }
+    }
+    if (!*rung) IVX_HIP_CHECK(ivx_stream_sync(s));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    *rung = *bell == want;
+    return IVX_OK;
+}
+
 // box sweep + region stages after an edit that changed voxels, enqueued and collected (extraction_api.hip): both halves, and the two apart for a
 // caller that has results of its own in flight behind the same doorbell
 int rederive(ivx_grid* g);
@@ -37,12 +57,14 @@ int rederive_enqueue(ivx_grid* g);
 int rederive_collect(ivx_grid* g);
 
 // for extraction_api.hip: grids that come into being together, from one device block and one pinned block (`who`: the call, for messages) | the
-// descriptors of all regions of a labelled object | a step's launches without event records around the stage slots | the launch half of
-// ivx_voxel_step_collect
+// descriptors of all regions of a labelled object
 int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, float voxel_extent, ivx_grid** out, const char* who);
 int describe_regions_internal(ivx_grid* g, const float* d_dens, std::vector<ivx_region_desc>& out);
+// the step unit (step_api.hip): a step's launches with no slot timed, whatever ivx_grid_set_stage_timing asked for (the one place that masks
+// timing) | the launch half of ivx_voxel_step_collect (many_fail calls the public half) | the stage clock's words and events given up
 int step_enqueue_untimed(ivx_grid* g, uint32_t stages);
 int ivx_step_collect_launch(ivx_grid* g);
+void stage_clock_free(ivx_grid* g);
 
 // What the collision and extraction calls ask of an object: derived state current, (needs_probes) probes picked from the current mesh, not a
 // slab of a decomposed grid. `item` non-null names the object or pair of a batched call in the message ("object 3: ...").
@@ -83,7 +105,7 @@ struct ManyClock {
     }
 };
 
-// ---- the mesh unit (mesh_api.hip) and the edit and step paths (ivx_api.hip) --------------------------------------------------------------
+// ---- the mesh unit (mesh_api.hip) and the edit and step paths (ivx_api.hip, step_api.hip) --------------------------------------------------------------
 // mesh -> edit: what the mesh of `chunk` needs (vertices, indices, kind | flags << 8) when the last edit counted it | the chunks the edit in
 // flight invalidates, from the records its count role delivers early (waits for the role's bell, not for the edit)
 bool edit_needs_lookup(ivx_grid* g, uint32_t chunk, uint32_t out3[3]);

@@ -9,6 +9,7 @@
 
 #include "../../include/impact_voxel_hip.h"
 #include "many.hpp"
+#include "stage_clock.hpp"
 
 // Every stream operation of the library goes through these: while a batch of objects is being recorded (many.hpp) whatever has been
 // recorded is issued first, so that the stream sees the operations in program order whether or not they have a merged form.
@@ -116,7 +117,6 @@ struct ivx_grid {
     int8_t* ghost_sdf[2];
     uint8_t* ghost_type[2];
     ivx_chunk_info* ghost_info[2];
-    uint32_t* ghost_rlabel[2];  // global region node of the neighbour's face voxel (0xFFFFFFFF empty)
     int has_ghost[2];
     // (slab protocol) the event behind the exchange that fills the ghost layers, while nobody has waited for it yet: the next derive sweep /
     // mesher count runs its ghost-free part, makes the stream wait, then runs the rest (a hipEvent_t of the communicator; null: nothing pending)
@@ -196,7 +196,6 @@ struct ivx_grid {
     int gather_launched;           // the step's gather is on the stream (or recorded): ivx_voxel_step_collect only waits
     int sn_tail_zero;  // the mesher's hand-off counter, list cursors and census word (IVX_SN_TAIL_WORDS) are known to be zero (ivx_launch_sn_emit_list)
     int needs_current;             // edit->needs holds what the last edit's invalidated chunks' meshes need (no voxel has changed since)
-    uint32_t stage_timing_off;  // timed slots WITHOUT event records (ivx_grid_set_stage_timing; zero-initialised: every slot is timed)
     float* dens_call;       // [256] a density table handed to one call (ivx_inertia, ivx_regions_describe) that is not the resident one
     float* dens_dev;        // [256] voxel type densities
     float dens_host[256];   // what dens_dev holds (entry points that are handed the same table again skip the upload)
@@ -218,7 +217,6 @@ struct ivx_grid {
     uint32_t eval_len[3];
     int eval_len_valid, eval_len_pending;
     int has_dens;
-    double* moments_dev;  // [10]
     uint32_t* samp_len;   // [n_chunks] length of the chunk's compact SDF program (sampler pre-pass)
     void* samp_ops;       // [n_chunks * 128] uint2 ops
     // Sample-ahead (ivx_grid_set_sample_ahead, sdf_sample.hip): the pre-pass of the NEXT sample stage under the resident program runs on the
@@ -231,26 +229,12 @@ struct ivx_grid {
     hipEvent_t ahead_go, ahead_done;
     uint32_t* samp_super;  // [super-blocks * ceil(nodes / 32)] "node certainly outside every chunk of the super-block" bits
     size_t samp_super_words;
-    hipEvent_t ev[2 * IVX_N_TIMED_STAGES];  // start/stop per timed stage
-    int ev_ready;
-    uint32_t* result_host;      // 64 words of host-mapped pinned memory the gather kernel writes the step's small results to
+    uint32_t* result_host;      // the result block (IVX_RB_*): host-mapped pinned memory the gather kernel writes the step's small results to
     uint32_t* result_host_dev;  // its device-side address
-    uint32_t result_seq;        // sequence number of the last gather launch (word 63 of the block = the completion doorbell)
-    hipEvent_t* ev_start_ref[IVX_N_TIMED_STAGES];  // the event a stage's duration starts from (the previous stage's stop when adjacent)
+    uint32_t result_seq;        // sequence number of the last gather launch (the block's bell = the completion doorbell)
     uint32_t pending_stages;  // stages enqueued since the last collect
-    uint32_t timed_mask;      // timed stages whose events were recorded since the last collect
-    // Stage stamps (step_enqueue, ivx_api.hip): on the step's fused path a timed slot is the distance between two clock words that block 0 of
-    // two launches writes on entry (ivx_stage_stamp), not a pair of event records. Words are handed out in stream order since the last collect.
-    unsigned long long* tick_dev;    // [IVX_TICK_WORDS] device words the launches stamp; k_step_gather copies them out and zeroes them
-    unsigned long long* tick_host;   // [IVX_TICK_WORDS] host-mapped copy, written by the gather ahead of the doorbell
-    unsigned long long* tick_host_dev;
-    unsigned long long* tick_next;   // the word the next stamping launch on this grid writes (ivx_take_tick), or null
-    uint32_t tick_used;              // words handed out since the last collect
-    int stage_events_only;           // this grid's timed slots always take event records (a slab of the slab protocol, ivx_slab_create)
-    uint32_t stamp_mask;             // timed slots whose words were armed since the last collect (their times come from tick_host)
-    int8_t tick_start_ref[IVX_N_TIMED_STAGES], tick_end_ref[IVX_N_TIMED_STAGES];  // word indices of a stamped slot's two ends (-1: the slot had no launch)
-    unsigned long long tick_last[2 * IVX_N_TIMED_STAGES];  // the last collect's raw stamps, start then end per slot (ivx_debug_stage_ticks)
-    uint32_t* pairs_dev;      // [4 + 128 + 2 * IVX_MAX_FACE_PAIRS]: count, seen table, (own, neighbour) component pairs across the upper x face
+    ivx_stage_timing timing;  // the stage clock (stage_clock.hpp; driven by step_enqueue, step_api.hip): stamps or event records per timed slot
+    uint32_t* pairs_dev;      // [IVX_PAIRS_WORDS]: count, seen table, (own, neighbour) component pairs across the upper x face
     unsigned long long* record_head_copy;  // (in-process slab transport) where the record role also puts the record's first `record_head_words` words:
     uint32_t record_head_words;            // this slab's place in the gathered block — the gather of the heads is then no copy at all
     int results_in_block;     // the step's small results are in the host-mapped block already (written by the slab record role): collect launches no gather
@@ -301,16 +285,34 @@ struct ivx_mutual_pass {
     float response[3];
 };
 
+// ---- layouts that host and device code share ------------------------------------------------------------------------------------------
+// The result block of a step (ivx_grid::result_host): 64 words of host-mapped memory that role_result_gather fills and the collect reads; the
+// blocks of grids that came into being together lie IVX_RB_STRIDE_BYTES apart in one pinned allocation (grid_create_pooled).
+#define IVX_RB_REGION_WORDS 28u  // [0, 28): the region scalars (ivx_grid::rscalar), of which ...
+#define IVX_RB_REGION_TOTAL 0u   // ... the region total,
+#define IVX_RB_FLAGS 1u          // ... the error flags: a chunk has more than 254 local regions | the region merge gave up waiting (k_step_post2)
+#define IVX_RB_FLAG_LOCAL_REGIONS 1u
+#define IVX_RB_FLAG_MERGE_GAVE_UP 8u
+#define IVX_RB_OCCUPIED 16u      // ... and the raw occupied minima / maxima, 12 words
+#define IVX_RB_MESH_TOTALS 28u   // vertices, indices, submeshes
+#define IVX_RB_ACTIVE 31u        // length of the active list
+#define IVX_RB_MOMENTS 32u       // the 10 moments, f64 as two words each
+#define IVX_RB_MOMENT_WORDS 20u
+#define IVX_RB_EVAL_LEN 52u      // lengths of the sampler's three evaluation lists
+#define IVX_RB_BELL 63u          // the doorbell: ivx_grid::result_seq, written last
+#define IVX_RB_WORDS 64u
+#define IVX_RB_STRIDE_BYTES 256u
+static_assert(IVX_RB_FLAGS < IVX_RB_OCCUPIED && IVX_RB_OCCUPIED + 12u <= IVX_RB_REGION_WORDS && IVX_RB_REGION_WORDS <= IVX_RB_MESH_TOTALS &&
+                  IVX_RB_MESH_TOTALS + 3u <= IVX_RB_ACTIVE && IVX_RB_ACTIVE < IVX_RB_MOMENTS && IVX_RB_MOMENTS + IVX_RB_MOMENT_WORDS <= IVX_RB_EVAL_LEN &&
+                  IVX_RB_EVAL_LEN + 3u <= IVX_RB_BELL && IVX_RB_BELL < IVX_RB_WORDS && IVX_RB_WORDS * sizeof(uint32_t) <= IVX_RB_STRIDE_BYTES,
+              "the parts of the result block overlap, leave its 64 words, or pooled blocks overlap");
+// The face-pair buffer (ivx_grid::pairs_dev): counters and the seen table (cleared as one), then the (own, neighbour) pairs. The step record
+// of a slab (role_step_record), in 64-bit words: the head, then the pairs.
+#define IVX_PAIRS_COUNTERS 4u
+#define IVX_PAIRS_HEAD_WORDS (IVX_PAIRS_COUNTERS + 128u)
+#define IVX_PAIRS_WORDS (IVX_PAIRS_HEAD_WORDS + 2u * IVX_MAX_FACE_PAIRS)
+#define IVX_RECORD_HEAD_WORDS 28u
 void ivx_set_error(const char* fmt, ...);
-#define IVX_TICK_WORDS 32
-// The clock word the launch being made stamps: the grid's pending one, handed out once. A launch that is only recorded into a batch of
-// several objects (its twin does not stamp) leaves the word to the next launch made directly.
-static inline unsigned long long* ivx_take_tick(ivx_grid* g) {
-    if (!g->tick_next || ivx_many_recording()) return nullptr;
-    unsigned long long* t = g->tick_next;
-    g->tick_next = nullptr;
-    return t;
-}
 void ivx_cull_release(ivx_ctx* c);  // cull.hip (ivx_shutdown)
 void ivx_bvol_release(ivx_ctx* c);  // bvol.hip (ivx_shutdown)
 // the occupied ranges the object holds (ivx_grid::occ_ref), refreshed first when something invalidated them; IVX_ERR_STATE when the grid has none yet
@@ -422,7 +424,7 @@ __device__ __forceinline__ Total ivx_scan_rounds(const uint32_t* counts, uint32_
 }
 
 // Stage stamp: thread 0 of block 0 writes the constant-rate clock to `tick` on entry (null: no stamp) — one ordinary store by one lane.
-// The launches that can open or close a timed slot of a step carry the address in their arguments (step_enqueue, ivx_api.hip).
+// The launches that can open or close a timed slot of a step carry the address in their arguments (step_enqueue, step_api.hip).
 __device__ __forceinline__ void ivx_stage_stamp(unsigned long long* tick) {
     if (tick && blockIdx.x == 0u && threadIdx.x == 0u) *tick = wall_clock64();
 }
@@ -493,6 +495,8 @@ static inline uint32_t ivx_list_grid(const ivx_grid* g) {
 // chunk planes of a slab that adjoin no ghost layer
 static inline bool ivx_has_interior_planes(const ivx_grid* g) { return (int)g->cc[0] - (g->has_ghost[0] ? 1 : 0) - (g->has_ghost[1] ? 1 : 0) > 0; }
 static inline uint32_t* ivx_wc(const ivx_grid* g) { return g->work_counts + g->wc_cur; }
+// a newly sampled or uploaded object: nothing derived stands, and whatever mesh the buffers hold is not a stale version of this one
+static inline void ivx_voxels_replaced(ivx_grid* g) { g->mesh_valid = g->mesh_built = g->occ_ref_valid = g->bbox_valid = g->regions_valid = 0; }
 // to be called by everything that writes voxel planes other than the sampler (uploads, edits, split / clip / repack, raw plane pointers handed out)
 static inline void ivx_planes_touched(ivx_grid* g) {
     g->signs_current = 0;

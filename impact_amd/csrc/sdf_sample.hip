@@ -1840,11 +1840,11 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
                 g->samp_super_words = need;
             }
             super_skip = reinterpret_cast<uint2*>(g->samp_super + (((size_t)sx * sy * sz * words + 1u) & ~(size_t)1u));
-            p.tick = ivx_take_tick(g);
+            p.tick = g->timing.take(ivx_many_recording());
             IVX_KLAUNCH(k_sdf_super, dim3(sx * sy * sz), dim3(64), words * sizeof(uint32_t), g->ctx->stream, p, d_nodes, g->samp_super, super_skip, words, sy, sz,
                                ivx_preset_args(g, super_presets));
         }
-        p.tick = ivx_take_tick(g);
+        p.tick = g->timing.take(ivx_many_recording());
         if (noise)
             IVX_KLAUNCH(k_sdf_prepass<true>, dim3(sx * sy * sz), dim3(PRE_T * PRE_WAVES), 0, g->ctx->stream, p, d_nodes, g->samp_len, ops, eval_count, eval_list,
                                g->n_chunks, g->info, g->samp_super, super_skip, words, sy, sz, sx * sy * sz, fused_super ? 1u : 0u, 0u, ivx_preset_args(g, prepass_presets));
@@ -1877,7 +1877,7 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
             // one level + 64 words of scratch: 16 640 bytes = 13 LDS granules, eight workgroups per CU (the waves a SIMD holds)
             const uint32_t scratch_off = IVX_CHUNK_VOXELS;
             const ivx_chunk_info* sh = take_shadow();
-            p.tick = ivx_take_tick(g);
+            p.tick = g->timing.take(ivx_many_recording());
             IVX_KLAUNCH(k_sdf_eval<2>, dim3(fit(g->eval_len[0])), dim3(256), (size_t)(scratch_off + 64u) * sizeof(float), g->ctx->stream, p, eval_count + 0, list0,
                                eval_count + 3, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
                                sh, g->n_chunks, sh ? first_presets : no_presets);
@@ -1886,7 +1886,7 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
             // two levels, the second one 15 rows long + 64 words of scratch: 32 000 bytes = 25 LDS granules, five workgroups per CU
             const uint32_t scratch_off = IVX_CHUNK_VOXELS + 15u * 256u;
             const ivx_chunk_info* sh = take_shadow();
-            p.tick = ivx_take_tick(g);
+            p.tick = g->timing.take(ivx_many_recording());
             if (merge01)
                 IVX_KLAUNCH(k_sdf_eval<1>, dim3(fit(g->eval_len[0] + g->eval_len[1])), dim3(256), (size_t)(scratch_off + 64u) * sizeof(float), g->ctx->stream, p, eval_count + 0, list0,
                                    eval_count + 3, eval_count + 1, list1, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
@@ -1902,7 +1902,7 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
             const uint32_t lv = stack_size ? stack_size : 1u;
             const uint32_t scratch_off = lv * IVX_CHUNK_VOXELS - 16u;
             const ivx_chunk_info* sh = take_shadow();
-            p.tick = ivx_take_tick(g);
+            p.tick = g->timing.take(ivx_many_recording());
             if (noise)
                 IVX_KLAUNCH((k_sdf_eval<0, true>), dim3(fit(g->eval_len[2])), dim3(256), (size_t)lv * IVX_CHUNK_VOXELS * sizeof(float), g->ctx->stream, p, eval_count + 2,
                                    eval_list + 2 * (size_t)g->n_chunks, nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info,

@@ -721,7 +721,7 @@ int ivx_slab_create(ivx_comm* m, ivx_grid* g, int rank, ivx_slab** out) {
     IVX_REQUIRE(sl, IVX_ERR_CAPACITY, "ivx_slab_create: out of host memory");
     sl->comm = m;
     sl->grid = g;
-    g->stage_events_only = 1;  // (a slab's step ends in its record, not in the gather that brings clock stamps home: its slots keep their event records)
+    g->timing.events_only = 1;  // (a slab's step ends in its record, not in the gather that brings clock stamps home: its slots keep their event records)
     sl->rank = rank;
     sl->halo_bytes = ivx_halo_bytes(g);
     sl->face_bytes = ivx_region_face_bytes(g);

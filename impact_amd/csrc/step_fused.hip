@@ -310,7 +310,7 @@ __device__ __forceinline__ void step_gather_body(const StepArgs& a, uint32_t, ui
     // sees it also knows that everything enqueued before this launch is complete (ivx_voxel_step_collect polls it instead of paying
     // the runtime's blocking wait when the step is short).
     __threadfence_system();
-    if (threadIdx.x == 0u) __hip_atomic_store(a.host_block + 63, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (threadIdx.x == 0u) __hip_atomic_store(a.host_block + IVX_RB_BELL, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __global__ __launch_bounds__(64) void k_step_gather(StepArgs a) { step_gather_body(a, 0u, 1u); }
 IVX_MANY_TWIN(k_step_gather_many, StepArgs, step_gather_body, __launch_bounds__(64))
@@ -421,7 +421,7 @@ int ivx_launch_step_post1(ivx_grid* g, uint32_t stages) {
             ai.nb[1] = ai.nb[3] = ai.nb[4] = ai.nb[5] = 0;
             ai.x_part = IVX_XPART_INTERIOR;
             a.x_part = IVX_XPART_FACES;
-            ai.tick = ivx_take_tick(g);
+            ai.tick = g->timing.take(ivx_many_recording());
             if (!ivx_many_try(g->ctx, g, IVX_MK_POST1, ai.nb[0], ai)) IVX_KLAUNCH(k_step_post1, dim3(ai.nb[0]), dim3(256), 0, g->ctx->stream, ai);
         }
         (void)ivx_many_break();
@@ -431,7 +431,7 @@ int ivx_launch_step_post1(ivx_grid* g, uint32_t stages) {
     }
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[3] + a.nb[4] + a.nb[5];
     if (total == 0) return IVX_OK;
-    a.tick = ivx_take_tick(g);
+    a.tick = g->timing.take(ivx_many_recording());
     if (!ivx_many_try(g->ctx, g, IVX_MK_POST1, total, a)) IVX_KLAUNCH(k_step_post1, dim3(total), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -443,8 +443,8 @@ static void face_pair_args(StepArgs& a, ivx_grid* g, const uint16_t* nbr_ids) {
     a.fp_cap = IVX_MAX_FACE_PAIRS;
     a.fp_nbr = nbr_ids;
     a.fp_count = nbr_ids ? g->pairs_dev : nullptr;
-    a.fp_seen = g->pairs_dev + 4;
-    a.fp_pairs = reinterpret_cast<uint2*>(g->pairs_dev + 4 + 128);
+    a.fp_seen = g->pairs_dev + IVX_PAIRS_COUNTERS;
+    a.fp_pairs = reinterpret_cast<uint2*>(g->pairs_dev + IVX_PAIRS_HEAD_WORDS);
 }
 
 int ivx_launch_step_post2(ivx_grid* g, uint32_t stages, const uint16_t* face_pair_ids) {
@@ -475,7 +475,7 @@ int ivx_launch_step_post2(ivx_grid* g, uint32_t stages, const uint16_t* face_pai
     if (stages & IVX_STAGE_OCCUPIED) a.nb[3] = 1;
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[2] + a.nb[3] + a.nb[4] + a.nb[5];
     if (total == 0) return IVX_OK;
-    a.tick = ivx_take_tick(g);
+    a.tick = g->timing.take(ivx_many_recording());
     if (!ivx_many_try(g->ctx, g, IVX_MK_POST2, total, a)) IVX_KLAUNCH(k_step_post2, dim3(total), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -502,7 +502,7 @@ int ivx_launch_step_emit(ivx_grid* g, uint32_t stages, bool general_in_assign, v
     }
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[2];
     if (total == 0) return IVX_OK;
-    a.tick = ivx_take_tick(g);
+    a.tick = g->timing.take(ivx_many_recording());
     if (single_type) IVX_KLAUNCH(k_step_emit<true>, dim3(total), dim3(256), 0, g->ctx->stream, a);
     else if (!ivx_many_try(g->ctx, g, IVX_MK_EMIT, total, a)) IVX_KLAUNCH(k_step_emit<false>, dim3(total), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
@@ -520,7 +520,7 @@ int ivx_launch_step_assign(ivx_grid* g, bool with_mesher_general, bool with_ccl)
     a.nb[0] = with_ccl ? (g->n_chunks + 255u) / 256u : 0u;
     a.nb[1] = with_mesher_general ? sn::ivx_emit_general_grid(g, g->n_chunks) : 0u;
     if (a.nb[0] + a.nb[1] == 0u) return IVX_OK;
-    a.tick = ivx_take_tick(g);
+    a.tick = g->timing.take(ivx_many_recording());
     if (!ivx_many_try(g->ctx, g, IVX_MK_ASSIGN, a.nb[0] + a.nb[1], a)) IVX_KLAUNCH(k_step_assign, dim3(a.nb[0] + a.nb[1]), dim3(256), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -531,11 +531,7 @@ int ivx_launch_step_gather(ivx_grid* g) {
     a.seq = ++g->result_seq;
     a.copy_src = g->gather_copy_src, a.copy_dst = g->gather_copy_dst, a.copy_words = g->gather_copy_words;  // (consumed by this launch)
     g->gather_copy_words = 0;
-    if (g->tick_used) {  // (stamped slots since the last collect: their words go out with the results; a word still pending is this launch's)
-        a.ticks_dev = g->tick_dev, a.ticks_host = g->tick_host_dev, a.n_ticks = g->tick_used;
-        a.tick = g->tick_next;
-        g->tick_next = nullptr;
-    }
+    g->timing.hand_to_gather(&a.ticks_dev, &a.ticks_host, &a.n_ticks, &a.tick);  // (stamped slots since the last collect: their words go out with the results)
     if (!ivx_many_try(g->ctx, g, IVX_MK_GATHER, 1u, a)) IVX_KLAUNCH(k_step_gather, dim3(1), dim3(64), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;

@@ -145,19 +145,19 @@ __device__ __forceinline__ void role_inertia_final(uint32_t n_blocks, float exte
     }
 }
 
-// The small results of a step into the host-mapped block (first 64 threads of the calling block): [0..28) region scalars +
-// occupied minima/maxima, [28..31) mesh totals, [31] active chunks, [32..52) the 10 moments (f64 as two words each), [52..55) the
-// sampler's three evaluation-list lengths. `region_total_known`: the caller computed word 0 itself in this launch.
+// The small results of a step into the host-mapped block (first 64 threads of the calling block), laid out as IVX_RB_* says
+// (ivx_internal.hpp): region scalars + occupied minima/maxima, mesh totals, active chunks, the 10 moments, the sampler's three
+// evaluation-list lengths. `region_total_known`: the caller computed the region total itself in this launch.
 __device__ __forceinline__ void role_result_gather(const uint32_t* __restrict__ rscalar, const uint32_t* __restrict__ mesh_totals,
                                                    const double* __restrict__ moments, const uint32_t* __restrict__ work_count,
                                                    const uint32_t* __restrict__ eval_count, uint32_t* __restrict__ host_block, bool region_total_known,
                                                    uint32_t region_total) {
     const uint32_t t = threadIdx.x;
-    if (t == 31u) host_block[31] = work_count[0];  // length of the active list (sizes the next step's list-driven grids)
-    if (t < 28u) host_block[t] = (t == 0u && region_total_known) ? region_total : rscalar[t];
-    if (t < 3u) host_block[28 + t] = mesh_totals[t];
-    if (t < 20u) host_block[32 + t] = reinterpret_cast<const uint32_t*>(moments)[t];
-    if (t < 3u && eval_count) host_block[52 + t] = eval_count[8u + t];  // (the rolled copy, see role_preset)
+    if (t == IVX_RB_ACTIVE) host_block[IVX_RB_ACTIVE] = work_count[0];  // length of the active list (sizes the next step's list-driven grids)
+    if (t < IVX_RB_REGION_WORDS) host_block[t] = (t == IVX_RB_REGION_TOTAL && region_total_known) ? region_total : rscalar[t];
+    if (t < 3u) host_block[IVX_RB_MESH_TOTALS + t] = mesh_totals[t];
+    if (t < IVX_RB_MOMENT_WORDS) host_block[IVX_RB_MOMENTS + t] = reinterpret_cast<const uint32_t*>(moments)[t];
+    if (t < 3u && eval_count) host_block[IVX_RB_EVAL_LEN + t] = eval_count[8u + t];  // (the rolled copy, see role_preset)
 }
 
 // Preset of the scratch words a step's stages start from (what k_step_preset did in a launch of its own), as a role of the

@@ -1,4 +1,4 @@
-"""Stage times from in-kernel clock stamps (`ivx_grid_set_stage_timing`, step_enqueue in csrc/ivx_api.hip): on the step's fused path a timed
+"""Stage times from in-kernel clock stamps (`ivx_grid_set_stage_timing`, step_enqueue in csrc/step_api.hip): on the step's fused path a timed
 slot is the distance between two clock words that the first workgroup of two launches writes on entry, not a pair of event records on the
 queue. The bodies here are a few chunks a side, so every kernel sits at the launch floor and no test compares durations with each other:
 they check that timing never changes what a step computes, which slots report, and that the stamps are ordered and bounded by the host's

@@ -217,6 +217,12 @@ FORCE_GENERATOR_DTYPE = np.dtype([("kind", "<u4"), ("body", "<u4"), ("body_b", "
 (FG_CONSTANT_ACCELERATION, FG_LOCAL_FORCE, FG_SPRING_DYNAMIC_DYNAMIC, FG_SPRING_DYNAMIC_KINEMATIC, FG_ALIGNMENT_FIXED,
  FG_ALIGNMENT_GRAVITY) = 0, 1, 2, 3, 4, 5
 assert FORCE_GENERATOR_DTYPE.itemsize == 64
+# detailed drag inside the force stage (csrc/forces.hip): `ivx_uniform_medium` (UniformMedium), `ivx_drag_generator` (DetailedDragForce on a dynamic
+# body, its map a slot of the world's table), `ivx_drag_map_view` (one slot in host memory, for `ivx_fg_apply_host_drag`)
+UNIFORM_MEDIUM_DTYPE = np.dtype([("mass_density", "<f4"), ("velocity", "<f4", (3,))])
+DRAG_GENERATOR_DTYPE = np.dtype([("body", "<u4"), ("map", "<u4"), ("drag_coefficient", "<f4"), ("scaling", "<f4")])
+DRAG_MAP_VIEW_DTYPE = np.dtype([("loads", "<u8"), ("n_theta", "<u4"), ("reserved", "<u4")])
+assert UNIFORM_MEDIUM_DTYPE.itemsize == 16 and DRAG_GENERATOR_DTYPE.itemsize == 16 and DRAG_MAP_VIEW_DTYPE.itemsize == 16
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -249,6 +255,8 @@ EXPORTED_SYMBOLS = [
     "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
     "ivx_world_set_motion_drivers", "ivx_world_set_time", "ivx_world_time", "ivx_world_apply_motion", "ivx_md_eval", "ivx_md_apply_host",
     "ivx_world_set_force_generators", "ivx_world_set_dynamic_gravity", "ivx_world_apply_forces", "ivx_world_gravity_loads", "ivx_fg_apply_host",
+    "ivx_world_set_medium", "ivx_world_medium", "ivx_world_set_drag_map", "ivx_world_set_drag_map_from_grid", "ivx_world_drag_map_download",
+    "ivx_world_set_detailed_drag", "ivx_fg_apply_host_drag",
 ]
 
 
@@ -282,6 +290,7 @@ def extra_struct_sizes():
         "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128),
         "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
         "ivx_force_generator": (FORCE_GENERATOR_DTYPE, 64),
+        "ivx_uniform_medium": (UNIFORM_MEDIUM_DTYPE, 16), "ivx_drag_generator": (DRAG_GENERATOR_DTYPE, 16), "ivx_drag_map_view": (DRAG_MAP_VIEW_DTYPE, 16),
     }
 
 
@@ -487,6 +496,13 @@ def lib():
         "ivx_world_apply_forces": (i32, [vp]),
         "ivx_world_gravity_loads": (i32, [vp, vp, sz]),
         "ivx_fg_apply_host": (i32, [vp, sz, vp, sz, f32, vp, sz, vp, sz, vp]),
+        "ivx_world_set_medium": (i32, [vp, vp]),
+        "ivx_world_medium": (i32, [vp, vp]),
+        "ivx_world_set_drag_map": (i32, [vp, u32, vp, u32]),
+        "ivx_world_set_drag_map_from_grid": (i32, [vp, u32, vp, vp, vp]),
+        "ivx_world_drag_map_download": (i32, [vp, u32, vp, sz, C.POINTER(u32)]),
+        "ivx_world_set_detailed_drag": (i32, [vp, vp, sz]),
+        "ivx_fg_apply_host_drag": (i32, [vp, sz, vp, sz, f32, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -24,36 +24,22 @@
 #include <vector>
 
 #include "device_common.hpp"
+#include "drag_internal.hpp"
 
 namespace {
 
-constexpr float PI_F = 3.14159265358979323846f;
-constexpr float TWO_PI_F = 6.28318530717958647692f;
+using ivx_drag::MAX_THETA;
+using ivx_drag::PI_F;
+using ivx_drag::TWO_PI_F;
+using ivx_drag::phi_idx_of;  // the cell index arithmetic: drag_internal.hpp, shared with the force stage
+using ivx_drag::theta_idx_of;
 
 constexpr uint32_t CHUNK_TRIS = 128;     // triangles a lane sums in f32 before the sum moves into its f64 accumulators
 constexpr uint32_t TARGET_WAVES = 8192;  // the triangle axis is split until about this many waves exist (256 CUs x 4 SIMDs x 8)
 constexpr uint32_t WIDE_DIRS = 512;      // from this many directions on a lane holds four of them (k_drag_loads<4>)
 constexpr uint32_t MAX_DIRS = 1u << 24;
-constexpr uint32_t MAX_THETA = 2048;
 constexpr float MAX_DISTANCE = 0.5f * PI_F;  // (scaled by up to 4 at the poles: a region of at most 4 n_theta + 1 cells across)
 
-// ---- shared host / device arithmetic of the map (f32, as the reference) ----------------------------------------------------------------
-__host__ __device__ __forceinline__ float rem_euclid_two_pi(float a) {
-    float r = fmodf(a, TWO_PI_F);
-    if (r < 0.0f) r += TWO_PI_F;
-    return r;
-}
-__host__ __device__ __forceinline__ uint32_t clamped_idx(float angle, float inv_cell, uint32_t n) {
-    const float f = floorf(angle * inv_cell);
-    const uint32_t i = f > 0.0f ? (uint32_t)f : 0u;
-    return i < n - 1u ? i : n - 1u;
-}
-__host__ __device__ __forceinline__ uint32_t phi_idx_of(float phi, float inv_cell, uint32_t n_phi) { return clamped_idx(rem_euclid_two_pi(phi), inv_cell, n_phi); }
-__host__ __device__ __forceinline__ uint32_t theta_idx_of(float theta, float inv_cell, uint32_t n_theta) {
-    float t = rem_euclid_two_pi(theta);
-    if (t > PI_F) t = TWO_PI_F - t;
-    return clamped_idx(t, inv_cell, n_theta);
-}
 __host__ __device__ __forceinline__ float clamp_unit(float v) { return fminf(1.0f, fmaxf(-1.0f, v)); }
 
 // ---- load pass -----------------------------------------------------------------------------------------------------------------------------
@@ -541,30 +527,56 @@ int ivx_drag_load_map_from_samples(ivx_ctx* c, const float* dirs3, const ivx_dra
 
 int ivx_drag_load_map(ivx_grid* g, const float com[3], const ivx_drag_map_config* cfg, ivx_drag_load* map) {
     IVX_REQUIRE(g && com && cfg && map, IVX_ERR_INVALID, "ivx_drag_load_map: null argument");
-    IVX_REQUIRE(cfg->n_direction_samples > 0, IVX_ERR_INVALID, "ivx_drag_load_map: n_direction_samples is zero");
-    IVX_REQUIRE(cfg->n_direction_samples <= MAX_DIRS, IVX_ERR_CAPACITY, "ivx_drag_load_map: %u direction samples exceed %u", cfg->n_direction_samples, MAX_DIRS);
-    IVX_REQUIRE(cfg->n_theta_coords > 0, IVX_ERR_INVALID, "ivx_drag_load_map: n_theta_coords is zero");
-    IVX_REQUIRE(cfg->smoothness > 0.0f, IVX_ERR_INVALID, "ivx_drag_load_map: the smoothness %g is not positive", (double)cfg->smoothness);
-    const uint32_t n = cfg->n_direction_samples, n_theta = cfg->n_theta_coords;
+    float* d_map = nullptr;
+    if (int rc = ivx_drag_map_build("ivx_drag_load_map", g, com, cfg, nullptr, &d_map)) return rc;
+    return download(g->ctx, map, d_map, 2u * (size_t)cfg->n_theta_coords * cfg->n_theta_coords * sizeof(ivx_drag_load));
+}
+
+}  // extern "C"
+
+// ---- the one entry that builds a map of a resident mesh (drag_internal.hpp): ivx_drag_load_map downloads what it leaves, the world keeps it ----
+int ivx_drag_map_check(const char* who, const ivx_grid* g, const float com[3], const ivx_drag_map_config* cfg) {
+    IVX_REQUIRE(g && com && cfg, IVX_ERR_INVALID, "%s: null argument", who);
+    IVX_REQUIRE(cfg->n_direction_samples > 0, IVX_ERR_INVALID, "%s: n_direction_samples is zero", who);
+    IVX_REQUIRE(cfg->n_direction_samples <= MAX_DIRS, IVX_ERR_CAPACITY, "%s: %u direction samples exceed %u", who, cfg->n_direction_samples, MAX_DIRS);
+    IVX_REQUIRE(cfg->n_theta_coords > 0, IVX_ERR_INVALID, "%s: n_theta_coords is zero", who);
+    IVX_REQUIRE(cfg->smoothness > 0.0f, IVX_ERR_INVALID, "%s: the smoothness %g is not positive", who, (double)cfg->smoothness);
     // (for a smoothness of one the square regions around the samples add up to the sphere's solid angle)
+    const float distance = cfg->smoothness * sqrtf(4.0f * PI_F / (float)cfg->n_direction_samples);
+    if (int rc = check_map_shape(who, cfg->n_theta_coords, distance)) return rc;
+    IVX_REQUIRE(g->mesh_valid, IVX_ERR_STATE, "%s: the grid has no current mesh (call ivx_remesh or ivx_mesh_sync first)", who);
+    return IVX_OK;
+}
+
+int ivx_drag_map_build(const char* who, ivx_grid* g, const float com[3], const ivx_drag_map_config* cfg, float* d_map, float** d_where) {
+    if (int rc = ivx_drag_map_check(who, g, com, cfg)) return rc;
+    const uint32_t n = cfg->n_direction_samples, n_theta = cfg->n_theta_coords;
     const float distance = cfg->smoothness * sqrtf(4.0f * PI_F / (float)n);
-    if (int rc = check_map_shape("ivx_drag_load_map", n_theta, distance)) return rc;
-    IVX_REQUIRE(g->mesh_valid, IVX_ERR_STATE, "ivx_drag_load_map: the grid has no current mesh (call ivx_remesh or ivx_mesh_sync first)");
     ivx_ctx* c = g->ctx;
     ivx_many_other_context other_(c);
     const size_t map_bytes = 2u * (size_t)n_theta * n_theta * sizeof(ivx_drag_load);
-    if (g->mesh_counts.n_indices < 3) {  // zero loads average to zero
-        memset(map, 0, map_bytes);
+    const bool empty = g->mesh_counts.n_indices < 3;  // zero loads average to zero
+    std::vector<float> dirs;
+    LoadPlan p = {};
+    ivx_layout l;
+    size_t o_dirs = 0, o_recs = 0, o_part = 0, o_loads = 0, o_samples = 0;
+    if (!empty) {
+        dirs.resize(3 * (size_t)n);
+        if (int rc = ivx_drag_directions(n, dirs.data())) return rc;
+        p = plan_loads(g->mesh_counts.n_indices / 3u, n);
+        o_dirs = l.take((size_t)n * 12), o_recs = l.take(p.recs_bytes()), o_part = l.take(p.partials_bytes()), o_loads = l.take((size_t)n * sizeof(ivx_drag_load)),
+        o_samples = l.take((size_t)n * sizeof(SampleRec));
+    }
+    const size_t o_map = d_map ? 0 : l.take(map_bytes);
+    if (l.bytes)
+        if (int rc = ensure_scratch(c, l.bytes)) return rc;
+    char* base = static_cast<char*>(c->drag_scratch.p);
+    float* d_out = d_map ? d_map : reinterpret_cast<float*>(base + o_map);
+    if (d_where) *d_where = d_out;
+    if (empty) {
+        IVX_HIP_CHECK(ivx_memset_async(d_out, 0, map_bytes, c->stream));
         return IVX_OK;
     }
-    std::vector<float> dirs(3 * (size_t)n);
-    if (int rc = ivx_drag_directions(n, dirs.data())) return rc;
-    const LoadPlan p = plan_loads(g->mesh_counts.n_indices / 3u, n);
-    ivx_layout l;
-    const size_t o_dirs = l.take((size_t)n * 12), o_recs = l.take(p.recs_bytes()), o_part = l.take(p.partials_bytes()), o_loads = l.take((size_t)n * sizeof(ivx_drag_load)),
-                 o_samples = l.take((size_t)n * sizeof(SampleRec)), o_map = l.take(map_bytes);
-    if (int rc = ensure_scratch(c, l.bytes)) return rc;
-    char* base = static_cast<char*>(c->drag_scratch.p);
     IVX_HIP_CHECK(ivx_memcpy_async(base + o_dirs, dirs.data(), (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));  // (`dirs` is pageable memory of this call)
     float4* d_recs = reinterpret_cast<float4*>(base + o_recs);
@@ -572,8 +584,5 @@ int ivx_drag_load_map(ivx_grid* g, const float com[3], const ivx_drag_map_config
     float* d_loads = reinterpret_cast<float*>(base + o_loads);
     if (int rc = launch_records_resident(g, p, com, d_recs)) return rc;
     if (int rc = launch_loads(c, p, d_recs, d_dirs, reinterpret_cast<double*>(base + o_part), d_loads)) return rc;
-    if (int rc = launch_map(c, d_dirs, d_loads, n, n_theta, distance, reinterpret_cast<SampleRec*>(base + o_samples), reinterpret_cast<float*>(base + o_map))) return rc;
-    return download(c, map, base + o_map, map_bytes);
+    return launch_map(c, d_dirs, d_loads, n, n_theta, distance, reinterpret_cast<SampleRec*>(base + o_samples), d_out);
 }
-
-}  // extern "C"

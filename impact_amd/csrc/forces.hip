@@ -8,12 +8,18 @@
 //   DynamicKinematicSpringForceGenerator::apply        spring_force.rs:191-243
 //   DynamicGravityManager::compute_and_apply           dynamic_gravity.rs:103-231
 //   AlignmentTorqueGenerator::apply                    alignment_torque.rs:107-241
+//   DetailedDragForce::apply                           detailed_drag.rs:200-243, drag_load.rs:42-67 (the maps: drag.hip)
 //   reset of all bodies, then the phases in order      force.rs:130-159
 //
 // ONE text for host and device, as in motion.hip: the evaluation functions (fg_spring, fg_alignment, fg_pair), the composition of one body
 // (fg_apply_body) and the walk of one field member over its partners (fg_pair_take) are shared with ivx_fg_apply_host. f32 throughout, no
 // contraction, IEEE sqrt / div, the operation order of the reference (stated once per kind in include/impact_voxel_hip.h); acos goes through
-// double precision rounded once (physics_internal.hpp, acos_rn).
+// double precision rounded once (physics_internal.hpp, acos_rn), and so does the drag phase's atan2.
+//
+// DETAILED DRAG is a set of its own (a registry of its own in the reference): generators sorted stably by body, in CSR form over the dynamic
+// bodies beside the entries of the other kinds. Its maps are resident in the world (FgMedia: a slot table of device allocations, the medium),
+// a table of {map address, n_theta} per slot travels with the plan. The table's base and the medium are wave-uniform (kernel arguments); the
+// generator, its table row and the map cell are per lane: one 24-byte gather per generator.
 //
 // EVERY BODY'S SUMS ARE MADE BY ONE LANE IN A FIXED ORDER; there is no float atomic. The host sorts once per set call: per dynamic body the
 // list of its entries (generator | role << 31), stably by (phase, list index), in CSR form over ALL dynamic bodies (the reset touches all of
@@ -32,6 +38,8 @@
 //                         torque_j as the higher: per body the very order of the reference's double loop, at twice its arithmetic.
 //   k_fg_apply            a lane per dynamic body, 256-thread workgroups, no LDS: reset, the body's entries in phase order, the resident
 //                         gravity load at gravity's place.
+//   k_fg_apply_drag       the same with the body's drag generators ahead of the gravity load: launched instead of k_fg_apply while a drag set
+//                         is installed (the launch count stays).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -40,6 +48,7 @@
 
 #include "ivx_internal.hpp"
 #include "device_common.hpp"
+#include "drag_internal.hpp"
 #include "physics_internal.hpp"
 #include "vec3.hpp"
 
@@ -47,6 +56,7 @@ namespace {
 
 using namespace ivx_vec;  // V3, Q4, mk, ld3, st3, the operators, dot, cross, qrot
 using ivx_phys::acos_rn;
+using ivx_phys::atan2_rn;
 
 #define FG_HD __host__ __device__ __forceinline__
 
@@ -250,24 +260,59 @@ FG_HD void fg_pair_take(float g, const FgGravBody& own, const FgGravBody& other,
     }
 }
 
+// ---- detailed drag ---------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(ivx_uniform_medium) == 16 && sizeof(ivx_drag_generator) == 16 && sizeof(ivx_drag_map_view) == 16 && sizeof(ivx_drag_load) == 24, "drag layouts");
+FG_HD bool fg_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }  // (false for NaN)
+// DetailedDragForce::apply + DragLoad::compute_world_space_drag_force_and_torque; `maps`: the slot table (device addresses on the device)
+FG_HD void fg_drag(const ivx_rigid_body& b, const ivx_drag_generator& gen, const ivx_drag_map_view* maps, const ivx_uniform_medium& medium, V3& F, V3& T) {
+    const V3 v_rel = div_recip(ld3(b.momentum), b.mass) - ld3(medium.velocity);
+    const float s2 = dot(v_rel, v_rel);
+    if (!(s2 > 0.0f)) return;  // at rest in the medium (or NaN)
+    const Q4 q = ldq(b.orientation);
+    const V3 d = div_recip(qrot(Q4{-q.x, -q.y, -q.z, q.w}, v_rel), sqrtf(s2));
+    if (!(fg_finite(d.x) && fg_finite(d.y) && fg_finite(d.z))) return;
+    const float phi = atan2_rn(d.y, d.x), theta = acos_rn(fg_clamp_unit(d.z));
+    const ivx_drag_map_view map = maps[gen.map];
+    const float cell = ivx_drag::PI_F / (float)map.n_theta, inv_cell = 1.0f / cell;
+    const ivx_drag_load& load = map.loads[(size_t)ivx_drag::theta_idx_of(theta, inv_cell, map.n_theta) * (2u * map.n_theta) + ivx_drag::phi_idx_of(phi, inv_cell, 2u * map.n_theta)];
+    const float fs = (((gen.scaling * gen.scaling) * medium.mass_density) * gen.drag_coefficient) * s2;
+    const float ts = gen.scaling * fs;
+    F = F + qrot(q, ld3(load.force)) * fs;
+    T = T + qrot(q, ld3(load.torque)) * ts;
+}
+// what the drag phase reads: the generators sorted by body, per body its range of them (null: no drag set), the slot table, the medium
+struct FgDrag {
+    const ivx_drag_generator* gens;
+    const uint32_t* offsets;
+    const ivx_drag_map_view* maps;
+    ivx_uniform_medium medium;
+};
+
 // ---- the composition for ONE body ----------------------------------------------------------------------------------------------------------
-// reset, then the body's entries [begin, end) in phase order, the gravity load between the springs and the alignment torques. `dyn` is the whole
-// array: the other end of a dynamic-dynamic spring is read from it field by field.
+// the body's drag generators in list order, then its gravity load (apply_loads): what stands between the springs and the alignment torques
+FG_HD void fg_drag_and_gravity(uint32_t body, const ivx_rigid_body& b, const FgDrag& drag, uint32_t rank, const FgLoad* loads, V3& F, V3& T) {
+    if (drag.offsets)  // (wave-uniform: a kernel argument)
+        for (uint32_t e = drag.offsets[body], end = drag.offsets[body + 1u]; e < end; ++e) fg_drag(b, drag.gens[e], drag.maps, drag.medium, F, T);
+    if (rank != FG_NOT_IN_FIELD) {
+        F = F + ld3(loads[rank].force);
+        T = T + ld3(loads[rank].torque);
+    }
+}
+
+// reset, then the body's entries [begin, end) in phase order, the drag generators and the gravity load between the springs and the alignment
+// torques. `dyn` is the whole array: the other end of a dynamic-dynamic spring is read from it field by field.
 FG_HD void fg_apply_body(uint32_t body, const ivx_rigid_body* dyn, const ivx_kinematic_body* kin, const ivx_force_generator* gens, const uint32_t* entries,
-                         uint32_t begin, uint32_t end, uint32_t rank, const FgLoad* loads, V3* force_out, V3* torque_out) {
+                         uint32_t begin, uint32_t end, uint32_t rank, const FgLoad* loads, const FgDrag& drag, V3* force_out, V3* torque_out) {
     const ivx_rigid_body& b = dyn[body];
     const V3 position = ld3(b.position);
     V3 F = mk(0.0f, 0.0f, 0.0f), T = mk(0.0f, 0.0f, 0.0f);
-    bool gravity_pending = rank != FG_NOT_IN_FIELD;
-    for (uint32_t e = begin; e < end; ++e) {
+    // (the entries are sorted by phase: those ahead of drag and gravity, that middle ONCE — one inlined copy of it —, then the alignment torques)
+    uint32_t e = begin;
+    for (; e < end; ++e) {
         const uint32_t entry = entries[e];
         const ivx_force_generator& gen = gens[entry & ~FG_ROLE_SECOND];
         const float* p = gen.p;
-        if (gen.kind >= IVX_FG_ALIGNMENT_FIXED && gravity_pending) {  // apply_loads, ahead of the first alignment torque
-            F = F + ld3(loads[rank].force);
-            T = T + ld3(loads[rank].torque);
-            gravity_pending = false;
-        }
+        if (gen.kind >= IVX_FG_ALIGNMENT_FIXED) break;
         switch (gen.kind) {
         case IVX_FG_CONSTANT_ACCELERATION: F = F + ld3(p) * b.mass; break;
         case IVX_FG_LOCAL_FORCE: {
@@ -287,7 +332,7 @@ FG_HD void fg_apply_body(uint32_t body, const ivx_rigid_body* dyn, const ivx_kin
                 else fg_add_force(F, T, position, -force_on_2, e1.attachment);
             }
         } break;
-        case IVX_FG_SPRING_DYNAMIC_KINEMATIC: {
+        default: {  // IVX_FG_SPRING_DYNAMIC_KINEMATIC (the kinds are validated on the host)
             const bool damped = fg_spring_damped(p);
             FgEnd e1, e2;
             fg_end_dynamic(b, ld3(p), damped, &e1);
@@ -295,19 +340,21 @@ FG_HD void fg_apply_body(uint32_t body, const ivx_rigid_body* dyn, const ivx_kin
             V3 force_on_2;
             if (fg_spring(e1, e2, p, damped, &force_on_2)) fg_add_force(F, T, position, -force_on_2, e1.attachment);
         } break;
-        case IVX_FG_ALIGNMENT_FIXED: T = T + fg_alignment(b, p, ld3(p + 3)); break;
-        default: {  // IVX_FG_ALIGNMENT_GRAVITY (the kinds are validated on the host)
-            if (rank == FG_NOT_IN_FIELD) break;
-            const V3 load = ld3(loads[rank].force);
-            const float n2 = (load.x * load.x + load.y * load.y) + load.z * load.z;
-            if (!(n2 > 1e-9f * 1e-9f)) break;
-            T = T + fg_alignment(b, p, div_recip(load, sqrtf(n2)));
-        } break;
         }
     }
-    if (gravity_pending) {
-        F = F + ld3(loads[rank].force);
-        T = T + ld3(loads[rank].torque);
+    fg_drag_and_gravity(body, b, drag, rank, loads, F, T);
+    for (; e < end; ++e) {
+        const ivx_force_generator& gen = gens[entries[e]];
+        const float* p = gen.p;
+        V3 direction = ld3(p + 3);  // IVX_FG_ALIGNMENT_FIXED
+        if (gen.kind != IVX_FG_ALIGNMENT_FIXED) {  // IVX_FG_ALIGNMENT_GRAVITY
+            if (rank == FG_NOT_IN_FIELD) continue;
+            const V3 load = ld3(loads[rank].force);
+            const float n2 = (load.x * load.x + load.y * load.y) + load.z * load.z;
+            if (!(n2 > 1e-9f * 1e-9f)) continue;
+            direction = div_recip(load, sqrtf(n2));
+        }
+        T = T + fg_alignment(b, p, direction);
     }
     *force_out = F, *torque_out = T;
 }
@@ -346,13 +393,27 @@ __global__ __launch_bounds__(FG_TILE) void k_fg_gravity(const FgGravBody* __rest
 }
 
 // (no __restrict__ on dyn: a lane reads other bodies' configurations and momenta from the array it writes its totals into)
+// Two forms of one body: without a drag set the kernel has the argument list and the code it had before the drag phase existed (the null CSR is
+// a constant there, and the phase is compiled out); with one it also takes the drag generators, their CSR, the slot table and the medium.
 __global__ __launch_bounds__(256) void k_fg_apply(ivx_rigid_body* dyn, uint32_t n_dyn, const ivx_kinematic_body* __restrict__ kin,
                                                   const ivx_force_generator* __restrict__ gens, const uint32_t* __restrict__ offsets,
                                                   const uint32_t* __restrict__ entries, const uint32_t* __restrict__ ranks, const FgLoad* __restrict__ loads) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_dyn) return;
     V3 F, T;
-    fg_apply_body(i, dyn, kin, gens, entries, offsets[i], offsets[i + 1u], ranks[i], loads, &F, &T);
+    fg_apply_body(i, dyn, kin, gens, entries, offsets[i], offsets[i + 1u], ranks[i], loads, FgDrag{nullptr, nullptr, nullptr, ivx_uniform_medium{0.0f, {0.0f, 0.0f, 0.0f}}}, &F, &T);
+    st3(dyn[i].total_force, F);
+    st3(dyn[i].total_torque, T);
+}
+__global__ __launch_bounds__(256) void k_fg_apply_drag(ivx_rigid_body* dyn, uint32_t n_dyn, const ivx_kinematic_body* __restrict__ kin,
+                                                       const ivx_force_generator* __restrict__ gens, const uint32_t* __restrict__ offsets,
+                                                       const uint32_t* __restrict__ entries, const uint32_t* __restrict__ ranks, const FgLoad* __restrict__ loads,
+                                                       const ivx_drag_generator* __restrict__ drag_gens, const uint32_t* __restrict__ drag_offsets,
+                                                       const ivx_drag_map_view* __restrict__ drag_maps, ivx_uniform_medium medium) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_dyn) return;
+    V3 F, T;
+    fg_apply_body(i, dyn, kin, gens, entries, offsets[i], offsets[i + 1u], ranks[i], loads, FgDrag{drag_gens, drag_offsets, drag_maps, medium}, &F, &T);
     st3(dyn[i].total_force, F);
     st3(dyn[i].total_torque, T);
 }
@@ -391,11 +452,34 @@ int fg_validate_field(const char* who, const uint32_t* field, size_t n, size_t n
     return IVX_OK;
 }
 
-// the plan of the two sets over n_dyn dynamic bodies: per body its entries in CSR form, stably by (phase, list index) — the phase of a kind is
+// detailed-drag generators against `n_dyn` bodies and a slot table of `n_maps` rows, of which has_map(row) says whether it holds a map
+template <typename HasMap>
+int fg_validate_drag(const char* who, const ivx_drag_generator* gens, size_t n, size_t n_dyn, size_t n_maps, HasMap has_map) {
+    for (size_t i = 0; i < n; ++i) {
+        const ivx_drag_generator& g = gens[i];
+        IVX_REQUIRE(g.body < n_dyn, IVX_ERR_INVALID, "%s: generator %zu (detailed drag) acts on dynamic body %u, there are %zu", who, i, g.body, n_dyn);
+        IVX_REQUIRE(g.map < n_maps, IVX_ERR_INVALID, "%s: generator %zu (detailed drag) names map slot %u, the table has %zu", who, i, g.map, n_maps);
+        IVX_REQUIRE(has_map(g.map), IVX_ERR_INVALID, "%s: generator %zu (detailed drag) names map slot %u, which holds no drag load map", who, i, g.map);
+    }
+    return IVX_OK;
+}
+
+// the plan of the sets over n_dyn dynamic bodies: per body its entries in CSR form, stably by (phase, list index) — the phase of a kind is
 // the kind, the two alignment kinds sharing one (they share one registry in the reference) — and its rank in the field
+// The drag set is a second CSR: its generators sorted stably by body (list order inside a body), and per body its range of them.
 struct FgPlan {
-    std::vector<uint32_t> offsets, entries, ranks;
+    std::vector<uint32_t> offsets, entries, ranks, drag_offsets;
+    std::vector<ivx_drag_generator> drag_sorted;
 };
+void fg_build_drag_plan(const ivx_drag_generator* drag, size_t n_drag, size_t n_dyn, FgPlan* plan) {
+    plan->drag_sorted.assign(drag, drag + n_drag);
+    plan->drag_offsets.clear();
+    if (n_drag == 0) return;
+    std::stable_sort(plan->drag_sorted.begin(), plan->drag_sorted.end(), [](const ivx_drag_generator& x, const ivx_drag_generator& y) { return x.body < y.body; });
+    plan->drag_offsets.assign(n_dyn + 1, 0);
+    for (const ivx_drag_generator& g : plan->drag_sorted) plan->drag_offsets[g.body + 1]++;
+    for (size_t b = 0; b < n_dyn; ++b) plan->drag_offsets[b + 1] += plan->drag_offsets[b];
+}
 void fg_build_plan(const ivx_force_generator* gens, size_t n, const uint32_t* field, size_t n_field, size_t n_dyn, FgPlan* plan) {
     struct Entry {
         uint32_t body, phase, entry;
@@ -419,16 +503,29 @@ void fg_build_plan(const ivx_force_generator* gens, size_t n, const uint32_t* fi
     for (size_t r = 0; r < n_field; ++r) plan->ranks[field[r]] = (uint32_t)r;
 }
 
-// world-owned state: the two sets as the caller gave them, and one device allocation (generators | offsets | entries | ranks | field | loads,
-// uploaded; then the gravity records, device-only) that only grows, with the pinned block its upload goes through. The plan is made for a
+// the world's medium and its drag load maps: a table of slots, each a device allocation of its own (a map is replaced in place, stream-ordered,
+// while it fits). They belong to the world and outlive the sets.
+#define FG_MAX_MAP_SLOTS 65536u
+struct FgMedia {
+    ivx_uniform_medium medium = {0.0f, {0.0f, 0.0f, 0.0f}};  // UniformMedium::vacuum()
+    struct Slot {
+        ivx_buf buf;
+        uint32_t n_theta = 0;  // 0: no map
+    };
+    std::vector<Slot> slots;
+};
+
+// world-owned state: the sets as the caller gave them, and one device allocation (generators | offsets | entries | ranks | field | loads | drag
+// generators | drag offsets | slot table, uploaded; then the gravity records, device-only) that only grows, with the pinned block its upload goes through. The plan is made for a
 // number of dynamic bodies; a world whose bodies have been replaced by another number since gets a new one at its next apply.
 struct FgState {
     std::vector<ivx_force_generator> gens;
     std::vector<uint32_t> field;
+    std::vector<ivx_drag_generator> drag;
     float g = 1.0f;
     ivx_buf dev;
     ivx_staging staging;
-    size_t at_offsets = 0, at_entries = 0, at_ranks = 0, at_field = 0, at_loads = 0, at_records = 0;
+    size_t at_offsets = 0, at_entries = 0, at_ranks = 0, at_field = 0, at_loads = 0, at_records = 0, at_drag = 0, at_drag_offsets = 0, at_maps = 0;
     uint32_t plan_dyn = 0;                // the plan on the device covers this many dynamic bodies
     bool installed = false;               // ... and stands
     uint32_t need_dyn = 0, need_kin = 0;  // the sets were checked against a world of at least this many bodies
@@ -439,9 +536,13 @@ int fg_install(ivx_world* w, FgState* st) {
     FgPlan plan;
     const size_t n = st->gens.size(), n_field = st->field.size(), n_dyn = w->n_dyn;
     fg_build_plan(st->gens.data(), n, st->field.data(), n_field, n_dyn, &plan);
+    fg_build_drag_plan(st->drag.data(), st->drag.size(), n_dyn, &plan);
+    const FgMedia* media = static_cast<const FgMedia*>(w->fg_media);
+    const size_t n_drag = st->drag.size(), n_slots = n_drag && media ? media->slots.size() : 0;
     ivx_layout l;
     const size_t at_gens = l.take(n * sizeof(ivx_force_generator)), at_offsets = l.take((n_dyn + 1) * 4), at_entries = l.take(plan.entries.size() * 4),
-                 at_ranks = l.take(n_dyn * 4), at_field = l.take(n_field * 4), at_loads = l.take(n_field * sizeof(FgLoad));
+                 at_ranks = l.take(n_dyn * 4), at_field = l.take(n_field * 4), at_loads = l.take(n_field * sizeof(FgLoad)), at_drag = l.take(n_drag * sizeof(ivx_drag_generator)), at_drag_offsets = l.take(plan.drag_offsets.size() * 4),
+                 at_maps = l.take(n_slots * sizeof(ivx_drag_map_view));
     const size_t upload = l.bytes;
     const size_t at_records = l.take(n_field * sizeof(FgGravBody));
     if (int rc = ivx_buf_grow(w->ctx, &st->dev, l.bytes, 1u << 12)) return rc;
@@ -454,11 +555,19 @@ int fg_install(ivx_world* w, FgState* st) {
     if (!plan.entries.empty()) memcpy(h + at_entries, plan.entries.data(), plan.entries.size() * 4);
     if (n_dyn) memcpy(h + at_ranks, plan.ranks.data(), n_dyn * 4);
     if (n_field) memcpy(h + at_field, st->field.data(), n_field * 4);
+    if (n_drag) {
+        memcpy(h + at_drag, plan.drag_sorted.data(), n_drag * sizeof(ivx_drag_generator));
+        memcpy(h + at_drag_offsets, plan.drag_offsets.data(), plan.drag_offsets.size() * 4);
+        ivx_drag_map_view* rows = reinterpret_cast<ivx_drag_map_view*>(h + at_maps);  // (device addresses; a slot without a map stays null and is named by no generator)
+        for (size_t s = 0; s < n_slots; ++s)
+            if (media->slots[s].n_theta) rows[s] = ivx_drag_map_view{static_cast<const ivx_drag_load*>(media->slots[s].buf.p), media->slots[s].n_theta, 0u};
+    }
     // (stream-ordered behind an apply that still reads the plan this one replaces)
     IVX_HIP_CHECK(ivx_memcpy_async(st->dev.p, h, upload, hipMemcpyHostToDevice, w->ctx->stream));
     IVX_HIP_CHECK(ivx_event_record(st->staging.staged, w->ctx->stream));
     st->staging.pending = true;
     st->at_offsets = at_offsets, st->at_entries = at_entries, st->at_ranks = at_ranks, st->at_field = at_field, st->at_loads = at_loads, st->at_records = at_records;
+    st->at_drag = at_drag, st->at_drag_offsets = at_drag_offsets, st->at_maps = at_maps;
     st->plan_dyn = (uint32_t)n_dyn;
     st->installed = true;
     return IVX_OK;
@@ -472,15 +581,25 @@ void fg_needs(FgState* st) {
         if (g.kind == IVX_FG_SPRING_DYNAMIC_KINEMATIC) need_kin = std::max(need_kin, g.body_b + 1u);
     }
     for (uint32_t b : st->field) need_dyn = std::max(need_dyn, b + 1u);
+    for (const ivx_drag_generator& g : st->drag) need_dyn = std::max(need_dyn, g.body + 1u);
     st->need_dyn = need_dyn, st->need_kin = need_kin;
 }
 
-// after one of the two sets has changed: both gone — the state leaves; else a new plan
+void fg_state_release(ivx_world* w) {
+    if (!w->fg_state) return;
+    FgState* st = static_cast<FgState*>(w->fg_state);
+    ivx_buf_free(&st->dev);
+    ivx_staging_release(&st->staging);
+    delete st;
+    w->fg_state = nullptr;
+}
+
+// after one of the three sets has changed: all gone — the state leaves (the medium and the maps stay); else a new plan
 int fg_sets_changed(ivx_world* w, FgState* st) {
     fg_needs(st);
-    if (st->gens.empty() && st->field.empty()) {  // (a launch in flight still reads the buffers: wait for it)
+    if (st->gens.empty() && st->field.empty() && st->drag.empty()) {  // (a launch in flight still reads the buffers: wait for it)
         IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));
-        ivx_fg_release(w);
+        fg_state_release(w);
         return IVX_OK;
     }
     if (w->n_dyn < st->need_dyn || w->n_kin < st->need_kin) {  // (the other set has outlived its bodies: no plan until both fit — ivx_forces_ready says so)
@@ -500,12 +619,51 @@ int fg_state_for(ivx_world* w, const char* who, FgState** out) {
     *out = st;
     return IVX_OK;
 }
+int fg_media_for(ivx_world* w, const char* who, FgMedia** out) {
+    FgMedia* m = static_cast<FgMedia*>(w->fg_media);
+    if (!m) {
+        m = new (std::nothrow) FgMedia();
+        IVX_REQUIRE(m, IVX_ERR_CAPACITY, "%s: out of host memory", who);
+        w->fg_media = m;
+    }
+    *out = m;
+    return IVX_OK;
+}
+// the slot's rows of the resident table are stale (another address or n_theta): the next apply uploads the plan again
+void fg_maps_changed(ivx_world* w) {
+    FgState* st = static_cast<FgState*>(w->fg_state);
+    if (st && !st->drag.empty()) st->installed = false;
+}
+bool fg_slot_in_use(const ivx_world* w, uint32_t slot) {
+    const FgState* st = static_cast<const FgState*>(w->fg_state);
+    if (st)
+        for (const ivx_drag_generator& g : st->drag)
+            if (g.map == slot) return true;
+    return false;
+}
+// slot `slot` exists and holds room for a map of n_theta rows (its contents are the caller's to write, on the stream)
+int fg_slot_for(ivx_world* w, const char* who, uint32_t slot, uint32_t n_theta, FgMedia::Slot** out) {
+    IVX_REQUIRE(slot < FG_MAX_MAP_SLOTS, IVX_ERR_CAPACITY, "%s: map slot %u, the table holds at most %u", who, slot, FG_MAX_MAP_SLOTS);
+    FgMedia* m;
+    if (int rc = fg_media_for(w, who, &m)) return rc;
+    if (m->slots.size() <= slot) m->slots.resize((size_t)slot + 1);
+    FgMedia::Slot* s = &m->slots[slot];
+    // (a buffer that has to grow waits for the stream first: an apply in flight may still read the old one)
+    if (int rc = ivx_buf_grow(w->ctx, &s->buf, 2u * (size_t)n_theta * n_theta * sizeof(ivx_drag_load), 1u << 12)) return rc;
+    s->n_theta = n_theta;
+    fg_maps_changed(w);
+    *out = s;
+    return IVX_OK;
+}
 
 // the whole stage over host arrays; gravity_loads6: 6 floats per field member or null
 void fg_apply_host(const ivx_force_generator* gens, size_t n, const uint32_t* field, size_t n_field, float g, ivx_rigid_body* dyn, size_t n_dyn,
-                   const ivx_kinematic_body* kin, float* gravity_loads6) {
+                   const ivx_kinematic_body* kin, float* gravity_loads6, const ivx_drag_generator* drag_gens = nullptr, size_t n_drag = 0,
+                   const ivx_drag_map_view* maps = nullptr, const ivx_uniform_medium* medium = nullptr) {
     FgPlan plan;
     fg_build_plan(gens, n, field, n_field, n_dyn, &plan);
+    fg_build_drag_plan(drag_gens, n_drag, n_dyn, &plan);
+    const FgDrag drag = {plan.drag_sorted.data(), n_drag ? plan.drag_offsets.data() : nullptr, maps, medium ? *medium : ivx_uniform_medium{0.0f, {0.0f, 0.0f, 0.0f}}};
     std::vector<FgGravBody> records(n_field);
     std::vector<FgLoad> loads(n_field);
     for (size_t k = 0; k < n_field; ++k) records[k] = fg_grav_record(dyn[field[k]]);
@@ -519,7 +677,7 @@ void fg_apply_host(const ivx_force_generator* gens, size_t n, const uint32_t* fi
     }
     for (size_t b = 0; b < n_dyn; ++b) {
         V3 F, T;
-        fg_apply_body((uint32_t)b, dyn, kin, gens, plan.entries.data(), plan.offsets[b], plan.offsets[b + 1], plan.ranks[b], loads.data(), &F, &T);
+        fg_apply_body((uint32_t)b, dyn, kin, gens, plan.entries.data(), plan.offsets[b], plan.offsets[b + 1], plan.ranks[b], loads.data(), drag, &F, &T);
         st3(dyn[b].total_force, F);
         st3(dyn[b].total_torque, T);
     }
@@ -528,20 +686,21 @@ void fg_apply_host(const ivx_force_generator* gens, size_t n, const uint32_t* fi
 }  // namespace
 
 void ivx_fg_release(ivx_world* w) {
-    if (!w || !w->fg_state) return;
-    FgState* st = static_cast<FgState*>(w->fg_state);
-    ivx_buf_free(&st->dev);
-    ivx_staging_release(&st->staging);
-    delete st;
-    w->fg_state = nullptr;
+    if (!w) return;
+    fg_state_release(w);
+    if (FgMedia* m = static_cast<FgMedia*>(w->fg_media)) {
+        for (FgMedia::Slot& s : m->slots) ivx_buf_free(&s.buf);
+        delete m;
+        w->fg_media = nullptr;
+    }
 }
 
 int ivx_forces_ready(ivx_world* w, const char* who) {
     FgState* st = static_cast<FgState*>(w->fg_state);
     if (!st) return IVX_OK;
     IVX_REQUIRE(w->n_dyn >= st->need_dyn && w->n_kin >= st->need_kin, IVX_ERR_STATE,
-                "%s: the force generators and the gravity field refer to %u dynamic and %u kinematic bodies, the world now has %u and %u (call "
-                "ivx_world_set_force_generators / ivx_world_set_dynamic_gravity again)",
+                "%s: the force generators, the gravity field and the detailed-drag set refer to %u dynamic and %u kinematic bodies, the world now has %u and %u (call "
+                "ivx_world_set_force_generators / ivx_world_set_dynamic_gravity / ivx_world_set_detailed_drag again)",
                 who, st->need_dyn, st->need_kin, w->n_dyn, w->n_kin);
     return IVX_OK;
 }
@@ -562,9 +721,15 @@ int ivx_launch_forces_apply(ivx_world* w, const char* who) {
                     records);
         IVX_KLAUNCH(k_fg_gravity, dim3((n_field + FG_TILE - 1u) / FG_TILE), dim3(FG_TILE), 0, w->ctx->stream, records, n_field, st->g, loads);
     }
-    IVX_KLAUNCH(k_fg_apply, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn, w->n_dyn, w->kin, reinterpret_cast<const ivx_force_generator*>(base),
-                reinterpret_cast<const uint32_t*>(base + st->at_offsets), reinterpret_cast<const uint32_t*>(base + st->at_entries),
-                reinterpret_cast<const uint32_t*>(base + st->at_ranks), loads);
+    const ivx_force_generator* d_gens = reinterpret_cast<const ivx_force_generator*>(base);
+    const uint32_t *d_offsets = reinterpret_cast<const uint32_t*>(base + st->at_offsets), *d_entries = reinterpret_cast<const uint32_t*>(base + st->at_entries),
+                   *d_ranks = reinterpret_cast<const uint32_t*>(base + st->at_ranks);
+    if (st->drag.empty())
+        IVX_KLAUNCH(k_fg_apply, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn, w->n_dyn, w->kin, d_gens, d_offsets, d_entries, d_ranks, loads);
+    else
+        IVX_KLAUNCH(k_fg_apply_drag, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn, w->n_dyn, w->kin, d_gens, d_offsets, d_entries, d_ranks, loads,
+                    reinterpret_cast<const ivx_drag_generator*>(base + st->at_drag), reinterpret_cast<const uint32_t*>(base + st->at_drag_offsets),
+                    reinterpret_cast<const ivx_drag_map_view*>(base + st->at_maps), static_cast<const FgMedia*>(w->fg_media)->medium);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -627,6 +792,100 @@ int ivx_fg_apply_host(const ivx_force_generator* gens, size_t n, const uint32_t*
     if (int rc = fg_validate(who, gens, n, n_dynamic, n_kinematic)) return rc;
     if (int rc = fg_validate_field(who, gravity_bodies, n_gravity, n_dynamic)) return rc;
     fg_apply_host(gens, n, gravity_bodies, n_gravity, gravitational_constant, dynamic, n_dynamic, kinematic, gravity_loads6);
+    return IVX_OK;
+}
+
+int ivx_world_set_medium(ivx_world* w, const ivx_uniform_medium* medium) {
+    const char* who = "ivx_world_set_medium";
+    IVX_REQUIRE(w && medium, IVX_ERR_INVALID, "%s: null argument", who);
+    FgMedia* m;
+    if (int rc = fg_media_for(w, who, &m)) return rc;
+    m->medium = *medium;  // (a kernel argument of the next apply)
+    return IVX_OK;
+}
+
+int ivx_world_medium(ivx_world* w, ivx_uniform_medium* out) {
+    IVX_REQUIRE(w && out, IVX_ERR_INVALID, "ivx_world_medium: null argument");
+    *out = w->fg_media ? static_cast<const FgMedia*>(w->fg_media)->medium : ivx_uniform_medium{0.0f, {0.0f, 0.0f, 0.0f}};
+    return IVX_OK;
+}
+
+int ivx_world_set_drag_map(ivx_world* w, uint32_t slot, const ivx_drag_load* map, uint32_t n_theta) {
+    const char* who = "ivx_world_set_drag_map";
+    IVX_REQUIRE(w && (map || n_theta == 0), IVX_ERR_INVALID, "%s: null argument", who);
+    IVX_REQUIRE(slot < FG_MAX_MAP_SLOTS, IVX_ERR_CAPACITY, "%s: map slot %u, the table holds at most %u", who, slot, FG_MAX_MAP_SLOTS);
+    IVX_REQUIRE(n_theta <= ivx_drag::MAX_THETA, IVX_ERR_CAPACITY, "%s: n_theta_coords %u exceeds %u", who, n_theta, ivx_drag::MAX_THETA);
+    if (n_theta == 0) {  // free the slot
+        FgMedia* m = static_cast<FgMedia*>(w->fg_media);
+        if (!m || slot >= m->slots.size() || m->slots[slot].n_theta == 0) return IVX_OK;
+        IVX_REQUIRE(!fg_slot_in_use(w, slot), IVX_ERR_STATE, "%s: map slot %u is named by the installed detailed-drag set (replace or remove the set first)", who, slot);
+        IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));  // (nothing in flight reads it any more; a later set that names it is refused)
+        ivx_buf_free(&m->slots[slot].buf);
+        m->slots[slot].n_theta = 0;
+        return IVX_OK;
+    }
+    FgMedia::Slot* s;
+    if (int rc = fg_slot_for(w, who, slot, n_theta, &s)) return rc;
+    // on the stream, behind an apply that still reads the map this one replaces; `map` is the caller's pageable memory: wait until it has left
+    IVX_HIP_CHECK(ivx_memcpy_async(s->buf.p, map, 2u * (size_t)n_theta * n_theta * sizeof(ivx_drag_load), hipMemcpyHostToDevice, w->ctx->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));
+    return IVX_OK;
+}
+
+int ivx_world_set_drag_map_from_grid(ivx_world* w, uint32_t slot, ivx_grid* g, const float com[3], const ivx_drag_map_config* cfg) {
+    const char* who = "ivx_world_set_drag_map_from_grid";
+    IVX_REQUIRE(w && g && com && cfg, IVX_ERR_INVALID, "%s: null argument", who);
+    IVX_REQUIRE(g->ctx == w->ctx, IVX_ERR_INVALID, "%s: the grid belongs to another context than the world", who);
+    IVX_REQUIRE(slot < FG_MAX_MAP_SLOTS, IVX_ERR_CAPACITY, "%s: map slot %u, the table holds at most %u", who, slot, FG_MAX_MAP_SLOTS);
+    if (int rc = ivx_drag_map_check(who, g, com, cfg)) return rc;  // (before the slot changes)
+    FgMedia::Slot* s;
+    if (int rc = fg_slot_for(w, who, slot, cfg->n_theta_coords, &s)) return rc;
+    return ivx_drag_map_build(who, g, com, cfg, static_cast<float*>(s->buf.p), nullptr);  // (enqueued: the map never crosses to the host)
+}
+
+int ivx_world_drag_map_download(ivx_world* w, uint32_t slot, ivx_drag_load* map, size_t cap_cells, uint32_t* n_theta) {
+    const char* who = "ivx_world_drag_map_download";
+    IVX_REQUIRE(w && n_theta, IVX_ERR_INVALID, "%s: null argument", who);
+    *n_theta = 0;
+    const FgMedia* m = static_cast<const FgMedia*>(w->fg_media);
+    if (!m || slot >= m->slots.size() || m->slots[slot].n_theta == 0) return IVX_OK;
+    const FgMedia::Slot& s = m->slots[slot];
+    const size_t cells = 2u * (size_t)s.n_theta * s.n_theta;
+    *n_theta = s.n_theta;
+    if (!map && cap_cells == 0) return IVX_OK;  // (the size alone)
+    IVX_REQUIRE(map, IVX_ERR_INVALID, "%s: null argument", who);
+    IVX_REQUIRE(cap_cells >= cells, IVX_ERR_CAPACITY, "%s: room for %zu cells, the map of slot %u has %zu", who, cap_cells, slot, cells);
+    IVX_HIP_CHECK(ivx_memcpy_async(map, s.buf.p, cells * sizeof(ivx_drag_load), hipMemcpyDeviceToHost, w->ctx->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));
+    return IVX_OK;
+}
+
+int ivx_world_set_detailed_drag(ivx_world* w, const ivx_drag_generator* gens, size_t n) {
+    const char* who = "ivx_world_set_detailed_drag";
+    IVX_REQUIRE(w && (gens || n == 0), IVX_ERR_INVALID, "%s: null argument", who);
+    IVX_REQUIRE(n < (1u << 24), IVX_ERR_CAPACITY, "%s: more than 2^24 generators", who);
+    if (n == 0 && !w->fg_state) return IVX_OK;
+    const FgMedia* m = static_cast<const FgMedia*>(w->fg_media);
+    if (int rc = fg_validate_drag(who, gens, n, w->n_dyn, m ? m->slots.size() : 0, [m](uint32_t slot) { return m->slots[slot].n_theta != 0; })) return rc;
+    FgState* st;
+    if (int rc = fg_state_for(w, who, &st)) return rc;
+    st->drag.assign(gens, gens + n);
+    return fg_sets_changed(w, st);
+}
+
+int ivx_fg_apply_host_drag(const ivx_force_generator* gens, size_t n, const uint32_t* gravity_bodies, size_t n_gravity, float gravitational_constant, ivx_rigid_body* dynamic,
+                           size_t n_dynamic, const ivx_kinematic_body* kinematic, size_t n_kinematic, float* gravity_loads6, const ivx_drag_generator* drag, size_t n_drag,
+                           const ivx_drag_map_view* maps, size_t n_maps, const ivx_uniform_medium* medium) {
+    const char* who = "ivx_fg_apply_host_drag";
+    IVX_REQUIRE((gens || n == 0) && (gravity_bodies || n_gravity == 0) && (dynamic || n_dynamic == 0) && (kinematic || n_kinematic == 0) && (drag || n_drag == 0) &&
+                    (maps || n_maps == 0) && (medium || n_drag == 0),
+                IVX_ERR_INVALID, "%s: null argument", who);
+    if (int rc = fg_validate(who, gens, n, n_dynamic, n_kinematic)) return rc;
+    if (int rc = fg_validate_field(who, gravity_bodies, n_gravity, n_dynamic)) return rc;
+    for (size_t s = 0; s < n_maps; ++s)
+        IVX_REQUIRE(maps[s].n_theta <= ivx_drag::MAX_THETA, IVX_ERR_CAPACITY, "%s: map slot %zu: n_theta_coords %u exceeds %u", who, s, maps[s].n_theta, ivx_drag::MAX_THETA);
+    if (int rc = fg_validate_drag(who, drag, n_drag, n_dynamic, n_maps, [maps](uint32_t slot) { return maps[slot].loads && maps[slot].n_theta != 0; })) return rc;
+    fg_apply_host(gens, n, gravity_bodies, n_gravity, gravitational_constant, dynamic, n_dynamic, kinematic, gravity_loads6, drag, n_drag, maps, medium);
     return IVX_OK;
 }
 

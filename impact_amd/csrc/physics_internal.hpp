@@ -22,6 +22,8 @@ IVX_PHYS_HD float cos_rn(float x) { return (float)cos((double)x); }
 IVX_PHYS_HD float tan_rn(float x) { return (float)tan((double)x); }
 // f32::acos of the alignment torque (forces.hip), for the same reason: the argument is clamped to [-1, 1] by the caller
 IVX_PHYS_HD float acos_rn(float x) { return (float)acos((double)x); }
+// f32::atan2 of the drag phase (forces.hip: the azimuth of a body's motion through the medium), for the same reason
+IVX_PHYS_HD float atan2_rn(float y, float x) { return (float)atan2((double)y, (double)x); }
 IVX_PHYS_HD Q4 qnormalize(Q4 q) {
     const float l = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
     return {q.x / l, q.y / l, q.z / l, q.w / l};
@@ -198,7 +200,8 @@ struct ivx_world {
     std::vector<uint32_t> chain_bodies, prev_chain_start, prev_chain_bodies;  // body pair per chain; last frame's chains (an unchanged contact structure keeps its schedule)
     float time;      // the simulation clock (ivx_world_set_time / ivx_world_time): every step adds its dt; host-side only
     void* md_state;  // motion drivers (motion.hip): the sorted driver set, the compact list of driven bodies and their offsets; made by ivx_world_set_motion_drivers, freed by ivx_md_release
-    void* fg_state;  // force generators and dynamic gravity (forces.hip): the two sets, their plan over the dynamic bodies, the resident gravity loads; null while neither set is installed; freed by ivx_fg_release
+    void* fg_state;  // force generators, dynamic gravity and detailed drag (forces.hip): the three sets, their plan over the dynamic bodies, the resident gravity loads; null while none of the sets is installed; freed by ivx_fg_release
+    void* fg_media;  // the uniform medium and the resident drag load maps (forces.hip): they belong to the world and outlive the sets; made on first use, freed by ivx_fg_release
     void* cw_state;  // primitive collidables (narrow.hip): local and world-space records, wave masks and offsets, contact and deferred buffers; made on first use, freed by ivx_cw_release
 };
 
@@ -206,9 +209,9 @@ void ivx_cw_release(ivx_world* w);  // narrow.hip (ivx_world_destroy)
 void ivx_md_release(ivx_world* w);  // motion.hip (ivx_world_destroy)
 int ivx_motion_ready(ivx_world* w, const char* who);  // motion.hip: IVX_ERR_STATE when the driver set refers to more kinematic bodies than the world holds (checked before a step launches anything)
 int ivx_launch_motion_apply(ivx_world* w, float time, const char* who);  // motion.hip: nothing without a driver set
-void ivx_fg_release(ivx_world* w);  // forces.hip (ivx_world_destroy)
+void ivx_fg_release(ivx_world* w);  // forces.hip (ivx_world_destroy): the sets, the medium and the maps
 int ivx_forces_ready(ivx_world* w, const char* who);  // forces.hip: IVX_ERR_STATE when the sets refer to more bodies than the world holds (checked before a step launches anything)
-int ivx_launch_forces_apply(ivx_world* w, const char* who);  // forces.hip: nothing while neither set is installed
+int ivx_launch_forces_apply(ivx_world* w, const char* who);  // forces.hip: nothing while none of the sets is installed
 int ivx_launch_phys_prepare_bodies(ivx_world* w);
 int ivx_launch_phys_prepare_contacts(ivx_world* w, const int32_t* d_prev_slot);
 int ivx_launch_phys_mark_joint_bodies(ivx_world* w);

@@ -609,6 +609,27 @@ static_assert(sizeof(ivx_force_generator) == 64 && sizeof(Spring) == 16 && sizeo
                   sizeof(GravityAlignmentTorque) == 24,
               "force generator layouts");
 
+// ---- detailed drag inside the force stage: the medium and the generator (medium.rs:11-68, detailed_drag.rs:44-57) -------------------------------
+struct UniformMedium {
+    float mass_density;
+    float velocity[3];
+    static constexpr float SEA_LEVEL_AIR_MASS_DENSITY = 1.2f;
+    static constexpr float WATER_MASS_DENSITY = 1e3f;
+    static UniformMedium vacuum() { return UniformMedium{0.0f, {0.0f, 0.0f, 0.0f}}; }
+    static UniformMedium moving_air(const float v[3]) { return UniformMedium{SEA_LEVEL_AIR_MASS_DENSITY, {v[0], v[1], v[2]}}; }
+    static UniformMedium still_air() { return UniformMedium{SEA_LEVEL_AIR_MASS_DENSITY, {0.0f, 0.0f, 0.0f}}; }
+    static UniformMedium moving_water(const float v[3]) { return UniformMedium{WATER_MASS_DENSITY, {v[0], v[1], v[2]}}; }
+    static UniformMedium still_water() { return UniformMedium{WATER_MASS_DENSITY, {0.0f, 0.0f, 0.0f}}; }
+    ivx_uniform_medium record() const { return ivx_uniform_medium{mass_density, {velocity[0], velocity[1], velocity[2]}}; }
+};
+struct DetailedDragForce {  // the map is a slot of the world's table (the reference's DragLoadMapID -> slot is the caller's mapping)
+    uint32_t drag_load_map;
+    float drag_coefficient;
+    float scaling = 1.0f;
+    ivx_drag_generator record(uint32_t body) const { return ivx_drag_generator{body, drag_load_map, drag_coefficient, scaling}; }
+};
+static_assert(sizeof(UniformMedium) == 16 && sizeof(ivx_uniform_medium) == 16 && sizeof(ivx_drag_generator) == 16 && sizeof(ivx_drag_map_view) == 16, "detailed drag layouts");
+
 // ---- rigid bodies + constraint solver (impact_physics/src/lib.rs:31-110) --------------------------------------------------------------
 class PhysicsWorld {
 public:
@@ -661,6 +682,29 @@ public:
         check(ivx_world_gravity_loads(w_, loads.data(), n_gravity_));
         return loads;
     }
+
+    // detailed drag: the medium and the maps belong to the world; the generators are a third set of the force stage
+    void set_medium(const UniformMedium& medium) {
+        const ivx_uniform_medium m = medium.record();
+        check(ivx_world_set_medium(w_, &m));
+    }
+    UniformMedium medium() {
+        ivx_uniform_medium m{};
+        check(ivx_world_medium(w_, &m));
+        return UniformMedium{m.mass_density, {m.velocity[0], m.velocity[1], m.velocity[2]}};
+    }
+    void set_drag_map(uint32_t slot, const std::vector<ivx_drag_load>& map, uint32_t n_theta) { check(ivx_world_set_drag_map(w_, slot, map.data(), n_theta)); }
+    void free_drag_map(uint32_t slot) { check(ivx_world_set_drag_map(w_, slot, nullptr, 0)); }
+    void set_drag_map_from_grid(uint32_t slot, ivx_grid* grid, const float center_of_mass[3], const ivx_drag_map_config& config) {
+        check(ivx_world_set_drag_map_from_grid(w_, slot, grid, center_of_mass, &config));
+    }
+    std::vector<ivx_drag_load> drag_map(uint32_t slot, uint32_t* n_theta) {
+        check(ivx_world_drag_map_download(w_, slot, nullptr, 0, n_theta));
+        std::vector<ivx_drag_load> map(2u * size_t(*n_theta) * *n_theta);
+        if (!map.empty()) check(ivx_world_drag_map_download(w_, slot, map.data(), map.size(), n_theta));
+        return map;
+    }
+    void set_detailed_drag(const std::vector<ivx_drag_generator>& generators) { check(ivx_world_set_detailed_drag(w_, generators.data(), generators.size())); }
 
 private:
     ivx_world* w_ = nullptr;

@@ -748,8 +748,8 @@ int ivx_world_set_spherical_joints(ivx_world*, const uint32_t* body_pairs, size_
  * advance momenta -> synchronise velocities, warm start, n_iterations sweeps, positional correction,
  * write back -> advance configurations -> motion drivers at the new simulation time (when a set is installed,
  * ivx_world_set_motion_drivers) -> force generators and dynamic gravity (when either is installed,
- * ivx_world_set_force_generators / ivx_world_set_dynamic_gravity; detailed drag is not part of that stage).
- * A world with neither keeps the total_force / total_torque the host gave its bodies. The stages are also exposed one by one. */
+ * ivx_world_set_force_generators / ivx_world_set_dynamic_gravity / ivx_world_set_detailed_drag).
+ * A world with none of them keeps the total_force / total_torque the host gave its bodies. The stages are also exposed one by one. */
 int ivx_world_step(ivx_world*, float dt, ivx_physics_result* out);
 /* the same step, only enqueued on the context's stream (no wait, no result): lets the rigid-body step of a frame run
  * behind the voxel step of the same frame with a single wait for both (ivx_voxel_step_collect / ivx_synchronize);
@@ -1268,8 +1268,8 @@ int ivx_md_apply_host(const ivx_motion_driver*, size_t n, ivx_kinematic_body* bo
  * Composition, the same code on the device and in ivx_fg_apply_host:
  *   - total_force and total_torque of ALL dynamic bodies are reset to +0.0;
  *   - the contributions are added in the reference's phase order: constant accelerations, local forces, dynamic-dynamic springs, dynamic-kinematic
- *     springs, [detailed drag: not part of this stage; ivx_drag_force_and_torque stays a host path], dynamic gravity, alignment torques (both
- *     kinds are one phase, as they are one registry);
+ *     springs, detailed drag (a set of its own, ivx_world_set_detailed_drag below), dynamic gravity, alignment torques (both kinds are one
+ *     phase, as they are one registry);
  *   - inside a phase the order is that of the caller's list. (The reference walks a hash map there, which nothing pins; the list order is this
  *     library's choice, as for the motion drivers.)
  *   - dynamic gravity: the field is the caller's list of dynamic bodies (KeyIndexMapper order). Per body the reference's double loop adds the pairs
@@ -1306,6 +1306,63 @@ int ivx_world_gravity_loads(ivx_world*, float* force3_torque3, size_t cap);
 /* The stage over host arrays, the code the kernels run (tests). Validates like the two set calls. gravity_loads6 (6 floats per field member) may be NULL. */
 int ivx_fg_apply_host(const ivx_force_generator*, size_t n, const uint32_t* gravity_bodies, size_t n_gravity, float gravitational_constant, ivx_rigid_body* dynamic,
                       size_t n_dynamic, const ivx_kinematic_body* kinematic, size_t n_kinematic, float* gravity_loads6);
+
+/* ---- detailed drag inside the force stage (force.rs:146-147, detailed_drag.rs:200-243, drag_load.rs:42-67, medium.rs:11-16) -----------------------
+ * The reference keeps drag load maps in a repository keyed by DragLoadMapID, a string hash; here a map lives in a numbered SLOT of the world's
+ * table (at most 65 536 slots), resident on the device. Which name goes to which slot is the caller's business, as entity ids are elsewhere.
+ * A detailed-drag generator names a dynamic body and a slot. The generators are a set of their own beside the force generators, as they are a
+ * registry of their own in the reference (and ivx_fg_apply_host keeps refusing kind 6).
+ *
+ * Arithmetic, one function for the kernel and for ivx_fg_apply_host_drag, in the conventions stated above (float32, uncontracted):
+ *   v      = momentum *recip mass
+ *   v_rel  = v - medium.velocity;  s2 = dot(v_rel, v_rel);  nothing unless s2 > 0 (so nothing for a NaN)
+ *   v_body = rotate(conjugate(q), v_rel);  d = v_body *recip sqrt(s2)
+ *   phi    = atan2(d.y, d.x);  theta = acos(clamp(d.z, -1, 1)), each the double-precision function rounded once
+ *   cell   = theta_idx * 2 n_theta + phi_idx, the indices those of ivx_drag_map_indices
+ *   fs     = (((scaling * scaling) * mass_density) * drag_coefficient) * s2;  ts = scaling * fs
+ *   total_force += fs * rotate(q, load.force);  total_torque += ts * rotate(q, load.torque)
+ * Deliberate differences from the reference: the acos argument is clamped (as in ivx_drag_force_and_torque); phi's index is clamped (as in
+ * ivx_drag_map_indices); a d with a non-finite component adds nothing — ivx_drag_force_and_torque refuses such a body, a stage cannot refuse
+ * in the middle of a step. ivx_drag_force_and_torque itself stays as it was: it DIVIDES by mass and by the speed where the reference, and this
+ * stage, multiply by the reciprocal (impact_math/src/vector.rs:679), sums its products without a stated association and takes atan2f / acosf;
+ * the two agree to tolerance, not to the bit.
+ * In the composition above the drag phase stands where the reference has it: behind the dynamic-kinematic springs and ahead of dynamic gravity;
+ * inside the phase the generators apply in list order, and several may name one body. */
+typedef struct {
+    float mass_density;
+    float velocity[3];
+} ivx_uniform_medium; /* UniformMedium. 16 bytes. */
+typedef struct {
+    uint32_t body; /* index into the dynamic bodies */
+    uint32_t map;  /* slot of the world's map table */
+    float drag_coefficient, scaling;
+} ivx_drag_generator; /* DetailedDragForce on one body. 16 bytes. */
+typedef struct {
+    const ivx_drag_load* loads; /* n_theta x 2 n_theta, theta-major; NULL: the slot holds no map */
+    uint32_t n_theta, reserved;
+} ivx_drag_map_view; /* one slot as ivx_fg_apply_host_drag reads it, in host memory. 16 bytes. */
+/* The world's medium; a new world has UniformMedium::vacuum() (all zero). Takes effect at the next apply. */
+int ivx_world_set_medium(ivx_world*, const ivx_uniform_medium*);
+int ivx_world_medium(ivx_world*, ivx_uniform_medium*);
+/* A host map into slot `slot` (n_theta in 1..2048); n_theta == 0 frees the slot. IVX_ERR_CAPACITY for a slot past 65 535; IVX_ERR_STATE when
+ * the installed drag set names the slot that is to be freed (the set and the map stay). Replacing a map is ordered on the context's stream
+ * behind an apply that still reads the old one. Maps and medium belong to the world: they outlive the sets. */
+int ivx_world_set_drag_map(ivx_world*, uint32_t slot, const ivx_drag_load* map, uint32_t n_theta);
+/* ivx_drag_load_map with the slot as destination: the same validation, passes and tiling; the map never crosses to the host. IVX_ERR_INVALID for
+ * a grid of another context, IVX_ERR_STATE for a grid without a current mesh; a mesh of fewer than 3 indices gives a zero map. */
+int ivx_world_set_drag_map_from_grid(ivx_world*, uint32_t slot, ivx_grid*, const float com[3], const ivx_drag_map_config*);
+/* The slot's map as it is resident; cap_cells counts ivx_drag_load records. *n_theta is 0 for a slot without a map (nothing is written); map
+ * NULL with cap_cells 0 asks for *n_theta alone. Waits for the stream. */
+int ivx_world_drag_map_download(ivx_world*, uint32_t slot, ivx_drag_load* map, size_t cap_cells, uint32_t* n_theta);
+/* The world's detailed-drag set, resident until replaced (n == 0 removes it). IVX_ERR_INVALID, with a message that names the generator (the set in
+ * force then stays): a body past the world's dynamic bodies, a slot past the table, a slot that holds no map (the reference panics: "Tried to
+ * obtain missing drag load map"). The set joins the other two: with any of the three installed every step ends with the force stage, and a world
+ * whose bodies have been replaced by fewer than the set refers to gets IVX_ERR_STATE at the next apply or step. */
+int ivx_world_set_detailed_drag(ivx_world*, const ivx_drag_generator*, size_t n);
+/* ivx_fg_apply_host with the drag phase: the stage over host arrays, the code the kernels run (tests). Validates like the set calls. */
+int ivx_fg_apply_host_drag(const ivx_force_generator*, size_t n, const uint32_t* gravity_bodies, size_t n_gravity, float gravitational_constant, ivx_rigid_body* dynamic,
+                           size_t n_dynamic, const ivx_kinematic_body* kinematic, size_t n_kinematic, float* gravity_loads6, const ivx_drag_generator*, size_t n_drag,
+                           const ivx_drag_map_view* maps, size_t n_maps, const ivx_uniform_medium*);
 
 #ifdef __cplusplus
 }

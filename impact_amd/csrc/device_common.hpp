@@ -22,6 +22,31 @@ static inline void ivx_buf_free(ivx_buf* b) {
     b->p = nullptr, b->bytes = 0;
 }
 
+// A typed device array that only grows: a pointer and a capacity in elements. `grow`: at least `need` elements afterwards; an array that has
+// to grow waits for the stream first, does not keep its contents and becomes max(need, twice what it was). (ivx_dev_grow is the same on an
+// array known by its element size only: a table of arrays of several types walks them with it.)
+static inline int ivx_dev_grow(void** p, size_t* cap, size_t elem_bytes, size_t need, hipStream_t s) {
+    if (need <= *cap) return IVX_OK;
+    const size_t ncap = need > *cap * 2 ? need : *cap * 2;
+    IVX_HIP_CHECK(ivx_stream_sync(s));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    IVX_HIP_CHECK(hipMalloc(p, ncap * elem_bytes));
+    *cap = ncap;
+    return IVX_OK;
+}
+template <class T>
+struct ivx_dev_array {
+    T* p = nullptr;
+    size_t cap = 0;
+    int grow(hipStream_t s, size_t need) { return ivx_dev_grow(reinterpret_cast<void**>(&p), &cap, sizeof(T), need, s); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+};
+
 // `m` holds at least `bytes` afterwards. A block that has to grow does not keep its contents and is made `want` bytes (the owner's growth
 // rule, at least `bytes`); `wait` non-null: what is in flight on that stream may still use the old block and is waited for first.
 static inline void ivx_mapped_free(ivx_mapped* m) {

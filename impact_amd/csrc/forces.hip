@@ -717,7 +717,7 @@ int ivx_launch_forces_apply(ivx_world* w, const char* who) {
     FgLoad* loads = reinterpret_cast<FgLoad*>(base + st->at_loads);
     if (n_field) {
         FgGravBody* records = reinterpret_cast<FgGravBody*>(base + st->at_records);
-        IVX_KLAUNCH(k_fg_gravity_records, dim3((n_field + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn, reinterpret_cast<const uint32_t*>(base + st->at_field), n_field,
+        IVX_KLAUNCH(k_fg_gravity_records, dim3((n_field + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn.p, reinterpret_cast<const uint32_t*>(base + st->at_field), n_field,
                     records);
         IVX_KLAUNCH(k_fg_gravity, dim3((n_field + FG_TILE - 1u) / FG_TILE), dim3(FG_TILE), 0, w->ctx->stream, records, n_field, st->g, loads);
     }
@@ -725,9 +725,9 @@ int ivx_launch_forces_apply(ivx_world* w, const char* who) {
     const uint32_t *d_offsets = reinterpret_cast<const uint32_t*>(base + st->at_offsets), *d_entries = reinterpret_cast<const uint32_t*>(base + st->at_entries),
                    *d_ranks = reinterpret_cast<const uint32_t*>(base + st->at_ranks);
     if (st->drag.empty())
-        IVX_KLAUNCH(k_fg_apply, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn, w->n_dyn, w->kin, d_gens, d_offsets, d_entries, d_ranks, loads);
+        IVX_KLAUNCH(k_fg_apply, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn.p, w->n_dyn, w->kin.p, d_gens, d_offsets, d_entries, d_ranks, loads);
     else
-        IVX_KLAUNCH(k_fg_apply_drag, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn, w->n_dyn, w->kin, d_gens, d_offsets, d_entries, d_ranks, loads,
+        IVX_KLAUNCH(k_fg_apply_drag, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->dyn.p, w->n_dyn, w->kin.p, d_gens, d_offsets, d_entries, d_ranks, loads,
                     reinterpret_cast<const ivx_drag_generator*>(base + st->at_drag), reinterpret_cast<const uint32_t*>(base + st->at_drag_offsets),
                     reinterpret_cast<const ivx_drag_map_view*>(base + st->at_maps), static_cast<const FgMedia*>(w->fg_media)->medium);
     IVX_HIP_CHECK(hipGetLastError());

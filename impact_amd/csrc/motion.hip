@@ -247,7 +247,7 @@ int ivx_launch_motion_apply(ivx_world* w, float time, const char* who) {
     if (int rc = ivx_motion_ready(w, who)) return rc;
     const char* base = static_cast<const char*>(st->dev.p);
     IVX_KLAUNCH(k_motion_apply, dim3((st->n_driven + 255u) / 256u), dim3(256), 0, w->ctx->stream, reinterpret_cast<const ivx_motion_driver*>(base),
-                reinterpret_cast<const uint32_t*>(base + st->at_bodies), reinterpret_cast<const uint32_t*>(base + st->at_offsets), st->n_driven, time, w->kin);
+                reinterpret_cast<const uint32_t*>(base + st->at_bodies), reinterpret_cast<const uint32_t*>(base + st->at_offsets), st->n_driven, time, w->kin.p);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }

@@ -457,8 +457,8 @@ int ivx_cw_synchronize(ivx_world* w) {
     if (int rc = ivx_bvol_set_begin(c, n, &d_boxes, &d_kinds)) return rc;
     if (n) {
         const uint32_t slots = ((n + 63u) / 64u) * 64u;
-        IVX_KLAUNCH(k_cw_sync, dim3((slots + 255u) / 256u), dim3(256), 0, c->stream, static_cast<const ivx_collidable*>(st->local.p), n, slots, (const ivx_rigid_body*)w->dyn,
-                    (const ivx_kinematic_body*)w->kin, static_cast<ivx_collidable*>(st->world.p), d_boxes, d_kinds);
+        IVX_KLAUNCH(k_cw_sync, dim3((slots + 255u) / 256u), dim3(256), 0, c->stream, static_cast<const ivx_collidable*>(st->local.p), n, slots, (const ivx_rigid_body*)w->dyn.p,
+                    (const ivx_kinematic_body*)w->kin.p, static_cast<ivx_collidable*>(st->world.p), d_boxes, d_kinds);
         IVX_HIP_CHECK(hipGetLastError());
     }
     if (int rc = ivx_bvol_set_finish(c, n)) return rc;

@@ -1361,30 +1361,30 @@ __global__ __launch_bounds__(256) void k_mark_bodies(uint32_t n, const uint32_t*
 int ivx_launch_phys_prepare_bodies(ivx_world* w) {
     const uint32_t n = w->n_dyn + w->n_kin;
     if (n == 0) return IVX_OK;
-    IVX_KLAUNCH(k_prepare_bodies, dim3((n + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, w->n_kin, w->dyn, w->kin, w->cb, w->touched);
+    IVX_KLAUNCH(k_prepare_bodies, dim3((n + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, w->n_kin, w->dyn.p, w->kin.p, w->cb.p, w->touched.p);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
 
 int ivx_launch_phys_prepare_contacts(ivx_world* w, const int32_t* d_prev_slot) {
     if (w->n_contacts == 0) return IVX_OK;
-    IVX_KLAUNCH(k_prepare_contacts, dim3((w->n_contacts + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_contacts, w->n_dyn, w->contacts,
-                       d_prev_slot, w->cb, w->pc[w->cur ^ 1], reinterpret_cast<const float4*>(w->acc[w->cur ^ 1]), w->n_prev,
-                       w->cfg.old_impulse_weight, w->pc[w->cur], reinterpret_cast<float4*>(w->acc[w->cur]), w->touched);
+    IVX_KLAUNCH(k_prepare_contacts, dim3((w->n_contacts + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_contacts, w->n_dyn, w->contacts.p,
+                       d_prev_slot, w->cb.p, w->pc[w->cur ^ 1].p, reinterpret_cast<const float4*>(w->acc[w->cur ^ 1].p), w->n_prev,
+                       w->cfg.old_impulse_weight, w->pc[w->cur].p, reinterpret_cast<float4*>(w->acc[w->cur].p), w->touched.p);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
 
 int ivx_launch_phys_mark_joint_bodies(ivx_world* w) {
     if (w->n_joint_refs == 0) return IVX_OK;
-    IVX_KLAUNCH(k_mark_bodies, dim3((w->n_joint_refs + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_joint_refs, w->joint_refs, w->n_dyn, w->n_kin, w->touched);
+    IVX_KLAUNCH(k_mark_bodies, dim3((w->n_joint_refs + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_joint_refs, w->joint_refs, w->n_dyn, w->n_kin, w->touched.p);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
 
 int ivx_launch_phys_pre_solve(ivx_world* w, float dt) {
     if (w->n_dyn == 0) return IVX_OK;
-    IVX_KLAUNCH(k_pre_solve, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, dt, w->dyn, w->cb);
+    IVX_KLAUNCH(k_pre_solve, dim3((w->n_dyn + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, dt, w->dyn.p, w->cb.p);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -1392,10 +1392,10 @@ int ivx_launch_phys_pre_solve(ivx_world* w, float dt) {
 template <bool LDS, int PHASE>
 static int launch_solve(ivx_world* w, size_t lds, ReplayView rv = ReplayView(), const uint32_t* replay_flag = nullptr) {
     if (LDS) IVX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve<LDS, PHASE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    IVX_KLAUNCH((k_solve<LDS, PHASE>), dim3(1), dim3(SOLVE_THREADS), LDS ? lds : 0, w->ctx->stream, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur],
-                       reinterpret_cast<float4*>(w->acc[w->cur]), w->cb, w->items + w->item_offset[PHASE],
-                       reinterpret_cast<const uint2*>(w->item_bodies) + w->item_offset[PHASE], w->level_start + w->level_offset[PHASE],
-                       w->n_levels[PHASE], rv, replay_flag);
+    IVX_KLAUNCH((k_solve<LDS, PHASE>), dim3(1), dim3(SOLVE_THREADS), LDS ? lds : 0, w->ctx->stream, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur].p,
+                       reinterpret_cast<float4*>(w->acc[w->cur].p), w->cb.p, w->items.p + w->sched.item_offset[PHASE],
+                       reinterpret_cast<const uint2*>(w->item_bodies.p) + w->sched.item_offset[PHASE], w->level_start.p + w->sched.level_offset[PHASE],
+                       w->sched.n_levels[PHASE], rv, replay_flag);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -1417,7 +1417,7 @@ static uint32_t solver_groups(const ivx_world* w) {
     const uint32_t fit = (uint32_t)(resident > 0 ? resident : 0) * (uint32_t)w->ctx->n_cu / 8u;  // (/ 8: every eighth block works, see k_solve_mg)
     if (fit < 2u) return 1u;
     if (w->solver_groups_forced && w->solver_groups_forced <= 16u) return w->solver_groups_forced < fit ? w->solver_groups_forced : fit;
-    const uint32_t widest = w->max_level_items[0] > w->max_level_items[1] ? w->max_level_items[0] : w->max_level_items[1];
+    const uint32_t widest = w->sched.max_level_items[0] > w->sched.max_level_items[1] ? w->sched.max_level_items[0] : w->sched.max_level_items[1];
     if (widest <= 256u) return 1u;  // (a level that fits one workgroup at one wave per SIMD gains nothing from more)
     uint32_t g = (widest + 159u) / 160u;  // (a few more waves than the widest level has tiles: measured on the 4096-body pile, 8 workgroups 0.85 ms, 5: 0.89, 16: 0.86)
     g = g < 16u ? g : 16u;
@@ -1438,7 +1438,7 @@ static uint32_t ivx_solver_dry() {
 // the first's). Reads the body array only: both phases' records are packed before either phase runs.
 template <int PHASE>
 static int pack_items_mg(ivx_world* w, hipStream_t stream) {
-    const size_t need = (size_t)w->n_tiles[PHASE] * Packed<PHASE>::NJ * 64u * sizeof(float4);
+    const size_t need = (size_t)w->sched.n_tiles[PHASE] * Packed<PHASE>::NJ * 64u * sizeof(float4);
     if (need > w->packed_cap[PHASE]) {
         IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));
         if (w->side_stream) IVX_HIP_CHECK(ivx_stream_sync(w->side_stream));
@@ -1448,9 +1448,9 @@ static int pack_items_mg(ivx_world* w, hipStream_t stream) {
         IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->packed[PHASE]), need + need / 8));
         w->packed_cap[PHASE] = need + need / 8;
     }
-    IVX_KLAUNCH((k_pack_items<PHASE>), dim3(w->n_tiles[PHASE]), dim3(64), 0, stream, w->tile_first + w->tile_offset[PHASE], w->items + w->item_offset[PHASE],
-                       reinterpret_cast<const uint2*>(w->item_bodies) + w->item_offset[PHASE], reinterpret_cast<const uint4*>(w->item_tags) + w->item_offset[PHASE],
-                       w->pc[w->cur], w->cb, reinterpret_cast<float4*>(w->packed[PHASE]));
+    IVX_KLAUNCH((k_pack_items<PHASE>), dim3(w->sched.n_tiles[PHASE]), dim3(64), 0, stream, w->tile_first.p + w->sched.tile_offset[PHASE], w->items.p + w->sched.item_offset[PHASE],
+                       reinterpret_cast<const uint2*>(w->item_bodies.p) + w->sched.item_offset[PHASE], reinterpret_cast<const uint4*>(w->item_tags.p) + w->sched.item_offset[PHASE],
+                       w->pc[w->cur].p, w->cb.p, reinterpret_cast<float4*>(w->packed[PHASE]));
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -1468,13 +1468,13 @@ static int launch_solve_mg(ivx_world* w, uint32_t groups, hipStream_t stream, Re
         const int v = e ? atoi(e) : 8;
         return (uint32_t)(v < 1 ? 1 : (v > 8 ? 8 : v));
     }();
-    IVX_KLAUNCH((k_solve_mg<PHASE>), dim3(groups * spread), dim3(MG_THREADS), 0, stream, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur],
-                       reinterpret_cast<float4*>(w->acc[w->cur]), w->n_contacts, w->cb, reinterpret_cast<float4*>(w->dynst + (PHASE ? w->body_cap * 16 : 0)),
-                       w->items + w->item_offset[PHASE],
-                       reinterpret_cast<const uint2*>(w->item_bodies) + w->item_offset[PHASE], w->level_start + w->level_offset[PHASE],
-                       w->tile_base + w->level_offset[PHASE], reinterpret_cast<const float4*>(w->packed[PHASE]),
-                       w->n_levels[PHASE], w->barrier_words + PHASE, base, w->mg_err_dev, ivx_solver_dry(), spread, rv, replay_flag, w->barrier_words + 4 + 20 * PHASE,
-                       w->tile_first + w->tile_offset[PHASE], w->n_tiles[PHASE]);
+    IVX_KLAUNCH((k_solve_mg<PHASE>), dim3(groups * spread), dim3(MG_THREADS), 0, stream, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur].p,
+                       reinterpret_cast<float4*>(w->acc[w->cur].p), w->n_contacts, w->cb.p, reinterpret_cast<float4*>(w->dynst.p + (PHASE ? w->body_cap * 16 : 0)),
+                       w->items.p + w->sched.item_offset[PHASE],
+                       reinterpret_cast<const uint2*>(w->item_bodies.p) + w->sched.item_offset[PHASE], w->level_start.p + w->sched.level_offset[PHASE],
+                       w->tile_base.p + w->sched.level_offset[PHASE], reinterpret_cast<const float4*>(w->packed[PHASE]),
+                       w->sched.n_levels[PHASE], w->barrier_words + PHASE, base, w->mg_err_dev, ivx_solver_dry(), spread, rv, replay_flag, w->barrier_words + 4 + 20 * PHASE,
+                       w->tile_first.p + w->sched.tile_offset[PHASE], w->sched.n_tiles[PHASE]);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -1484,8 +1484,8 @@ static int launch_solve_mg(ivx_world* w, uint32_t groups, hipStream_t stream, Re
 static bool solver_stationary(const ivx_world* w) {
     if (w->mg_disabled || w->solver_groups_forced == 1u || (w->solver_groups_forced >= 2u && w->solver_groups_forced <= 16u)) return false;
     for (int p = 0; p < 2; ++p)
-        if (w->n_levels[p] && !w->cs_feasible[p]) return false;
-    if (!w->n_levels[0] && !w->n_levels[1]) return false;
+        if (w->sched.n_levels[p] && !w->sched.cs_feasible[p]) return false;
+    if (!w->sched.n_levels[0] && !w->sched.n_levels[1]) return false;
     static const int per_cu = [] {
         int n = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_solve_cs, (int)CS_THREADS, 0) != hipSuccess) n = 0;
@@ -1493,22 +1493,22 @@ static bool solver_stationary(const ivx_world* w) {
     }();
     if (per_cu < 1) return false;
     for (int p = 0; p < 2; ++p)
-        if (w->n_levels[p] && (((uint32_t)w->chain_start.size() - 1u + 31u) / 32u + PHYS_CS_WAVES - 1u) / PHYS_CS_WAVES > (uint32_t)w->ctx->n_cu / 8u) return false;
+        if (w->sched.n_levels[p] && (((uint32_t)w->sched.chain_start.size() - 1u + 31u) / 32u + PHYS_CS_WAVES - 1u) / PHYS_CS_WAVES > (uint32_t)w->ctx->n_cu / 8u) return false;
     if (w->solver_groups_forced == PHYS_SOLVER_STATIONARY) return true;
     // One workgroup with the bodies in LDS (k_solve) walks a level in ~4-5 us whatever its width — a barrier and the contacts' trip from memory —,
     // the chain-stationary solve in ~2.3 (velocity) / ~3.5 (positional) plus ~25 us of launches and census around it: it wins wherever the chain of
     // levels is long, wide or not (81 bodies of 48 contacts each on a ground plane: 297 + 99 levels of at most 79 chains, 0.55 -> 0.21 ms;
     // tools/time_world_frames.py). A handful of levels stays with the one workgroup.
-    const uint32_t widest = w->max_level_items[0] > w->max_level_items[1] ? w->max_level_items[0] : w->max_level_items[1];
-    return widest > 256u || w->n_levels[0] + w->n_levels[1] >= 48u;
+    const uint32_t widest = w->sched.max_level_items[0] > w->sched.max_level_items[1] ? w->sched.max_level_items[0] : w->sched.max_level_items[1];
+    return widest > 256u || w->sched.n_levels[0] + w->sched.n_levels[1] >= 48u;
 }
 
 static int launch_solve_cs(ivx_world* w) {
     hipStream_t s = w->ctx->stream;
-    const bool replay = w->n_levels[1] && w->n_kin_items > 0;
+    const bool replay = w->sched.n_levels[1] && w->sched.n_kin_items > 0;
     uint32_t* flag = w->barrier_words + 2;
-    float4* dyn_vel = reinterpret_cast<float4*>(w->dynst);
-    float4* dyn_pos = reinterpret_cast<float4*>(w->dynst + w->body_cap * 16);
+    float4* dyn_vel = reinterpret_cast<float4*>(w->dynst.p);
+    float4* dyn_pos = reinterpret_cast<float4*>(w->dynst.p + w->body_cap * 16);
     static const uint32_t spread = [] {  // (developer switch; 8 = a phase's workgroups share one XCD under round-robin placement, 1 = consecutive blocks)
         const char* e = getenv("IVX_SOLVER_SPREAD");
         const int v = e ? atoi(e) : 8;
@@ -1519,8 +1519,8 @@ static int launch_solve_cs(ivx_world* w) {
     static const char* trace_path = getenv("IVX_SOLVER_TRACE");
     static unsigned long long* trace_dev = nullptr;
     static size_t trace_cap = 0;
-    const size_t n_rounds[2] = {w->n_levels[0] ? w->cs_round_start_host[w->cs[0].round_start_offset + w->cs[0].n_tiles] : 0u,
-                                w->n_levels[1] ? w->cs_round_start_host[w->cs[1].round_start_offset + w->cs[1].n_tiles] : 0u};
+    const size_t n_rounds[2] = {w->sched.n_levels[0] ? w->sched.cs_round_start_host[w->sched.cs[0].round_start_offset + w->sched.cs[0].n_tiles] : 0u,
+                                w->sched.n_levels[1] ? w->sched.cs_round_start_host[w->sched.cs[1].round_start_offset + w->sched.cs[1].n_tiles] : 0u};
     if (trace_path && 4 * (n_rounds[0] + n_rounds[1]) > trace_cap) {
         if (trace_dev) (void)hipFree(trace_dev);
         trace_cap = 4 * (n_rounds[0] + n_rounds[1]);
@@ -1533,19 +1533,19 @@ static int launch_solve_cs(ivx_world* w) {
     }();
     auto phase_args = [&](int p, bool on, const ReplayView& rv, const uint32_t* replay_flag) {
         CsPhase a = {};
-        if (!on || !w->n_levels[p]) return a;
-        const ivx_world::CsSchedule& cs = w->cs[p];
-        a.item = w->cs_item + cs.slot_offset;
-        a.bodies = reinterpret_cast<const uint2*>(w->cs_bodies) + cs.slot_offset;
-        a.vers = w->cs_vers + cs.slot_offset;
-        a.round_start = w->cs_round_start + cs.round_start_offset;
-        a.round_mask = w->cs_round_mask + cs.round_offset;
-        a.round_level = w->cs_round_level + cs.round_offset;
+        if (!on || !w->sched.n_levels[p]) return a;
+        const ivx_contact_schedule::CsSchedule& cs = w->sched.cs[p];
+        a.item = w->cs_item.p + cs.slot_offset;
+        a.bodies = reinterpret_cast<const uint2*>(w->cs_bodies.p) + cs.slot_offset;
+        a.vers = w->cs_vers.p + cs.slot_offset;
+        a.round_start = w->cs_round_start.p + cs.round_start_offset;
+        a.round_mask = w->cs_round_mask.p + cs.round_offset;
+        a.round_level = w->cs_round_level.p + cs.round_offset;
         a.nap = nap;
         a.dynst = p ? dyn_pos : dyn_vel;
         a.counter = w->barrier_words + p;
         a.xcc_table = w->barrier_words + 64 + 32 * p;
-        a.slot_of = w->cs_slot_of;
+        a.slot_of = w->cs_slot_of.p;
         a.replay_flag = replay_flag;
         a.trace = trace_path && !replay_flag ? trace_dev + (p ? 4 * n_rounds[0] : 0) : nullptr;
         a.rv = rv;
@@ -1561,20 +1561,20 @@ static int launch_solve_cs(ivx_world* w) {
     auto launch = [&](const CsPhase& v, const CsPhase& p) -> int {
         const uint32_t blocks = spread > 1u ? spread * (v.n_groups > p.n_groups ? v.n_groups : p.n_groups) : v.n_groups + p.n_groups;
         if (!blocks) return IVX_OK;
-        IVX_KLAUNCH(k_solve_cs, dim3(blocks), dim3(CS_THREADS), 0, s, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur],
-                    reinterpret_cast<float4*>(w->acc[w->cur]), w->n_contacts, w->cb, v, p, w->mg_err_dev, ivx_solver_dry(), spread);
+        IVX_KLAUNCH(k_solve_cs, dim3(blocks), dim3(CS_THREADS), 0, s, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur].p,
+                    reinterpret_cast<float4*>(w->acc[w->cur].p), w->n_contacts, w->cb.p, v, p, w->mg_err_dev, ivx_solver_dry(), spread);
         IVX_HIP_CHECK(hipGetLastError());
         return IVX_OK;
     };
     const uint32_t body_blocks = (w->n_dyn + 255u) / 256u;
     ReplayView pass1, pass2;
     if (replay) {
-        pass1.applied = w->kin_applied;
-        pass2.qstart = reinterpret_cast<const float4*>(w->kin_qstart);
+        pass1.applied = w->kin_applied.p;
+        pass2.qstart = reinterpret_cast<const float4*>(w->kin_qstart.p);
         IVX_HIP_CHECK(ivx_memset_async(flag, 0, sizeof(uint32_t), s));
     }
     if (body_blocks) {
-        IVX_KLAUNCH(k_cs_init, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb, w->n_levels[0] ? dyn_vel : nullptr, w->n_levels[1] ? dyn_pos : nullptr, nullptr);
+        IVX_KLAUNCH(k_cs_init, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb.p, w->sched.n_levels[0] ? dyn_vel : nullptr, w->sched.n_levels[1] ? dyn_pos : nullptr, nullptr);
         IVX_HIP_CHECK(hipGetLastError());
     }
     const CsPhase v = phase_args(0, true, ReplayView(), nullptr), p1 = phase_args(1, true, pass1, nullptr);
@@ -1582,9 +1582,9 @@ static int launch_solve_cs(ivx_world* w) {
     int rc;
     if ((rc = launch(v, p1))) return rc;
     if (replay) {  // the positional phase again where a kinematic orientation moved (ReplayView): its bodies' records from the untouched body array
-        IVX_KLAUNCH(k_kin_prefix, dim3(w->n_kin), dim3(64), 0, s, w->n_kin, w->n_dyn, w->kin_offsets, w->kin_list, w->kin_applied,
-                    reinterpret_cast<float4*>(w->kin_qstart), w->cb, flag);
-        if (body_blocks) IVX_KLAUNCH(k_cs_init, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb, nullptr, dyn_pos, flag);
+        IVX_KLAUNCH(k_kin_prefix, dim3(w->n_kin), dim3(64), 0, s, w->n_kin, w->n_dyn, w->kin_offsets.p, w->kin_list.p, w->kin_applied.p,
+                    reinterpret_cast<float4*>(w->kin_qstart.p), w->cb.p, flag);
+        if (body_blocks) IVX_KLAUNCH(k_cs_init, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb.p, nullptr, dyn_pos, flag);
         IVX_HIP_CHECK(hipGetLastError());
         const CsPhase none = phase_args(0, false, ReplayView(), nullptr), p2 = phase_args(1, true, pass2, flag);
         if ((rc = launch(none, p2))) return rc;
@@ -1597,12 +1597,12 @@ static int launch_solve_cs(ivx_world* w) {
         if (FILE* f = fopen(trace_path, "wb")) {
             fwrite(host.data(), 8, 2 + 4 * (n_rounds[0] + n_rounds[1]), f);
             for (int p = 0; p < 2; ++p)
-                if (n_rounds[p]) fwrite(w->cs_round_level_host.data() + w->cs[p].round_offset, 4, n_rounds[p], f);
+                if (n_rounds[p]) fwrite(w->sched.cs_round_level_host.data() + w->sched.cs[p].round_offset, 4, n_rounds[p], f);
             fclose(f);
         }
     }
     if (body_blocks) {
-        IVX_KLAUNCH(k_cs_finish, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb, w->n_levels[0] ? dyn_vel : nullptr, w->n_levels[1] ? dyn_pos : nullptr);
+        IVX_KLAUNCH(k_cs_finish, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb.p, w->sched.n_levels[0] ? dyn_vel : nullptr, w->sched.n_levels[1] ? dyn_pos : nullptr);
         IVX_HIP_CHECK(hipGetLastError());
     }
     return IVX_OK;
@@ -1621,24 +1621,24 @@ int ivx_launch_phys_solve(ivx_world* w) {
     w->solver_groups_used = groups;
     w->solver_kind_used = groups > 1u ? 1u : 0u;
     // the positional phase runs twice when kinematic bodies take part in it (ReplayView): counts, then — where an orientation moves — again
-    const bool replay = w->n_levels[1] && w->n_kin_items > 0;
+    const bool replay = w->sched.n_levels[1] && w->sched.n_kin_items > 0;
     uint32_t* flag = w->barrier_words + 2;
     ReplayView pass1, pass2;
     if (replay) {
-        pass1.applied = w->kin_applied;
-        pass2.qstart = reinterpret_cast<const float4*>(w->kin_qstart);
+        pass1.applied = w->kin_applied.p;
+        pass2.qstart = reinterpret_cast<const float4*>(w->kin_qstart.p);
     }
     auto before_positional = [&](hipStream_t st) -> int {
         if (!replay) return IVX_OK;
         IVX_HIP_CHECK(ivx_memset_async(flag, 0, sizeof(uint32_t), st));
-        IVX_KLAUNCH(k_kin_snapshot, dim3((w->n_dyn + 255u) / 256u + 1u), dim3(256), 0, st, w->n_dyn, w->cb, reinterpret_cast<float4*>(w->kin_snap));
+        IVX_KLAUNCH(k_kin_snapshot, dim3((w->n_dyn + 255u) / 256u + 1u), dim3(256), 0, st, w->n_dyn, w->cb.p, reinterpret_cast<float4*>(w->kin_snap.p));
         IVX_HIP_CHECK(hipGetLastError());
         return IVX_OK;
     };
     auto between_passes = [&](hipStream_t st) -> int {
-        IVX_KLAUNCH(k_kin_prefix, dim3(w->n_kin), dim3(64), 0, st, w->n_kin, w->n_dyn, w->kin_offsets, w->kin_list, w->kin_applied,
-                           reinterpret_cast<float4*>(w->kin_qstart), w->cb, flag);
-        IVX_KLAUNCH(k_kin_restore, dim3((w->n_dyn + 255u) / 256u + 1u), dim3(256), 0, st, w->n_dyn, w->cb, reinterpret_cast<const float4*>(w->kin_snap), flag);
+        IVX_KLAUNCH(k_kin_prefix, dim3(w->n_kin), dim3(64), 0, st, w->n_kin, w->n_dyn, w->kin_offsets.p, w->kin_list.p, w->kin_applied.p,
+                           reinterpret_cast<float4*>(w->kin_qstart.p), w->cb.p, flag);
+        IVX_KLAUNCH(k_kin_restore, dim3((w->n_dyn + 255u) / 256u + 1u), dim3(256), 0, st, w->n_dyn, w->cb.p, reinterpret_cast<const float4*>(w->kin_snap.p), flag);
         IVX_HIP_CHECK(hipGetLastError());
         return IVX_OK;
     };
@@ -1654,7 +1654,7 @@ int ivx_launch_phys_solve(ivx_world* w) {
             const char* e = getenv("IVX_SOLVER_SERIAL");  // (developer switch: the phases one after the other on the context's stream)
             return e && atoi(e) != 0;
         }();
-        const bool both = w->n_levels[0] && w->n_levels[1] && !serial;
+        const bool both = w->sched.n_levels[0] && w->sched.n_levels[1] && !serial;
         if (both) {
             if (!w->side_stream) {
                 IVX_HIP_CHECK(hipStreamCreateWithFlags(&w->side_stream, hipStreamNonBlocking));
@@ -1663,13 +1663,13 @@ int ivx_launch_phys_solve(ivx_world* w) {
             }
             s1 = w->side_stream;
         }
-        if (w->n_levels[0] && (rc = pack_items_mg<0>(w, s0))) return rc;
-        if (w->n_levels[1] && (rc = pack_items_mg<1>(w, s0))) return rc;
+        if (w->sched.n_levels[0] && (rc = pack_items_mg<0>(w, s0))) return rc;
+        if (w->sched.n_levels[1] && (rc = pack_items_mg<1>(w, s0))) return rc;
         if (both) {
             IVX_HIP_CHECK(ivx_event_record(w->ev_fork, s0));
             IVX_HIP_CHECK(hipStreamWaitEvent(s1, w->ev_fork, 0));
         }
-        if (w->n_levels[1] && both) {  // (the side stream first: its launches are in flight while the host enqueues the velocity phase)
+        if (w->sched.n_levels[1] && both) {  // (the side stream first: its launches are in flight while the host enqueues the velocity phase)
             if ((rc = before_positional(s1))) return rc;
             if ((rc = launch_solve_mg<1>(w, groups, s1, pass1))) return rc;
             if (replay) {
@@ -1678,8 +1678,8 @@ int ivx_launch_phys_solve(ivx_world* w) {
             }
             IVX_HIP_CHECK(ivx_event_record(w->ev_join, s1));
         }
-        if (w->n_levels[0] && (rc = launch_solve_mg<0>(w, groups, s0))) return rc;
-        if (w->n_levels[1] && !both) {
+        if (w->sched.n_levels[0] && (rc = launch_solve_mg<0>(w, groups, s0))) return rc;
+        if (w->sched.n_levels[1] && !both) {
             if ((rc = before_positional(s0))) return rc;
             if ((rc = launch_solve_mg<1>(w, groups, s0, pass1))) return rc;
             if (replay) {
@@ -1692,12 +1692,12 @@ int ivx_launch_phys_solve(ivx_world* w) {
     }
     // the phase's mutable body state (24 / 28 bytes per dynamic body) goes to LDS when it fits one CU
     const size_t lds0 = (size_t)w->n_dyn * 24, lds1 = (size_t)w->n_dyn * 28;
-    if (w->n_levels[0]) {
+    if (w->sched.n_levels[0]) {
         if (lds0 <= 140 * 1024) rc = launch_solve<true, 0>(w, lds0);
         else rc = launch_solve<false, 0>(w, 0);
         if (rc) return rc;
     }
-    if (w->n_levels[1]) {
+    if (w->sched.n_levels[1]) {
         if ((rc = before_positional(w->ctx->stream))) return rc;
         if (lds1 <= 140 * 1024) rc = launch_solve<true, 1>(w, lds1, pass1);
         else rc = launch_solve<false, 1>(w, 0, pass1);
@@ -1715,7 +1715,7 @@ int ivx_launch_phys_solve(ivx_world* w) {
 int ivx_launch_phys_free_step(ivx_world* w, float dt) {
     const uint32_t n = w->n_dyn + w->n_kin;
     if (n == 0) return IVX_OK;
-    IVX_KLAUNCH(k_free_step, dim3((n + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, w->n_kin, dt, w->dyn, w->kin, w->cb, w->touched);
+    IVX_KLAUNCH(k_free_step, dim3((n + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, w->n_kin, dt, w->dyn.p, w->kin.p, w->cb.p, w->touched.p);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -1723,8 +1723,8 @@ int ivx_launch_phys_free_step(ivx_world* w, float dt) {
 int ivx_launch_phys_post_solve(ivx_world* w, float dt, int write_back, int advance) {
     const uint32_t n = w->n_dyn + w->n_kin;
     if (n == 0) return IVX_OK;
-    IVX_KLAUNCH(k_post_solve, dim3((n + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, w->n_kin, dt, write_back, advance, w->cb, w->touched,
-                       w->dyn, w->kin);
+    IVX_KLAUNCH(k_post_solve, dim3((n + 255u) / 256u), dim3(256), 0, w->ctx->stream, w->n_dyn, w->n_kin, dt, write_back, advance, w->cb.p, w->touched.p,
+                       w->dyn.p, w->kin.p);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }

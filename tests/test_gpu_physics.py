@@ -220,6 +220,25 @@ def test_repeated_and_changing_contact_sets_alternate(ctx):
     w.close()
 
 
+def test_contact_arrays_grow_with_a_previous_state_to_keep(ctx):
+    """a world whose first contact set is not its largest: the 4^3 pile (64 bodies, 144 manifolds of 4 contacts) with every second manifold
+    (288 contacts, and room for 288), then all of them — the device arrays grow while the 288 prepared contacts and accumulated impulses of
+    the frame before are the warm-start sources —, all again, every second again: every frame against the oracle"""
+    rng = np.random.default_rng(5)
+    bodies, contacts = scenes.sphere_pile_scene(4)
+    bodies["momentum"] += rng.normal(0, 0.05, bodies["momentum"].shape).astype(np.float32)
+    bodies["angular_momentum"] += rng.normal(0, 0.01, bodies["angular_momentum"].shape).astype(np.float32)
+    w, o = pu.make_pair(ctx, bodies)
+    manifolds = contacts.reshape(-1, 4)
+    assert len(bodies) == 64 and len(manifolds) == 144
+    full, half = np.arange(len(manifolds)), np.arange(0, len(manifolds), 2)
+    for s, keep in enumerate([half, full, full, half]):
+        pu.step_both(w, o, manifolds[keep].reshape(-1), 0.004)
+        pu.assert_bodies_close(w.bodies()[0], o.bodies()[0], what=f"frame {s}: ")
+        pu.compare_contact_state(w, o)
+    w.close()
+
+
 def test_interlocked_manifold(ctx):
     """contact.rs:610-780 through the GPU path: opposing penetration vectors are replaced by one
     separating contact (needs the bodies' current positions from the device)"""

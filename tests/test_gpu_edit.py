@@ -6,6 +6,7 @@ mesh chunks equal."""
 import numpy as np
 import pytest
 
+import moments_ref as mr
 import oracle_lib as ol
 import parity_util as pu
 from impact_amd import scenes
@@ -25,7 +26,14 @@ def both(ctx, graph, extent=1.0):
     return o, g
 
 
+def assert_removed_exact(before, o, g, rg, dens, what=""):
+    """the removed moments against the exact restatement (tests/moments_ref.py) over the oracle's voxels that the edit emptied (`before`: the
+    oracle's type and flag planes ahead of the edit; its state after is asserted equal to the device's)"""
+    mr.assert_moments(rg["removed_moments"], *mr.emptied_exact(before[1], before[0], o, dens, g.voxel_extent), what + "removed moments")
+
+
 def absorb_both(o, g, center, radius, dens=None):
+    before = o.export_dense()[1:3]
     ro = o.absorb_sphere(center, radius + 2.0, radius, dens)
     rg = g.absorb_sphere(center, radius + 2.0, radius, dens)
     assert rg["touched_chunks"] == ro["touched_chunks"] and rg["removed_chunks"] == ro["removed_chunks"]
@@ -33,6 +41,7 @@ def absorb_both(o, g, center, radius, dens=None):
     np.testing.assert_array_equal(rg["invalidated"], ro["invalidated"])
     scale = np.maximum(np.abs(ro["removed64"]), 1e-300)
     assert np.all(np.abs(rg["removed_moments"] - ro["removed64"]) <= 1e-5 * scale + 1e-9), (rg["removed_moments"], ro["removed64"])
+    assert_removed_exact(before, o, g, rg, dens)
     ro["regions"] = pu.assert_edited_objects_equal(o, g, densities=dens)
     return ro
 
@@ -124,6 +133,7 @@ def test_multi_material_object_reports_absorbed_types(ctx):
 
 # ---- absorbing capsule ------------------------------------------------------------------------------------------------------------
 def absorb_capsule_both(o, g, start, vec, radius, dens=None):
+    before = o.export_dense()[1:3]
     ro = o.absorb_capsule(start, vec, radius + 2.0, radius, dens)
     rg = g.absorb_capsule(start, vec, radius + 2.0, radius, dens)
     assert rg["touched_chunks"] == ro["touched_chunks"] and rg["removed_chunks"] == ro["removed_chunks"]
@@ -131,6 +141,7 @@ def absorb_capsule_both(o, g, start, vec, radius, dens=None):
     np.testing.assert_array_equal(rg["invalidated"], ro["invalidated"])
     scale = np.maximum(np.abs(ro["removed64"]), 1e-300)
     assert np.all(np.abs(rg["removed_moments"] - ro["removed64"]) <= 1e-5 * scale + 1e-9), (rg["removed_moments"], ro["removed64"])
+    assert_removed_exact(before, o, g, rg, dens)
     ro["regions"] = pu.assert_edited_objects_equal(o, g, densities=dens)
     return ro
 
@@ -218,14 +229,16 @@ def rot64(q, v):
 
 
 def absorb_mutual_both(A, GA, qa, ta, B, GB, qb, tb, smooth, dens_a=None, dens_b=None):
+    before_a, before_b = A.export_dense()[1:3], B.export_dense()[1:3]
     roa, rob = A.absorb_mutual(qa, ta, B, qb, tb, smooth, dens_a, dens_b)
     rga, rgb = GA.absorb_mutual(qa, ta, GB, qb, tb, smooth, dens_a, dens_b)
-    for ro, rg, o, g, dens in ((roa, rga, A, GA, dens_a), (rob, rgb, B, GB, dens_b)):
+    for ro, rg, o, g, dens, before in ((roa, rga, A, GA, dens_a, before_a), (rob, rgb, B, GB, dens_b, before_b)):
         assert rg["emptied_voxels"] == ro["emptied_voxels"]
         assert rg["touched_chunks"] == ro["touched_chunks"] and rg["removed_chunks"] == ro["removed_chunks"]
         np.testing.assert_array_equal(rg["invalidated"], ro["invalidated"])
         scale = np.maximum(np.abs(ro["removed64"]), 1e-300)
         assert np.all(np.abs(rg["removed_moments"] - ro["removed64"]) <= 1e-5 * scale + 1e-9), (rg["removed_moments"], ro["removed64"])
+        assert_removed_exact(before, o, g, rg, dens)
         ro["regions"] = pu.assert_edited_objects_equal(o, g, densities=dens)
     return roa, rob
 

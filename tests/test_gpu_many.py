@@ -5,6 +5,7 @@ the single-object calls."""
 import numpy as np
 import pytest
 
+import moments_ref as mr
 import oracle_lib as ol
 import parity_util as pu
 from impact_amd import capi, many, scenes
@@ -54,6 +55,7 @@ def test_fragments_stepped_edited_and_synced_together(ctx):
         _, o64 = o.inertia(dens)
         g64 = np.asarray(res[k]["moments"]["m64"], dtype=np.float64)
         assert np.all(np.abs(g64 - o64) <= 1e-5 * np.maximum(np.abs(o64), 1e-300) + 1e-12), k
+        mr.assert_moments(g64, *mr.exact_of_oracle(o, dens, g.voxel_extent), f"fragment {k} after the step of all")
         n_regions, _ = o.region_labels()
         assert int(res[k]["region_count"]) == n_regions
         gm = VoxelObjectMesh(g)
@@ -76,6 +78,7 @@ def test_fragments_stepped_edited_and_synced_together(ctx):
             c[frame % 3] = occ[frame % 3, 1] - 1.0  # at the object's upper face along the frame's axis
             centers.append(c)
             radii.append(3.0 + frame)
+        before = [o.export_dense()[1:3] for o in os_]  # (type and flag planes ahead of the edit: what the removed moments are summed over)
         ros = [o.absorb_sphere(c, r + 2.0, r, dens) for o, c, r in zip(os_, centers, radii)]
         rgs = many.absorb_sphere_many(gs, centers, [r + 2.0 for r in radii], radii, dens)
         for k, (ro, rg) in enumerate(zip(ros, rgs)):
@@ -83,6 +86,7 @@ def test_fragments_stepped_edited_and_synced_together(ctx):
             assert (rg["touched_chunks"], rg["removed_chunks"], rg["emptied_voxels"]) == (ro["touched_chunks"], ro["removed_chunks"], int(ro["emptied_by_type"].sum()))
             scale = np.maximum(np.abs(ro["removed64"]), 1e-300)
             assert np.all(np.abs(rg["removed_moments"] - ro["removed64"]) <= 1e-5 * scale + 1e-9), (k, frame, rg["emptied_voxels"], rg["removed_moments"][0], ro["removed64"][0])
+            mr.assert_moments(rg["removed_moments"], *mr.emptied_exact(before[k][1], before[k][0], os_[k], dens, gs[k].voxel_extent), f"fragment {k}, frame {frame}")
             pu.assert_edited_objects_equal(os_[k], gs[k], f"fragment {k}, frame {frame}: ", with_mesh=False)
         for om, ro in zip(oms, ros):
             om.sync(ro["invalidated"])
@@ -94,6 +98,7 @@ def test_fragments_stepped_edited_and_synced_together(ctx):
             _, o64 = o.inertia(dens)
             g64 = np.asarray(mom[k]["moments"]["m64"], dtype=np.float64)
             assert np.all(np.abs(g64 - o64) <= 1e-5 * np.maximum(np.abs(o64), 1e-300) + 1e-12), (k, frame)
+            mr.assert_moments(g64, *mr.exact_of_oracle(o, dens, gs[k].voxel_extent), f"fragment {k}, frame {frame}")
     for g in gs:
         g.close()
 
@@ -335,6 +340,7 @@ def test_calls_without_a_guard_on_another_context_are_not_recorded(ctx):
         got = VoxelObjectInertialPropertyManager.initialized_from(gb, dens).m64  # B: moment sweep
         capi.check(lib.ivx_many_flush(ctx.h))
         assert np.all(np.abs(got - want) <= 1e-5 * np.maximum(np.abs(want), 1e-300) + 1e-12)
+        mr.assert_moments(got, *mr.exact_of_oracle(ob, dens, gb.voxel_extent), "context B")
         xa = ga.absorb_collect()
         np.testing.assert_array_equal(xa["invalidated"], ra["invalidated"])
         pu.assert_edited_objects_equal(oa, ga, "context A: ", with_mesh=False)

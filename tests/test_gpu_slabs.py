@@ -6,6 +6,7 @@ moments (1e-5 rel), occupied ranges and the connected-region partition."""
 import numpy as np
 import pytest
 
+import moments_ref as mr
 import oracle_lib as ol
 import typed_util as tu
 from impact_amd import capi, scenes
@@ -98,8 +99,11 @@ def run_and_compare(ctx, graph, world, expect_regions=None, extent=1.0, driver="
         assert results[0].total_triangles == om.indices.size // 3
         # moments, occupied ranges
         _, o64 = o.inertia(dens)
-        for r in results:
+        exact = mr.exact_of_oracle(o, dens, extent)
+        for r_index, r in enumerate(results):
             np.testing.assert_allclose(r.moments, o64, rtol=1e-5)
+            # (the host sum of `world` slabs' separately scaled moments against the exact restatement over the oracle's voxels)
+            mr.assert_moments(r.moments, *exact, f"rank {r_index}", parts=world)
             np.testing.assert_array_equal(r.moments, results[0].moments)  # identical on every rank
         info = o.info()
         occ = results[0].occupied
@@ -255,6 +259,10 @@ def test_config5_1024_in_8_slabs(ctx):
         assert int(ref["region_count"]) == gold["regions"]
         g64 = np.asarray(ref["moments"]["m64"], dtype=np.float64)
         assert float(np.max(np.abs(g64 - m64) / np.maximum(np.abs(m64), 1e-300))) <= 1e-5
+        # the exact restatement over the voxels just compared with the oracle's by digest (1024^3: the margin form of the integer sums)
+        exact = mr.moments_of_sums(mr.integer_sums_by_margins(w_flg, w_typ, gen.chunk_counts()), dens, 1.0)
+        assert exact[1] == gold["non_empty_voxels"]
+        mr.assert_moments(g64, *exact, "the single grid")
         occ = np.asarray(ref["occupied"]).reshape(-1)
         want_occ = np.array([x for r in gold["occupied_chunk_ranges"] for x in r] + [x for r in gold["occupied_voxel_ranges"] for x in r])  # (lo, hi) per axis
         np.testing.assert_array_equal(occ, want_occ)
@@ -268,6 +276,7 @@ def test_config5_1024_in_8_slabs(ctx):
             assert sum(r.mesh_counts[0] for r in results) == gold["vertices"]
             rm = np.asarray(results[0].moments, dtype=np.float64)
             assert float(np.max(np.abs(rm - m64) / np.maximum(np.abs(m64), 1e-300))) <= 1e-5
+            mr.assert_moments(rm, *exact, "the host sum of eight slabs", parts=8)
             np.testing.assert_allclose(results[0].moments, g64, rtol=1e-12)
             np.testing.assert_array_equal(np.asarray(results[0].occupied).reshape(-1), want_occ)
             per = gen.chunk_counts()[1] * gen.chunk_counts()[2] * 4096

@@ -6,6 +6,7 @@ children agree after every extraction."""
 import numpy as np
 import pytest
 
+import moments_ref as mr
 import oracle_lib as ol
 import parity_util as pu
 from impact_amd import scenes
@@ -37,6 +38,7 @@ def split_all(ctx, o, g, expect):
     children = 0
     outcomes = []
     for it in range(64):
+        before = o.export_dense()[1:3]  # (type and flag planes ahead of the split: the moved moments are sums over what leaves)
         rc_o, co, org_o = o.split_off_smallest_region()
         rc_g, cg, org_g, moved = g.extract_any_disconnected_region()
         assert rc_g == rc_o, f"iteration {it}"
@@ -51,6 +53,8 @@ def split_all(ctx, o, g, expect):
             _, c64 = co.inertia()
             # child moments are about the child's origin; shift check via mass only + voxel count
             assert abs(moved["moments"][0] - c64[0]) <= 1e-9 * max(c64[0], 1.0)
+            # all ten, in the parent's frame: the exact restatement over the oracle's voxels that were non-empty before and are empty after
+            mr.assert_moments(moved["moments"], *mr.emptied_exact(before[1], before[0], o, None, g.voxel_extent), f"moved by split {it}")
             assert int(moved["voxel_count"]) == int(np.count_nonzero((co.export_dense()[2] & 1) == 0))
             cg.close()
             children += 1

@@ -223,6 +223,15 @@ UNIFORM_MEDIUM_DTYPE = np.dtype([("mass_density", "<f4"), ("velocity", "<f4", (3
 DRAG_GENERATOR_DTYPE = np.dtype([("body", "<u4"), ("map", "<u4"), ("drag_coefficient", "<f4"), ("scaling", "<f4")])
 DRAG_MAP_VIEW_DTYPE = np.dtype([("loads", "<u8"), ("n_theta", "<u4"), ("reserved", "<u4")])
 assert UNIFORM_MEDIUM_DTYPE.itemsize == 16 and DRAG_GENERATOR_DTYPE.itemsize == 16 and DRAG_MAP_VIEW_DTYPE.itemsize == 16
+# SDF queries (csrc/sdf_query.hip): `ivx_sdf_query_instance` (the subject's node-to-parent similarity, the sphere of the cast in subject space) and
+# `ivx_sdf_query_result` (status, steps, translation or rotation quaternion, which Some exit of the cast)
+SDF_QUERY_INSTANCE_DTYPE = np.dtype([("subject_to_parent", SIMILARITY_DTYPE), ("sphere_center", "<f4", (3,)), ("sphere_radius", "<f4")])
+SDF_QUERY_RESULT_DTYPE = np.dtype([("status", "<u4"), ("steps", "<u4"), ("v", "<f4", (4,)), ("exit", "<u4"), ("reserved", "<u4")])
+assert SDF_QUERY_INSTANCE_DTYPE.itemsize == 48 and SDF_QUERY_RESULT_DTYPE.itemsize == 32
+SDF_QUERY_MAX_STACK, SDF_QUERY_MAX_ITEMS = 64, 1 << 24
+(SQ_OK, SQ_ZERO_GRADIENT, SQ_NO_GRADIENT_DIRECTION, SQ_RAY_MISSES_DOMAIN, SQ_DEGENERATE_DIRECTION, SQ_PENETRATING, SQ_LEFT_INTERVAL, SQ_MAX_STEPS,
+ SQ_DEGENERATE_Y_AXIS) = range(9)
+SQ_EXIT_CONVERGED, SQ_EXIT_CROSSED = 0, 1
 
 # every symbol include/impact_voxel_hip.h declares
 EXPORTED_SYMBOLS = [
@@ -257,6 +266,7 @@ EXPORTED_SYMBOLS = [
     "ivx_world_set_force_generators", "ivx_world_set_dynamic_gravity", "ivx_world_apply_forces", "ivx_world_gravity_loads", "ivx_fg_apply_host",
     "ivx_world_set_medium", "ivx_world_medium", "ivx_world_set_drag_map", "ivx_world_set_drag_map_from_grid", "ivx_world_drag_map_download",
     "ivx_world_set_detailed_drag", "ivx_fg_apply_host_drag",
+    "ivx_sdf_query_create", "ivx_sdf_query_destroy", "ivx_sdf_query_points", "ivx_sdf_query_closest", "ivx_sdf_query_spherecast", "ivx_sdf_query_rotation",
 ]
 
 
@@ -291,6 +301,7 @@ def extra_struct_sizes():
         "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
         "ivx_force_generator": (FORCE_GENERATOR_DTYPE, 64),
         "ivx_uniform_medium": (UNIFORM_MEDIUM_DTYPE, 16), "ivx_drag_generator": (DRAG_GENERATOR_DTYPE, 16), "ivx_drag_map_view": (DRAG_MAP_VIEW_DTYPE, 16),
+        "ivx_sdf_query_instance": (SDF_QUERY_INSTANCE_DTYPE, 48), "ivx_sdf_query_result": (SDF_QUERY_RESULT_DTYPE, 32),
     }
 
 
@@ -503,6 +514,12 @@ def lib():
         "ivx_world_drag_map_download": (i32, [vp, u32, vp, sz, C.POINTER(u32)]),
         "ivx_world_set_detailed_drag": (i32, [vp, vp, sz]),
         "ivx_fg_apply_host_drag": (i32, [vp, sz, vp, sz, f32, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp]),
+        "ivx_sdf_query_create": (i32, [vp, vp, sz, u32, vp, C.POINTER(vp)]),
+        "ivx_sdf_query_destroy": (None, [vp]),
+        "ivx_sdf_query_points": (i32, [vp, i32, vp, sz, vp]),
+        "ivx_sdf_query_closest": (i32, [vp, vp, vp, sz, u32, f32, vp]),
+        "ivx_sdf_query_spherecast": (i32, [vp, vp, vp, sz, vp, u32, f32, f32, vp]),
+        "ivx_sdf_query_rotation": (i32, [vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

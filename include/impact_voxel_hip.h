@@ -1364,6 +1364,75 @@ int ivx_fg_apply_host_drag(const ivx_force_generator*, size_t n, const uint32_t*
                            size_t n_dynamic, const ivx_kinematic_body* kinematic, size_t n_kinematic, float* gravity_loads6, const ivx_drag_generator*, size_t n_drag,
                            const ivx_drag_map_view* maps, size_t n_maps, const ivx_uniform_medium*);
 
+/* ---- SDF queries: distance, gradient and surface casts of a compiled program (csrc/sdf_query.hip) ------------------------------------------------
+ * The value of a compiled atomic SDF program at arbitrary root-space points, and the three placements the reference's meta-SDF graph makes with it
+ * (impact_voxel/src/generation/sdf/meta.rs): MetaClosestTranslationToSurface (:1620-1688, compute_translation_to_closest_point_on_surface :2411-2479),
+ * MetaRayTranslationToSurface (:1690-1796, compute_spherecast_translation_to_surface :2534-2703) and MetaRotationToGradient (:1798-1863,
+ * compute_rotation_to_gradient :2481-2532), all over sample_signed_distance_with_gradient (:2728-2770) and SDFGenerator::compute_signed_distance
+ * (atomic.rs:877-1010): f32, uncontracted, one evaluation order per expression; NO domain test, early-out or clamp (the difference from ivx_sdf_sample).
+ *   block positions (atomic.rs:1601-1660): origin = T * block_origin, position (i, j, k) = ((origin + i dx) + j dy), then += dz once for k = 1; a 2x2x2
+ *   block's origin is p - 0.5, sample i*4 + j*2 + k; centre value = (((d0 + d1) + d2) ... + d7) * 0.125; gradient = 0.25 * the three bracketed
+ *   differences of meta.rs:2763-2770. Leaves and combinations as in ivx_sdf_sample; scaling multiplies the top of the stack; translation and rotation are
+ *   no-ops; a noise node adds noise * noise_scale at (o.z + k, o.y + j, o.x + i) in noise space, or at the per-voxel positions when its transform is
+ *   rotated or scaled (atomic.rs:1423-1507), with the library's own noise (csrc/noise.hpp).
+ *   similarities (impact_math/src/transform/similarity.rs:206-242): point -> rotate(scaling * p) + translation; vector -> rotate(scaling * v); the
+ *   inverses rotate by the conjugate and multiply by 1 / scaling (impact_math's `/ f32` is `* recip`). normalized_from_if_above(v, 1e-8): norm squared
+ *   > 1e-8 * 1e-8, then v / sqrt(norm squared). rotation_between_axes is glam's Quat::from_rotation_arc (DESIGN.md lists the glam forms whose bits
+ *   are unpinned).
+ * The program is the list, stack size and domain exactly as ivx_sdf_compile returns them (noise parameters in reserved[]); the query object keeps a
+ * copy (and, with a context, a device copy) until it is destroyed. ctx == NULL: the object runs the host build of the functions the kernels run.
+ * The kernels work eight lanes to an instance (one corner of the 2x2x2 block each) and keep one value-stack column per lane in LDS: 256 bytes per
+ * stack level and wave. IVX_SDF_QUERY_MAX_STACK is bounded by that: 64 levels are 16 KiB per one-wave workgroup, which leaves ten waves on a
+ * compute unit's 160 KiB; the host build holds the same number of levels on its call stack. */
+#define IVX_SDF_QUERY_MAX_STACK 64u
+#define IVX_SDF_QUERY_MAX_ITEMS (1u << 24) /* points or instances per call */
+typedef struct ivx_sdf_query ivx_sdf_query;
+/* The subject of a placement: its node-to-parent similarity and, for the cast only, the sphere in subject space (sphere_for_shape, meta.rs:1745-1765,
+ * derived by the caller). 48 bytes. */
+typedef struct {
+    ivx_similarity subject_to_parent;
+    float sphere_center[3];
+    float sphere_radius;
+} ivx_sdf_query_instance;
+/* status: 0 where the reference returns Some, else the way it returned None */
+#define IVX_SQ_OK 0u
+#define IVX_SQ_ZERO_GRADIENT 1u         /* closest: gradient norm squared within 1e-8 of zero (meta.rs:2455) */
+#define IVX_SQ_NO_GRADIENT_DIRECTION 2u /* cast, rotation: gradient direction below 1e-8 (meta.rs:2715, :2526) */
+#define IVX_SQ_RAY_MISSES_DOMAIN 3u     /* cast: find_ray_intersection found none (meta.rs:2623, impact_geometry/src/axis_aligned_box.rs:420-455) */
+#define IVX_SQ_DEGENERATE_DIRECTION 4u  /* cast: the direction in surface space is below 1e-8 (meta.rs:2579-2582) */
+#define IVX_SQ_PENETRATING 5u           /* cast: the sphere starts below the surface (meta.rs:2644) */
+#define IVX_SQ_LEFT_INTERVAL 6u         /* cast: the centre left the ray's domain interval (meta.rs:2682-2686) */
+#define IVX_SQ_MAX_STEPS 7u             /* cast: max_steps without a crossing (meta.rs:2662-2667) */
+#define IVX_SQ_DEGENERATE_Y_AXIS 8u     /* rotation: the subject's y-axis in parent space is below 1e-8 (meta.rs:2525) */
+/* exit (status 0 only): which of the cast's two Some exits was taken */
+#define IVX_SQ_EXIT_CONVERGED 0u /* within the tolerance (every closest and rotation result has this) */
+#define IVX_SQ_EXIT_CROSSED 1u   /* max_steps reached after crossing the surface (meta.rs:2663-2664) */
+/* 32 bytes. steps: closest: iteration_count when the loop ended; cast: step_count; rotation: 0. v: the translation in parent space (v[3] = 0), or the
+ * rotation quaternion xyzw; all zero where status != 0. */
+typedef struct {
+    uint32_t status, steps;
+    float v[4];
+    uint32_t exit, reserved;
+} ivx_sdf_query_result;
+/* Walks the postfix list on the host (leaves push, kinds 3-6 need depth >= 1, kinds 7-9 need >= 2, the walk ends at depth 1). IVX_ERR_INVALID: a
+ * list that does not reduce this way, a kind above 9, a depth above stack_size, a null argument; IVX_ERR_CAPACITY: stack_size above
+ * IVX_SDF_QUERY_MAX_STACK. n_nodes == 0 is legal (nodes may be NULL): every distance is VoxelSignedDistance::MAX_F32 (0.02f * 127.0f), every gradient
+ * zero. */
+int ivx_sdf_query_create(ivx_ctx* ctx, const ivx_sdf_processed_node* nodes, size_t n_nodes, uint32_t stack_size, const float domain[6], ivx_sdf_query** out);
+void ivx_sdf_query_destroy(ivx_sdf_query*); /* before ivx_shutdown of its context */
+/* points: n x 3 floats in root space. which 0: compute_signed_distance, one float each; which 1: sample_signed_distance_with_gradient, four floats
+ * each (centre value, gradient). Host arrays; one upload and one download through the object's pinned block; waits for the stream. */
+int ivx_sdf_query_points(ivx_sdf_query*, int which, const float* points, size_t n, float* out);
+/* surface_to_parent: the surface node's node_to_parent_transform. One result per instance, in order; two calls leave the same bytes. The reference's
+ * constants (5 and 0.1; unit_y, 128, 0.1 and 0.5) are the Python mirror's defaults. IVX_ERR_INVALID for a safety_factor outside (0, 1] (the
+ * reference asserts it). */
+int ivx_sdf_query_closest(ivx_sdf_query*, const ivx_similarity* surface_to_parent, const ivx_sdf_query_instance* instances, size_t n, uint32_t max_iterations,
+                          float max_distance, ivx_sdf_query_result* results);
+int ivx_sdf_query_spherecast(ivx_sdf_query*, const ivx_similarity* surface_to_parent, const ivx_sdf_query_instance* instances, size_t n,
+                             const float direction[3], uint32_t max_steps, float tolerance, float safety_factor, ivx_sdf_query_result* results);
+int ivx_sdf_query_rotation(ivx_sdf_query*, const ivx_similarity* surface_to_parent, const ivx_sdf_query_instance* instances, size_t n,
+                           ivx_sdf_query_result* results);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,10 @@
   for_each_intersecting_bounding_volume_pair       collision.rs:215-349    (`BoundingVolumeSet.pairs`)
   for_each_bounding_volume_in_* / _maybe_in_*      absorption.rs:474, model.rs:191, light.rs:172-543  (`BoundingVolumeSet.query`)
 
-The world boxes, the pairs and the masks stay in context-owned device buffers (`device_ptr`). Nothing here computes, and nothing falls back to
+The pair pass has a second form that leaves the same bytes: a linear hierarchy over the set (csrc/bvh.hip; hierarchy.rs in the reference), built
+on request (`BoundingVolumeSet.build_hierarchy`, `.hierarchy`, `.pairs_hierarchy`; `morton_key`, `hierarchy_host` and `node_info` on the host).
+
+The world boxes, the pairs, the masks and the tree stay in context-owned device buffers (`device_ptr`). Nothing here computes, and nothing falls back to
 the CPU.
 """
 from __future__ import annotations
@@ -16,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import AABB_DTYPE, BV_QUERY_DTYPE, SIMILARITY_DTYPE, check, ptr
+from .capi import AABB_DTYPE, BV_NODE_DTYPE, BV_QUERY_DTYPE, SIMILARITY_DTYPE, check, ptr
 from .many import _handles
 
 
@@ -143,8 +146,77 @@ class BoundingVolumeSet:
         return masks, counts
 
     def device_ptr(self, which: int) -> int:
-        """`ivx_bv_device_ptr`: capi.BV_PTR_WORLD_BOXES / _PAIRS / _MASKS"""
+        """`ivx_bv_device_ptr`: capi.BV_PTR_WORLD_BOXES / _PAIRS / _MASKS / _NODES / _LEAF_OBJECTS"""
         return int(capi.lib().ivx_bv_device_ptr(self._h, int(which)) or 0)
+
+    def build_hierarchy(self) -> None:
+        """`ivx_bv_build_hierarchy`: the linear BVH over this set, enqueued on the context's stream"""
+        check(capi.lib().ivx_bv_build_hierarchy(self._h))
+
+    def hierarchy(self):
+        """`ivx_bv_hierarchy_download` -> (nodes [max(n - 1, 0)] BV_NODE_DTYPE, leaf objects [n] uint32 in Morton order)"""
+        nodes, leaves = np.zeros(max(self.n - 1, 0), dtype=BV_NODE_DTYPE), np.zeros(self.n, dtype=np.uint32)
+        found = C.c_size_t(0)
+        check(capi.lib().ivx_bv_hierarchy_download(self._h, ptr(nodes) if nodes.size else None, nodes.size, ptr(leaves) if self.n else None, self.n, C.byref(found)))
+        assert found.value == nodes.size, (found.value, nodes.size)
+        return nodes, leaves
+
+    def pairs_hierarchy(self, mode: int = capi.BV_ALL_PAIRS, capacity: int | None = None) -> np.ndarray:
+        """`ivx_bv_pairs_hierarchy` -> what `pairs` returns, found through the tree. `capacity` None: sized by a first call that only counts"""
+        found = C.c_size_t(0)
+        if capacity is None:
+            rc = capi.lib().ivx_bv_pairs_hierarchy(self._h, int(mode), ptr(np.zeros((1, 2), dtype=np.uint32)), 0, C.byref(found))
+            if rc != capi.IVX_ERR_CAPACITY:
+                check(rc)
+                return np.zeros((0, 2), dtype=np.uint32)
+            capacity = found.value
+        out = np.zeros((max(1, capacity), 2), dtype=np.uint32)
+        check(capi.lib().ivx_bv_pairs_hierarchy(self._h, int(mode), ptr(out), capacity, C.byref(found)))
+        return out[: found.value]
+
+
+def morton_key(frame, box, index: int) -> int:
+    """`ivx_bv_morton_key`: (code << 32) | index of one box in a frame, host arithmetic of the library"""
+    key = C.c_uint64(0)
+    check(capi.lib().ivx_bv_morton_key(ptr(_rec(frame, AABB_DTYPE, 1)), ptr(_rec(box, AABB_DTYPE, 1)), int(index), C.byref(key)))
+    return int(key.value)
+
+
+def hierarchy_host(world_boxes, nodes=None, leaf_objects=None):
+    """`ivx_bv_hierarchy_host`: the hierarchy of n world boxes on the host -> (nodes [max(n - 1, 0)], leaf objects [n], frame). The C call takes no
+    capacities, so arrays given to be filled are measured here: one that is too short raises an IvxError of IVX_ERR_CAPACITY before the call."""
+    w = _rec(world_boxes, AABB_DTYPE)
+    n, nn = w.size, max(w.size - 1, 0)
+    nodes = np.zeros(nn, dtype=BV_NODE_DTYPE) if nodes is None else nodes
+    leaf_objects = np.zeros(n, dtype=np.uint32) if leaf_objects is None else leaf_objects
+    for a, dtype, need, what in ((nodes, BV_NODE_DTYPE, nn, "node"), (leaf_objects, np.dtype(np.uint32), n, "leaf object")):
+        assert a.dtype == dtype and a.flags.c_contiguous, what
+        if a.size < need:
+            raise capi.IvxError(capi.IVX_ERR_CAPACITY, f"hierarchy_host: {need} {what}s, the array holds {a.size}")
+    frame = np.zeros(1, dtype=AABB_DTYPE)
+    check(capi.lib().ivx_bv_hierarchy_host(ptr(w) if n else None, n, ptr(nodes) if nn else None, ptr(leaf_objects) if n else None, ptr(frame)))
+    return nodes[:nn], leaf_objects[:n], frame[0]
+
+
+def node_info(nodes, n: int):
+    """per internal node its depth (the root: 0) and the number of leaves below it — what the reference's BVHNodeInfo carries for its gizmo
+    (hierarchy.rs) -> (depth [n - 1] uint32, primitive_count [n - 1] uint32). A tree deeper than 64 or with a child out of range is refused."""
+    nn = max(int(n) - 1, 0)
+    depth, count = np.zeros(nn, dtype=np.uint32), np.zeros(nn, dtype=np.uint32)
+    if nn == 0:
+        return depth, count
+    left, right = nodes["left"].astype(np.int64), nodes["right"].astype(np.int64)
+    order, stack = [], [(0, 0)]
+    while stack:
+        i, d = stack.pop()
+        if not (0 <= i < nn) or d > 64 or len(order) >= nn:
+            raise ValueError(f"node_info: node {i} at depth {d} is not part of a tree of {nn} nodes")
+        depth[i] = d
+        order.append(i)
+        stack.extend((c, d + 1) for c in (int(left[i]), int(right[i])) if not c & capi.BV_LEAF)
+    for i in reversed(order):  # (children come behind their parent in `order`)
+        count[i] = sum(1 if c & capi.BV_LEAF else int(count[c]) for c in (int(left[i]), int(right[i])))
+    return depth, count
 
 
 def _kinds(kinds, n):

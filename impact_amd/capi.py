@@ -199,9 +199,14 @@ BV_QUERY_DTYPE = np.dtype({
 BV_DYNAMIC, BV_STATIC, BV_PHANTOM = 0, 1, 2
 BV_QUERY_BOX, BV_QUERY_SPHERE, BV_QUERY_FRUSTUM, BV_QUERY_ORIENTED_BOX = 0, 1, 2, 3
 BV_ALL_PAIRS, BV_DYNAMIC_PAIRS = 0, 1
-BV_PTR_WORLD_BOXES, BV_PTR_PAIRS, BV_PTR_MASKS = 0, 1, 2
+BV_PTR_WORLD_BOXES, BV_PTR_PAIRS, BV_PTR_MASKS, BV_PTR_NODES, BV_PTR_LEAF_OBJECTS = 0, 1, 2, 3, 4
 BV_MAX_OBJECTS, BV_MAX_QUERIES = 1 << 20, 1024
 assert AABB_DTYPE.itemsize == 24 and SIMILARITY_DTYPE.itemsize == 32 and BV_QUERY_DTYPE.itemsize == 128
+# the hierarchy over a set (csrc/bvh.hip): `ivx_bv_node`; a child reference with BV_LEAF set names a leaf position, else a node
+BV_NODE_DTYPE = np.dtype([("lower", "<f4", (3,)), ("upper", "<f4", (3,)), ("left", "<u4"), ("right", "<u4")])
+BV_LEAF = 0x80000000
+CW_BROAD_FLAT, CW_BROAD_HIERARCHY = 0, 1
+assert BV_NODE_DTYPE.itemsize == 32
 # primitive collidables (csrc/narrow.hip): `ivx_collidable`, in its body's frame or in world space
 COLLIDABLE_DTYPE = np.dtype([("shape", "<u4"), ("kind", "<u4"), ("body", "<u4"), ("reserved", "<u4"), ("id", "<u8"), ("a", "<f4", (3,)), ("b", "<f4", (3,)), ("s", "<f4"),
                              ("response", "<f4", (3,))])
@@ -261,6 +266,7 @@ EXPORTED_SYMBOLS = [
     "ivx_cull_collect", "ivx_cull_many_frusta", "ivx_cull_download", "ivx_cull_device_ptr",
     "ivx_bv_world_aabb", "ivx_bv_frustum_query", "ivx_grid_model_aabb", "ivx_bv_set", "ivx_bv_set_grids", "ivx_bv_download", "ivx_bv_pairs", "ivx_bv_queries",
     "ivx_bv_device_ptr",
+    "ivx_bv_morton_key", "ivx_bv_hierarchy_host", "ivx_bv_build_hierarchy", "ivx_bv_hierarchy_download", "ivx_bv_pairs_hierarchy", "ivx_cw_set_broad_phase",
     "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
     "ivx_world_set_motion_drivers", "ivx_world_set_time", "ivx_world_time", "ivx_world_apply_motion", "ivx_md_eval", "ivx_md_apply_host",
     "ivx_world_set_force_generators", "ivx_world_set_dynamic_gravity", "ivx_world_apply_forces", "ivx_world_gravity_loads", "ivx_fg_apply_host",
@@ -297,7 +303,7 @@ def extra_struct_sizes():
         "ivx_culling_frustum": (CULLING_FRUSTUM_DTYPE, 136), "ivx_cull_view": (CULL_VIEW_DTYPE, 152), "ivx_cull_pair": (CULL_PAIR_DTYPE, 40),
         "ivx_cull_object": (CULL_OBJECT_DTYPE, 8), "ivx_draw_args": (DRAW_ARGS_DTYPE, 16), "ivx_draw_indexed_args": (DRAW_INDEXED_ARGS_DTYPE, 20),
         "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
-        "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128),
+        "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128), "ivx_bv_node": (BV_NODE_DTYPE, 32),
         "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
         "ivx_force_generator": (FORCE_GENERATOR_DTYPE, 64),
         "ivx_uniform_medium": (UNIFORM_MEDIUM_DTYPE, 16), "ivx_drag_generator": (DRAG_GENERATOR_DTYPE, 16), "ivx_drag_map_view": (DRAG_MAP_VIEW_DTYPE, 16),
@@ -489,6 +495,12 @@ def lib():
         "ivx_bv_pairs": (i32, [vp, u32, vp, sz, C.POINTER(sz)]),
         "ivx_bv_queries": (i32, [vp, vp, sz, vp, vp]),
         "ivx_bv_device_ptr": (vp, [vp, i32]),
+        "ivx_bv_morton_key": (i32, [vp, vp, u32, C.POINTER(C.c_uint64)]),
+        "ivx_bv_hierarchy_host": (i32, [vp, sz, vp, vp, vp]),
+        "ivx_bv_build_hierarchy": (i32, [vp]),
+        "ivx_bv_hierarchy_download": (i32, [vp, vp, sz, vp, sz, C.POINTER(sz)]),
+        "ivx_bv_pairs_hierarchy": (i32, [vp, u32, vp, sz, C.POINTER(sz)]),
+        "ivx_cw_set_broad_phase": (i32, [vp, u32]),
         "ivx_cw_transform": (i32, [vp, vp, vp, vp, vp]),
         "ivx_cw_contact": (i32, [vp, vp, vp, C.POINTER(i32)]),
         "ivx_cw_set_collidables": (i32, [vp, vp, sz]),

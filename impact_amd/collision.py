@@ -93,6 +93,10 @@ class CollisionWorld:
         check(capi.lib().ivx_cw_set_collidables(self.world.h, ptr(c) if c.size else None, c.size))
         self.n = c.size
 
+    def set_broad_phase(self, which: int) -> None:
+        """`ivx_cw_set_broad_phase`: capi.CW_BROAD_FLAT (the default) or capi.CW_BROAD_HIERARCHY — where `collide` takes its pairs from"""
+        check(capi.lib().ivx_cw_set_broad_phase(self.world.h, int(which)))
+
     def synchronize(self) -> BoundingVolumeSet:
         """`ivx_cw_synchronize`: enqueued behind whatever the stream holds -> the context's bounding-volume set of the world boxes"""
         check(capi.lib().ivx_cw_synchronize(self.world.h))

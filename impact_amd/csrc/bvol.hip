@@ -4,7 +4,7 @@
 //   impact_geometry/src/axis_aligned_box.rs:350-363 (aabb_of_transformed), :619-623 (box_lies_outside), sphere.rs:167-181, frustum.rs:456-471,
 //   oriented_box.rs:129-143, impact_physics/src/collision.rs:215-262, 317-349 (which pairs a frame asks for), impact_voxel/src/object.rs:886-907 and
 //   interaction.rs:202-222 (a voxel object's entry). The reference answers all of these from a bounding volume hierarchy; its tests and fuzz targets
-//   use the `_brute_force` forms as ground truth. This file IS the brute-force form: no hierarchy, no sort, no atomics.
+//   use the `_brute_force` forms as ground truth. This file IS the brute-force form: no hierarchy, no sort, no atomics (the hierarchy: bvh.hip).
 //
 // WORLD — k_bv_world, one wave per 64 consecutive objects: a lane derives its object's world box (world_aabb below, the very function the host
 //   export runs) or takes it as given, then a shuffle min / max tree in input order leaves the block's box. Minima and maxima are taken in the total
@@ -265,6 +265,7 @@ struct BvState {
     bool has_set = false;
     uint32_t n = 0;
     uint64_t serial = 0;  // counts the sets the context has held (ivx_bvol_set_serial)
+    void* hierarchy = nullptr;  // bvh.hip's state: a tree over one of those sets
     size_t o_kinds = 0, o_world = 0, o_blocks = 0, o_total = 0;
 };
 
@@ -378,8 +379,19 @@ void ivx_bvol_release(ivx_ctx* c) {
     BvState* s = static_cast<BvState*>(c->bvol_state);
     for (ivx_buf* b : {&s->set, &s->scratch, &s->pairs, &s->masks}) ivx_buf_free(b);
     ivx_staging_release(&s->staging);
+    ivx_bvh_release(s->hierarchy);
     delete s;
     c->bvol_state = nullptr;
+}
+
+int ivx_bvol_view_of(ivx_ctx* c, const char* who, ivx_bvol_view* out) {
+    BvState* st;
+    if (int rc = set_state(c, who, &st)) return rc;
+    const char* d = static_cast<const char*>(st->set.p);
+    out->n = st->n, out->serial = st->serial, out->pairs = &st->pairs, out->hierarchy = &st->hierarchy;
+    out->world = st->n ? reinterpret_cast<const ivx_aabb*>(d + st->o_world) : nullptr;
+    out->kinds = st->n ? reinterpret_cast<const uint32_t*>(d + st->o_kinds) : nullptr;
+    return IVX_OK;
 }
 
 int ivx_bvol_set_begin(ivx_ctx* c, size_t n, ivx_aabb** d_boxes, uint32_t** d_kinds) {
@@ -586,6 +598,8 @@ void* ivx_bv_device_ptr(ivx_ctx* c, int which) {
         case IVX_BV_PTR_WORLD_BOXES: return st->has_set && st->n ? static_cast<char*>(st->set.p) + st->o_world : nullptr;
         case IVX_BV_PTR_PAIRS: return st->pairs.p;
         case IVX_BV_PTR_MASKS: return st->masks.p;
+        case IVX_BV_PTR_NODES:
+        case IVX_BV_PTR_LEAF_OBJECTS: return st->has_set ? ivx_bvh_device_ptr(st->hierarchy, st->serial, which) : nullptr;
         default: return nullptr;
     }
 }

@@ -1,5 +1,6 @@
-// What bvol.hip shares with narrow.hip: the world box derivation both files run on the host and on the device, and the two halves of the
-// bounding-volume calls that narrow.hip drives with inputs that are on the device already.
+// What bvol.hip, bvh.hip and narrow.hip share: the world box derivation run on the host and on the device, the hierarchy's rules as functions
+// its host call and its kernels both run, and the halves of the bounding-volume calls that narrow.hip drives with inputs that are on the
+// device already.
 #pragma once
 #include "ivx_internal.hpp"
 
@@ -24,6 +25,115 @@ __host__ __device__ inline void ivx_bv_world_aabb_of(const ivx_aabb& m, const iv
         out->upper[i] = ct + ht;
     }
 }
+
+// ---- the hierarchy (bvh.hip): what its host function and its kernels both run, so that both leave the same bytes ----------------------------
+// (include/impact_voxel_hip.h states the rules: frame, key, leaves, nodes)
+__host__ __device__ __forceinline__ uint32_t ivx_bv_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
+// the bit pattern of a float as a signed integer that orders like the float, with -0.0 below +0.0 (bvol.hip's order of the block boxes)
+__host__ __device__ __forceinline__ int32_t ivx_bv_order_key(float v) {
+    const int32_t b = (int32_t)ivx_bv_bits(v);
+    return b < 0 ? (int32_t)((uint32_t)b ^ 0x7FFFFFFFu) : b;
+}
+__host__ __device__ __forceinline__ float ivx_bv_order_min(float a, float b) { return ivx_bv_order_key(b) < ivx_bv_order_key(a) ? b : a; }
+__host__ __device__ __forceinline__ float ivx_bv_order_max(float a, float b) { return ivx_bv_order_key(b) > ivx_bv_order_key(a) ? b : a; }
+__host__ __device__ __forceinline__ void ivx_bv_union(ivx_aabb* into, const ivx_aabb& b) {
+    for (int k = 0; k < 3; ++k) into->lower[k] = ivx_bv_order_min(into->lower[k], b.lower[k]), into->upper[k] = ivx_bv_order_max(into->upper[k], b.upper[k]);
+}
+__host__ __device__ __forceinline__ ivx_aabb ivx_bv_neutral_box() {
+    ivx_aabb b;
+    for (int k = 0; k < 3; ++k) b.lower[k] = __builtin_inff(), b.upper[k] = -__builtin_inff();
+    return b;
+}
+__host__ __device__ __forceinline__ bool ivx_bv_has_nan(const ivx_aabb& b) {
+    bool nan = false;
+    for (int k = 0; k < 3; ++k) nan = nan || b.lower[k] != b.lower[k] || b.upper[k] != b.upper[k];
+    return nan;
+}
+// box_lies_outside, the header's box decision: a difference with its sign bit set, or a NaN one (bvol.hip's pair walk decides the same way)
+__host__ __device__ __forceinline__ bool ivx_bv_lies_outside(const ivx_aabb& self, const ivx_aabb& other) {
+    uint32_t bits = 0u;
+    bool nan = false;
+    for (int k = 0; k < 3; ++k) {
+        const float d0 = other.upper[k] - self.lower[k], d1 = self.upper[k] - other.lower[k];
+        bits |= ivx_bv_bits(d0) | ivx_bv_bits(d1);
+        nan = nan || d0 != d0 || d1 != d1;
+    }
+    return (bits >> 31) != 0u || nan;
+}
+// a NaN bound, or a bound of magnitude 1e30f or more: the box stays out of the frame and takes the last code
+__host__ __device__ __forceinline__ bool ivx_bv_unkeyed(const ivx_aabb& b) {
+    bool out = ivx_bv_has_nan(b);
+    for (int k = 0; k < 3; ++k) out = out || ivx_bv_abs(b.lower[k]) >= 1e30f || ivx_bv_abs(b.upper[k]) >= 1e30f;
+    return out;
+}
+// the frame of no box at all (the union's neutral element came through): the all-zero box
+__host__ __device__ __forceinline__ void ivx_bv_frame_finish(ivx_aabb* f) {
+    if (ivx_bv_order_key(f->lower[0]) > ivx_bv_order_key(f->upper[0]))
+        for (int k = 0; k < 3; ++k) f->lower[k] = 0.0f, f->upper[k] = 0.0f;
+}
+__host__ __device__ __forceinline__ uint32_t ivx_bv_spread3(uint32_t q) {  // bit k of a 10-bit value to bit 3 k
+    uint32_t r = 0u;
+    for (int k = 0; k < 10; ++k) r |= ((q >> k) & 1u) << (3 * k);
+    return r;
+}
+__host__ __device__ __forceinline__ uint64_t ivx_bv_key_of(const ivx_aabb& frame, const ivx_aabb& box, uint32_t index) {
+    uint32_t code = 0x3FFFFFFFu;
+    if (!ivx_bv_unkeyed(box)) {
+        uint32_t q[3];
+        for (int k = 0; k < 3; ++k) {
+            const float c = 0.5f * (box.lower[k] + box.upper[k]);
+            const float t = (c - frame.lower[k]) / (frame.upper[k] - frame.lower[k]);
+            q[k] = !(t > 0.0f) ? 0u : (t < 1.0f ? (uint32_t)(t * 1024.0f) : 1023u);
+        }
+        code = (ivx_bv_spread3(q[0]) << 2) | (ivx_bv_spread3(q[1]) << 1) | ivx_bv_spread3(q[2]);
+    }
+    return ((uint64_t)code << 32) | index;
+}
+// Karras's delta: the length of the common prefix of keys i and j, -1 when j lies past either end (the keys are unique)
+__host__ __device__ __forceinline__ int ivx_bv_delta(const uint64_t* keys, int n, int i, int j) {
+    if (j < 0 || j >= n) return -1;
+    return __builtin_clzll(keys[i] ^ keys[j]);
+}
+// Karras's node i of n sorted keys (0 <= i <= n - 2): its leaf range [first, last] and its two children as IVX_BV_LEAF | position or a node index.
+// Every loop is bounded by the 21 doublings n <= 2^20 allows.
+__host__ __device__ inline void ivx_bv_karras(const uint64_t* keys, int n, int i, uint32_t* left, uint32_t* right, uint32_t* first, uint32_t* last) {
+    const int d = ivx_bv_delta(keys, n, i, i + 1) - ivx_bv_delta(keys, n, i, i - 1) < 0 ? -1 : 1;
+    const int dmin = ivx_bv_delta(keys, n, i, i - d);
+    int lmax = 2;
+    for (int k = 0; k < 24 && ivx_bv_delta(keys, n, i, i + lmax * d) > dmin; ++k) lmax *= 2;
+    int l = 0;
+    for (int t = lmax / 2; t >= 1; t /= 2)
+        if (ivx_bv_delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
+    const int j = i + l * d;
+    const int dnode = ivx_bv_delta(keys, n, i, j);
+    int s = 0;
+    for (int t = (l + 1) / 2, k = 0; k < 24; t = (t + 1) / 2, ++k) {
+        if (ivx_bv_delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
+        if (t <= 1) break;
+    }
+    const int split = i + s * d + (d < 0 ? -1 : 0);
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    *left = lo == split ? (IVX_BV_LEAF | (uint32_t)split) : (uint32_t)split;
+    *right = hi == split + 1 ? (IVX_BV_LEAF | (uint32_t)(split + 1)) : (uint32_t)(split + 1);
+    *first = (uint32_t)lo, *last = (uint32_t)hi;
+}
+
+// What bvh.hip takes from the context's set (bvol.hip owns it): the resident world boxes and kinds, the set's serial, the pair buffer both pair
+// passes leave their result in, and the slot that holds the hierarchy's own state (freed through ivx_bvh_release when the set's state goes).
+struct ivx_bvol_view {
+    const ivx_aabb* world = nullptr;
+    const uint32_t* kinds = nullptr;
+    uint32_t n = 0;
+    uint64_t serial = 0;
+    ivx_buf* pairs = nullptr;
+    void** hierarchy = nullptr;
+};
+int ivx_bvol_view_of(ivx_ctx* c, const char* who, ivx_bvol_view* out);  // IVX_ERR_STATE without a set
+void ivx_bvh_release(void* hierarchy);
+void* ivx_bvh_device_ptr(void* hierarchy, uint64_t set_serial, int which);  // IVX_BV_PTR_NODES / _LEAF_OBJECTS
+// ivx_bv_build_hierarchy and the pair pass of ivx_bv_pairs_hierarchy, with ivx_bvol_pairs_enqueue's contract (narrow.hip drives both)
+int ivx_bvh_build_enqueue(ivx_ctx* c, const char* who);
+int ivx_bvh_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool check_cap, size_t cap, size_t* n_pairs);
 
 // A set of n world boxes whose inputs a kernel of the caller writes on the context's stream, no host copy involved:
 //   begin:  lays the context's set buffer out for n objects (the context holds no set until `finish`) and hands out where the boxes (n, world

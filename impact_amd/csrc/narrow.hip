@@ -355,6 +355,7 @@ struct CwState {
     uint32_t need_dyn = 0, need_kin = 0;  // body counts the collidables' indices were checked against need at least
     uint64_t set_serial = 0;              // the context's bounding-volume set the last synchronize installed
     size_t n_contacts = 0, n_deferred = 0;
+    uint32_t broad_phase = IVX_CW_BROAD_FLAT;  // where ivx_cw_collide takes its pairs from (ivx_cw_set_broad_phase)
 };
 
 int state_of(ivx_world* w, CwState** out) {
@@ -495,7 +496,12 @@ int ivx_cw_collide(ivx_world* w, uint32_t mode, ivx_contact* out, size_t cap, si
     ivx_many_other_context other_(c);
     st->n_contacts = 0, st->n_deferred = 0;
     size_t n_pairs = 0;
-    if (int rc = ivx_bvol_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) return rc;  // (the call's first wait: the grand total)
+    if (st->broad_phase == IVX_CW_BROAD_HIERARCHY) {
+        if (int rc = ivx_bvh_build_enqueue(c, who)) return rc;  // (nothing waits)
+        if (int rc = ivx_bvh_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) return rc;
+    } else if (int rc = ivx_bvol_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) {  // (either way the call's first wait: the grand total)
+        return rc;
+    }
     if (n_pairs == 0) return IVX_OK;
     const uint32_t np = (uint32_t)n_pairs, n_waves = (np + 63u) / 64u;
     ivx_layout l;
@@ -536,6 +542,16 @@ int ivx_cw_collide(ivx_world* w, uint32_t mode, ivx_contact* out, size_t cap, si
     IVX_REQUIRE(!deferred_pairs || totals[1] <= deferred_cap, IVX_ERR_CAPACITY, "%s: %u deferred pairs, the buffer holds %zu", who, totals[1], deferred_cap);
     if (out && totals[0]) memcpy(out, hs + h_contacts, (size_t)totals[0] * sizeof(ivx_contact));
     if (deferred_pairs && totals[1]) memcpy(deferred_pairs, hs + h_deferred, (size_t)totals[1] * 8);
+    return IVX_OK;
+}
+
+int ivx_cw_set_broad_phase(ivx_world* w, uint32_t which) {
+    const char* who = "ivx_cw_set_broad_phase";
+    IVX_REQUIRE(w, IVX_ERR_INVALID, "%s: null world", who);
+    IVX_REQUIRE(which <= IVX_CW_BROAD_HIERARCHY, IVX_ERR_INVALID, "%s: broad phase %u (0 = flat, 1 = hierarchy)", who, which);
+    CwState* st;
+    if (int rc = state_of(w, &st)) return rc;
+    st->broad_phase = which;
     return IVX_OK;
 }
 

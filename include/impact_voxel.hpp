@@ -456,6 +456,28 @@ public:
         if (n) check(ivx_bv_pairs(ctx_->handle(), mode, &out[0][0], out.size(), &n));
         return out;
     }
+    // the hierarchy over the set (hierarchy.rs): built on request, valid until the next `set`; its pair pass returns the bytes of the flat one
+    void build_hierarchy() { check(ivx_bv_build_hierarchy(ctx_->handle())); }
+    std::vector<ivx_bv_node> hierarchy(size_t n_objects, std::vector<uint32_t>* leaf_objects = nullptr) {
+        std::vector<ivx_bv_node> nodes(n_objects ? n_objects - 1 : 0);
+        if (leaf_objects) leaf_objects->resize(n_objects);
+        size_t n_nodes = 0;
+        check(ivx_bv_hierarchy_download(ctx_->handle(), nodes.data(), nodes.size(), leaf_objects ? leaf_objects->data() : nullptr, n_objects, &n_nodes));
+        return nodes;
+    }
+    std::vector<std::array<uint32_t, 2>> intersecting_pairs_hierarchy(uint32_t mode = IVX_BV_ALL_PAIRS) {
+        std::vector<std::array<uint32_t, 2>> out;
+        size_t n = 0;
+        check(ivx_bv_pairs_hierarchy(ctx_->handle(), mode, nullptr, 0, &n));  // (counts, and leaves the pairs on the device)
+        out.resize(n);
+        if (n) check(ivx_bv_pairs_hierarchy(ctx_->handle(), mode, &out[0][0], out.size(), &n));
+        return out;
+    }
+    static uint64_t morton_key(const ivx_aabb& frame, const ivx_aabb& box, uint32_t index) {
+        uint64_t key = 0;
+        check(ivx_bv_morton_key(&frame, &box, index, &key));
+        return key;
+    }
     // for_each_bounding_volume_in_axis_aligned_box / _in_sphere / _maybe_in_frustum / _maybe_in_oriented_box: ceil(n / 64) mask words per query
     std::vector<uint64_t> query(const std::vector<ivx_bv_query>& queries, size_t n_objects, std::vector<uint32_t>* counts = nullptr) {
         std::vector<uint64_t> masks(queries.size() * ((n_objects + 63) / 64));
@@ -705,6 +727,9 @@ public:
         return map;
     }
     void set_detailed_drag(const std::vector<ivx_drag_generator>& generators) { check(ivx_world_set_detailed_drag(w_, generators.data(), generators.size())); }
+
+    // the collision world's broad phase: IVX_CW_BROAD_FLAT (the default) or IVX_CW_BROAD_HIERARCHY — where ivx_cw_collide takes its pairs from
+    void set_broad_phase(uint32_t which) { check(ivx_cw_set_broad_phase(w_, which)); }
 
 private:
     ivx_world* w_ = nullptr;

@@ -947,7 +947,9 @@ void* ivx_cull_device_ptr(ivx_ctx*, int which);
  * impact_geometry/src/axis_aligned_box.rs, sphere.rs, frustum.rs, oriented_box.rs; impact_physics/src/collision.rs:215-349) ----
  * What the batched calls above take as input and nothing else here produced: the pairs of ivx_*_contacts_many (ivx_bv_pairs), the objects an absorber
  * touches (ivx_bv_queries with a box or a sphere), the per-(view, object) IVX_CULL_PAIR_SKIP bit (ivx_bv_queries with frusta / oriented boxes).
- * No hierarchy: the pair pass is the exact upper triangle (the reference's own `_brute_force` form), csrc/bvol.hip. */
+ * Two forms of the pair pass that leave the same bytes: the exact upper triangle (the reference's own `_brute_force` form, csrc/bvol.hip; the
+ * default everywhere) and a linear hierarchy built over the set on request (ivx_bv_build_hierarchy, csrc/bvh.hip; further down). Region queries
+ * use the flat form only. */
 /* AxisAlignedBoxC. 24 bytes. */
 typedef struct {
     float lower[3], upper[3];
@@ -1059,6 +1061,62 @@ int ivx_bv_download(ivx_ctx*, ivx_aabb* world_boxes, size_t cap, ivx_aabb* total
 int ivx_bv_pairs(ivx_ctx*, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n_out);
 int ivx_bv_queries(ivx_ctx*, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, uint32_t* counts);
 void* ivx_bv_device_ptr(ivx_ctx*, int which);
+
+/* The hierarchy over the context's set (hierarchy.rs, built by hierarchy/fast_bottom_up.rs in the reference; here a linear BVH in Morton order with
+ * Karras's construction — the reference's tree shape is an artefact of its clustering and is not reproduced). csrc/bvh.hip; the host functions run
+ * the very functions the kernels run and give the same bytes. All f32, this order, no contraction.
+ * FRAME. A box is UNBOUNDED when one of its bounds has magnitude >= 1e30f (a plane's +-FLT_MAX box is). The frame is the union of the world boxes
+ *   that have no NaN bound and are not unbounded, minima and maxima taken in the total order of the bit patterns (order_min / order_max: -0.0 below
+ *   +0.0); the all-zero box when no world box qualifies.
+ * KEY (ivx_bv_morton_key). For a box with no NaN bound that is not unbounded, per axis: c = 0.5f (lower + upper),
+ *   t = (c - frame.lower) / (frame.upper - frame.lower), q = t < 1 ? (uint32_t)(t 1024.0f) : 1023; a t that is not greater than zero — a NaN, which a
+ *   zero-extent axis gives, included — gives q = 0. code = the 30-bit interleave of qx, qy, qz, x above y above z (bit 3 k + 2 / + 1 / + 0 = bit k of
+ *   qx / qy / qz). A NaN-bounded or unbounded box gets the code 0x3FFFFFFF. key = (code << 32) | index: unique, ties in the code fall in index
+ *   order, and the tree is never deeper than 50 (30 code bits, 20 index bits).
+ * LEAVES. leaf_objects[p] is the object at Morton position p, in ascending key order. A leaf's box is its object's world box, except for an object
+ *   with a NaN bound: its leaf box is the neutral box (lower = +inf, upper = -inf), which meets nothing and adds nothing to a union.
+ * NODES. For n >= 2 there are n - 1 internal nodes, node 0 the root. Node i is Karras's node i over the sorted keys: with
+ *   delta(i, j) = clz(key_i ^ key_j) over the 64 bits, -1 when j lies past either end, its direction is the sign of delta(i, i + 1) - delta(i, i - 1),
+ *   its range the longest run in that direction whose delta exceeds delta(i, i - d), its split the last position whose delta exceeds the range's
+ *   own. left / right name an internal node by its index or a leaf by IVX_BV_LEAF | position. A node's box is the union of its two children's boxes
+ *   in the bit order above — the order of the flat form's block boxes, for its reason: under the sign-bit decision an fminf union could reject a
+ *   member pair that intersects. n == 1: no nodes (*n_nodes = 0), leaf_objects[0] = 0. n == 0: nothing.
+ * ivx_bv_hierarchy_host: all of the above on the host for n world boxes (n <= IVX_BV_MAX_OBJECTS, else IVX_ERR_CAPACITY): nodes[n - 1],
+ *   leaf_objects[n], *frame (may be NULL). nodes may be NULL for n < 2, leaf_objects for n == 0.
+ * ivx_bv_build_hierarchy: the same over the context's set on its stream, nothing waits: frame, keys, a stable radix sort of the code bits (8 bits a
+ *   pass, no atomic decides a position), a lane per node, and the boxes from the leaves up — a workgroup hands a box to another through an
+ *   agent-scope release, a per-node ticket and an agent-scope acquire; the second arriver carries on, nobody waits, and the union does not depend
+ *   on who came first: two builds leave the same bytes.
+ * STATE. A hierarchy belongs to the set it was built from: after a new ivx_bv_set* (or ivx_cw_synchronize) ivx_bv_hierarchy_download and
+ *   ivx_bv_pairs_hierarchy return IVX_ERR_STATE until ivx_bv_build_hierarchy has run again; without a set all three do. Inside an ivx_many_begin
+ *   bracket what has been recorded is flushed first, as by ivx_bv_pairs.
+ * ivx_bv_hierarchy_download: nodes (node_cap >= n - 1) and leaf objects (leaf_cap >= n), else IVX_ERR_CAPACITY; either may be NULL; *n_nodes (may be
+ *   NULL). ivx_bv_device_ptr(IVX_BV_PTR_NODES / _LEAF_OBJECTS) names the resident arrays (NULL without a current hierarchy of two objects or more).
+ * ivx_bv_pairs_hierarchy: THE CONTRACT AND THE BYTES OF ivx_bv_pairs — modes 0 and 1, (a, b) with a < b as object indices sorted lexicographically,
+ *   *n_out beyond cap: IVX_ERR_CAPACITY and nothing written, pairs == NULL with cap == 0, 2^31 pairs or more: IVX_ERR_CAPACITY; the result also stays
+ *   in the context's pair buffer (IVX_BV_PTR_PAIRS). A lane per leaf position p walks the tree to the right of p: a subtree is entered when its box
+ *   does not lie outside the lane's (the box decision above) — a subtree whose leaf range ends at or before p is never entered, so each pair is
+ *   found once, from its lower position; at a leaf the mode's kind filter applies. The walk runs twice (count, scan, the call's one wait, emit) and
+ *   the pairs are then brought into (a, b) order by the same radix sort. A walk visits at most 2 n - 1 nodes and stops there: a hierarchy that is
+ *   inconsistent ends the call with IVX_ERR_STATE and a message. Device scratch: O(n) for the tree, 8 bytes per pair for the sort.
+ * ivx_cw_set_broad_phase (a collision world, below): IVX_CW_BROAD_FLAT (the default) or IVX_CW_BROAD_HIERARCHY; any other value is IVX_ERR_INVALID
+ *   and leaves the setting as it was. With the hierarchy, ivx_cw_collide builds it over the set ivx_cw_synchronize installed and takes its pairs
+ *   from the tree; contacts and deferred pairs are the same bytes under both settings. */
+#define IVX_BV_LEAF 0x80000000u /* child reference: bit 31 set = leaf, low bits = leaf position in Morton order */
+typedef struct {
+    float lower[3], upper[3];
+    uint32_t left, right;
+} ivx_bv_node; /* 32 bytes */
+#define IVX_BV_PTR_NODES 3
+#define IVX_BV_PTR_LEAF_OBJECTS 4
+#define IVX_CW_BROAD_FLAT 0u
+#define IVX_CW_BROAD_HIERARCHY 1u
+int ivx_bv_morton_key(const ivx_aabb* frame, const ivx_aabb* box, uint32_t index, uint64_t* key);
+int ivx_bv_hierarchy_host(const ivx_aabb* world, size_t n, ivx_bv_node* nodes, uint32_t* leaf_objects, ivx_aabb* frame);
+int ivx_bv_build_hierarchy(ivx_ctx*);
+int ivx_bv_hierarchy_download(ivx_ctx*, ivx_bv_node* nodes, size_t node_cap, uint32_t* leaf_objects, size_t leaf_cap, size_t* n_nodes);
+int ivx_bv_pairs_hierarchy(ivx_ctx*, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n_out);
+int ivx_cw_set_broad_phase(ivx_world*, uint32_t which);
 
 /* ---- primitive collidables: follow the bodies, narrow phase over the pairs (impact_physics/src/collision.rs:175-261, 317-373
  * synchronize_collidables_with_rigid_bodies and the collision pass; collision/collidable/basic.rs:57-151, sphere.rs:105-157, capsule.rs:142-303;

@@ -257,7 +257,7 @@ EXPORTED_SYMBOLS = [
     "ivx_world_set_spherical_joints", "ivx_world_step", "ivx_world_step_enqueue", "ivx_world_prepare", "ivx_world_advance_momenta", "ivx_world_solve", "ivx_world_advance_configurations",
     "ivx_impact_fracturing_config_default", "ivx_generate_impact_fracture_points", "ivx_delaunay_construct", "ivx_delaunay_destroy", "ivx_delaunay_counts",
     "ivx_delaunay_download", "ivx_delaunay_aabb", "ivx_delaunay_displace_vertices", "ivx_delaunay_boundary_face_planes", "ivx_voronoi_polyhedron", "ivx_voronoi_bounded_aabb",
-    "ivx_comm_unique_id", "ivx_comm_init", "ivx_comm_init_local", "ivx_comm_init_ipc", "ivx_comm_info", "ivx_comm_set_local_copies", "ivx_comm_selftest", "ivx_selftest_mesher_division", "ivx_noise_eval", "ivx_voxel_types_eval", "ivx_comm_destroy", "ivx_slab_create", "ivx_slab_destroy",
+    "ivx_comm_unique_id", "ivx_comm_init", "ivx_comm_init_local", "ivx_comm_init_ipc", "ivx_comm_info", "ivx_comm_set_local_copies", "ivx_comm_selftest", "ivx_selftest_mesher_division", "ivx_noise_eval", "ivx_voxel_types_eval", "ivx_sampler_plan", "ivx_comm_destroy", "ivx_slab_create", "ivx_slab_destroy",
     "ivx_slabs_step_enqueue", "ivx_slabs_step_collect", "ivx_slab_region_map",
     "ivx_world_set_solver_groups", "ivx_world_solver_info", "ivx_world_contact_state",
     "ivx_drag_map_config_default", "ivx_drag_directions", "ivx_drag_map_indices", "ivx_drag_force_and_torque",
@@ -311,6 +311,10 @@ def extra_struct_sizes():
     }
 
 
+# ivx_sampler_plan (developer export): word counts of its two arrays, the header's IVX_SAMPLER_PLAN_*_WORDS
+SAMPLER_PLAN_IN_WORDS, SAMPLER_PLAN_OUT_WORDS = 19, 48
+
+
 class IvxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"ivx error {code}: {msg}")
@@ -353,6 +357,7 @@ def lib():
         "ivx_sdf_grid_shape": (i32, [vp, vp, vp]),
         "ivx_noise_eval": (i32, [vp, i32, vp, vp, sz, vp]),
         "ivx_voxel_types_eval": (i32, [vp, u32, f32, f32, u32, vp, vp]),
+        "ivx_sampler_plan": (i32, [vp, vp]),
         "ivx_sdf_sample": (i32, [vp, vp, sz, u32, vp, vp, C.c_uint8]),
         "ivx_derive_state": (i32, [vp]),
         "ivx_occupied_ranges": (i32, [vp, vp]),

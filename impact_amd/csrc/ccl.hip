@@ -413,7 +413,7 @@ int ivx_launch_face_pairs(ivx_grid* g, int side, const uint16_t* d_nbr, uint32_t
 int ivx_launch_step_record(ivx_grid* g, const uint32_t* d_pair_count, const void* d_pairs, uint32_t max_pairs, void* d_record, bool with_results) {
     IVX_KLAUNCH(k_step_record, dim3(1), dim3(256), 0, g->ctx->stream, g->rscalar, d_pair_count, static_cast<const uint2*>(d_pairs),
                        g->chunk_offsets + 2 * (size_t)g->n_chunks, g->partials + g->partial_blocks * 10, g->x_off, max_pairs,
-                       static_cast<unsigned long long*>(d_record), ivx_wc(g), g->samp_len ? g->samp_len + g->n_chunks : nullptr,
+                       static_cast<unsigned long long*>(d_record), ivx_wc(g), ivx_eval_count(g),
                        with_results ? g->result_host_dev : nullptr, g->timing.take(ivx_many_recording()));
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;

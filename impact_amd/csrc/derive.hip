@@ -1262,7 +1262,7 @@ ivx_roles::PresetArgs ivx_preset_args(ivx_grid* g, uint32_t groups) {
     a.rscalar = g->rscalar;
     a.sn_sums = g->group_sums + n_groups;
     a.n_sn = IVX_SN_GROUP_WORDS * n_groups;  // (role_preset also clears the nine words in use behind them: the general pass's counter, the main pass's list cursors)
-    a.eval_count = g->samp_len ? g->samp_len + g->n_chunks : nullptr;
+    a.eval_count = ivx_eval_count(g);
     return a;
 }
 
@@ -1310,7 +1310,7 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
     uint32_t* next_count = ivx_wc(g);  // the counter of the sweep before: zeroed by this one for the sweep after
     g->wc_cur ^= 1u;
     // (the sampler's list counters have had their last reader by now: rolled over on the way, see role_preset)
-    const uint32_t roll = ((g->scratch_dirty & IVX_SCRATCH_EVAL) && g->samp_len) ? IVX_SCRATCH_EVAL_ROLL : 0u;
+    const uint32_t roll = ((g->scratch_dirty & IVX_SCRATCH_EVAL) && ivx_eval_count(g)) ? IVX_SCRATCH_EVAL_ROLL : 0u;
     ChunkPreArgs face_settle;  // (the arguments of k_face_settle: k_chunk_pre's)
     {
         ChunkPreArgs pa;

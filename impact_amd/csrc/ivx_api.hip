@@ -367,7 +367,7 @@ static void ivx_edit_state_free(struct ivx_edit_state* e);
 void ivx_grid_destroy(ivx_grid* g) {
     if (!g) return;
     (void)ivx_stream_sync(g->ctx->stream);
-    ivx_sampler_ahead_free(g);  // (a pre-pass running ahead on the second stream is waited for)
+    ivx_sampler_free(g);  // (a pre-pass running ahead on the second stream is waited for)
     ivx_edit_state_free(g->edit);
     g->edit = nullptr;
     ivx_submesh_manager_free(g->submesh_manager);  // (host mirrors of the incremental remesh and of the probes' ranges)
@@ -384,8 +384,8 @@ void ivx_grid_destroy(ivx_grid* g) {
         block_release(g->host_block);
         g->result_host = nullptr;
     }
-    void* ptrs[] = {g->arena, g->positions, g->normals, g->indices, g->index_materials, g->vertex_materials, g->submeshes, g->dev_scratch, g->prog_nodes,
-                    g->samp_len, g->samp_ops, g->pairs_dev, g->samp_super, g->probe_points, g->probe_chunk, g->probe_entries};
+    void* ptrs[] = {g->arena, g->positions, g->normals, g->indices, g->index_materials, g->vertex_materials, g->submeshes, g->dev_scratch,
+                    g->pairs_dev, g->probe_points, g->probe_chunk, g->probe_entries};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (g->host_scratch) (void)hipHostFree(g->host_scratch);
@@ -429,10 +429,10 @@ int ivx_grid_stage_counters(ivx_grid* g, uint32_t out[4]) {
     IVX_REQUIRE(g && out, IVX_ERR_INVALID, "ivx_grid_stage_counters: null argument");
     for (int i = 0; i < 4; ++i) out[i] = 0;
     int rc;
-    if (g->samp_len) {  // chunks evaluated per voxel by the sampler (three lists by LDS class)
+    if (ivx_eval_count(g)) {  // chunks evaluated per voxel by the sampler (three lists by LDS class)
         uint32_t ev[3];
         // (the live counters until the derive sweep has rolled them over into their statistics words, role_preset)
-        if ((rc = d2h(g, ev, g->samp_len + g->n_chunks + ((g->scratch_dirty & IVX_SCRATCH_EVAL) ? 0 : 8), sizeof(ev)))) return rc;
+        if ((rc = d2h(g, ev, ivx_eval_count(g) + ((g->scratch_dirty & IVX_SCRATCH_EVAL) ? 0 : 8), sizeof(ev)))) return rc;
         out[0] = ev[0] + ev[1] + ev[2];
     }
     if ((rc = d2h(g, &out[1], g->rscalar + 2, sizeof(uint32_t)))) return rc;                            // chunks with several local regions
@@ -455,8 +455,8 @@ void* ivx_grid_device_ptr(ivx_grid* g, int which) {
 #ifdef IVX_WG_TRACE
         case 6: return g->chunk_moments;
 #endif
-        case 7: return g->samp_len;  // developer tools (tools/prog_stats.py): per-chunk compact program lengths, then the three list counters and lists
-        case 8: return g->samp_ops;  // ... and the programs, OP_CAP (128) uint2 per chunk
+        case 7: return g->smp.set[g->smp.cur].len;  // developer tools (tools/prog_stats.py): per-chunk compact program lengths, then the three list counters and lists
+        case 8: return g->smp.set[g->smp.cur].ops;  // ... and the programs, OP_CAP (128) uint2 per chunk
         case 10: return g->sn_hard;  // ... and which (entries of the emit list)
         case 9: return ivx_sn_hard_count(g);  // developer tools: [0] how many chunks the mesher's last main pass handed to the general pass
         default: return nullptr;
@@ -982,29 +982,21 @@ int ivx_grid_set_sdf_program(ivx_grid* g, const ivx_sdf_processed_node* nodes, s
         const int rc_a = ivx_sampler_ahead_cancel(g);
         if (rc_a) return rc_a;
     }
-    if (n_nodes > g->prog_cap) {
+    auto& prog = g->smp.prog;
+    if (n_nodes > prog.cap) {
         IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
-        if (g->prog_nodes) (void)hipFree(g->prog_nodes);
-        g->prog_nodes = nullptr;
-        g->prog_cap = 0;
-        int rc = dev_alloc(&g->prog_nodes, n_nodes);
+        if (prog.nodes) (void)hipFree(prog.nodes);
+        prog.nodes = nullptr;
+        prog.cap = 0;
+        int rc = dev_alloc(&prog.nodes, n_nodes);
         if (rc) return rc;
-        g->prog_cap = (uint32_t)n_nodes;
+        prog.cap = (uint32_t)n_nodes;
     }
     std::vector<ivx_sdf_processed_node> annotated(nodes, nodes + n_nodes);
     ivx_sdf_annotate_host(annotated.data(), n_nodes);
-    int rc = h2d(g, g->prog_nodes, annotated.data(), n_nodes * sizeof(ivx_sdf_processed_node));
+    int rc = h2d(g, prog.nodes, annotated.data(), n_nodes * sizeof(ivx_sdf_processed_node));
     if (rc) return rc;
-    g->prog_n = (uint32_t)n_nodes;
-    g->prog_stack = (uint32_t)max_depth;
-    for (int d = 0; d < 3; ++d) {
-        g->prog_shape[d] = grid_shape[d];
-        g->prog_center[d] = shifted_grid_center[d];
-    }
-    g->prog_type = voxel_type;
-    g->prog_noise = ivx_sdf_has_noise(nodes, n_nodes) ? 1 : 0;
-    g->eval_len_valid = 0;
-    g->eval_len_pending = 0;
+    ivx_sampler_set_program(g, (uint32_t)n_nodes, (uint32_t)max_depth, grid_shape, shifted_grid_center, voxel_type, ivx_sdf_has_noise(nodes, n_nodes));
     return IVX_OK;
 }
 
@@ -1012,15 +1004,12 @@ int ivx_grid_set_voxel_type_noise(ivx_grid* g, uint32_t n_voxel_types, float noi
     IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_grid_set_voxel_type_noise: null grid");
     IVX_REQUIRE(n_voxel_types <= 255u, IVX_ERR_INVALID, "ivx_grid_set_voxel_type_noise: %u voxel types (at most 255: 255 is the dummy type)", n_voxel_types);
     IVX_REQUIRE(std::isfinite(noise_frequency) && std::isfinite(voxel_type_frequency), IVX_ERR_INVALID, "ivx_grid_set_voxel_type_noise: non-finite frequency");
-    if (g->vt_n == 0u && n_voxel_types == 0u) return IVX_OK;  // (SameVoxelTypeGenerator before and after: the parameters say nothing)
+    if (g->smp.vt.n == 0u && n_voxel_types == 0u) return IVX_OK;  // (SameVoxelTypeGenerator before and after: the parameters say nothing)
     {  // the records a pre-pass that runs ahead has parked carry the type of the generator it ran under: wait for it, drop what it wrote
         const int rc_a = ivx_sampler_ahead_cancel(g);
         if (rc_a) return rc_a;
     }
-    g->vt_n = n_voxel_types;
-    g->vt_noise_freq = noise_frequency;
-    g->vt_type_freq = voxel_type_frequency;
-    g->vt_seed = seed;
+    ivx_sampler_set_types(g, n_voxel_types, noise_frequency, voxel_type_frequency, seed);
     return IVX_OK;
 }
 

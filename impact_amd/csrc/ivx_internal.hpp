@@ -33,6 +33,10 @@ static inline hipError_t ivx_event_record(hipEvent_t e, hipStream_t s) {
     (void)ivx_many_break();
     return hipEventRecord(e, s);
 }
+static inline hipError_t ivx_stream_wait_event(hipStream_t s, hipEvent_t e) {
+    (void)ivx_many_break();
+    return hipStreamWaitEvent(s, e, 0);
+}
 
 #define IVX_CHUNK 16
 #define IVX_CHUNK_VOXELS 4096
@@ -94,6 +98,55 @@ struct ivx_block {
     void* dev;
     void* pinned;
     int refs;
+};
+
+// The sampler's host state, one record per grid (ivx_grid::smp). sampler_host.hpp has its functions and the launch plan, sdf_sample.hip the
+// launches; nothing outside those two writes the `ahead` part.
+enum ivx_ahead_state : int { AHEAD_IDLE = 0, AHEAD_WANTED = 1, AHEAD_PENDING = 2 };
+struct ivx_sampler_set {
+    uint32_t* len;  // [n_chunks] length of the chunk's compact SDF program (sampler pre-pass), [16] counters of the three evaluation lists, [3 n_chunks] the lists
+    void* ops;      // [n_chunks * 128] uint2 ops
+};
+struct ivx_sampler {
+    struct {  // resident SDF program (ivx_grid_set_sdf_program -> ivx_sampler_set_program)
+        ivx_sdf_processed_node* nodes;
+        uint32_t n, cap, stack;
+        uint32_t shape[3];
+        float center[3];
+        uint8_t type;
+        uint8_t noise;  // the resident program holds a noise node (kind 6): the sampler's noise forms run it
+    } prog;
+    // voxel type generator (ivx_grid_set_voxel_type_noise -> ivx_sampler_set_types): n = 0 SameVoxelTypeGenerator (the voxel_type argument of the sample
+    // calls), 1..255 GradientNoiseVoxelTypeGenerator over that many types (k_voxel_type_noise behind the evaluator launches, sdf_sample.hip)
+    struct {
+        uint32_t n, seed;
+        float noise_freq, type_freq;
+    } vt;
+    // lengths of the three evaluation lists under the resident program, as the last collected step with a derive sweep reported them
+    // (`valid`; a function of the program and the grid alone): a class whose list is known to be empty is not launched
+    struct {
+        uint32_t len[3];
+        int valid, pending;
+    } lens;
+    struct {
+        uint32_t* bits;  // [super-blocks * ceil(nodes / 32)] "node certainly outside every chunk of the super-block" bits, then the skip table
+        size_t words;
+    } super;
+    // Two sets of buffers: set[cur] is the one the evaluator reads (and an own pre-pass writes); the other exists only under sample-ahead.
+    ivx_sampler_set set[2];
+    int cur;
+    // Sample-ahead (ivx_grid_set_sample_ahead): the pre-pass of the NEXT sample stage under the resident program runs on the context's second
+    // stream behind this step's evaluator, into set[cur ^ 1]; the records it would write for constant chunks wait in `info_shadow` until the
+    // next evaluator launch commits them. `state`: IDLE -> WANTED at the end of a sample stage that could be consumed (ahead_want), WANTED ->
+    // PENDING when the step launches the pre-pass (ahead_take_wish, ahead_launched), PENDING -> IDLE when the next stage consumes it, and
+    // WANTED / PENDING -> IDLE by ahead_cancel (a new program or type generator, sample-ahead turned off, the grid goes).
+    struct {
+        int on;
+        ivx_ahead_state state;
+        int shadow_sel, other_dirty, events_ready;  // (other_dirty: the eight list counters of set[cur ^ 1] are not known to be zero)
+        ivx_chunk_info* info_shadow;
+        hipEvent_t go, done;
+    } ahead;
 };
 
 struct ivx_grid {
@@ -201,34 +254,8 @@ struct ivx_grid {
     float dens_host[256];   // what dens_dev holds (entry points that are handed the same table again skip the upload)
     void* dev_scratch;      // grown on demand (node programs, dense label export, region statistics)
     size_t dev_scratch_bytes;
-    // resident SDF program (ivx_grid_set_sdf_program)
-    ivx_sdf_processed_node* prog_nodes;
-    uint32_t prog_n, prog_cap, prog_stack;
-    uint32_t prog_shape[3];
-    float prog_center[3];
-    uint8_t prog_type;
-    uint8_t prog_noise;  // the resident program holds a noise node (kind 6): the sampler's noise forms run it
-    // voxel type generator of the sampler (ivx_grid_set_voxel_type_noise): vt_n = 0 SameVoxelTypeGenerator (the voxel_type argument of the sample
-    // calls), 1..255 GradientNoiseVoxelTypeGenerator over that many types (k_voxel_type_noise behind the evaluator launches, sdf_sample.hip)
-    uint32_t vt_n, vt_seed;
-    float vt_noise_freq, vt_type_freq;
-    // lengths of the sampler's three evaluation lists under the resident program, as the last collected step with a derive sweep reported them
-    // (`eval_len_valid`; a function of the program and the grid alone): a class whose list is known to be empty is not launched
-    uint32_t eval_len[3];
-    int eval_len_valid, eval_len_pending;
+    ivx_sampler smp;  // the sampler's program, type generator, list lengths, buffers and sample-ahead state
     int has_dens;
-    uint32_t* samp_len;   // [n_chunks] length of the chunk's compact SDF program (sampler pre-pass)
-    void* samp_ops;       // [n_chunks * 128] uint2 ops
-    // Sample-ahead (ivx_grid_set_sample_ahead, sdf_sample.hip): the pre-pass of the NEXT sample stage under the resident program runs on the
-    // context's second stream behind this step's evaluator, into a second set of the sampler's buffers; the records it would write for constant
-    // chunks wait in `info_shadow` until the next evaluator launch commits them.
-    int ahead_on, ahead_pending, ahead_wanted, ahead_unordered_ok, shadow_sel, alt_eval_dirty, ahead_events_ready;
-    uint32_t* samp_len_alt;
-    void* samp_ops_alt;
-    ivx_chunk_info* info_shadow;
-    hipEvent_t ahead_go, ahead_done;
-    uint32_t* samp_super;  // [super-blocks * ceil(nodes / 32)] "node certainly outside every chunk of the super-block" bits
-    size_t samp_super_words;
     uint32_t* result_host;      // the result block (IVX_RB_*): host-mapped pinned memory the gather kernel writes the step's small results to
     uint32_t* result_host_dev;  // its device-side address
     uint32_t result_seq;        // sequence number of the last gather launch (the block's bell = the completion doorbell)
@@ -495,6 +522,10 @@ static inline uint32_t ivx_list_grid(const ivx_grid* g) {
 // chunk planes of a slab that adjoin no ghost layer
 static inline bool ivx_has_interior_planes(const ivx_grid* g) { return (int)g->cc[0] - (g->has_ghost[0] ? 1 : 0) - (g->has_ghost[1] ? 1 : 0) > 0; }
 static inline uint32_t* ivx_wc(const ivx_grid* g) { return g->work_counts + g->wc_cur; }
+// the sampler's [16] list counters ([0..3) the three lists, [3] the long / short split of the first, [8..13) their rolled copy) and the three
+// lists of n_chunks entries behind them, in the active set of buffers; null before the first sample stage has made them
+static inline uint32_t* ivx_eval_count(const ivx_grid* g) { return g->smp.set[g->smp.cur].len ? g->smp.set[g->smp.cur].len + g->n_chunks : nullptr; }
+static inline uint32_t* ivx_eval_list(const ivx_grid* g) { return g->smp.set[g->smp.cur].len ? ivx_eval_count(g) + 16 : nullptr; }
 // a newly sampled or uploaded object: nothing derived stands, and whatever mesh the buffers hold is not a stale version of this one
 static inline void ivx_voxels_replaced(ivx_grid* g) { g->mesh_valid = g->mesh_built = g->occ_ref_valid = g->bbox_valid = g->regions_valid = 0; }
 // to be called by everything that writes voxel planes other than the sampler (uploads, edits, split / clip / repack, raw plane pointers handed out)
@@ -546,7 +577,7 @@ static inline GridView ivx_view(const ivx_grid* g) {
 int ivx_launch_classify(ivx_grid* g);
 int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, uint32_t n_nodes, uint32_t stack_size,
                           const uint32_t shape[3], const float shifted_center[3], uint8_t voxel_type, uint32_t preset_groups = 0,
-                          bool resident_program = false, bool noise = false);
+                          bool resident_program = false, bool noise = false, bool ahead_unordered_ok = false);
 bool ivx_sdf_has_noise(const ivx_sdf_processed_node* nodes, size_t n);  // sdf_compile.cpp
 // parts of the fused sweep: k_derive can label the chunk-local regions and compute the chunk moments of the chunks it visits
 #define IVX_PART_REGIONS 1u
@@ -568,9 +599,13 @@ int ivx_launch_step_assign(ivx_grid* g, bool with_mesher_general = false, bool w
 int ivx_launch_step_gather(ivx_grid* g);
 bool ivx_step_assign_fits(const ivx_grid* g);
 int ivx_sampler_buffers(ivx_grid* g);
-int ivx_sampler_ahead_cancel(ivx_grid* g);  // sample-ahead (sdf_sample.hip): wait for a pre-pass that runs ahead and drop it
-void ivx_sampler_ahead_free(ivx_grid* g);
+int ivx_sampler_ahead_cancel(ivx_grid* g);  // sample-ahead (sdf_sample.hip): forget the wish for a pre-pass ahead, wait for one that is under way and drop it
 int ivx_sampler_launch_ahead(ivx_grid* g, bool behind_stream);
+// the program record (what prog.nodes now holds; the remembered list lengths go with the old program) and the type generator's; the caller
+// has cancelled whatever ran ahead under the old ones
+void ivx_sampler_set_program(ivx_grid* g, uint32_t n_nodes, uint32_t stack, const uint32_t shape[3], const float center[3], uint8_t voxel_type, bool noise);
+void ivx_sampler_set_types(ivx_grid* g, uint32_t n_voxel_types, float noise_frequency, float voxel_type_frequency, uint32_t seed);
+void ivx_sampler_free(ivx_grid* g);  // everything the sampler owns (ivx_grid_destroy): a pre-pass running ahead is waited for
 void ivx_sdf_annotate_host(ivx_sdf_processed_node* nodes, size_t n);  // sdf_compile.cpp: reserved[] fields for the pre-pass
 int ivx_launch_occupied(ivx_grid* g, uint32_t* d_raw);
 void ivx_occupied_from_raw(const ivx_grid* g, const uint32_t raw[12], uint32_t out[12]);

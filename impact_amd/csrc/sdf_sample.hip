@@ -22,6 +22,7 @@
 #include "ivx_internal.hpp"
 #include "device_common.hpp"
 #include "noise.hpp"
+#include "sampler_host.hpp"
 #include "table_roles.hpp"
 
 namespace {
@@ -451,8 +452,8 @@ __device__ __forceinline__ void load_node_tile(PaddedNode* tile, const ivx_sdf_p
 // taken with a safety distance that dwarfs the rounding of the two box computations. One thread per (super-block, node).
 // The pre-pass then replaces whole far bodies by their folded constant and skips the box arithmetic of single far nodes: its
 // cost no longer grows with the number of bodies in the scene.
-constexpr int SUPER = 4;
-constexpr uint32_t SUPER_MAX_WORDS = 64;  // programs of up to 2048 nodes get their super-block tables inside the pre-pass (k_sdf_super beyond)
+using ivx_smp::SUPER;
+using ivx_smp::SUPER_MAX_WORDS;  // programs of up to 2048 nodes get their super-block tables inside the pre-pass (k_sdf_super beyond)
 // per super-block and node: .x = for a leaf, the root of the largest subtree starting at it whose nodes are all far (the
 // pre-pass replaces the range by one constant), else the node's own index; .y = that subtree's folded constant
 __device__ __forceinline__ bool range_all_far(const uint32_t* mask, uint32_t a, uint32_t b);
@@ -1691,13 +1692,31 @@ __global__ __launch_bounds__(256) void k_voxel_types_eval(TypeNoiseParams p, uin
 
 }  // namespace
 
+// ---- host code: the sampler's buffers, sample-ahead's hand-over, the execution of a sample_plan (sampler_host.hpp) ----------------------
+using namespace ivx_smp;
+
+static void free_set(ivx_sampler_set& t) {
+    if (t.len) (void)hipFree(t.len);
+    if (t.ops) (void)hipFree(t.ops);
+    t = ivx_sampler_set{};
+}
+// one set of the sampler's buffers, published whole or not at all; its counters are cleared on `stream`
+static int alloc_set(ivx_grid* g, ivx_sampler_set& out, hipStream_t stream) {
+    ivx_sampler_set t{};
+    const int rc = [&]() -> int {
+        // [n] program lengths, [16] counters of the three evaluation lists (+ the long / short split of the first; [8..13) their rolled copy), [3 n] the lists
+        IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t.len), sizeof(uint32_t) * (4 * (size_t)g->n_chunks + 16)));
+        IVX_HIP_CHECK(ivx_memset_async(t.len + g->n_chunks, 0, 16 * sizeof(uint32_t), stream));  // the counters start at zero
+        IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t.ops), sizeof(uint2) * (size_t)OP_CAP * g->n_chunks));
+        return IVX_OK;
+    }();
+    if (rc) free_set(t);
+    else out = t;
+    return rc;
+}
 int ivx_sampler_buffers(ivx_grid* g) {
-    if (g->samp_ops) return IVX_OK;
-    // [n] program lengths, [16] counters of the three evaluation lists (+ the long / short split of the first; [8..13) their rolled copy), [3 n] the lists
-    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->samp_len), sizeof(uint32_t) * (4 * (size_t)g->n_chunks + 16)));
-    IVX_HIP_CHECK(ivx_memset_async(g->samp_len + g->n_chunks, 0, 16 * sizeof(uint32_t), g->ctx->stream));  // the counters start at zero
-    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->samp_ops), sizeof(uint2) * (size_t)OP_CAP * g->n_chunks));
-    return IVX_OK;
+    ivx_sampler_set& cur = g->smp.set[g->smp.cur];
+    return cur.ops ? IVX_OK : alloc_set(g, cur, g->ctx->stream);
 }
 
 // the context's second stream (sample-ahead), made on first use
@@ -1709,233 +1728,196 @@ static int ivx_aux_stream(ivx_ctx* c, hipStream_t* out) {
     return IVX_OK;
 }
 // second set of the sampler's buffers + the shadow records + the two events of the hand-over
-static int ivx_sampler_ahead_buffers(ivx_grid* g, hipStream_t aux) {
-    if (!g->ahead_events_ready) {
-        IVX_HIP_CHECK(hipEventCreateWithFlags(&g->ahead_go, hipEventDisableTiming));
-        IVX_HIP_CHECK(hipEventCreateWithFlags(&g->ahead_done, hipEventDisableTiming));
-        g->ahead_events_ready = 1;
+static int ahead_buffers(ivx_grid* g, hipStream_t aux) {
+    ivx_sampler& s = g->smp;
+    if (!s.ahead.events_ready) {
+        IVX_HIP_CHECK(hipEventCreateWithFlags(&s.ahead.go, hipEventDisableTiming));
+        IVX_HIP_CHECK(hipEventCreateWithFlags(&s.ahead.done, hipEventDisableTiming));
+        s.ahead.events_ready = 1;
     }
-    if (g->samp_ops_alt) return IVX_OK;
-    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->samp_len_alt), sizeof(uint32_t) * (4 * (size_t)g->n_chunks + 16)));
-    IVX_HIP_CHECK(hipMemsetAsync(g->samp_len_alt + g->n_chunks, 0, 16 * sizeof(uint32_t), aux));
-    g->alt_eval_dirty = 0;
-    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->samp_ops_alt), sizeof(uint2) * (size_t)OP_CAP * g->n_chunks));
-    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->info_shadow), 2 * sizeof(ivx_chunk_info) * (size_t)g->n_chunks));  // (two: one being committed, one being written)
+    if (s.ahead.info_shadow) return IVX_OK;  // (published last, behind the set)
+    ivx_sampler_set t{};
+    const int rc = alloc_set(g, t, aux);
+    if (rc) return rc;
+    ivx_chunk_info* shadow = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&shadow), 2 * sizeof(ivx_chunk_info) * (size_t)g->n_chunks) != hipSuccess) {  // (two: one being committed, one being written)
+        free_set(t);
+        ivx_set_error("sample-ahead: no device memory for the shadow chunk records of %u chunks", g->n_chunks);
+        return IVX_ERR_HIP;
+    }
+    s.set[s.cur ^ 1] = t;
+    s.ahead.other_dirty = 0;
+    s.ahead.info_shadow = shadow;
     return IVX_OK;
 }
-// A pre-pass that runs ahead is waited for and forgotten (the resident program changes, the grid goes): what it wrote into the second set is dropped
+// The wish for a pre-pass ahead is forgotten; one that runs ahead is waited for and forgotten (the resident program changes, sample-ahead is
+// turned off, the grid goes): what it wrote into the second set is dropped
 int ivx_sampler_ahead_cancel(ivx_grid* g) {
-    if (!g->ahead_pending) return IVX_OK;
-    g->ahead_pending = 0;
-    g->alt_eval_dirty = 1;
-    IVX_HIP_CHECK(hipEventSynchronize(g->ahead_done));
+    if (ahead_cancel(g->smp)) IVX_HIP_CHECK(hipEventSynchronize(g->smp.ahead.done));
     return IVX_OK;
 }
-void ivx_sampler_ahead_free(ivx_grid* g) {
+void ivx_sampler_free(ivx_grid* g) {
+    ivx_sampler& s = g->smp;
     (void)ivx_sampler_ahead_cancel(g);
-    if (g->samp_len_alt) (void)hipFree(g->samp_len_alt);
-    if (g->samp_ops_alt) (void)hipFree(g->samp_ops_alt);
-    if (g->info_shadow) (void)hipFree(g->info_shadow);
-    g->samp_len_alt = nullptr, g->samp_ops_alt = nullptr, g->info_shadow = nullptr;
-    if (g->ahead_events_ready) {
-        (void)hipEventDestroy(g->ahead_go);
-        (void)hipEventDestroy(g->ahead_done);
-        g->ahead_events_ready = 0;
+    free_set(s.set[0]), free_set(s.set[1]);
+    void* rest[] = {s.prog.nodes, s.super.bits, s.ahead.info_shadow};
+    for (void* p : rest)
+        if (p) (void)hipFree(p);
+    if (s.ahead.events_ready) {
+        (void)hipEventDestroy(s.ahead.go);
+        (void)hipEventDestroy(s.ahead.done);
     }
+    s = ivx_sampler{};
+}
+void ivx_sampler_set_program(ivx_grid* g, uint32_t n_nodes, uint32_t stack, const uint32_t shape[3], const float center[3], uint8_t voxel_type, bool noise) {
+    auto& pr = g->smp.prog;
+    pr.n = n_nodes, pr.stack = stack, pr.type = voxel_type, pr.noise = noise ? 1 : 0;
+    for (int d = 0; d < 3; ++d) pr.shape[d] = shape[d], pr.center[d] = center[d];
+    g->smp.lens.valid = g->smp.lens.pending = 0;
+}
+void ivx_sampler_set_types(ivx_grid* g, uint32_t n_voxel_types, float noise_frequency, float voxel_type_frequency, uint32_t seed) {
+    g->smp.vt = {n_voxel_types, seed, noise_frequency, voxel_type_frequency};
+}
+// Sample-ahead: with `on`, every sample stage under the resident program also enqueues the NEXT sample stage's pre-pass — on the context's
+// second stream, behind its own evaluator —, and the next sample stage starts at its evaluator. For callers that sample the same program
+// step after step (the bench's headline step); the results are the same bytes either way. Off (the default): the pre-pass is the stage's
+// first kernel. Turning it off drops a pre-pass that is under way.
+int ivx_grid_set_sample_ahead(ivx_grid* g, int on) {
+    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_grid_set_sample_ahead: null grid");
+    g->smp.ahead.on = on ? 1 : 0;
+    return on ? IVX_OK : ivx_sampler_ahead_cancel(g);
 }
 
 ivx_roles::PresetArgs ivx_preset_args(ivx_grid* g, uint32_t groups);  // derive.hip
 
-int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, uint32_t n_nodes, uint32_t stack_size,
-                          const uint32_t shape[3], const float shifted_center[3], uint8_t voxel_type, uint32_t preset_groups,
-                          bool resident_program, bool noise) {
+static SampleParams sample_params(const ivx_grid* g, const uint32_t shape[3], const float shifted_center[3], uint32_t n_nodes, uint32_t stack_size, uint8_t voxel_type) {
     SampleParams p;
-    p.cx = g->cc[0];
-    p.cy = g->cc[1];
-    p.cz = g->cc[2];
-    p.x_off = g->x_off;
-    for (int d = 0; d < 3; ++d) {
-        p.shape[d] = shape[d];
-        p.shifted_center[d] = shifted_center[d];
-    }
-    p.n_nodes = n_nodes;
-    p.stack_size = stack_size;
-    p.tick = nullptr;  // (set for the stage's first launch alone, below)
+    p.cx = g->cc[0], p.cy = g->cc[1], p.cz = g->cc[2], p.x_off = g->x_off;
+    for (int d = 0; d < 3; ++d) p.shape[d] = shape[d], p.shifted_center[d] = shifted_center[d];
+    p.n_nodes = n_nodes, p.stack_size = stack_size;
+    p.tick = nullptr;  // (set for the launches that can open a timed slot, below; a launch on the second stream is no part of one)
 #ifdef IVX_WG_TRACE
     p.trace = reinterpret_cast<unsigned long long*>(g->chunk_moments);
 #endif
     // (gradient-noise voxel types, ivx_grid_set_voxel_type_noise: the argument is ignored; the evaluator writes type 0 — all there is to a
-    // generator of one type — and the type pass below puts the noise types of two or more in its place)
-    if (g->vt_n) voxel_type = 0;
-    p.voxel_type = voxel_type;
-    size_t lds = (size_t)(stack_size ? stack_size : 1) * IVX_CHUNK_VOXELS * sizeof(float);
-    IVX_REQUIRE(lds <= 150 * 1024, IVX_ERR_CAPACITY, "SDF graph needs a forward stack of %u blocks (at most 9 fit the 160 KiB LDS)", stack_size);
+    // generator of one type — and the type pass puts the noise types of two or more in its place)
+    p.voxel_type = g->smp.vt.n ? 0u : (uint32_t)voxel_type;
+    return p;
+}
+static size_t stack_lds_bytes(uint32_t stack_size) { return (size_t)(stack_size ? stack_size : 1) * IVX_CHUNK_VOXELS * sizeof(float); }
+static int check_stack(uint32_t stack_size) {
+    IVX_REQUIRE(stack_lds_bytes(stack_size) <= MAX_LDS_BYTES, IVX_ERR_CAPACITY, "SDF graph needs a forward stack of %u blocks (at most 9 fit the 160 KiB LDS)", stack_size);
+    return IVX_OK;
+}
+// the general class's forward stack is dynamic LDS beyond the default limit
+static int allow_stack_lds(bool noise, uint32_t stack_size) {
     IVX_HIP_CHECK(hipFuncSetAttribute(noise ? reinterpret_cast<const void*>(k_sdf_eval<0, true>) : reinterpret_cast<const void*>(k_sdf_eval<0>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    {
-        int rc_b = ivx_sampler_buffers(g);
-        if (rc_b) return rc_b;
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)stack_lds_bytes(stack_size)));
+    return IVX_OK;
+}
+// far bits + a uint2 per node of every super-block (k_sdf_super's tables, programs beyond SUPER_MAX_WORDS): grown behind a stream wait
+static int super_table_reserve(ivx_grid* g, size_t need) {
+    auto& t = g->smp.super;
+    if (need <= t.words) return IVX_OK;
+    IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
+    if (t.bits) (void)hipFree(t.bits);
+    t.bits = nullptr;
+    t.words = 0;
+    IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t.bits), need * sizeof(uint32_t)));
+    t.words = need;
+    return IVX_OK;
+}
+// the pre-pass by `blocks` blocks on `stream`, into the set `set` and the records `info_out`
+static void launch_prepass(ivx_grid* g, hipStream_t stream, bool noise, uint32_t blocks, const SampleParams& p, const ivx_sdf_processed_node* d_nodes,
+                           const ivx_sampler_set& set, ivx_chunk_info* info_out, const uint32_t* super_bits, const uint2* super_skip, const SuperGrid& sb,
+                           bool fused_super, bool ahead, uint32_t presets) {
+    uint32_t* const count = set.len + g->n_chunks;
+    IVX_KLAUNCH(noise ? k_sdf_prepass<true> : k_sdf_prepass<false>, dim3(blocks), dim3(PRE_T * PRE_WAVES), 0, stream, p, d_nodes, set.len, reinterpret_cast<uint2*>(set.ops),
+                count, count + 16, g->n_chunks, info_out, super_bits, super_skip, sb.words, sb.sy, sb.sz, sb.blocks(), fused_super ? 1u : 0u, ahead ? 1u : 0u,
+                ivx_preset_args(g, presets));
+}
+// one evaluator launch of the plan, on the active set (`shadow`, `presets`: for the launch that commits a pre-pass that ran ahead)
+static void launch_eval(ivx_grid* g, const EvalLaunch& e, SampleParams& p, const ivx_sdf_processed_node* d_nodes, const ivx_chunk_info* shadow, uint32_t presets) {
+    const ivx_sampler_set& set = g->smp.set[g->smp.cur];
+    uint32_t* const count = ivx_eval_count(g);
+    uint32_t* const list = ivx_eval_list(g);
+    p.tick = g->timing.take(ivx_many_recording());
+    auto go = [&](auto kernel) {
+        IVX_KLAUNCH(kernel, dim3(e.grid), dim3(256), e.lds_bytes, g->ctx->stream, p, count + e.list, list + e.list * (size_t)g->n_chunks, e.long_count ? count + 3 : nullptr,
+                    e.first ? count + 1 : nullptr, e.first ? list + g->n_chunks : nullptr, g->n_chunks, e.scratch_off, set.len, reinterpret_cast<uint2*>(set.ops), d_nodes, g->sdf,
+                    g->type, g->info, g->chunk_signs, g->kface, shadow, g->n_chunks, ivx_preset_args(g, presets));
+    };
+    switch (e.mode) {
+        case 2: go(k_sdf_eval<2>); break;
+        case 1: go(k_sdf_eval<1>); break;
+        default: e.noise ? go(k_sdf_eval<0, true>) : go(k_sdf_eval<0>); break;
     }
-    // Programs of up to SUPER_MAX_WORDS * 32 nodes get their super-block tables inside the pre-pass (no launch of their own); the
-    // pre-pass is then the call's first kernel and hosts the presets of the later stages' scratch words. The sampler's own list
-    // counters are zero already when the derive sweep of the step before rolled them over (role_preset), else cleared here.
-    const uint32_t words = (n_nodes + 31u) / 32u > 0u ? (n_nodes + 31u) / 32u : 1u;
-    const bool fused_super = words <= SUPER_MAX_WORDS;
-    const uint32_t sx = (g->cc[0] + SUPER - 1) / SUPER, sy = (g->cc[1] + SUPER - 1) / SUPER, sz = (g->cc[2] + SUPER - 1) / SUPER;
-    // One evaluator launch per LDS class (see k_sdf_prepass); a class the program cannot reach is not launched, nor one whose list the last step
-    // under this program found empty (the lists are a function of the program and the grid). Two launches one after the other each pay
-    // their own ramp and tail: when both of the first two classes have work and one of them is too short to fill the chip a few times
-    // over, the two-level kernel takes both lists in one launch (the one-level programs run there as well, five workgroups per CU).
-    // (`resident_program`: the step path. The remembered lengths are the RESIDENT program's; ivx_sdf_sample runs any program through
-    // this launcher and must launch every class that program can reach)
-    const bool known = resident_program && g->eval_len_valid != 0;
-    const uint32_t fill = 4u * 5u * (uint32_t)g->ctx->n_cu;
-    // (a program with a noise node lists every chunk for the general class and runs in k_sdf_eval<0, true> alone)
-    const bool merge01 = !noise && known && g->eval_len[0] && g->eval_len[1] && (g->eval_len[0] < fill || g->eval_len[1] < fill);
-    const bool launch2 = !noise && !merge01 && !(known && g->eval_len[0] == 0u);            // k_sdf_eval<2>: the one-level class
-    const bool launch1 = !noise && (merge01 || !(known && g->eval_len[1] == 0u));           // k_sdf_eval<1>: the two-level class (or both)
-    const bool launch0 = (noise || stack_size >= 3u) && !(known && g->eval_len[2] == 0u);   // k_sdf_eval<0>: the general class
-    // Sample-ahead: this stage's pre-pass may have run already, behind the evaluator of the step before (see below); the stage then starts at
-    // its first evaluator launch, which commits the parked records and hosts the presets. Only with an evaluator launch to host them.
-    const bool ahead_fits = resident_program && fused_super && (launch0 || launch1 || launch2);
-    bool consume = resident_program && g->ahead_pending != 0;
-    if (consume && !ahead_fits) {
-        int rc_c = ivx_sampler_ahead_cancel(g);
-        if (rc_c) return rc_c;
-        consume = false;
-    }
+}
+
+int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, uint32_t n_nodes, uint32_t stack_size, const uint32_t shape[3],
+                          const float shifted_center[3], uint8_t voxel_type, uint32_t preset_groups, bool resident_program, bool noise, bool ahead_unordered_ok) {
+    ivx_sampler& s = g->smp;
+    SampleParams p = sample_params(g, shape, shifted_center, n_nodes, stack_size, voxel_type);
+    int rc;
+    if ((rc = check_stack(stack_size)) || (rc = allow_stack_lds(noise, stack_size)) || (rc = ivx_sampler_buffers(g))) return rc;
     const bool eval_dirty = (g->scratch_dirty & IVX_SCRATCH_EVAL) != 0u;
+    const SamplePlan pl = sample_plan(SamplePlanIn{n_nodes, stack_size, noise, resident_program, s.lens.valid != 0, {s.lens.len[0], s.lens.len[1], s.lens.len[2]}, g->n_chunks,
+                                                   {g->cc[0], g->cc[1], g->cc[2]}, (uint32_t)g->ctx->n_cu, eval_dirty, preset_groups, s.ahead.on != 0,
+                                                   s.ahead.state == AHEAD_PENDING});
     static const bool ahead_trace = getenv("IVX_AHEAD_TRACE") != nullptr;  // (developer aid: what every sample stage did about its pre-pass)
-    if (ahead_trace)
+    if (ahead_trace) {
+        uint32_t modes = 0;  // bit m: k_sdf_eval<m> is launched
+        for (uint32_t i = 0; i < pl.n_launches; ++i) modes |= 1u << pl.launch[i].mode;
         fprintf(stderr, "[ivx sample] grid %p: resident %d ahead_on %d pending %d fits %d (known %d launches %d%d%d) unordered_ok %d -> %s\n", (void*)g, (int)resident_program,
-                g->ahead_on, g->ahead_pending, (int)ahead_fits, (int)known, (int)launch2, (int)launch1, (int)launch0, g->ahead_unordered_ok, consume ? "consume" : "own pre-pass");
-    if (consume) {
-        std::swap(g->samp_len, g->samp_len_alt);
-        void* t_ops = g->samp_ops;
-        g->samp_ops = g->samp_ops_alt;
-        g->samp_ops_alt = t_ops;
-        g->alt_eval_dirty = eval_dirty ? 1 : 0;  // (the set that steps back: its counters are zero if a derive sweep rolled them over)
-        g->ahead_pending = 0;
-        // (normally long over — it was enqueued a step ago —, and then the stream need not hear of it: a wait is a packet on the queue)
-        if (hipEventQuery(g->ahead_done) != hipSuccess) IVX_HIP_CHECK(hipStreamWaitEvent(g->ctx->stream, g->ahead_done, 0));
+                s.ahead.on, (int)(s.ahead.state == AHEAD_PENDING), (int)(resident_program && pl.fused_super && pl.n_launches), (int)(resident_program && s.lens.valid),
+                (int)(modes >> 2 & 1u), (int)(modes >> 1 & 1u), (int)(modes & 1u), (int)ahead_unordered_ok, pl.consume ? "consume" : "own pre-pass");
     }
-    uint2* ops = reinterpret_cast<uint2*>(g->samp_ops);
-    uint32_t* eval_count = g->samp_len + g->n_chunks;
-    uint32_t* eval_list = eval_count + 16;
-    const uint32_t host_presets = preset_groups & ~IVX_SCRATCH_EVAL;  // what the stage's first kernel presets for the later stages
-    if (!consume) {
-        uint32_t super_presets = fused_super ? 0u : preset_groups;
-        const uint32_t prepass_presets = fused_super ? host_presets : 0u;
-        if (eval_dirty && !(super_presets & IVX_SCRATCH_EVAL)) IVX_HIP_CHECK(ivx_memset_async(eval_count, 0, 8 * sizeof(uint32_t), g->ctx->stream));
-        if (!eval_dirty) super_presets &= ~IVX_SCRATCH_EVAL;
+    if (pl.cancel && (rc = ivx_sampler_ahead_cancel(g))) return rc;
+    if (pl.consume) {
+        ahead_consume(s, eval_dirty);
+        // (normally long over — it was enqueued a step ago —, and then the stream need not hear of it: a wait is a packet on the queue)
+        if (hipEventQuery(s.ahead.done) != hipSuccess) IVX_HIP_CHECK(ivx_stream_wait_event(g->ctx->stream, s.ahead.done));
+    } else {
+        if (pl.clear_counters) IVX_HIP_CHECK(ivx_memset_async(ivx_eval_count(g), 0, 8 * sizeof(uint32_t), g->ctx->stream));
         uint2* super_skip = nullptr;
-        if (!fused_super) {
-            const size_t need = (((size_t)sx * sy * sz * words + 1u) & ~(size_t)1u) + (size_t)sx * sy * sz * words * 64u;  // far bits + a uint2 per node
-            if (need > g->samp_super_words) {
-                IVX_HIP_CHECK(ivx_stream_sync(g->ctx->stream));
-                if (g->samp_super) (void)hipFree(g->samp_super);
-                g->samp_super = nullptr;
-                g->samp_super_words = 0;
-                IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->samp_super), need * sizeof(uint32_t)));
-                g->samp_super_words = need;
-            }
-            super_skip = reinterpret_cast<uint2*>(g->samp_super + (((size_t)sx * sy * sz * words + 1u) & ~(size_t)1u));
+        if (!pl.fused_super) {
+            const size_t entries = (size_t)pl.sb.blocks() * pl.sb.words, bits = (entries + 1u) & ~(size_t)1u;
+            if ((rc = super_table_reserve(g, bits + entries * 64u))) return rc;  // far bits + a uint2 per node
+            super_skip = reinterpret_cast<uint2*>(s.super.bits + bits);
             p.tick = g->timing.take(ivx_many_recording());
-            IVX_KLAUNCH(k_sdf_super, dim3(sx * sy * sz), dim3(64), words * sizeof(uint32_t), g->ctx->stream, p, d_nodes, g->samp_super, super_skip, words, sy, sz,
-                               ivx_preset_args(g, super_presets));
+            IVX_KLAUNCH(k_sdf_super, dim3(pl.sb.blocks()), dim3(64), pl.sb.words * sizeof(uint32_t), g->ctx->stream, p, d_nodes, s.super.bits, super_skip, pl.sb.words,
+                        pl.sb.sy, pl.sb.sz, ivx_preset_args(g, pl.super_presets));
         }
         p.tick = g->timing.take(ivx_many_recording());
-        if (noise)
-            IVX_KLAUNCH(k_sdf_prepass<true>, dim3(sx * sy * sz), dim3(PRE_T * PRE_WAVES), 0, g->ctx->stream, p, d_nodes, g->samp_len, ops, eval_count, eval_list,
-                               g->n_chunks, g->info, g->samp_super, super_skip, words, sy, sz, sx * sy * sz, fused_super ? 1u : 0u, 0u, ivx_preset_args(g, prepass_presets));
-        else
-            IVX_KLAUNCH(k_sdf_prepass<false>, dim3(sx * sy * sz), dim3(PRE_T * PRE_WAVES), 0, g->ctx->stream, p, d_nodes, g->samp_len, ops, eval_count, eval_list,
-                               g->n_chunks, g->info, g->samp_super, super_skip, words, sy, sz, sx * sy * sz, fused_super ? 1u : 0u, 0u, ivx_preset_args(g, prepass_presets));
+        launch_prepass(g, g->ctx->stream, noise, pl.sb.blocks(), p, d_nodes, s.set[s.cur], g->info, s.super.bits, super_skip, pl.sb, pl.fused_super, false,
+                       pl.prepass_presets);
     }
     g->scratch_dirty = (g->scratch_dirty & ~preset_groups) | IVX_SCRATCH_EVAL;
     g->planes_compact = 1;
-    {
-        // (grids: a whole number of list entries per workgroup once the lists' lengths are known — a launch's last wave of workgroups costs as
-        // much as a full one, see ivx_launch_derive)
-        auto fit = [&](uint32_t n) {
-            const uint32_t cap = g->n_chunks < 16384u ? g->n_chunks : 16384u;  // (measured on 512^3: 4 096 and 32 768 are both slower on the all-surface grid)
-            if (!known || n == 0u) return cap;
-            const uint32_t each = (n + cap - 1u) / cap;
-            return (n + each - 1u) / each;
-        };
-        // (consume: the first launch commits the shadow records and hosts the presets)
-        const ivx_chunk_info* shadow = consume ? g->info_shadow + (size_t)g->shadow_sel * g->n_chunks : nullptr;
-        const ivx_roles::PresetArgs no_presets = ivx_preset_args(g, 0u), first_presets = ivx_preset_args(g, consume ? host_presets : 0u);
-        auto take_shadow = [&]() {
-            const ivx_chunk_info* s_ = shadow;
-            shadow = nullptr;
-            return s_;
-        };
-        uint32_t* const list0 = eval_list;
-        uint32_t* const list1 = eval_list + (size_t)g->n_chunks;
-        if (launch2) {
-            // one level + 64 words of scratch: 16 640 bytes = 13 LDS granules, eight workgroups per CU (the waves a SIMD holds)
-            const uint32_t scratch_off = IVX_CHUNK_VOXELS;
-            const ivx_chunk_info* sh = take_shadow();
-            p.tick = g->timing.take(ivx_many_recording());
-            IVX_KLAUNCH(k_sdf_eval<2>, dim3(fit(g->eval_len[0])), dim3(256), (size_t)(scratch_off + 64u) * sizeof(float), g->ctx->stream, p, eval_count + 0, list0,
-                               eval_count + 3, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
-                               sh, g->n_chunks, sh ? first_presets : no_presets);
-        }
-        if (launch1) {
-            // two levels, the second one 15 rows long + 64 words of scratch: 32 000 bytes = 25 LDS granules, five workgroups per CU
-            const uint32_t scratch_off = IVX_CHUNK_VOXELS + 15u * 256u;
-            const ivx_chunk_info* sh = take_shadow();
-            p.tick = g->timing.take(ivx_many_recording());
-            if (merge01)
-                IVX_KLAUNCH(k_sdf_eval<1>, dim3(fit(g->eval_len[0] + g->eval_len[1])), dim3(256), (size_t)(scratch_off + 64u) * sizeof(float), g->ctx->stream, p, eval_count + 0, list0,
-                                   eval_count + 3, eval_count + 1, list1, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
-                                   sh, g->n_chunks, sh ? first_presets : no_presets);
-            else
-                IVX_KLAUNCH(k_sdf_eval<1>, dim3(fit(g->eval_len[1])), dim3(256), (size_t)(scratch_off + 64u) * sizeof(float), g->ctx->stream, p, eval_count + 1, list1,
-                                   nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info, g->chunk_signs, g->kface,
-                                   sh, g->n_chunks, sh ? first_presets : no_presets);
-        }
-        if (launch0) {
-            // (the scratch words are the last sixteen of the stack: rows 15 of the last level's threads 240..255, dead when they are used
-            // — the votes — and never used as published test voxels, which only the trimmed launch has)
-            const uint32_t lv = stack_size ? stack_size : 1u;
-            const uint32_t scratch_off = lv * IVX_CHUNK_VOXELS - 16u;
-            const ivx_chunk_info* sh = take_shadow();
-            p.tick = g->timing.take(ivx_many_recording());
-            if (noise)
-                IVX_KLAUNCH((k_sdf_eval<0, true>), dim3(fit(g->eval_len[2])), dim3(256), (size_t)lv * IVX_CHUNK_VOXELS * sizeof(float), g->ctx->stream, p, eval_count + 2,
-                                   eval_list + 2 * (size_t)g->n_chunks, nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info,
-                                   g->chunk_signs, g->kface, sh, g->n_chunks, sh ? first_presets : no_presets);
-            else
-                IVX_KLAUNCH(k_sdf_eval<0>, dim3(fit(g->eval_len[2])), dim3(256), (size_t)lv * IVX_CHUNK_VOXELS * sizeof(float), g->ctx->stream, p, eval_count + 2,
-                                   eval_list + 2 * (size_t)g->n_chunks, nullptr, nullptr, nullptr, g->n_chunks, scratch_off, g->samp_len, ops, d_nodes, g->sdf, g->type, g->info,
-                                   g->chunk_signs, g->kface, sh, g->n_chunks, sh ? first_presets : no_presets);
-        }
+    for (uint32_t i = 0; i < pl.n_launches; ++i) {
+        const bool commits = pl.launch[i].commits_shadow;
+        launch_eval(g, pl.launch[i], p, d_nodes, commits ? s.ahead.info_shadow + (size_t)s.ahead.shadow_sel * g->n_chunks : nullptr, commits ? pl.first_presets : 0u);
     }
-    const bool type_noise = g->vt_n >= 2u;
+    const bool type_noise = s.vt.n >= 2u;
     if (type_noise) {
         // behind the evaluator launches: every chunk record is in place (those a pre-pass that ran ahead parked in the shadow array were
         // committed by the first of them)
         TypeNoiseParams tp;
-        tp.cy = g->cc[1], tp.cz = g->cc[2], tp.x_off = g->x_off, tp.n = g->vt_n;
+        tp.cy = g->cc[1], tp.cz = g->cc[2], tp.x_off = g->x_off, tp.n = s.vt.n;
         for (int d = 0; d < 3; ++d) tp.shifted_center[d] = shifted_center[d];
-        tp.noise_freq = g->vt_noise_freq, tp.type_freq = g->vt_type_freq, tp.seed = g->vt_seed;
+        tp.noise_freq = s.vt.noise_freq, tp.type_freq = s.vt.type_freq, tp.seed = s.vt.seed;
         IVX_KLAUNCH(k_voxel_type_noise, dim3(g->n_chunks), dim3(256), 0, g->ctx->stream, tp, g->sdf, g->type, g->info, g->chunk_signs, g->kface);
     }
     IVX_HIP_CHECK(hipGetLastError());
-    g->ahead_wanted = (g->ahead_on && ahead_fits) ? 1 : 0;
+    ahead_want(s, pl.ahead_wanted);
     // (everything enqueued before this call has been collected: the sampler's other set of buffers is idle and the pre-pass needs no place in
     // the stream's order; else the step puts it behind its last big launch)
-    if (g->ahead_wanted && g->ahead_unordered_ok) {
-        const int rc_a = ivx_sampler_launch_ahead(g, false);
-        if (rc_a) return rc_a;
-    }
+    if (ahead_unordered_ok && (rc = ivx_sampler_launch_ahead(g, false))) return rc;
     // every chunk that has planes now has its sign rows and k-face bytes too, and one type throughout (SameVoxelTypeGenerator, or noise
     // types of one type): the derive sweep may work from those (until something else rewrites voxels: ivx_planes_touched). With noise types
     // of two or more the types are in the type plane alone, and the sweep and the mesher run their general forms.
     g->signs_current = type_noise ? 0 : 1;
-    g->signs_type = voxel_type;
+    g->signs_type = (uint8_t)p.voxel_type;
     return IVX_OK;
 }
 
@@ -1946,52 +1928,66 @@ int ivx_launch_sdf_sample(ivx_grid* g, const ivx_sdf_processed_node* d_nodes, ui
 // per super-block or per CU alike; a block per four CUs no longer finishes inside the step.
 // `behind_stream`: the launch waits for what the context's stream holds now (a caller that has NOT collected its earlier steps: the other
 // set may still be read). A step that never comes costs one unused pre-pass; ivx_grid_set_sdf_program and ivx_grid_destroy wait for one
-// that is under way.
+// that is under way. Nothing happens unless the last sample stage left the wish for it (ahead_take_wish).
 int ivx_sampler_launch_ahead(ivx_grid* g, bool behind_stream) {
-    if (!g->ahead_wanted) return IVX_OK;
-    g->ahead_wanted = 0;
-    if (g->ahead_pending) return IVX_OK;
+    ivx_sampler& s = g->smp;
+    if (!ahead_take_wish(s)) return IVX_OK;
     hipStream_t aux;
     int rc = ivx_aux_stream(g->ctx, &aux);
     if (rc) return rc;
-    if ((rc = ivx_sampler_ahead_buffers(g, aux))) return rc;
-    SampleParams p;
-    p.cx = g->cc[0];
-    p.cy = g->cc[1];
-    p.cz = g->cc[2];
-    p.x_off = g->x_off;
-    for (int d = 0; d < 3; ++d) {
-        p.shape[d] = g->prog_shape[d];
-        p.shifted_center[d] = g->prog_center[d];
-    }
-    p.n_nodes = g->prog_n;
-    p.stack_size = g->prog_stack;
-    p.tick = nullptr;  // (a launch on the second stream is no part of a timed slot)
-#ifdef IVX_WG_TRACE
-    p.trace = reinterpret_cast<unsigned long long*>(g->chunk_moments);
-#endif
-    p.voxel_type = g->vt_n ? 0u : (uint32_t)g->prog_type;
-    const uint32_t words = (g->prog_n + 31u) / 32u > 0u ? (g->prog_n + 31u) / 32u : 1u;
-    const uint32_t sx = (g->cc[0] + SUPER - 1) / SUPER, sy = (g->cc[1] + SUPER - 1) / SUPER, sz = (g->cc[2] + SUPER - 1) / SUPER;
+    if ((rc = ahead_buffers(g, aux))) return rc;
+    const SampleParams p = sample_params(g, s.prog.shape, s.prog.center, s.prog.n, s.prog.stack, s.prog.type);
+    const SuperGrid sb = super_grid(s.prog.n, g->cc);
     if (behind_stream) {
-        IVX_HIP_CHECK(hipEventRecord(g->ahead_go, g->ctx->stream));
-        IVX_HIP_CHECK(hipStreamWaitEvent(aux, g->ahead_go, 0));
+        IVX_HIP_CHECK(ivx_event_record(s.ahead.go, g->ctx->stream));
+        IVX_HIP_CHECK(ivx_stream_wait_event(aux, s.ahead.go));
     }
-    uint32_t* alt_count = g->samp_len_alt + g->n_chunks;
-    if (g->alt_eval_dirty) IVX_HIP_CHECK(hipMemsetAsync(alt_count, 0, 8 * sizeof(uint32_t), aux));
-    g->alt_eval_dirty = 0;
+    const ivx_sampler_set& other = s.set[s.cur ^ 1];
+    if (s.ahead.other_dirty) IVX_HIP_CHECK(ivx_memset_async(other.len + g->n_chunks, 0, 8 * sizeof(uint32_t), aux));
+    s.ahead.other_dirty = 0;
     static const uint32_t blocks_env = [] {
         const char* e = getenv("IVX_AHEAD_BLOCKS");
         return e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
     }();
-    const uint32_t n_sb = sx * sy * sz, blocks = std::min(n_sb, blocks_env ? blocks_env : 2u * (uint32_t)g->ctx->n_cu);
-    g->shadow_sel ^= 1;
-    hipLaunchKernelGGL(g->prog_noise ? k_sdf_prepass<true> : k_sdf_prepass<false>, dim3(blocks), dim3(PRE_T * PRE_WAVES), 0, aux, p, g->prog_nodes, g->samp_len_alt, reinterpret_cast<uint2*>(g->samp_ops_alt),
-                       alt_count, alt_count + 16, g->n_chunks, g->info_shadow + (size_t)g->shadow_sel * g->n_chunks, nullptr, nullptr, words, sy, sz, n_sb, 1u, 1u,
-                       ivx_preset_args(g, 0u));
+    const uint32_t blocks = std::min(sb.blocks(), blocks_env ? blocks_env : 2u * (uint32_t)g->ctx->n_cu);
+    s.ahead.shadow_sel ^= 1;
+    launch_prepass(g, aux, s.prog.noise != 0, blocks, p, s.prog.nodes, other, s.ahead.info_shadow + (size_t)s.ahead.shadow_sel * g->n_chunks, nullptr, nullptr, sb, true, true, 0u);
     IVX_HIP_CHECK(hipGetLastError());
-    IVX_HIP_CHECK(hipEventRecord(g->ahead_done, aux));
-    g->ahead_pending = 1;
+    IVX_HIP_CHECK(ivx_event_record(s.ahead.done, aux));
+    ahead_launched(s);
+    return IVX_OK;
+}
+
+// developer export (tests without a GPU): sample_plan and sample-ahead's transitions over plain words, see include/impact_voxel_hip.h
+int ivx_sampler_plan(const uint32_t in[IVX_SAMPLER_PLAN_IN_WORDS], uint32_t out[IVX_SAMPLER_PLAN_OUT_WORDS]) {
+    IVX_REQUIRE(in && out, IVX_ERR_INVALID, "ivx_sampler_plan: null argument");
+    IVX_REQUIRE(in[16] <= (uint32_t)AHEAD_PENDING, IVX_ERR_INVALID, "ivx_sampler_plan: sample-ahead state %u (0 idle, 1 wanted, 2 pending)", in[16]);
+    if (int rc = check_stack(in[1])) return rc;
+    const SamplePlan pl = sample_plan(SamplePlanIn{in[0], in[1], in[2] != 0u, in[3] != 0u, in[4] != 0u, {in[5], in[6], in[7]}, in[8], {in[9], in[10], in[11]}, in[12],
+                                                   in[13] != 0u, in[14], in[15] != 0u, in[16] == (uint32_t)AHEAD_PENDING});
+    const uint32_t head[13] = {pl.sb.words, pl.fused_super, pl.sb.sx, pl.sb.sy, pl.sb.sz, pl.consume, pl.cancel, pl.super_presets, pl.prepass_presets, pl.first_presets,
+                               pl.clear_counters, pl.ahead_wanted, pl.n_launches};
+    memset(out, 0, IVX_SAMPLER_PLAN_OUT_WORDS * sizeof(uint32_t));
+    memcpy(out, head, sizeof(head));
+    for (uint32_t i = 0; i < pl.n_launches; ++i) {
+        const EvalLaunch& e = pl.launch[i];
+        const uint32_t w[9] = {e.mode, e.noise, e.grid, e.lds_bytes, e.scratch_off, e.list, e.long_count, e.first, e.commits_shadow};
+        memcpy(out + 13 + 10 * i, w, sizeof(w));
+    }
+    // the state through the stage as ivx_launch_sdf_sample drives it, then through a step that acts on the wish under the LATER setting and program
+    ivx_sampler s{};
+    s.ahead.on = in[15] != 0u, s.ahead.state = (ivx_ahead_state)in[16];
+    if (pl.cancel) (void)ahead_cancel(s);
+    if (pl.consume) ahead_consume(s, in[13] != 0u);
+    ahead_want(s, pl.ahead_wanted);
+    out[43] = (uint32_t)s.ahead.state;
+    s.ahead.on = in[17] != 0u, s.prog.n = in[18];
+    out[45] = ahead_take_wish(s);
+    out[44] = (uint32_t)s.ahead.state;
+    // ... and through a cancel instead of the stage
+    s.ahead.state = (ivx_ahead_state)in[16];
+    out[47] = ahead_cancel(s);
+    out[46] = (uint32_t)s.ahead.state;
     return IVX_OK;
 }
 

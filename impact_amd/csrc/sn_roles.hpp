@@ -385,62 +385,6 @@ __device__ __forceinline__ void upper_finish(const GridView& g, int ci, int cj, 
     if (hz && (U.k[2] & 0xFFu) == KIND_NONUNIFORM) upper[2] -= 1;
 }
 
-// Walks the active list (the chunks k_chunk_pre settled have no mesh and got their zero counts there).
-__device__ __forceinline__ void role_sn_count(uint32_t bid, uint32_t nb, SnParams p, uint32_t* __restrict__ counts, uint32_t* __restrict__ group_sums,
-
-                                                  const uint32_t* __restrict__ work_counts, const uint32_t* __restrict__ active_list) {
-    __shared__ uint32_t s_neg[NROWS];
-    __shared__ uint32_t s_acc[2];
-    const GridView& g = p.g;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t n_active = work_counts[0];
-    for (uint32_t li = ivx_xcd_remap(bid, nb); li < n_active; li += nb) {
-    __syncthreads();  // the previous chunk's LDS use is over
-    const uint32_t entry = active_list[li];
-    const uint32_t chunk = IVX_LIST_CHUNK(entry);
-    if (!IVX_LIST_EXPOSED(entry)) {
-        if (tid == 0) {
-            counts[2 * chunk] = 0;
-            counts[2 * chunk + 1] = 0;
-        }
-        continue;
-    }
-    const int ck = chunk % g.cz, cj = (chunk / g.cz) % g.cy, ci = chunk / (g.cz * g.cy);
-    if (tid < 2) s_acc[tid] = 0;
-    UpperLoads ul;
-    upper_issue(g, ci, cj, ck, ul);
-    load_tile(g, ci, cj, ck, nullptr, nullptr, s_neg, tid);
-    int upper[3];
-    upper_finish(g, ci, cj, ck, ul, upper);
-    __syncthreads();
-    uint32_t nv = 0, nq = 0;
-    for (int cr = tid; cr < NCROWS; cr += 256) {
-        uint32_t vb, qx, qy, qz;
-        cube_row_bits(s_neg, cr / 17, cr % 17, upper, vb, qx, qy, qz);
-        nv += __popc(vb);
-        nq += __popc(qx) + __popc(qy) + __popc(qz);
-    }
-    {  // wave totals in registers, one LDS add per wave (same-address LDS atomics of many lanes are very slow)
-        const uint32_t wv = ivx_wave_sum(nv), wq = ivx_wave_sum(nq);
-        if ((tid & 63u) == 0) {
-            atomicAdd(&s_acc[0], wv);
-            atomicAdd(&s_acc[1], wq);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        counts[2 * chunk] = s_acc[0];
-        counts[2 * chunk + 1] = s_acc[1] * 6u;
-        if (s_acc[1]) {  // first level of the scan over chunks: totals per group of 256 chunks (vertices, indices, submeshes)
-            uint32_t* gs = group_sums + 3 * (chunk >> 8);
-            atomicAdd(gs, s_acc[0]);
-            atomicAdd(gs + 1, s_acc[1] * 6u);
-            atomicAdd(gs + 2, 1u);
-        }
-    }
-    }
-}
-
 // After an edit: which chunks of the touched box grown by one chunk each way (the box the derive sweep has just gone over) have a mesh to
 // renew — handle_chunk_voxels_modified (object/intersection.rs:560-598): a touched chunk, and a neighbour when the touched voxel range of
 // the chunk comes within two voxels of the face they share —, and what their meshes need now (the count pass of the remesh for just these

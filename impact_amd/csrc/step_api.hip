@@ -80,10 +80,10 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
     IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_voxel_step_enqueue: null grid");
     const bool front = (part & 1u) != 0u, back = (part & 2u) != 0u;
     ivx_many_other_context other_(g->ctx);
-    IVX_REQUIRE(!(stages & IVX_STAGE_SAMPLE) || g->prog_n > 0, IVX_ERR_STATE, "ivx_voxel_step: no SDF program resident (ivx_grid_set_sdf_program)");
+    IVX_REQUIRE(!(stages & IVX_STAGE_SAMPLE) || g->smp.prog.n > 0, IVX_ERR_STATE, "ivx_voxel_step: no SDF program resident (ivx_grid_set_sdf_program)");
     IVX_REQUIRE(!(stages & IVX_STAGE_INERTIA) || g->has_dens, IVX_ERR_STATE, "ivx_voxel_step: no densities resident (ivx_grid_set_densities)");
     hipStream_t s = g->ctx->stream;
-    g->ahead_unordered_ok = g->pending_stages == 0;  // (sample-ahead: whatever was enqueued before has been collected)
+    const bool ahead_unordered_ok = g->pending_stages == 0;  // (sample-ahead: whatever was enqueued before has been collected)
     // stages enqueued after a record change the step's results: the block the record role wrote is stale (this call sets the flag again
     // further down when it carries the slab record itself)
     g->results_in_block = 0;
@@ -128,17 +128,18 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
     if ((rc = clk.begin(rt, ivx_stage_call{part, g_stage_timing_events, slab_record != nullptr, ivx_step_assign_fits(g), standalone_first, ivx_many_recording()}))) return rc;
     if (front && (stages & IVX_STAGE_SAMPLE)) {
         if ((rc = clk.open(rt, 0))) return rc;
-        if ((rc = ivx_launch_sdf_sample(g, g->prog_nodes, g->prog_n, g->prog_stack, g->prog_shape, g->prog_center, g->prog_type, preset_in_sample, true,
-                                        g->prog_noise != 0))) return rc;
+        const auto& prog = g->smp.prog;
+        if ((rc = ivx_launch_sdf_sample(g, prog.nodes, prog.n, prog.stack, prog.shape, prog.center, prog.type, preset_in_sample, true, prog.noise != 0, ahead_unordered_ok)))
+            return rc;
         if ((rc = clk.close(rt, 0))) return rc;
-        g->eval_len_pending = 1;  // (the list lengths reach the result block once a derive sweep has rolled the counters over)
+        g->smp.lens.pending = 1;  // (the list lengths reach the result block once a derive sweep has rolled the counters over)
         ivx_voxels_replaced(g);
     }
     if (front && (stages & IVX_STAGE_DERIVE)) {
         if ((rc = clk.open(rt, 1))) return rc;
         if ((rc = ivx_launch_derive(g, fused_parts, preset_in_derive))) return rc;
         if ((rc = clk.close(rt, 1))) return rc;
-        if (g->eval_len_pending == 1) g->eval_len_pending = 2;
+        if (g->smp.lens.pending == 1) g->smp.lens.pending = 2;
     }
     if (post) {
         // stages that were not swept inside k_derive get their stand-alone per-chunk kernels first (a call without the derive stage)
@@ -175,7 +176,7 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
             if ((rc = clk.close(rt, 4))) return rc;
         }
         // (sample-ahead: the next sample stage's pre-pass goes behind the step's last big launch, beside the small ones that follow)
-        if (!g->ahead_unordered_ok && (rc = ivx_sampler_launch_ahead(g, true))) return rc;
+        if (!ahead_unordered_ok && (rc = ivx_sampler_launch_ahead(g, true))) return rc;
         if ((post & IVX_STAGE_REGIONS) && fused_assign) {
             if ((rc = clk.open(rt, 5))) return rc;
             if ((rc = ivx_launch_step_assign(g, (post & IVX_STAGE_REMESH) != 0))) return rc;
@@ -187,7 +188,7 @@ static int step_enqueue(ivx_grid* g, uint32_t stages, const uint16_t* slab_nbr_i
         }
         if (post & IVX_STAGE_REGIONS) g->scratch_dirty |= IVX_SCRATCH_REGIONS;
     }
-    if (back && (rc = ivx_sampler_launch_ahead(g, !g->ahead_unordered_ok))) return rc;  // (a call without the stages behind the derive sweep)
+    if (back && (rc = ivx_sampler_launch_ahead(g, !ahead_unordered_ok))) return rc;  // (a call without the stages behind the derive sweep)
     g->pending_stages |= stages;
     return IVX_OK;
 }
@@ -223,17 +224,6 @@ int ivx_slab_remesh_enqueue(ivx_grid* g, const void* neighbour_face_ids, void* d
     }
     g->pairs_enqueued = 0;
     return step_enqueue(g, IVX_STAGE_REMESH, static_cast<const uint16_t*>(neighbour_face_ids), device_record);
-}
-
-// Sample-ahead: with `on`, every sample stage under the resident program also enqueues the NEXT sample stage's pre-pass — on the context's
-// second stream, behind its own evaluator —, and the next sample stage starts at its evaluator. For callers that sample the same program
-// step after step (the bench's headline step); the results are the same bytes either way. Off (the default): the pre-pass is the stage's
-// first kernel. Turning it off drops a pre-pass that is under way.
-int ivx_grid_set_sample_ahead(ivx_grid* g, int on) {
-    IVX_REQUIRE(g, IVX_ERR_INVALID, "ivx_grid_set_sample_ahead: null grid");
-    g->ahead_on = on ? 1 : 0;
-    if (!on) return ivx_sampler_ahead_cancel(g);
-    return IVX_OK;
 }
 
 int ivx_grid_set_stage_timing(ivx_grid* g, uint32_t slot_mask) {
@@ -312,11 +302,12 @@ int ivx_voxel_step_collect(ivx_grid* g, ivx_step_result* out) {
     }
     const uint32_t* sc = g->result_host;
     if (sc[IVX_RB_ACTIVE]) g->last_active = sc[IVX_RB_ACTIVE];
-    if (g->eval_len_pending == 2 && g->samp_len) {  // a sample stage and a derive sweep behind it have run under the resident program
-        for (int c = 0; c < 3; ++c) g->eval_len[c] = sc[IVX_RB_EVAL_LEN + c];
-        g->eval_len_valid = 1;
+    auto& lens = g->smp.lens;
+    if (lens.pending == 2 && ivx_eval_count(g)) {  // a sample stage and a derive sweep behind it have run under the resident program
+        for (int c = 0; c < 3; ++c) lens.len[c] = sc[IVX_RB_EVAL_LEN + c];
+        lens.valid = 1;
     }
-    g->eval_len_pending = 0;
+    lens.pending = 0;
     if (stages & IVX_STAGE_REGIONS) {
         IVX_REQUIRE((sc[IVX_RB_FLAGS] & IVX_RB_FLAG_LOCAL_REGIONS) == 0, IVX_ERR_CAPACITY, "ivx_voxel_step: a chunk has more than 254 local regions");
         IVX_REQUIRE((sc[IVX_RB_FLAGS] & IVX_RB_FLAG_MERGE_GAVE_UP) == 0, IVX_ERR_HIP, "ivx_voxel_step: the region merge gave up waiting for the numbering of the multi-region chunks (k_step_post2)");

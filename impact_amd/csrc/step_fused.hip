@@ -381,7 +381,7 @@ static StepArgs make_args(ivx_grid* g) {
     a.partials = g->partials;
     a.moments_out = g->partials + g->partial_blocks * 10;
     a.host_block = g->result_host_dev;
-    a.eval_count = g->samp_len ? g->samp_len + g->n_chunks : nullptr;
+    a.eval_count = ivx_eval_count(g);
     return a;
 }
 

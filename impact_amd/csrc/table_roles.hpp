@@ -162,7 +162,7 @@ __device__ __forceinline__ void role_result_gather(const uint32_t* __restrict__ 
 
 // Preset of the scratch words a step's stages start from (what k_step_preset did in a launch of its own), as a role of the
 // step's first kernel: `gid` = global thread index of that launch (it must have at least max(28, n_sn) threads).
-// n_sn = the group totals proper (3 per group of 256 chunks).
+// n_sn = the group totals proper (IVX_SN_GROUP_WORDS per group of 256 chunks).
 struct PresetArgs {
     uint32_t groups;        // IVX_SCRATCH_* bits to preset
     uint32_t* rscalar;      // [0..16) region scalars

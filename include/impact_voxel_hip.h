@@ -545,6 +545,20 @@ int ivx_noise_eval(ivx_ctx* ctx, int which, const float* params, const float* po
  * same function. */
 int ivx_voxel_types_eval(ivx_ctx* ctx, uint32_t n_voxel_types, float noise_frequency, float voxel_type_frequency, uint32_t seed,
                          const float chunk_origin[3], uint8_t out[4096]);
+/* Developer export (tests): what a sample stage would launch, decided on the host alone — no device is touched, no context needed.
+ * in[0] nodes, [1] stack size, [2] the program has a noise node, [3] it is the grid's resident program, [4] the list lengths are known,
+ * [5..8) the lengths, [8] chunks, [9..12) chunk counts, [12] compute units, [13] the list counters are dirty, [14] scratch groups to preset,
+ * [15] sample-ahead on, [16] its state (0 idle, 1 wanted, 2 pending), [17], [18] sample-ahead on and the resident program's nodes when a
+ * later step acts on the wish.
+ * out[0] program words, [1] super-block tables made inside the pre-pass, [2..5) super-blocks per axis, [5] the pending pre-pass is consumed,
+ * [6] ... is cancelled, [7..10) groups preset by the super-block launch, the pre-pass, the first evaluator launch, [10] counters cleared by a
+ * memset, [11] the next pre-pass may run ahead, [12] evaluator launches n <= 3; launch i at [13 + 10 i]: class (2 one-level, 1 two-level,
+ * 0 general), noise form, grid, LDS bytes, scratch offset, list, with the long-entry split, with list 1 behind it, commits the shadow records.
+ * [43] state after the stage, [44] state after a step acted on the wish, [45] that step launches the pre-pass, [46] state after a cancel
+ * (from in[16]), [47] the cancel waits for a pre-pass. IVX_ERR_CAPACITY: the stack does not fit the LDS (as a sample call would report). */
+#define IVX_SAMPLER_PLAN_IN_WORDS 19
+#define IVX_SAMPLER_PLAN_OUT_WORDS 48
+int ivx_sampler_plan(const uint32_t in[IVX_SAMPLER_PLAN_IN_WORDS], uint32_t out[IVX_SAMPLER_PLAN_OUT_WORDS]);
 int ivx_slab_create(ivx_comm*, ivx_grid* slab_grid, int rank, ivx_slab** out);
 void ivx_slab_destroy(ivx_slab*);
 int ivx_slabs_step_enqueue(ivx_slab** slabs, size_t n);

@@ -213,6 +213,142 @@ def test_steps_enqueued_without_a_collect_in_between(ctx):
     obj.close()
 
 
+# ---- a 2 x 2 x 2-chunk grid whose setting and program change between steps, against a twin that never samples ahead --------------------
+SUPER_MAX_NODES = 2048  # (32 * SUPER_MAX_WORDS: beyond it k_sdf_super builds the far tables and no pre-pass runs ahead)
+
+
+def small_body():
+    """a ball with a smooth crater: 28^3 voxels"""
+    g = SDFGraph()
+    ball = g.add_node(SDFNode.new_sphere(13.0))
+    dent = g.add_node(SDFNode.new_translation(g.add_node(SDFNode.new_sphere(6.0)), (9.0, 4.0, -3.0)))
+    g.add_node(SDFNode.new_subtraction(ball, dent, 2.0))
+    return g
+
+
+def sphere_chain(n_nodes):
+    """small spheres on a 9^3 lattice under a left-deep chain of hard unions, 3 K - 1 nodes, padded by translations to exactly `n_nodes`: 28^3 voxels"""
+    k = (n_nodes + 1) // 3
+    pad = n_nodes - (3 * k - 1)
+    assert k <= 729 and 0 <= pad < 3
+    g = SDFGraph()
+    acc = None
+    for i in range(k):
+        s = g.add_node(SDFNode.new_sphere(1.0))
+        for _ in range(pad if i == 0 else 0):
+            s = g.add_node(SDFNode.new_translation(s, (0.0, 0.0, 0.0)))
+        s = g.add_node(SDFNode.new_translation(s, (3.0 * (i % 9) - 12.0, 3.0 * ((i // 9) % 9) - 12.0, 3.0 * (i // 81) - 12.0)))
+        acc = s if acc is None else g.add_node(SDFNode.new_union(acc, s, 0.0))
+    return g
+
+
+def everything(obj):
+    sdf, typ, flg, lab, info = obj.download()
+    return {"sdf": sdf, "type": typ, "flags": flg, "labels": lab, "info": info.view(np.uint8)}
+
+
+def assert_same_bytes(a, b, what):
+    ea, eb = everything(a), everything(b)
+    for k in ea:
+        np.testing.assert_array_equal(ea[k], eb[k], err_msg=f"{what}: {k}")
+
+
+def active_set_words(obj):
+    """the active set of the sampler's buffers (developer pointer 7): [n] program lengths, [16] list counters, [3 n] lists"""
+    import ctypes as C
+
+    lib = capi.lib()
+    lib.ivx_grid_device_ptr.restype = C.c_void_p
+    hip = C.CDLL("libamdhip64.so")
+    words = np.zeros(4 * obj.n_chunks + 16, dtype=np.uint32)
+    hip.hipDeviceSynchronize()
+    assert hip.hipMemcpy(words.ctypes.data_as(C.c_void_p), C.c_void_p(lib.ivx_grid_device_ptr(obj.h, 7)), words.nbytes, 2) == 0
+    return words
+
+
+def test_program_swapped_from_short_to_long_and_back(ctx):
+    """sample-ahead on: two steps of a short program (the second consumes), then one of 2049 nodes (the pre-pass under way is dropped, the stage
+    runs its own behind k_sdf_super, nothing runs ahead of the next), then the short one again (its pre-pass comes back): every step's
+    bytes and records are those of a twin with sample-ahead off, which are the oracle's"""
+    g_short, g_long = small_body(), sphere_chain(SUPER_MAX_NODES + 1)
+    gens = {"short": SDFVoxelGenerator(1.0, g_short, 0), "long": SDFVoxelGenerator(1.0, g_long, 0)}
+    assert len(gens["long"].sdf_generator.nodes) == SUPER_MAX_NODES + 1
+    assert tuple(gens["short"].chunk_counts()) == tuple(gens["long"].chunk_counts()) == (2, 2, 2)
+    oracles = {"short": oracle_of(g_short), "long": oracle_of(g_long)}
+    objs = []
+    for ahead in (True, False):
+        obj = VoxelObject(ctx, (2, 2, 2), 1.0)
+        obj.set_densities(np.ones(256, dtype=np.float32))
+        obj.set_sample_ahead(ahead)
+        objs.append(obj)
+    a, b = objs
+    for which in ("short", "long", "short"):
+        for obj in objs:
+            obj.set_sdf_program(gens[which])
+        for i in range(2):
+            ra, rb = a.step(capi.STAGE_ALL), b.step(capi.STAGE_ALL)
+            p = pu.step_parity(oracles[which], a, ra)
+            assert p["equal"], (which, i, p)
+            assert ra["mesh"] == rb["mesh"] and ra["region_count"] == rb["region_count"]
+            assert_same_bytes(a, b, (which, i))
+            clobber(a)
+            clobber(b)
+    a.close()
+    b.close()
+
+
+def test_sample_ahead_turned_off_and_on_between_steps(ctx):
+    """the setting changes between collected steps and between steps enqueued back to back: the bytes are the twin's that never samples ahead,
+    and a step behind set_sample_ahead(0) leaves the active set's counters and lists as its own pre-pass made them"""
+    graph = small_body()
+    o = oracle_of(graph)
+    _, a = resident_object(ctx, graph, True)
+    _, b = resident_object(ctx, graph, False)
+    assert a.chunk_counts == (2, 2, 2)
+    n = a.n_chunks
+
+    def both(what, settings, collect_each):
+        """one step per entry of `settings` (sample-ahead of `a` before the step; None: left as it is)"""
+        for on in settings:
+            if on is not None:
+                a.set_sample_ahead(on)
+            for obj in (a, b):
+                obj.step(capi.STAGE_ALL) if collect_each else obj.step_enqueue(capi.STAGE_ALL)
+        ra = a.step_collect().copy() if not collect_each else None
+        if not collect_each:
+            b.step_collect()
+            p = pu.step_parity(o, a, ra)
+            assert p["equal"], (what, p)
+        assert_same_bytes(a, b, what)
+
+    both("on, collected", [None, None], True)  # (the second consumes; a pre-pass is under way behind it)
+    both("off", [False], True)
+    wa, wb = active_set_words(a), active_set_words(b)
+    np.testing.assert_array_equal(wa[n:n + 16], wb[n:n + 16])  # live counters zero (rolled over by the derive sweep), their rolled copy this step's
+    assert not wa[n:n + 8].any() and wa[n + 8:n + 11].sum() > 0
+    np.testing.assert_array_equal(wa[:n], wb[:n])
+    for c in range(3):  # (the order within a list is the order the pre-pass's blocks came by)
+        cnt = int(wa[n + 8 + c])
+        seg = slice(n + 16 + c * n, n + 16 + c * n + cnt)
+        if c == 0:  # long entries from the front, short ones from the back
+            cnt_long = int(wa[n + 8 + 3])
+            np.testing.assert_array_equal(np.sort(wa[n + 16:n + 16 + cnt_long]), np.sort(wb[n + 16:n + 16 + cnt_long]))
+            np.testing.assert_array_equal(np.sort(wa[n + 16 + n - (cnt - cnt_long):n + 16 + n]), np.sort(wb[n + 16 + n - (cnt - cnt_long):n + 16 + n]))
+        else:
+            np.testing.assert_array_equal(np.sort(wa[seg]), np.sort(wb[seg]))
+    clobber(a), clobber(b)
+    both("on again, collected", [True, None], True)
+    clobber(a), clobber(b)
+    both("back to back", [None, None, None], False)
+    clobber(a), clobber(b)
+    both("off and on back to back", [None, False, True, None], False)
+    clobber(a), clobber(b)
+    both("off back to back, then collected", [False, None], False)
+    both("on after that", [True, None], True)
+    a.close()
+    b.close()
+
+
 def _poisoned_seeds():
     from test_gpu_random_sdf import WITNESSED
 

@@ -8,9 +8,11 @@
 
 The pair pass has a second form that leaves the same bytes: a linear hierarchy over the set (csrc/bvh.hip; hierarchy.rs in the reference), built
 on request (`BoundingVolumeSet.build_hierarchy`, `.hierarchy`, `.pairs_hierarchy`; `morton_key`, `hierarchy_host` and `node_info` on the host).
+So have the region queries (`.query_hierarchy`; `queries_hierarchy_host` and `query_skips_boxes` on the host), and the masks of either form
+become hit lists on the device (`.query_lists`). The flat forms are the default.
 
-The world boxes, the pairs, the masks and the tree stay in context-owned device buffers (`device_ptr`). Nothing here computes, and nothing falls back to
-the CPU.
+The world boxes, the pairs, the masks, the hit lists and the tree stay in context-owned device buffers (`device_ptr`). Nothing here computes,
+and nothing falls back to the CPU.
 """
 from __future__ import annotations
 
@@ -145,8 +147,29 @@ class BoundingVolumeSet:
         check(capi.lib().ivx_bv_queries(self._h, ptr(q) if q.size else None, q.size, ptr(masks) if masks.size else None, ptr(counts) if q.size else None))
         return masks, counts
 
+    def query_hierarchy(self, queries):
+        """`ivx_bv_queries_hierarchy` -> what `query` returns, found through the tree (`build_hierarchy` first)"""
+        q = query_array(queries)
+        words = (self.n + 63) // 64
+        masks, counts = np.zeros((q.size, words), dtype=np.uint64), np.zeros(q.size, dtype=np.uint32)
+        check(capi.lib().ivx_bv_queries_hierarchy(self._h, ptr(q) if q.size else None, q.size, ptr(masks) if masks.size else None, ptr(counts) if q.size else None))
+        return masks, counts
+
+    def query_lists(self, capacity: int | None = None):
+        """`ivx_bv_query_lists`: the hits of the last `query` / `query_hierarchy` as lists made on the device -> (offsets [n_queries + 1] uint32,
+        objects [offsets[-1]] uint32; query q's objects are objects[offsets[q]:offsets[q + 1]], ascending). `capacity` None: sized by a first call
+        that leaves the lists on the device only"""
+        found = C.c_size_t(0)
+        if capacity is None:
+            check(capi.lib().ivx_bv_query_lists(self._h, None, None, 0, C.byref(found)))
+            capacity = found.value
+        # (the call knows how many queries the context's last call had; an offset never reaches 2^32 - 1, so what it wrote can be told)
+        offsets, objects = np.full(capi.BV_MAX_QUERIES + 1, 0xFFFFFFFF, dtype=np.uint32), np.zeros(max(1, capacity), dtype=np.uint32)
+        check(capi.lib().ivx_bv_query_lists(self._h, ptr(offsets), ptr(objects), capacity, C.byref(found)))
+        return offsets[: int(np.count_nonzero(offsets != 0xFFFFFFFF))].copy(), objects[: found.value]
+
     def device_ptr(self, which: int) -> int:
-        """`ivx_bv_device_ptr`: capi.BV_PTR_WORLD_BOXES / _PAIRS / _MASKS / _NODES / _LEAF_OBJECTS"""
+        """`ivx_bv_device_ptr`: capi.BV_PTR_WORLD_BOXES / _PAIRS / _MASKS / _NODES / _LEAF_OBJECTS / _HIT_OFFSETS / _HIT_OBJECTS"""
         return int(capi.lib().ivx_bv_device_ptr(self._h, int(which)) or 0)
 
     def build_hierarchy(self) -> None:
@@ -196,6 +219,30 @@ def hierarchy_host(world_boxes, nodes=None, leaf_objects=None):
     frame = np.zeros(1, dtype=AABB_DTYPE)
     check(capi.lib().ivx_bv_hierarchy_host(ptr(w) if n else None, n, ptr(nodes) if nn else None, ptr(leaf_objects) if n else None, ptr(frame)))
     return nodes[:nn], leaf_objects[:n], frame[0]
+
+
+def queries_hierarchy_host(world_boxes, nodes, leaf_objects, queries):
+    """`ivx_bv_queries_hierarchy_host`: the queries through a tree on the host (`hierarchy_host`'s, say), with the decision functions the kernels
+    run -> (masks [n_queries, ceil(n / 64)] uint64, counts [n_queries] uint32). A tree that is none raises an IvxError of IVX_ERR_STATE."""
+    w, q = _rec(world_boxes, AABB_DTYPE), query_array(queries)
+    n, nn = w.size, max(w.size - 1, 0)
+    nodes, leaf_objects = _rec(nodes, BV_NODE_DTYPE, nn), _rec(leaf_objects, np.uint32, n)
+    masks, counts = np.zeros((q.size, (n + 63) // 64), dtype=np.uint64), np.zeros(q.size, dtype=np.uint32)
+    check(capi.lib().ivx_bv_queries_hierarchy_host(ptr(w) if n else None, n, ptr(nodes) if nn else None, ptr(leaf_objects) if n else None, ptr(q) if q.size else None, q.size,
+                                                   ptr(masks) if masks.size else None, ptr(counts) if q.size else None))
+    return masks, counts
+
+
+def query_skips_boxes(queries, node_boxes) -> np.ndarray:
+    """`ivx_bv_query_skips_boxes`: the node decision of the queries' walk for every query and every box (AABB_DTYPE or BV_NODE_DTYPE records), host
+    arithmetic of the library -> [n_queries, n_boxes] bool, True where no proper box inside the box can be hit"""
+    q, b = query_array(queries), np.asarray(node_boxes)
+    if b.dtype != AABB_DTYPE:
+        b = boxes(b["lower"], b["upper"])
+    b = _rec(b, AABB_DTYPE)
+    skips = np.zeros((q.size, b.size), dtype=np.uint8)
+    check(capi.lib().ivx_bv_query_skips_boxes(ptr(q) if q.size else None, q.size, ptr(b) if b.size else None, b.size, ptr(skips) if skips.size else None))
+    return skips.astype(bool)
 
 
 def node_info(nodes, n: int):

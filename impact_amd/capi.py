@@ -199,7 +199,7 @@ BV_QUERY_DTYPE = np.dtype({
 BV_DYNAMIC, BV_STATIC, BV_PHANTOM = 0, 1, 2
 BV_QUERY_BOX, BV_QUERY_SPHERE, BV_QUERY_FRUSTUM, BV_QUERY_ORIENTED_BOX = 0, 1, 2, 3
 BV_ALL_PAIRS, BV_DYNAMIC_PAIRS = 0, 1
-BV_PTR_WORLD_BOXES, BV_PTR_PAIRS, BV_PTR_MASKS, BV_PTR_NODES, BV_PTR_LEAF_OBJECTS = 0, 1, 2, 3, 4
+BV_PTR_WORLD_BOXES, BV_PTR_PAIRS, BV_PTR_MASKS, BV_PTR_NODES, BV_PTR_LEAF_OBJECTS, BV_PTR_HIT_OFFSETS, BV_PTR_HIT_OBJECTS = 0, 1, 2, 3, 4, 5, 6
 BV_MAX_OBJECTS, BV_MAX_QUERIES = 1 << 20, 1024
 assert AABB_DTYPE.itemsize == 24 and SIMILARITY_DTYPE.itemsize == 32 and BV_QUERY_DTYPE.itemsize == 128
 # the hierarchy over a set (csrc/bvh.hip): `ivx_bv_node`; a child reference with BV_LEAF set names a leaf position, else a node
@@ -267,6 +267,7 @@ EXPORTED_SYMBOLS = [
     "ivx_bv_world_aabb", "ivx_bv_frustum_query", "ivx_grid_model_aabb", "ivx_bv_set", "ivx_bv_set_grids", "ivx_bv_download", "ivx_bv_pairs", "ivx_bv_queries",
     "ivx_bv_device_ptr",
     "ivx_bv_morton_key", "ivx_bv_hierarchy_host", "ivx_bv_build_hierarchy", "ivx_bv_hierarchy_download", "ivx_bv_pairs_hierarchy", "ivx_cw_set_broad_phase",
+    "ivx_bv_queries_hierarchy", "ivx_bv_queries_hierarchy_host", "ivx_bv_query_skips_boxes", "ivx_bv_query_lists",
     "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
     "ivx_world_set_motion_drivers", "ivx_world_set_time", "ivx_world_time", "ivx_world_apply_motion", "ivx_md_eval", "ivx_md_apply_host",
     "ivx_world_set_force_generators", "ivx_world_set_dynamic_gravity", "ivx_world_apply_forces", "ivx_world_gravity_loads", "ivx_fg_apply_host",
@@ -505,6 +506,10 @@ def lib():
         "ivx_bv_build_hierarchy": (i32, [vp]),
         "ivx_bv_hierarchy_download": (i32, [vp, vp, sz, vp, sz, C.POINTER(sz)]),
         "ivx_bv_pairs_hierarchy": (i32, [vp, u32, vp, sz, C.POINTER(sz)]),
+        "ivx_bv_queries_hierarchy": (i32, [vp, vp, sz, vp, vp]),
+        "ivx_bv_queries_hierarchy_host": (i32, [vp, sz, vp, vp, vp, sz, vp, vp]),
+        "ivx_bv_query_skips_boxes": (i32, [vp, sz, vp, sz, vp]),
+        "ivx_bv_query_lists": (i32, [vp, vp, vp, sz, C.POINTER(sz)]),
         "ivx_cw_set_broad_phase": (i32, [vp, u32]),
         "ivx_cw_transform": (i32, [vp, vp, vp, vp, vp]),
         "ivx_cw_contact": (i32, [vp, vp, vp, C.POINTER(i32)]),

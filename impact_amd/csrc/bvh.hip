@@ -21,6 +21,9 @@
 //   it sees ends beyond p — and goes on in preorder: into a node whose box does not lie outside the lane's, over it otherwise; at a leaf the kind
 //   filter and the box decision. Counts, then k_bvh_scan and the call's one wait, then emits (min, max) of the two objects; the sort above brings
 //   the pairs into (a, b) order. A walk takes at most 2 n steps, a climb 64: beyond that the launch sets the error word and the call fails.
+// QUERIES — k_bvh_query (described at the kernel): the four kinds of region query through the tree, with the bytes of bvol.hip's flat k_bv_query.
+//   Leaves are decided by the flat kernel's own function; a node is skipped only where bvol_internal.hpp's node decision proves that no proper
+//   leaf below can be hit in f32; the irregular objects (a NaN bound, lower > upper) are listed by k_bvh_nodes and decided outside the walk.
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -37,8 +40,11 @@ constexpr uint32_t ERR_REFIT = 1u, ERR_WALK = 2u, ERR_SORT = 4u;
 
 struct Status {  // 16 bytes at the start of the tree buffer, zeroed with the tickets by every build
     unsigned long long grand;
-    uint32_t error, reserved;
+    uint32_t error, n_irregular;  // (n_irregular: the length of the build's list of irregular objects)
 };
+constexpr uint32_t QUERY_FRONT = 512;   // subtree roots the top expansion of a query holds in LDS (it stops at 256 or more: at most 510)
+constexpr uint32_t QUERY_STACK = 1024;  // entries of a workgroup's stack in LDS: the front's share and 256 more per level below it, then lanes walk alone
+constexpr uint32_t QUERY_GROUP_LEAVES = 16384, QUERY_MAX_GROUPS = 16;  // workgroups per query: one per so many leaves, at most so many
 
 typedef uint64_t u64;
 
@@ -147,17 +153,22 @@ __device__ __forceinline__ uint32_t skip_behind(const u64* keys, int n, int last
 
 struct TreeArrays {
     ivx_bv_node* nodes;
-    uint32_t *leaf_objects, *leaf_kinds, *leaf_skip, *leaf_parent, *node_skip, *node_parent, *tickets;
+    uint32_t *leaf_objects, *leaf_kinds, *leaf_skip, *leaf_parent, *node_skip, *node_parent, *tickets, *irregular;
     ivx_aabb* leaf_boxes;
 };
 
-__global__ __launch_bounds__(256) void k_bvh_nodes(const u64* __restrict__ keys, uint32_t n, const ivx_aabb* __restrict__ world, const uint32_t* __restrict__ kinds, TreeArrays t) {
+__global__ __launch_bounds__(256) void k_bvh_nodes(const u64* __restrict__ keys, uint32_t n, const ivx_aabb* __restrict__ world, const uint32_t* __restrict__ kinds, TreeArrays t,
+                                                   Status* __restrict__ status) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint32_t o = (uint32_t)keys[i];  // (o < n: the keys are a permutation of what k_bvh_keys wrote; checked all the same)
     ivx_aabb b = ivx_bv_neutral_box();
     if (o < n) {
         b = world[o];
+        if (ivx_bv_irregular(b)) {  // the queries decide these outside their walk. The list's order is whoever came first: it decides no byte
+            const uint32_t at = __hip_atomic_fetch_add(&status->n_irregular, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (at < n) t.irregular[at] = o;
+        }
         if (ivx_bv_has_nan(b)) b = ivx_bv_neutral_box();
     }
     t.leaf_objects[i] = o, t.leaf_boxes[i] = b, t.leaf_kinds[i] = o < n ? kinds[o] : IVX_BV_PHANTOM;
@@ -280,9 +291,162 @@ __global__ __launch_bounds__(SCAN_ROUND) void k_bvh_scan(uint32_t* __restrict__ 
     if (threadIdx.x == 0u) status->grand = total;
 }
 
+__device__ __forceinline__ ivx_aabb box_of(const ivx_bv_node& node) {
+    ivx_aabb box;
+    for (int k = 0; k < 3; ++k) box.lower[k] = node.lower[k], box.upper[k] = node.upper[k];
+    return box;
+}
+__device__ __forceinline__ void set_hit(unsigned long long* __restrict__ row, uint32_t object) {
+    __hip_atomic_fetch_or(row + (object >> 6), 1ull << (object & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void decide_directly(const ivx_bv_query* __restrict__ q, const ivx_aabb* __restrict__ world, uint32_t object, unsigned long long* __restrict__ row) {
+    const ivx_aabb b = world[object];
+    float c[3], h[3];
+    ivx_bv_center_half(b, c, h);
+    if (ivx_bv_query_hits(q, b, c, h)) set_hit(row, object);
+}
+
+struct QueryTree {  // what a query's walk reads of the tree
+    const ivx_bv_node* __restrict__ nodes;
+    const uint32_t* __restrict__ node_skip;
+    const ivx_aabb* __restrict__ leaf_boxes;
+    const uint32_t* __restrict__ leaf_skip;
+    const uint32_t* __restrict__ leaf_objects;
+};
+
+// the leaf decision at position p < n. The leaf's box is its object's world box, or the neutral box of a NaN-bounded object: an irregular box is
+// left to the pass over the build's list. false: the leaf names no object
+__device__ __forceinline__ bool query_leaf(uint32_t n, const ivx_bv_query* __restrict__ q, const QueryTree& t, uint32_t p, unsigned long long* __restrict__ row) {
+    const ivx_aabb box = t.leaf_boxes[p];
+    if (ivx_bv_irregular(box)) return true;
+    float c[3], h[3];
+    ivx_bv_center_half(box, c, h);
+    if (!ivx_bv_query_hits(q, box, c, h)) return true;
+    const uint32_t object = t.leaf_objects[p];
+    if (object >= n) return false;
+    set_hit(row, object);
+    return true;
+}
+
+// one lane walks the subtree of `start` in preorder without a stack, by k_bvh_walk's skip links, and stops at start's own skip link: every link
+// inside a subtree leads to a place inside it or to that one. At most 2 n steps. false: a link points nowhere, or the steps ran out
+__device__ bool query_subtree(uint32_t n, const ivx_bv_query* __restrict__ q, const QueryTree& t, uint32_t start, unsigned long long* __restrict__ row) {
+    const uint32_t at0 = start & ~IVX_BV_LEAF;
+    if (start & IVX_BV_LEAF ? at0 >= n : at0 >= n - 1u) return false;
+    const uint32_t end = start & IVX_BV_LEAF ? t.leaf_skip[at0] : t.node_skip[at0];
+    uint32_t at = start;
+    for (uint32_t steps = 0; at != end && at != NONE; ++steps) {
+        if (steps >= 2u * n) return false;
+        if (at & IVX_BV_LEAF) {
+            const uint32_t p = at & ~IVX_BV_LEAF;
+            if (p >= n || !query_leaf(n, q, t, p, row)) return false;
+            at = t.leaf_skip[p];
+        } else {
+            if (at >= n - 1u) return false;
+            const ivx_bv_node node = t.nodes[at];
+            at = ivx_bv_query_skips_node(q, box_of(node)) ? t.node_skip[at] : node.left;
+        }
+    }
+    return true;
+}
+
+// QUERIES — k_bvh_query, `groups` workgroups per query over (query, subtree) items; the masks are zeroed on the stream beforehand and a hit is an
+//   agent-scope OR into its word: idempotent and commutative, so the bytes do not depend on who came first, and no workgroup waits for another.
+//   The query's record has a workgroup-uniform address (scalar loads).
+//   TOP: every workgroup of the query expands the tree from the root breadth-first in LDS, a lane per front entry: a leaf stays, a node the
+//     node decision (ivx_bv_query_skips_node) skips is dropped, any other node is replaced by its two children (undecided); places come from a
+//     workgroup prefix sum, so the groups hold the same front in the same order. Until the front holds 256 entries or more (at most
+//     510 < QUERY_FRONT), or no node. Group g takes entries g, g + groups, ...
+//   STACK: the group's entries become a stack in LDS that its 256 lanes work off together, up to 256 entries from the top a round: a leaf is
+//     decided (the leaf decision of the flat kernel, ivx_bv_query_hits), a node is dropped or replaced by its children as above. Every entry is
+//     popped once and a round pops one at least: at most 2 n rounds, else ERR_WALK. A fully covered subtree is so shared by all lanes, however
+//     the front fell. When a round's children would not fit (QUERY_STACK), nothing is pushed and each lane walks the subtree of its node
+//     by itself (query_subtree): the stack holds 256 more entries per level it has gone down, so these are the small subtrees at the bottom.
+//   IRREGULAR: the objects of the build's list (a NaN bound, lower > upper), which the node decisions do not cover and the walk leaves alone,
+//     are decided by every query from their world boxes, shared among its groups. n == 1 has no tree: the one object is decided this way.
+__global__ __launch_bounds__(256) void k_bvh_query(uint32_t n, uint32_t groups, const ivx_bv_query* __restrict__ queries, const ivx_aabb* __restrict__ world, QueryTree tree,
+                                                   const uint32_t* __restrict__ irregular, uint32_t n_words, unsigned long long* __restrict__ masks,
+                                                   Status* __restrict__ status) {
+    __shared__ uint32_t front[2][QUERY_FRONT];
+    __shared__ uint32_t stack[QUERY_STACK];
+    __shared__ uint32_t wave_sums[4];
+    const uint32_t t = threadIdx.x, query = blockIdx.x / groups, g = blockIdx.x - query * groups;
+    const ivx_bv_query* __restrict__ q = queries + query;
+    unsigned long long* __restrict__ row = masks + (size_t)query * n_words;
+    if (n == 1u) {
+        if (t == 0u && g == 0u) decide_directly(q, world, 0u, row);
+        return;
+    }
+    bool sound = true;
+    if (t == 0u) front[0][0] = 0u;  // the root
+    __syncthreads();
+    uint32_t cur = 0u, m = 1u;
+    for (uint32_t round = 0; round < 64u && m < 256u; ++round) {  // (m and every exit are workgroup-uniform)
+        const uint32_t ref = t < m ? front[cur][t] : NONE;
+        const bool is_node = t < m && !(ref & IVX_BV_LEAF);
+        uint32_t keep = t < m ? 1u : 0u, a = ref, b = NONE;
+        if (is_node) {
+            keep = 0u;
+            if (ref < n - 1u) {
+                const ivx_bv_node node = tree.nodes[ref];
+                if (!ivx_bv_query_skips_node(q, box_of(node))) keep = 2u, a = node.left, b = node.right;
+            } else {
+                sound = false;
+            }
+        }
+        uint32_t total;  // low half: the entries kept; high half: the nodes this round looked at
+        const uint32_t at = ivx_block_prefix(keep | (is_node ? 1u << 16 : 0u), wave_sums, t, total) & 0xFFFFu;
+        if (keep >= 1u) front[cur ^ 1u][at] = a;
+        if (keep == 2u) front[cur ^ 1u][at + 1u] = b;
+        __syncthreads();
+        cur ^= 1u, m = total & 0xFFFFu;
+        if ((total >> 16) == 0u) break;  // leaves only: nothing left to expand
+    }
+    uint32_t size = m > g ? (m - g + groups - 1u) / groups : 0u;  // (at most 510 <= QUERY_STACK)
+    for (uint32_t i = t; i < size; i += 256u) stack[i] = front[cur][g + i * groups];
+    __syncthreads();
+    for (uint32_t round = 0; size != 0u; ++round) {  // (size and every exit are workgroup-uniform)
+        if (round >= 2u * n) {
+            sound = false;
+            break;
+        }
+        const uint32_t take = min(size, 256u), base = size - take;
+        const uint32_t ref = t < take ? stack[base + t] : NONE;
+        uint32_t keep = 0u, a = NONE, b = NONE;
+        if (t < take) {
+            const uint32_t at = ref & ~IVX_BV_LEAF;
+            if (ref & IVX_BV_LEAF) {
+                if (at >= n || !query_leaf(n, q, tree, at, row)) sound = false;
+            } else if (at < n - 1u) {
+                const ivx_bv_node node = tree.nodes[at];
+                if (!ivx_bv_query_skips_node(q, box_of(node))) keep = 2u, a = node.left, b = node.right;
+            } else {
+                sound = false;
+            }
+        }
+        uint32_t total;
+        const uint32_t at = ivx_block_prefix(keep, wave_sums, t, total);  // (its barriers: every lane has read its entry before one is written)
+        if (base + total <= QUERY_STACK) {
+            if (keep == 2u) stack[base + at] = a, stack[base + at + 1u] = b;
+            size = base + total;
+        } else {
+            if (keep == 2u && !query_subtree(n, q, tree, ref, row)) sound = false;
+            size = base;
+        }
+        __syncthreads();
+    }
+    const uint32_t n_irregular = min(status->n_irregular, n);
+    for (uint32_t i = g * 256u + t; i < n_irregular; i += groups * 256u) {
+        const uint32_t object = irregular[i];
+        if (object < n) decide_directly(q, world, object, row);
+        else sound = false;
+    }
+    if (!sound) flag(status, ERR_WALK);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 struct BvhState {
-    ivx_buf tree;     // status | tickets || frame | keys | keys (the sort's other side) | histogram | nodes | the leaf and node side arrays
+    ivx_buf tree;     // status | tickets || frame | keys | keys (the sort's other side) | histogram | nodes | the leaf and node side arrays | irregular objects
     ivx_buf walk;     // counts per leaf position
     ivx_buf sorting;  // the pair sort's other side | its histogram
     bool built = false;
@@ -292,7 +456,7 @@ struct BvhState {
 
 struct TreeLayout {
     size_t o_status = 0, o_tickets = 0, zero_bytes = 0, o_frame = 0, o_keys = 0, o_keys2 = 0, o_hist = 0, o_nodes = 0, o_leaf_objects = 0, o_leaf_boxes = 0, o_leaf_kinds = 0,
-           o_leaf_skip = 0, o_leaf_parent = 0, o_node_skip = 0, o_node_parent = 0, bytes = 0;
+           o_leaf_skip = 0, o_leaf_parent = 0, o_node_skip = 0, o_node_parent = 0, o_irregular = 0, bytes = 0;
 };
 uint32_t tiles_of(size_t n) { return (uint32_t)((n + SORT_TILE - 1u) / SORT_TILE); }
 TreeLayout tree_layout(size_t n) {
@@ -303,6 +467,7 @@ TreeLayout tree_layout(size_t n) {
     t.o_frame = l.take(sizeof(ivx_aabb)), t.o_keys = l.take(n * 8), t.o_keys2 = l.take(n * 8), t.o_hist = l.take((size_t)tiles_of(n) * 256u * 4);
     t.o_nodes = l.take(n * sizeof(ivx_bv_node)), t.o_leaf_objects = l.take(n * 4), t.o_leaf_boxes = l.take(n * sizeof(ivx_aabb)), t.o_leaf_kinds = l.take(n * 4);
     t.o_leaf_skip = l.take(n * 4), t.o_leaf_parent = l.take(n * 4), t.o_node_skip = l.take(n * 4), t.o_node_parent = l.take(n * 4);
+    t.o_irregular = l.take(n * 4);  // (behind everything the pair pass knows)
     t.bytes = l.bytes;
     return t;
 }
@@ -314,6 +479,7 @@ TreeArrays tree_arrays(const BvhState* st, const TreeLayout& l) {
     t.leaf_skip = reinterpret_cast<uint32_t*>(d + l.o_leaf_skip), t.leaf_parent = reinterpret_cast<uint32_t*>(d + l.o_leaf_parent);
     t.node_skip = reinterpret_cast<uint32_t*>(d + l.o_node_skip), t.node_parent = reinterpret_cast<uint32_t*>(d + l.o_node_parent);
     t.tickets = reinterpret_cast<uint32_t*>(d + l.o_tickets), t.leaf_boxes = reinterpret_cast<ivx_aabb*>(d + l.o_leaf_boxes);
+    t.irregular = reinterpret_cast<uint32_t*>(d + l.o_irregular);
     return t;
 }
 
@@ -389,6 +555,48 @@ void hierarchy_host(const ivx_aabb* world, size_t n, ivx_bv_node* nodes, uint32_
     }
 }
 
+// the queries over a tree the caller brings, with the decisions the kernel runs: a descent from the root with a stack of its own in place of the
+// skip links (which are not part of ivx_bv_node), the irregular objects found by a loop. false: the tree is no tree over n leaves
+bool queries_host(const ivx_aabb* world, size_t n, const ivx_bv_node* nodes, const uint32_t* leaf_objects, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks) {
+    const size_t n_words = (n + 63u) / 64u;
+    auto decide_directly = [&](const ivx_bv_query* q, size_t object, uint64_t* row) {
+        float c[3], h[3];
+        ivx_bv_center_half(world[object], c, h);
+        if (ivx_bv_query_hits(q, world[object], c, h)) row[object >> 6] |= 1ull << (object & 63u);
+    };
+    std::vector<uint32_t> irregular, stack;
+    for (size_t o = 0; o < n; ++o)
+        if (ivx_bv_irregular(world[o])) irregular.push_back((uint32_t)o);
+    for (size_t qi = 0; qi < n_queries; ++qi) {
+        const ivx_bv_query* q = queries + qi;
+        uint64_t* row = masks + qi * n_words;
+        std::fill(row, row + n_words, (uint64_t)0);
+        if (n == 1) {
+            decide_directly(q, 0, row);
+            continue;
+        }
+        stack.assign(1, 0u);
+        for (size_t steps = 0; !stack.empty(); ++steps) {
+            if (steps >= 2 * n) return false;
+            const uint32_t at = stack.back();
+            stack.pop_back();
+            if (at & IVX_BV_LEAF) {
+                const uint32_t p = at & ~IVX_BV_LEAF;
+                if (p >= n || leaf_objects[p] >= n) return false;
+                const uint32_t object = leaf_objects[p];
+                if (!ivx_bv_irregular(world[object])) decide_directly(q, object, row);
+            } else {
+                if (at >= n - 1) return false;
+                ivx_aabb box;
+                for (int k = 0; k < 3; ++k) box.lower[k] = nodes[at].lower[k], box.upper[k] = nodes[at].upper[k];
+                if (!ivx_bv_query_skips_node(q, box)) stack.push_back(nodes[at].right), stack.push_back(nodes[at].left);
+            }
+        }
+        for (uint32_t object : irregular) decide_directly(q, object, row);
+    }
+    return true;
+}
+
 }  // namespace
 
 void ivx_bvh_release(void* hierarchy) {
@@ -431,7 +639,7 @@ int ivx_bvh_build_enqueue(ivx_ctx* c, const char* who) {
         IVX_KLAUNCH(k_bvh_keys, lanes, dim3(256), 0, c->stream, view.world, n, (const ivx_aabb*)frame, keys);
         static const uint32_t code_bytes[4] = {32u, 40u, 48u, 56u};
         if (int rc = sort_enqueue(c, keys, reinterpret_cast<u64*>(d + l.o_keys2), n, reinterpret_cast<uint32_t*>(d + l.o_hist), code_bytes, 4, status)) return rc;
-        IVX_KLAUNCH(k_bvh_nodes, lanes, dim3(256), 0, c->stream, (const u64*)keys, n, view.world, view.kinds, t);
+        IVX_KLAUNCH(k_bvh_nodes, lanes, dim3(256), 0, c->stream, (const u64*)keys, n, view.world, view.kinds, t, status);
         IVX_KLAUNCH(k_bvh_refit, lanes, dim3(256), 0, c->stream, n, t, status);
         IVX_HIP_CHECK(hipGetLastError());
     }
@@ -548,6 +756,77 @@ int ivx_bv_pairs_hierarchy(ivx_ctx* c, uint32_t mode, uint32_t* pairs, size_t ca
     if (pairs) IVX_HIP_CHECK(ivx_memcpy_async(pairs, view.pairs->p, *n_out * 8, hipMemcpyDeviceToHost, c->stream));
     IVX_HIP_CHECK(ivx_memcpy_async(&status, static_cast<const char*>(st->tree.p) + l.o_status, sizeof(Status), hipMemcpyDeviceToHost, c->stream));
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    return check_status(status, who);
+}
+
+int ivx_bv_query_skips_boxes(const ivx_bv_query* queries, size_t n_queries, const ivx_aabb* boxes, size_t n_boxes, uint8_t* skips) {
+    const char* who = "ivx_bv_query_skips_boxes";
+    IVX_REQUIRE((queries && boxes && skips) || n_queries == 0 || n_boxes == 0, IVX_ERR_INVALID, "%s: null argument", who);
+    for (size_t q = 0; q < n_queries && n_boxes != 0; ++q)
+        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    for (size_t q = 0; q < n_queries; ++q)
+        for (size_t b = 0; b < n_boxes; ++b) skips[q * n_boxes + b] = ivx_bv_query_skips_node(queries + q, boxes[b]) ? 1u : 0u;
+    return IVX_OK;
+}
+
+int ivx_bv_queries_hierarchy_host(const ivx_aabb* world, size_t n, const ivx_bv_node* nodes, const uint32_t* leaf_objects, const ivx_bv_query* queries, size_t n_queries,
+                                  uint64_t* masks, uint32_t* counts) {
+    const char* who = "ivx_bv_queries_hierarchy_host";
+    IVX_REQUIRE(n <= IVX_BV_MAX_OBJECTS, IVX_ERR_CAPACITY, "%s: %zu objects exceed %u", who, n, IVX_BV_MAX_OBJECTS);
+    IVX_REQUIRE(n_queries <= IVX_BV_MAX_QUERIES, IVX_ERR_CAPACITY, "%s: %zu queries exceed %u per call", who, n_queries, IVX_BV_MAX_QUERIES);
+    IVX_REQUIRE(queries || n_queries == 0, IVX_ERR_INVALID, "%s: null queries", who);
+    for (size_t q = 0; q < n_queries; ++q)
+        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    IVX_REQUIRE((world && leaf_objects) || n == 0, IVX_ERR_INVALID, "%s: null argument", who);
+    IVX_REQUIRE(nodes || n < 2, IVX_ERR_INVALID, "%s: null node buffer", who);
+    if (n_queries == 0) return IVX_OK;
+    if (n == 0) {
+        for (size_t q = 0; q < n_queries && counts; ++q) counts[q] = 0u;
+        return IVX_OK;
+    }
+    IVX_REQUIRE(masks, IVX_ERR_INVALID, "%s: null mask buffer", who);
+    IVX_REQUIRE(queries_host(world, n, nodes, leaf_objects, queries, n_queries, masks), IVX_ERR_STATE,
+                "%s: the hierarchy is inconsistent: a walk ran past its %zu steps or a link points nowhere", who, 2 * n);
+    const size_t n_words = (n + 63u) / 64u;
+    for (size_t q = 0; q < n_queries && counts; ++q) {
+        uint32_t hit = 0u;
+        for (size_t w = 0; w < n_words; ++w) hit += (uint32_t)__builtin_popcountll(masks[q * n_words + w]);
+        counts[q] = hit;
+    }
+    return IVX_OK;
+}
+
+int ivx_bv_queries_hierarchy(ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, uint32_t* counts) {
+    const char* who = "ivx_bv_queries_hierarchy";
+    if (int rc = ivx_bvol_queries_check(who, c, queries, n_queries)) return rc;
+    ivx_bvol_view view;
+    BvhState* st;
+    if (int rc = current_tree(c, who, &view, &st)) return rc;
+    ivx_bvol_query_run run;
+    if (n_queries == 0 || st->n == 0u) {  // (nothing reaches the stream)
+        if (int rc = ivx_bvol_queries_begin(c, who, queries, n_queries, masks, &run)) return rc;
+        return ivx_bvol_queries_finish(c, run, masks, counts);
+    }
+    IVX_REQUIRE(masks, IVX_ERR_INVALID, "%s: null mask buffer", who);
+    ivx_many_other_context other_(c);
+    if (int rc = ivx_bvol_queries_begin(c, who, queries, n_queries, masks, &run)) return rc;
+    IVX_HIP_CHECK(ivx_memset_async(run.d_masks, 0, run.mask_bytes, c->stream));
+    const uint32_t n = st->n;
+    TreeArrays t = {};
+    Status* d_status = nullptr;
+    if (n >= 2u) {
+        const TreeLayout l = tree_layout(n);
+        t = tree_arrays(st, l);
+        d_status = reinterpret_cast<Status*>(static_cast<char*>(st->tree.p) + l.o_status);
+    }
+    const QueryTree tree = {t.nodes, t.node_skip, t.leaf_boxes, t.leaf_skip, t.leaf_objects};
+    const uint32_t groups = std::min(std::max(n / QUERY_GROUP_LEAVES, 1u), QUERY_MAX_GROUPS);
+    IVX_KLAUNCH(k_bvh_query, dim3(run.n_queries * groups), dim3(256), 0, c->stream, n, groups, run.d_queries, view.world, tree, (const uint32_t*)t.irregular, run.n_words, run.d_masks,
+                d_status);
+    IVX_HIP_CHECK(hipGetLastError());
+    Status status = {};
+    if (d_status) IVX_HIP_CHECK(ivx_memcpy_async(&status, d_status, sizeof(Status), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = ivx_bvol_queries_finish(c, run, masks, counts)) return rc;  // (the call's one wait)
     return check_status(status, who);
 }
 

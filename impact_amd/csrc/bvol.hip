@@ -19,7 +19,9 @@
 //   The host reads the grand total (the call's one wait before the emit), grows the pair buffer and launches
 // EMIT — k_bv_pair_walk<true>: the same walk; each lane writes its hits from its own offset in column order.
 // QUERY — k_bv_query, one wave per 64 consecutive objects, a world box per lane: walks the queries (the record's address is wave-uniform: scalar
-//   loads), __ballot is the mask word of (query, tile). k_bv_query_counts, one wave per query: the popcounts of its words.
+//   loads), __ballot is the mask word of (query, tile). k_bv_query_counts, one wave per query: the popcounts of its words. The call's two halves
+//   (upload and buffers; counts, download and wait) are shared with bvh.hip's form, which fills the masks through the tree instead.
+// LISTS — ivx_bv_query_lists: the resident masks of either form as per-query object lists; the four kernels are described where they stand.
 #include <cmath>
 #include <new>
 #include <vector>
@@ -46,12 +48,7 @@ __host__ __device__ __forceinline__ float f_abs(float v) { return ivx_bv_abs(v);
 __host__ __device__ __forceinline__ void world_aabb(const ivx_aabb& m, const ivx_similarity& s, ivx_aabb* out) { ivx_bv_world_aabb_of(m, s, out); }  // (bvol_internal.hpp: narrow.hip runs it too)
 
 // ---- device side -------------------------------------------------------------------------------------------------------------------------
-// "has its sign bit set, or is a NaN" for any of six differences
-__device__ __forceinline__ bool any_negative(float d0, float d1, float d2, float d3, float d4, float d5) {
-    const uint32_t bits = ((__float_as_uint(d0) | __float_as_uint(d1)) | (__float_as_uint(d2) | __float_as_uint(d3))) | (__float_as_uint(d4) | __float_as_uint(d5));
-    const bool nan = __builtin_isunordered(d0, d1) || __builtin_isunordered(d2, d3) || __builtin_isunordered(d4, d5);
-    return (bits >> 31) != 0u || nan;
-}
+__device__ __forceinline__ bool any_negative(float d0, float d1, float d2, float d3, float d4, float d5) { return ivx_bv_any_negative(d0, d1, d2, d3, d4, d5); }  // (bvol_internal.hpp)
 // box_lies_outside
 __device__ __forceinline__ bool lies_outside(const ivx_aabb& self, const ivx_aabb& other) {
     return any_negative(other.upper[0] - self.lower[0], other.upper[1] - self.lower[1], other.upper[2] - self.lower[2], self.upper[0] - other.lower[0],
@@ -179,54 +176,6 @@ __global__ __launch_bounds__(SCAN_ROUND) void k_bv_scan(uint32_t* __restrict__ r
     if (threadIdx.x == 0u) *grand_total = total;
 }
 
-__device__ __forceinline__ bool query_hits(const ivx_bv_query* __restrict__ q, const ivx_aabb& b, const float c[3], const float h[3]) {
-    switch (q->kind) {  // (uniform)
-        case IVX_BV_QUERY_BOX: {
-            ivx_aabb self;
-            for (int k = 0; k < 3; ++k) self.lower[k] = q->u.box.lower[k], self.upper[k] = q->u.box.upper[k];
-            return !lies_outside(self, b);
-        }
-        case IVX_BV_QUERY_SPHERE: {
-            float s = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float ck = q->u.sphere.center[k];
-                if (b.upper[k] < ck) {
-                    const float d = ck - b.upper[k];
-                    s += d * d;
-                } else if (b.lower[k] > ck) {
-                    const float d = b.lower[k] - ck;
-                    s += d * d;
-                }
-            }
-            return !(s > q->u.sphere.radius * q->u.sphere.radius);
-        }
-        case IVX_BV_QUERY_FRUSTUM: {
-            bool hit = true;
-#pragma unroll
-            for (int p = 0; p < 6; ++p) {
-                const uint32_t corner = q->u.frustum.corners[p];
-                const float px = (corner & 4u) ? b.upper[0] : b.lower[0], py = (corner & 2u) ? b.upper[1] : b.lower[1], pz = (corner & 1u) ? b.upper[2] : b.lower[2];
-                const float dist = ((q->u.frustum.planes[p][0] * px + q->u.frustum.planes[p][1] * py) + q->u.frustum.planes[p][2] * pz) - q->u.frustum.planes[p][3];
-                hit = hit && dist >= 0.0f;
-            }
-            return hit;
-        }
-        default: {  // IVX_BV_QUERY_ORIENTED_BOX
-            const float dx = c[0] - q->u.oriented_box.center[0], dy = c[1] - q->u.oriented_box.center[1], dz = c[2] - q->u.oriented_box.center[2];
-            float diff[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float a0 = q->u.oriented_box.axes[a][0], a1 = q->u.oriented_box.axes[a][1], a2 = q->u.oriented_box.axes[a][2];
-                const float e = ((f_abs(a0) * h[0] + f_abs(a1) * h[1]) + f_abs(a2) * h[2]) + q->u.oriented_box.half_extents[a];
-                const float l = (a0 * dx + a1 * dy) + a2 * dz;
-                diff[a] = e - f_abs(l);
-            }
-            return !any_negative(diff[0], diff[1], diff[2], 0.0f, 0.0f, 0.0f);
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_bv_query(const ivx_aabb* __restrict__ world, uint32_t n, const ivx_bv_query* __restrict__ queries, uint32_t n_queries,
                                                   unsigned long long* __restrict__ masks) {
     const uint32_t lane = threadIdx.x & 63u, tile = wave_index();
@@ -236,10 +185,10 @@ __global__ __launch_bounds__(256) void k_bv_query(const ivx_aabb* __restrict__ w
     const bool live = o < n;
     ivx_aabb b = neutral_box();
     if (live) b = world[o];
-    const float c[3] = {0.5f * (b.lower[0] + b.upper[0]), 0.5f * (b.lower[1] + b.upper[1]), 0.5f * (b.lower[2] + b.upper[2])};
-    const float h[3] = {0.5f * (b.upper[0] - b.lower[0]), 0.5f * (b.upper[1] - b.lower[1]), 0.5f * (b.upper[2] - b.lower[2])};
+    float c[3], h[3];
+    ivx_bv_center_half(b, c, h);
     for (uint32_t q = 0; q < n_queries; ++q) {
-        const bool hit = live && query_hits(queries + q, b, c, h);
+        const bool hit = live && ivx_bv_query_hits(queries + q, b, c, h);  // (bvol_internal.hpp: the hierarchy's walk decides its leaves with it too)
         const unsigned long long mask = __ballot(hit);
         if (lane == 0u) masks[(size_t)q * n_words + tile] = mask;
     }
@@ -255,15 +204,59 @@ __global__ __launch_bounds__(64) void k_bv_query_counts(const unsigned long long
     if (lane == 0u) counts[q] = c;
 }
 
+// LISTS — the resident masks as hit lists, every position a prefix of popcounts (no sort, no atomic). k_bv_list_words, a lane per mask word: its
+//   popcount. k_bv_list_rows, a workgroup per query: the exclusive prefix over the query's words in place, and the query's total. k_bv_list_offsets,
+//   one workgroup: the exclusive prefix of the totals, offsets[n_queries] and the grand total. k_bv_list_emit, a lane per mask word again: the
+//   objects of its set bits, ascending, from offsets[q] + the word's prefix.
+__global__ __launch_bounds__(256) void k_bv_list_words(const unsigned long long* __restrict__ masks, uint32_t n_all_words, uint32_t* __restrict__ prefix) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n_all_words) prefix[i] = (uint32_t)__popcll(masks[i]);
+}
+
+__global__ __launch_bounds__(SCAN_ROUND) void k_bv_list_rows(uint32_t* __restrict__ prefix, uint32_t n_words, uint32_t* __restrict__ totals) {
+    __shared__ uint32_t wave_totals[SCAN_ROUND / 64u];
+    uint32_t* row = prefix + (size_t)blockIdx.x * n_words;
+    const uint32_t total = ivx_scan_rounds<SCAN_ROUND, uint32_t>(row, row, n_words, wave_totals);  // (at most 2^20 objects a query)
+    if (threadIdx.x == 0u) totals[blockIdx.x] = total;
+}
+
+// offsets[n_queries + 1] (at most 2^10 queries of at most 2^20 objects: no 32-bit sum overflows)
+__global__ __launch_bounds__(SCAN_ROUND) void k_bv_list_offsets(const uint32_t* __restrict__ totals, uint32_t n_queries, uint32_t* __restrict__ offsets) {
+    __shared__ uint32_t wave_totals[SCAN_ROUND / 64u];
+    const uint32_t total = ivx_scan_rounds<SCAN_ROUND, uint32_t>(totals, offsets, n_queries, wave_totals);
+    if (threadIdx.x == 0u) offsets[n_queries] = total;
+}
+
+__global__ __launch_bounds__(256) void k_bv_list_emit(const unsigned long long* __restrict__ masks, uint32_t n_words, uint32_t n_all_words, const uint32_t* __restrict__ prefix,
+                                                      const uint32_t* __restrict__ offsets, uint32_t n_hits, uint32_t* __restrict__ objects) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_all_words) return;
+    const uint32_t q = i / n_words, w = i - q * n_words;
+    unsigned long long word = masks[i];
+    uint32_t at = offsets[q] + prefix[i];
+    while (word != 0ull) {
+        const uint32_t bit = (uint32_t)__ffsll((long long)word) - 1u;
+        if (at < n_hits) objects[at] = w * 64u + bit;  // (always: the prefix came from these very words)
+        ++at;
+        word &= word - 1ull;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 // context-owned state: device buffers that only grow, a pinned staging block for the one upload of a call (device_common.hpp), and the set the context holds
 struct BvState {
     ivx_buf set;      // input boxes | similarities || kinds | world boxes | block boxes | total  (the part before || is the upload's scratch)
     ivx_buf scratch;  // pairs: counts | row totals | grand total;  queries: records | counts
     ivx_buf pairs, masks;
+    ivx_buf lists;  // ivx_bv_query_lists: per-word prefixes | per-query totals | offsets
+    ivx_buf hits;   // ... and the objects
     ivx_staging staging;  // (with its event: behind the last upload from the block)
     bool has_set = false;
     uint32_t n = 0;
+    bool queried = false;      // a queries call (either form) has left masks of the set that stands
+    uint32_t n_queried = 0;    // ... of this many queries
+    size_t o_list_offsets = 0;  // where `lists` holds the offsets of the last ivx_bv_query_lists (n_listed != 0)
+    uint32_t n_listed = 0;
     uint64_t serial = 0;  // counts the sets the context has held (ivx_bvol_set_serial)
     void* hierarchy = nullptr;  // bvh.hip's state: a tree over one of those sets
     size_t o_kinds = 0, o_world = 0, o_blocks = 0, o_total = 0;
@@ -331,7 +324,7 @@ int set_launch(ivx_ctx* c, BvState* st, const SetLayout& l, size_t n, bool deriv
 int set_enqueue(ivx_ctx* c, const ivx_aabb* boxes, const ivx_similarity* sims, const uint32_t* kinds, size_t n) {
     BvState* st;
     if (int rc = state_of(c, &st)) return rc;
-    st->has_set = false, st->n = 0;  // (until this call's set stands)
+    st->has_set = false, st->n = 0, st->queried = false, st->n_listed = 0u;  // (until this call's set stands)
     if (n == 0) {
         st->has_set = true, ++st->serial;
         return IVX_OK;
@@ -377,7 +370,7 @@ int set_state(ivx_ctx* c, const char* who, BvState** out) {
 void ivx_bvol_release(ivx_ctx* c) {
     if (!c || !c->bvol_state) return;
     BvState* s = static_cast<BvState*>(c->bvol_state);
-    for (ivx_buf* b : {&s->set, &s->scratch, &s->pairs, &s->masks}) ivx_buf_free(b);
+    for (ivx_buf* b : {&s->set, &s->scratch, &s->pairs, &s->masks, &s->lists, &s->hits}) ivx_buf_free(b);
     ivx_staging_release(&s->staging);
     ivx_bvh_release(s->hierarchy);
     delete s;
@@ -398,7 +391,7 @@ int ivx_bvol_set_begin(ivx_ctx* c, size_t n, ivx_aabb** d_boxes, uint32_t** d_ki
     *d_boxes = nullptr, *d_kinds = nullptr;
     BvState* st;
     if (int rc = state_of(c, &st)) return rc;
-    st->has_set = false, st->n = 0;  // (until ivx_bvol_set_finish)
+    st->has_set = false, st->n = 0, st->queried = false, st->n_listed = 0u;  // (until ivx_bvol_set_finish)
     if (n == 0) return IVX_OK;
     const SetLayout l = set_layout(n, false);
     if (int rc = ivx_buf_grow(c, &st->set, l.bytes, 1u << 16)) return rc;
@@ -456,6 +449,57 @@ int ivx_bvol_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool chec
     IVX_KLAUNCH(k_bv_pair_walk<true>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)d_rows,
                 static_cast<uint2*>(st->pairs.p));
     IVX_HIP_CHECK(hipGetLastError());
+    return IVX_OK;
+}
+
+int ivx_bvol_queries_check(const char* who, ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries) {
+    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
+    IVX_REQUIRE(n_queries <= IVX_BV_MAX_QUERIES, IVX_ERR_CAPACITY, "%s: %zu queries exceed %u per call", who, n_queries, IVX_BV_MAX_QUERIES);
+    IVX_REQUIRE(queries || n_queries == 0, IVX_ERR_INVALID, "%s: null queries", who);
+    for (size_t q = 0; q < n_queries; ++q)
+        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    return IVX_OK;
+}
+
+int ivx_bvol_queries_begin(ivx_ctx* c, const char* who, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, ivx_bvol_query_run* run) {
+    *run = ivx_bvol_query_run();
+    BvState* st;
+    if (int rc = set_state(c, who, &st)) return rc;
+    run->n = st->n, run->n_words = (st->n + 63u) / 64u, run->n_queries = (uint32_t)n_queries;
+    if (n_queries == 0 || st->n == 0) return IVX_OK;
+    IVX_REQUIRE(masks, IVX_ERR_INVALID, "%s: null mask buffer", who);
+    ivx_layout l;
+    const size_t o_q = l.take(n_queries * sizeof(ivx_bv_query)), o_c = l.take(n_queries * 4);
+    if (int rc = ivx_staging_for(&st->staging, n_queries * sizeof(ivx_bv_query))) return rc;
+    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
+    run->mask_bytes = n_queries * (size_t)run->n_words * 8;
+    if (int rc = ivx_buf_grow(c, &st->masks, run->mask_bytes, 1u << 16)) return rc;
+    st->queried = false, st->n_listed = 0u;  // (until this call's masks stand)
+    char* s = static_cast<char*>(st->scratch.p);
+    memcpy(st->staging.p, queries, n_queries * sizeof(ivx_bv_query));
+    IVX_HIP_CHECK(ivx_memcpy_async(s + o_q, st->staging.p, n_queries * sizeof(ivx_bv_query), hipMemcpyHostToDevice, c->stream));
+    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
+    st->staging.pending = true;
+    run->d_queries = reinterpret_cast<const ivx_bv_query*>(s + o_q);
+    run->d_masks = static_cast<unsigned long long*>(st->masks.p);
+    run->d_counts = reinterpret_cast<uint32_t*>(s + o_c);
+    return IVX_OK;
+}
+
+int ivx_bvol_queries_finish(ivx_ctx* c, const ivx_bvol_query_run& run, uint64_t* masks, uint32_t* counts) {
+    BvState* st = static_cast<BvState*>(c->bvol_state);
+    if (run.n_queries == 0u) return IVX_OK;
+    if (run.n == 0u) {
+        for (size_t q = 0; q < run.n_queries && counts; ++q) counts[q] = 0u;
+        st->queried = true, st->n_queried = run.n_queries, st->n_listed = 0u;
+        return IVX_OK;
+    }
+    IVX_KLAUNCH(k_bv_query_counts, dim3(run.n_queries), dim3(64), 0, c->stream, (const unsigned long long*)run.d_masks, run.n_words, run.d_counts);
+    IVX_HIP_CHECK(hipGetLastError());
+    IVX_HIP_CHECK(ivx_memcpy_async(masks, run.d_masks, run.mask_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (counts) IVX_HIP_CHECK(ivx_memcpy_async(counts, run.d_counts, (size_t)run.n_queries * 4, hipMemcpyDeviceToHost, c->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    st->queried = true, st->n_queried = run.n_queries;
     return IVX_OK;
 }
 
@@ -553,41 +597,61 @@ int ivx_bv_pairs(ivx_ctx* c, uint32_t mode, uint32_t* pairs, size_t cap, size_t*
 
 int ivx_bv_queries(ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, uint32_t* counts) {
     const char* who = "ivx_bv_queries";
-    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
-    IVX_REQUIRE(n_queries <= IVX_BV_MAX_QUERIES, IVX_ERR_CAPACITY, "%s: %zu queries exceed %u per call", who, n_queries, IVX_BV_MAX_QUERIES);
-    IVX_REQUIRE(queries || n_queries == 0, IVX_ERR_INVALID, "%s: null queries", who);
-    for (size_t q = 0; q < n_queries; ++q)
-        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    if (int rc = ivx_bvol_queries_check(who, c, queries, n_queries)) return rc;
     BvState* st;
     if (int rc = set_state(c, who, &st)) return rc;
-    if (n_queries == 0) return IVX_OK;
-    const uint32_t n = st->n, n_words = (n + 63u) / 64u;
-    if (n == 0) {
-        for (size_t q = 0; q < n_queries && counts; ++q) counts[q] = 0u;
-        return IVX_OK;
+    ivx_bvol_query_run run;
+    if (n_queries == 0 || st->n == 0) {  // (nothing reaches the stream)
+        if (int rc = ivx_bvol_queries_begin(c, who, queries, n_queries, masks, &run)) return rc;
+        return ivx_bvol_queries_finish(c, run, masks, counts);
     }
     IVX_REQUIRE(masks, IVX_ERR_INVALID, "%s: null mask buffer", who);
     ivx_many_other_context other_(c);
+    if (int rc = ivx_bvol_queries_begin(c, who, queries, n_queries, masks, &run)) return rc;
+    IVX_KLAUNCH(k_bv_query, dim3((run.n_words + 3u) / 4u), dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(static_cast<const char*>(st->set.p) + st->o_world), run.n,
+                run.d_queries, run.n_queries, run.d_masks);
+    return ivx_bvol_queries_finish(c, run, masks, counts);
+}
+
+int ivx_bv_query_lists(ivx_ctx* c, uint32_t* offsets, uint32_t* objects, size_t cap, size_t* n_out) {
+    const char* who = "ivx_bv_query_lists";
+    IVX_REQUIRE(n_out, IVX_ERR_INVALID, "%s: null argument", who);
+    *n_out = 0;
+    IVX_REQUIRE(objects || cap == 0, IVX_ERR_INVALID, "%s: null object buffer of capacity %zu", who, cap);
+    BvState* st;
+    if (int rc = set_state(c, who, &st)) return rc;
+    IVX_REQUIRE(st->queried && st->n != 0u, IVX_ERR_STATE, "%s: no masks of the context's current set (call ivx_bv_queries or ivx_bv_queries_hierarchy after the set; an empty set has none)", who);
+    const uint32_t nq = st->n_queried, n_words = (st->n + 63u) / 64u, n_all = nq * n_words;  // (at most 2^10 x 2^14)
+    ivx_many_other_context other_(c);
     ivx_layout l;
-    const size_t o_q = l.take(n_queries * sizeof(ivx_bv_query)), o_c = l.take(n_queries * 4);
-    if (int rc = ivx_staging_for(&st->staging, n_queries * sizeof(ivx_bv_query))) return rc;
-    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
-    const size_t mask_bytes = n_queries * (size_t)n_words * 8;
-    if (int rc = ivx_buf_grow(c, &st->masks, mask_bytes, 1u << 16)) return rc;
-    char* s = static_cast<char*>(st->scratch.p);
-    memcpy(st->staging.p, queries, n_queries * sizeof(ivx_bv_query));
-    IVX_HIP_CHECK(ivx_memcpy_async(s + o_q, st->staging.p, n_queries * sizeof(ivx_bv_query), hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
-    st->staging.pending = true;
-    unsigned long long* d_masks = static_cast<unsigned long long*>(st->masks.p);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(s + o_c);
-    IVX_KLAUNCH(k_bv_query, dim3((n_words + 3u) / 4u), dim3(256), 0, c->stream, reinterpret_cast<const ivx_aabb*>(static_cast<const char*>(st->set.p) + st->o_world), n,
-                reinterpret_cast<const ivx_bv_query*>(s + o_q), (uint32_t)n_queries, d_masks);
-    IVX_KLAUNCH(k_bv_query_counts, dim3((uint32_t)n_queries), dim3(64), 0, c->stream, (const unsigned long long*)d_masks, n_words, d_counts);
+    const size_t o_prefix = l.take((size_t)n_all * 4), o_totals = l.take((size_t)nq * 4), o_offsets = l.take(((size_t)nq + 1u) * 4);
+    if (int rc = ivx_buf_grow(c, &st->lists, l.bytes, 1u << 16)) return rc;
+    st->n_listed = 0u;  // (until this call's lists stand)
+    char* d = static_cast<char*>(st->lists.p);
+    const unsigned long long* d_masks = static_cast<const unsigned long long*>(st->masks.p);
+    uint32_t* d_prefix = reinterpret_cast<uint32_t*>(d + o_prefix);
+    uint32_t* d_totals = reinterpret_cast<uint32_t*>(d + o_totals);
+    uint32_t* d_offsets = reinterpret_cast<uint32_t*>(d + o_offsets);
+    const dim3 words_grid((n_all + 255u) / 256u);
+    IVX_KLAUNCH(k_bv_list_words, words_grid, dim3(256), 0, c->stream, d_masks, n_all, d_prefix);
+    IVX_KLAUNCH(k_bv_list_rows, dim3(nq), dim3(SCAN_ROUND), 0, c->stream, d_prefix, n_words, d_totals);
+    IVX_KLAUNCH(k_bv_list_offsets, dim3(1), dim3(SCAN_ROUND), 0, c->stream, (const uint32_t*)d_totals, nq, d_offsets);
     IVX_HIP_CHECK(hipGetLastError());
-    IVX_HIP_CHECK(ivx_memcpy_async(masks, d_masks, mask_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (counts) IVX_HIP_CHECK(ivx_memcpy_async(counts, d_counts, n_queries * 4, hipMemcpyDeviceToHost, c->stream));
+    uint32_t total = 0;
+    IVX_HIP_CHECK(ivx_memcpy_async(&total, d_offsets + nq, 4, hipMemcpyDeviceToHost, c->stream));
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    *n_out = total;
+    IVX_REQUIRE(!objects || total <= cap, IVX_ERR_CAPACITY, "%s: %u objects hit, the buffer holds %zu", who, total, cap);
+    if (total != 0u) {
+        if (int rc = ivx_buf_grow(c, &st->hits, (size_t)total * 4, 1u << 16)) return rc;
+        IVX_KLAUNCH(k_bv_list_emit, words_grid, dim3(256), 0, c->stream, d_masks, n_words, n_all, (const uint32_t*)d_prefix, (const uint32_t*)d_offsets, total,
+                    static_cast<uint32_t*>(st->hits.p));
+        IVX_HIP_CHECK(hipGetLastError());
+    }
+    st->o_list_offsets = o_offsets, st->n_listed = nq + 1u;
+    if (offsets) IVX_HIP_CHECK(ivx_memcpy_async(offsets, d_offsets, ((size_t)nq + 1u) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (objects && total != 0u) IVX_HIP_CHECK(ivx_memcpy_async(objects, st->hits.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+    if (offsets || (objects && total != 0u)) IVX_HIP_CHECK(ivx_stream_sync(c->stream));
     return IVX_OK;
 }
 
@@ -600,6 +664,8 @@ void* ivx_bv_device_ptr(ivx_ctx* c, int which) {
         case IVX_BV_PTR_MASKS: return st->masks.p;
         case IVX_BV_PTR_NODES:
         case IVX_BV_PTR_LEAF_OBJECTS: return st->has_set ? ivx_bvh_device_ptr(st->hierarchy, st->serial, which) : nullptr;
+        case IVX_BV_PTR_HIT_OFFSETS: return st->has_set && st->n_listed ? static_cast<char*>(st->lists.p) + st->o_list_offsets : nullptr;
+        case IVX_BV_PTR_HIT_OBJECTS: return st->has_set && st->n_listed ? st->hits.p : nullptr;
         default: return nullptr;
     }
 }

@@ -118,6 +118,150 @@ __host__ __device__ inline void ivx_bv_karras(const uint64_t* keys, int n, int i
     *first = (uint32_t)lo, *last = (uint32_t)hi;
 }
 
+// ---- region queries: the leaf decision (bvol.hip's flat kernel, bvh.hip's walk and both host forms run it) and the hierarchy's node decisions ------
+// "has its sign bit set, or is a NaN" for any of six differences
+__host__ __device__ __forceinline__ bool ivx_bv_any_negative(float d0, float d1, float d2, float d3, float d4, float d5) {
+    const uint32_t bits = ((ivx_bv_bits(d0) | ivx_bv_bits(d1)) | (ivx_bv_bits(d2) | ivx_bv_bits(d3))) | (ivx_bv_bits(d4) | ivx_bv_bits(d5));
+    const bool nan = __builtin_isunordered(d0, d1) || __builtin_isunordered(d2, d3) || __builtin_isunordered(d4, d5);
+    return (bits >> 31) != 0u || nan;
+}
+// c and h of a world box, as ivx_bv_world_aabb takes them of a model box
+__host__ __device__ __forceinline__ void ivx_bv_center_half(const ivx_aabb& b, float c[3], float h[3]) {
+    for (int k = 0; k < 3; ++k) c[k] = 0.5f * (b.lower[k] + b.upper[k]), h[k] = 0.5f * (b.upper[k] - b.lower[k]);
+}
+// the four decisions of include/impact_voxel_hip.h over one world box b (c, h: ivx_bv_center_half of b)
+__host__ __device__ __forceinline__ bool ivx_bv_query_hits(const ivx_bv_query* __restrict__ q, const ivx_aabb& b, const float c[3], const float h[3]) {
+    switch (q->kind) {  // (uniform)
+        case IVX_BV_QUERY_BOX:  // box_lies_outside, self = the query
+            return !ivx_bv_any_negative(b.upper[0] - q->u.box.lower[0], b.upper[1] - q->u.box.lower[1], b.upper[2] - q->u.box.lower[2], q->u.box.upper[0] - b.lower[0],
+                                        q->u.box.upper[1] - b.lower[1], q->u.box.upper[2] - b.lower[2]);
+        case IVX_BV_QUERY_SPHERE: {
+            float s = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float ck = q->u.sphere.center[k];
+                if (b.upper[k] < ck) {
+                    const float d = ck - b.upper[k];
+                    s += d * d;
+                } else if (b.lower[k] > ck) {
+                    const float d = b.lower[k] - ck;
+                    s += d * d;
+                }
+            }
+            return !(s > q->u.sphere.radius * q->u.sphere.radius);
+        }
+        case IVX_BV_QUERY_FRUSTUM: {
+            bool hit = true;
+#pragma unroll
+            for (int p = 0; p < 6; ++p) {
+                const uint32_t corner = q->u.frustum.corners[p];
+                const float px = (corner & 4u) ? b.upper[0] : b.lower[0], py = (corner & 2u) ? b.upper[1] : b.lower[1], pz = (corner & 1u) ? b.upper[2] : b.lower[2];
+                const float dist = ((q->u.frustum.planes[p][0] * px + q->u.frustum.planes[p][1] * py) + q->u.frustum.planes[p][2] * pz) - q->u.frustum.planes[p][3];
+                hit = hit && dist >= 0.0f;
+            }
+            return hit;
+        }
+        default: {  // IVX_BV_QUERY_ORIENTED_BOX
+            const float dx = c[0] - q->u.oriented_box.center[0], dy = c[1] - q->u.oriented_box.center[1], dz = c[2] - q->u.oriented_box.center[2];
+            float diff[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float a0 = q->u.oriented_box.axes[a][0], a1 = q->u.oriented_box.axes[a][1], a2 = q->u.oriented_box.axes[a][2];
+                const float e = ((ivx_bv_abs(a0) * h[0] + ivx_bv_abs(a1) * h[1]) + ivx_bv_abs(a2) * h[2]) + q->u.oriented_box.half_extents[a];
+                const float l = (a0 * dx + a1 * dy) + a2 * dz;
+                diff[a] = e - ivx_bv_abs(l);
+            }
+            return !ivx_bv_any_negative(diff[0], diff[1], diff[2], 0.0f, 0.0f, 0.0f);
+        }
+    }
+}
+// An IRREGULAR box: a NaN bound, or lower > upper on an axis (a set stored as given may hold one; the neutral leaf box of a NaN-bounded object is
+// one). The node decisions below are sound for PROPER boxes only — lower <= upper on every axis — so the walk leaves irregular objects alone
+// and every query decides them with the leaf decision, outside the walk.
+__host__ __device__ __forceinline__ bool ivx_bv_irregular(const ivx_aabb& b) {
+    bool r = false;
+    for (int k = 0; k < 3; ++k) r = r || !(b.lower[k] <= b.upper[k]);
+    return r;
+}
+// The node decision: true only when NO proper box inside `nb` (lower >= nb.lower, upper <= nb.upper per component, which the union in the bit
+// order gives every leaf under a node) can be hit by ivx_bv_query_hits in f32. DESIGN.md section 4 gives the argument per kind; in short:
+//   box      box_lies_outside on the node box: each difference is monotone in the bound it takes, the sign-bit and NaN cases included.
+//   sphere   the leaf expression on the node box: per axis the node adds a term only where every leaf inside adds a larger one, and subtraction,
+//            squaring of a non-negative and the running sum are monotone in f32. A NaN compares false: entered.
+//   frustum  NOT the leaf expression (corners[] is caller data, and an unbounded member makes inf - inf): per plane and axis the larger of
+//            n lower and n upper, summed in the leaf's order, minus d; skipped only when that is < 0. A NaN anywhere: entered.
+//   oriented e - |l| is not monotone under f32 rounding, so the node is evaluated in f64 and skipped only when |l| - e exceeds a margin that bounds
+//            the f32 error of the leaf expression for any proper box inside (IVX_BV_OBB_MARGIN_ULPS x 2^-24 x the magnitudes that enter it, plus a
+//            floor for underflow); magnitudes near the f32 range, or a NaN: entered.
+#define IVX_BV_OBB_MARGIN_ULPS 16.0
+__host__ __device__ inline bool ivx_bv_query_skips_node(const ivx_bv_query* __restrict__ q, const ivx_aabb& nb) {
+    switch (q->kind) {  // (uniform)
+        case IVX_BV_QUERY_BOX: {
+            ivx_aabb self;
+            for (int k = 0; k < 3; ++k) self.lower[k] = q->u.box.lower[k], self.upper[k] = q->u.box.upper[k];
+            return ivx_bv_lies_outside(self, nb);
+        }
+        case IVX_BV_QUERY_SPHERE: {
+            float s = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float ck = q->u.sphere.center[k];
+                if (nb.upper[k] < ck) {
+                    const float d = ck - nb.upper[k];
+                    s += d * d;
+                } else if (nb.lower[k] > ck) {
+                    const float d = nb.lower[k] - ck;
+                    s += d * d;
+                }
+            }
+            return s > q->u.sphere.radius * q->u.sphere.radius;
+        }
+        case IVX_BV_QUERY_FRUSTUM: {
+            bool skip = false;
+#pragma unroll
+            for (int p = 0; p < 6; ++p) {
+                float m[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float lo = q->u.frustum.planes[p][k] * nb.lower[k], hi = q->u.frustum.planes[p][k] * nb.upper[k];
+                    m[k] = lo > hi ? lo : hi;  // (hi when either is a NaN ...
+                    if (lo != lo) m[k] = lo;   //  ... so a NaN lo is put back: a NaN on either side stays one)
+                }
+                const float dist = ((m[0] + m[1]) + m[2]) - q->u.frustum.planes[p][3];
+                skip = skip || dist < 0.0f;
+            }
+            return skip;
+        }
+        default: {  // IVX_BV_QUERY_ORIENTED_BOX
+            const double u24 = 5.9604644775390625e-08;  // 2^-24, the unit roundoff of f32
+            double D[3], M[3], H[3], dc[3], reach = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double lo = (double)nb.lower[k], hi = (double)nb.upper[k], ck = (double)q->u.oriented_box.center[k];
+                H[k] = 0.5 * (hi - lo), dc[k] = 0.5 * (lo + hi) - ck;
+                M[k] = __builtin_fmax(__builtin_fabs(lo), __builtin_fabs(hi));
+                D[k] = __builtin_fabs(dc[k]) + H[k];
+                reach = __builtin_fmax(reach, M[k] + __builtin_fabs(ck));  // (fmax drops a NaN; `scale` below keeps it, through D)
+            }
+            bool skip = false;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double a0 = (double)q->u.oriented_box.axes[a][0], a1 = (double)q->u.oriented_box.axes[a][1], a2 = (double)q->u.oriented_box.axes[a][2];
+                const double b0 = __builtin_fabs(a0), b1 = __builtin_fabs(a1), b2 = __builtin_fabs(a2), half = (double)q->u.oriented_box.half_extents[a];
+                const double e = ((b0 * H[0] + b1 * H[1]) + b2 * H[2]) + half;
+                const double l = (a0 * dc[0] + a1 * dc[1]) + a2 * dc[2];
+                // what the f32 leaf expression's intermediates are bounded by, and its error in units of 2^-24 of
+                const double scale = ((b0 * (D[0] + M[0]) + b1 * (D[1] + M[1])) + b2 * (D[2] + M[2])) + __builtin_fabs(half);
+                // the floor: 2^-126 a product or a halving may lose when f32 results are flushed (2^-150 when they are not), the halving's times |A|
+                const double margin = IVX_BV_OBB_MARGIN_ULPS * (u24 * scale + ((b0 + b1) + b2 + 1.0) * 1.1754943508222875e-38);
+                const bool in_range = scale < 0x1p+120 && reach < 0x1p+120;  // (no f32 intermediate overflows; false for a NaN)
+                skip = skip || (in_range && __builtin_fabs(l) - e > margin);
+            }
+            return skip;
+        }
+    }
+}
+
 // What bvh.hip takes from the context's set (bvol.hip owns it): the resident world boxes and kinds, the set's serial, the pair buffer both pair
 // passes leave their result in, and the slot that holds the hierarchy's own state (freed through ivx_bvh_release when the set's state goes).
 struct ivx_bvol_view {
@@ -134,6 +278,21 @@ void* ivx_bvh_device_ptr(void* hierarchy, uint64_t set_serial, int which);  // I
 // ivx_bv_build_hierarchy and the pair pass of ivx_bv_pairs_hierarchy, with ivx_bvol_pairs_enqueue's contract (narrow.hip drives both)
 int ivx_bvh_build_enqueue(ivx_ctx* c, const char* who);
 int ivx_bvh_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool check_cap, size_t cap, size_t* n_pairs);
+
+// ivx_bv_queries in two halves, with whoever fills the masks in between (bvol.hip's flat kernel; bvh.hip's walk):
+//   begin:  the flat call's refusals (who names the caller), then the records uploaded, the mask buffer grown. run->n_queries == 0 or run->n == 0:
+//           nothing is on the device and `finish` only fills the counts with zeros.
+//   finish: k_bv_query_counts, the download of masks and counts, the call's one wait; remembers the call for ivx_bv_query_lists.
+struct ivx_bvol_query_run {
+    const ivx_bv_query* d_queries = nullptr;
+    unsigned long long* d_masks = nullptr;
+    uint32_t* d_counts = nullptr;
+    uint32_t n = 0, n_words = 0, n_queries = 0;
+    size_t mask_bytes = 0;
+};
+int ivx_bvol_queries_check(const char* who, ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries);
+int ivx_bvol_queries_begin(ivx_ctx* c, const char* who, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, ivx_bvol_query_run* run);
+int ivx_bvol_queries_finish(ivx_ctx* c, const ivx_bvol_query_run& run, uint64_t* masks, uint32_t* counts);
 
 // A set of n world boxes whose inputs a kernel of the caller writes on the context's stream, no host copy involved:
 //   begin:  lays the context's set buffer out for n objects (the context holds no set until `finish`) and hands out where the boxes (n, world

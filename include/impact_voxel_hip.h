@@ -963,7 +963,8 @@ void* ivx_cull_device_ptr(ivx_ctx*, int which);
  * touches (ivx_bv_queries with a box or a sphere), the per-(view, object) IVX_CULL_PAIR_SKIP bit (ivx_bv_queries with frusta / oriented boxes).
  * Two forms of the pair pass that leave the same bytes: the exact upper triangle (the reference's own `_brute_force` form, csrc/bvol.hip; the
  * default everywhere) and a linear hierarchy built over the set on request (ivx_bv_build_hierarchy, csrc/bvh.hip; further down). Region queries
- * use the flat form only. */
+ * have the same two forms with the same bytes (ivx_bv_queries, the default; ivx_bv_queries_hierarchy), and their masks become hit lists on the
+ * device (ivx_bv_query_lists). */
 /* AxisAlignedBoxC. 24 bytes. */
 typedef struct {
     float lower[3], upper[3];
@@ -1115,7 +1116,37 @@ void* ivx_bv_device_ptr(ivx_ctx*, int which);
  *   inconsistent ends the call with IVX_ERR_STATE and a message. Device scratch: O(n) for the tree, 8 bytes per pair for the sort.
  * ivx_cw_set_broad_phase (a collision world, below): IVX_CW_BROAD_FLAT (the default) or IVX_CW_BROAD_HIERARCHY; any other value is IVX_ERR_INVALID
  *   and leaves the setting as it was. With the hierarchy, ivx_cw_collide builds it over the set ivx_cw_synchronize installed and takes its pairs
- *   from the tree; contacts and deferred pairs are the same bytes under both settings. */
+ *   from the tree; contacts and deferred pairs are the same bytes under both settings.
+ * ivx_bv_queries_hierarchy: THE CONTRACT AND THE BYTES OF ivx_bv_queries — the same masks (bits past n zero), counts, limits and refusals, the masks
+ *   left in the context's mask buffer (IVX_BV_PTR_MASKS); n == 0 and n_queries == 0 as there. State as ivx_bv_pairs_hierarchy: IVX_ERR_STATE
+ *   without a set or without a hierarchy of the current set; a bracket is flushed first; a walk past its 2 n steps ends the call with
+ *   IVX_ERR_STATE and a message. A workgroup per query: it expands the top of the tree until it holds 256 subtrees or more, then a lane walks
+ *   each without a stack. A leaf is decided by the decisions above on its object's world box; a hit is an OR into the mask, which the call
+ *   zeroes first: two calls leave the same bytes. n == 1 has no nodes: the one object is decided directly.
+ *   A NODE IS SKIPPED only if no leaf under it can be hit by those decisions in f32 (DESIGN.md section 4 has the arguments). This holds for
+ *   PROPER boxes, lower <= upper on every axis, which a node's box contains bound by bound. An IRREGULAR object — a NaN bound (the sphere decision
+ *   hits it), or lower > upper on an axis (a set stored as given may hold one) — is left out by the walk and decided by every query directly;
+ *   the build keeps their list. With nb the node's box:
+ *     box:      skipped when nb lies outside the query (the box decision above, self = the query).
+ *     sphere:   the sphere expression on nb; skipped when s > radius x radius. A NaN compares false: entered.
+ *     frustum:  not the leaf expression — corners[] is the caller's, and an unbounded member gives inf - inf. Per plane p and axis k
+ *               m[k] = the larger of n[k] nb.lower[k] and n[k] nb.upper[k], a NaN if either is; skipped when ((m[0] + m[1]) + m[2]) - d < 0 for
+ *               some plane. A NaN: entered.
+ *     oriented: evaluated in f64 — e - |l| is not monotone in the box under f32 rounding. With H = 0.5 (nb.upper - nb.lower),
+ *               dc = 0.5 (nb.lower + nb.upper) - center, M[k] = max(|nb.lower[k]|, |nb.upper[k]|), D[k] = |dc[k]| + H[k], per axis a of the query
+ *               E = sum_k |A[a][k]| H[k] + half[a], L = sum_k A[a][k] dc[k], S = sum_k |A[a][k]| (D[k] + M[k]) + |half[a]|:
+ *               skipped when |L| - E > 16 (2^-24 S + (sum_k |A[a][k]| + 1) 2^-126) for some a, provided S < 2^120 and
+ *               M[k] + |center[k]| < 2^120 for every k. A NaN: entered.
+ *   ivx_bv_query_skips_boxes: that decision for every query and every box, on the host (skips[q * n_boxes + b] = 1: skipped).
+ * ivx_bv_queries_hierarchy_host: the same over a tree of the caller's (ivx_bv_hierarchy_host's output, say), with the same decision functions, on
+ *   the host; n above IVX_BV_MAX_OBJECTS or n_queries above IVX_BV_MAX_QUERIES: IVX_ERR_CAPACITY; a tree that is none (a child out of range, a
+ *   walk past 2 n steps): IVX_ERR_STATE. nodes may be NULL for n < 2.
+ * ivx_bv_query_lists: the hit lists of the context's last queries call (either form), expanded on the device from the resident masks: a popcount per
+ *   mask word, a prefix per query and over the queries, then every word emits its objects — no sort, no atomic. offsets[n_queries + 1] (may be
+ *   NULL); query q's objects are objects[offsets[q] .. offsets[q + 1]) in ascending object index. *n_out is the total even when it exceeds cap; the
+ *   call then returns IVX_ERR_CAPACITY and writes nothing. objects == NULL with cap == 0 leaves the lists on the device only:
+ *   ivx_bv_device_ptr(IVX_BV_PTR_HIT_OFFSETS / _HIT_OBJECTS) names them (NULL until a call has made them, and again after the next queries call
+ *   or set). IVX_ERR_STATE when no queries call with n_queries > 0 has run since the last set, or when the set is empty. */
 #define IVX_BV_LEAF 0x80000000u /* child reference: bit 31 set = leaf, low bits = leaf position in Morton order */
 typedef struct {
     float lower[3], upper[3];
@@ -1130,6 +1161,13 @@ int ivx_bv_hierarchy_host(const ivx_aabb* world, size_t n, ivx_bv_node* nodes, u
 int ivx_bv_build_hierarchy(ivx_ctx*);
 int ivx_bv_hierarchy_download(ivx_ctx*, ivx_bv_node* nodes, size_t node_cap, uint32_t* leaf_objects, size_t leaf_cap, size_t* n_nodes);
 int ivx_bv_pairs_hierarchy(ivx_ctx*, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n_out);
+#define IVX_BV_PTR_HIT_OFFSETS 5
+#define IVX_BV_PTR_HIT_OBJECTS 6
+int ivx_bv_queries_hierarchy(ivx_ctx*, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, uint32_t* counts);
+int ivx_bv_queries_hierarchy_host(const ivx_aabb* world, size_t n, const ivx_bv_node* nodes, const uint32_t* leaf_objects, const ivx_bv_query* queries, size_t n_queries,
+                                  uint64_t* masks, uint32_t* counts);
+int ivx_bv_query_skips_boxes(const ivx_bv_query* queries, size_t n_queries, const ivx_aabb* boxes, size_t n_boxes, uint8_t* skips);
+int ivx_bv_query_lists(ivx_ctx*, uint32_t* offsets, uint32_t* objects, size_t cap, size_t* n_out);
 int ivx_cw_set_broad_phase(ivx_world*, uint32_t which);
 
 /* ---- primitive collidables: follow the bodies, narrow phase over the pairs (impact_physics/src/collision.rs:175-261, 317-373

@@ -13,6 +13,13 @@ pairs, and set + pairs + download for both forms (the tree form's includes its b
 `--sizes` adds the seeded recipe at the given sizes, to find where the tree form first wins.
 
   python tools/time_bvh.py            all scenes, each in a child process under its own time limit, one child at a time
+  python tools/time_bvh.py --leg queries
+                                      the region queries instead (`ivx_bv_queries_hierarchy` against `ivx_bv_queries`, and `ivx_bv_query_lists`):
+                                      refbench, the shape of the reference's own benchmark (25 000 stratified boxes under 1 000 box queries of half
+                                      extent 0.5 to half the scene), and small<n> (64 absorber-sized boxes and 11 frusta) over 4 096, 65 536 and
+                                      2^20 stratified boxes. Per workload: both forms, twice each, alternating; the masks' download on its own
+                                      (the calls always download: `_without_download_ms` is the better call less that copy); the build; the
+                                      list expansion with its results left on the device and downloaded
   python tools/time_bvh.py --trace    also each scene once more under `rocprofv3 --kernel-trace --stats` (a run of its own) and the average
                                       time of every k_bv_ / k_bvh_ kernel"""
 import argparse
@@ -116,6 +123,124 @@ def workload(scene, calls, warmup):
     return out
 
 
+QUERY_WORKLOADS = ["refbench", "small4096", "small65536", "small1048576"]
+
+
+def stratified_boxes(n, seed=1):
+    """the shape of the reference benchmark's set: one box per cell of a cubic lattice of cell size 2, its centre offset by up to 1 per axis in
+    steps of 1/256, its half extent 0.25 .. 0.75 in steps of 1/512 (seeded here; the reference hashes the index)"""
+    import numpy as np
+
+    from impact_amd import bvol
+
+    rng = np.random.default_rng(seed)
+    per_axis = int(np.ceil(np.cbrt(n)))
+    i = np.arange(n)
+    cell = np.stack([i % per_axis, (i // per_axis) % per_axis, i // (per_axis * per_axis)], axis=1).astype(np.float64)
+    centre = 2.0 * cell + rng.integers(0, 256, (n, 3)) / 256.0
+    half = (0.25 + rng.integers(0, 256, n) / 512.0)[:, None]
+    return bvol.boxes(centre - half, centre + half)
+
+
+def query_records(name, boxes, seed=2):
+    """refbench: 1 000 box queries centred anywhere in the set's extent, half extent 0.5 .. 0.5 + half the largest extent. small<n>: 64
+    absorber-sized boxes (half extent 1 .. 3) and 11 frusta (a camera, six cube faces and four cascades' worth: boxes of a tenth to a half of the
+    extent under rotations uniform on the sphere)"""
+    import numpy as np
+
+    import bvh_query_cases as qc
+    from impact_amd import bvol
+
+    rng = np.random.default_rng(seed)
+    lo, hi = boxes["lower"].min(axis=0).astype(np.float64), boxes["upper"].max(axis=0).astype(np.float64)
+    out = []
+    if name == "refbench":
+        for _ in range(1000):
+            centre, half = rng.uniform(lo, hi), 0.5 + rng.integers(0, 256) / 255.0 * float((hi - lo).max()) * 0.5
+            out.append(bvol.box_query(centre - half, centre + half))
+        return bvol.query_array(out)
+    for _ in range(64):
+        centre, half = rng.uniform(lo, hi), rng.uniform(1.0, 3.0, 3)
+        out.append(bvol.box_query(centre - half, centre + half))
+    for _ in range(11):
+        half = rng.uniform(0.1, 0.5) * (hi - lo) * 0.5
+        out.append(bvol.frustum_query(qc.box_planes(rng.uniform(lo, hi), qc.random_rotation(rng), half)))
+    return bvol.query_array(out)
+
+
+def query_workload(name, calls, warmup):
+    """one workload of the queries leg: both forms in the same process, alternating; the masks' download timed on its own (the calls always
+    download: `without` is the call less that copy), and the list expansion on its own"""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    from impact_amd import capi
+    from impact_amd.voxel import Context
+
+    stream = torch.cuda.Stream()
+    ctx = Context(0, stream.cuda_stream)
+    lib = capi.lib()
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    n = 25000 if name == "refbench" else int(name[5:])
+    boxes = stratified_boxes(n)
+    queries = query_records(name, boxes)
+    nq, words = len(queries), (n + 63) // 64
+    found = C.c_size_t(0)
+
+    def ok(rc):
+        if rc:
+            capi.check(rc)
+
+    ok(lib.ivx_bv_set(ctx.h, boxes.ctypes.data, None, None, n))
+    ok(lib.ivx_bv_build_hierarchy(ctx.h))
+    flat_masks, tree_masks = np.zeros((nq, words), dtype=np.uint64), np.zeros((nq, words), dtype=np.uint64)
+    flat_counts, tree_counts = np.zeros(nq, dtype=np.uint32), np.zeros(nq, dtype=np.uint32)
+    flat_call = lambda: ok(lib.ivx_bv_queries(ctx.h, queries.ctypes.data, nq, flat_masks.ctypes.data, flat_counts.ctypes.data))
+    tree_call = lambda: ok(lib.ivx_bv_queries_hierarchy(ctx.h, queries.ctypes.data, nq, tree_masks.ctypes.data, tree_counts.ctypes.data))
+    build_call = lambda: ok(lib.ivx_bv_build_hierarchy(ctx.h))
+    flat_call()
+    d_masks = lib.ivx_bv_device_ptr(ctx.h, capi.BV_PTR_MASKS)
+    copy = np.zeros((nq, words), dtype=np.uint64)
+
+    def download_call():
+        assert hip.hipMemcpyAsync(copy.ctypes.data, d_masks, copy.nbytes, 2, stream.cuda_stream) == 0
+        stream.synchronize()
+
+    ok(lib.ivx_bv_query_lists(ctx.h, None, None, 0, C.byref(found)))
+    total = found.value
+    offsets, objects = np.zeros(nq + 1, dtype=np.uint32), np.zeros(max(1, total), dtype=np.uint32)
+    lists_resident = lambda: ok(lib.ivx_bv_query_lists(ctx.h, None, None, 0, C.byref(found)))
+    lists_download = lambda: ok(lib.ivx_bv_query_lists(ctx.h, offsets.ctypes.data, objects.ctypes.data, total, C.byref(found)))
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            start.record(stream)
+            for _ in range(calls):
+                fn()
+            stop.record(stream)
+        stop.synchronize()
+        return round(start.elapsed_time(stop) / calls, 4)
+
+    out = {"workload": name, "objects": n, "queries": nq, "calls": calls, "warmup": warmup}
+    out["tree_queries_ms"], out["flat_queries_ms"] = timed(tree_call), timed(flat_call)
+    out["tree_queries_again_ms"], out["flat_queries_again_ms"] = timed(tree_call), timed(flat_call)
+    out["mask_download_ms"], out["build_ms"] = timed(download_call), timed(build_call)
+    for form in ("tree", "flat"):
+        out[f"{form}_without_download_ms"] = round(min(out[f"{form}_queries_ms"], out[f"{form}_queries_again_ms"]) - out["mask_download_ms"], 4)
+    out["lists_resident_ms"], out["lists_download_ms"] = timed(lists_resident), timed(lists_download)
+    out["hits"], out["mask_bytes"] = int(total), int(copy.nbytes)
+    if tree_masks.tobytes() != flat_masks.tobytes() or tree_counts.tobytes() != flat_counts.tobytes():
+        raise SystemExit(f"{name}: the two forms returned different masks")
+    ctx.close()
+    return out
+
+
 def kernel_times(db_path):
     db = sqlite3.connect(db_path)
     rows = db.execute("select name, count(*), avg(end-start) from kernels where name like '%k_bv%' group by name order by 3 desc")
@@ -132,13 +257,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trace", action="store_true", help="also run each scene under rocprofv3 --kernel-trace --stats and report the kernel times")
     ap.add_argument("--limit", type=int, default=240, help="time limit of each child process in seconds")
+    ap.add_argument("--leg", choices=["pairs", "queries"], default="pairs", help="queries: the region queries through both forms, --scene one of " + ", ".join(QUERY_WORKLOADS))
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        print(json.dumps(workload(args.scene, args.calls, args.warmup)))
+        print(json.dumps((query_workload if args.leg == "queries" else workload)(args.scene, args.calls, args.warmup)))
         return
-    me = [sys.executable, os.path.abspath(__file__), "--child", "--calls", str(args.calls), "--warmup", str(args.warmup)]
-    for scene in (SCENES if args.scene == "all" else [args.scene]) + [f"seeded{n}" for n in args.sizes]:
+    me = [sys.executable, os.path.abspath(__file__), "--child", "--leg", args.leg, "--calls", str(args.calls), "--warmup", str(args.warmup)]
+    scenes_of_leg = QUERY_WORKLOADS if args.leg == "queries" else SCENES
+    for scene in (scenes_of_leg if args.scene == "all" else [args.scene]) + [f"seeded{n}" for n in args.sizes]:
         # (a step that fails or runs out of time ends the run: nothing more is started on the device)
         out = json.loads(run_limited(me + ["--scene", scene], args.limit).strip().splitlines()[-1])
         if args.trace:

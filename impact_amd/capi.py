@@ -207,6 +207,15 @@ BV_NODE_DTYPE = np.dtype([("lower", "<f4", (3,)), ("upper", "<f4", (3,)), ("left
 BV_LEAF = 0x80000000
 CW_BROAD_FLAT, CW_BROAD_HIERARCHY = 0, 1
 assert BV_NODE_DTYPE.itemsize == 32
+# frame instances (csrc/instances.hip): `ivx_fi_instance` (one per object of the context's set), `ivx_fi_view`, `ivx_fi_view_result`
+FI_INSTANCE_DTYPE = np.dtype([("model_to_world", SIMILARITY_DTYPE), ("flags", "<u4"), ("entity", "<u4"), ("reserved", "<u4", (2,))])
+FI_VIEW_DTYPE = np.dtype([("world_to_view", SIMILARITY_DTYPE), ("query", "<u4"), ("reject_flags", "<u4"), ("exclude_entity", "<u4"), ("and_view", "<u4"),
+                          ("instance_base", "<u4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("squared_reach", "<f4")])
+FI_VIEW_RESULT_DTYPE = np.dtype([("count", "<u4"), ("world_box", AABB_DTYPE), ("view_box", AABB_DTYPE), ("min_squared_distance", "<f4"), ("max_squared_distance", "<f4")])
+FI_ABSENT, FI_HIDDEN, FI_CASTS_NO_SHADOWS, FI_SHADOWS_OFF_BY_DISTANCE, FI_NO_SHADOW_FEATURES, FI_ALL_FLAGS = 1, 2, 4, 8, 16, 31
+FI_NONE, FI_VIEW_REACH, FI_VIEW_BOX, FI_MAX_VIEWS = 0xFFFFFFFF, 1, 2, 64
+FI_PTR_INSTANCES, FI_PTR_PAIRS, FI_PTR_OFFSETS, FI_PTR_OBJECTS, FI_PTR_TRANSFORMS, FI_PTR_KEPT_MASKS, FI_PTR_RESULTS = 0, 1, 2, 3, 4, 5, 6
+assert FI_INSTANCE_DTYPE.itemsize == 48 and FI_VIEW_DTYPE.itemsize == 72 and FI_VIEW_RESULT_DTYPE.itemsize == 60
 # primitive collidables (csrc/narrow.hip): `ivx_collidable`, in its body's frame or in world space
 COLLIDABLE_DTYPE = np.dtype([("shape", "<u4"), ("kind", "<u4"), ("body", "<u4"), ("reserved", "<u4"), ("id", "<u8"), ("a", "<f4", (3,)), ("b", "<f4", (3,)), ("s", "<f4"),
                              ("response", "<f4", (3,))])
@@ -268,6 +277,7 @@ EXPORTED_SYMBOLS = [
     "ivx_bv_device_ptr",
     "ivx_bv_morton_key", "ivx_bv_hierarchy_host", "ivx_bv_build_hierarchy", "ivx_bv_hierarchy_download", "ivx_bv_pairs_hierarchy", "ivx_cw_set_broad_phase",
     "ivx_bv_queries_hierarchy", "ivx_bv_queries_hierarchy_host", "ivx_bv_query_skips_boxes", "ivx_bv_query_lists",
+    "ivx_fi_set_instances", "ivx_fi_views", "ivx_fi_download", "ivx_fi_device_ptr", "ivx_fi_views_host", "ivx_cull_many_resident",
     "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
     "ivx_world_set_motion_drivers", "ivx_world_set_time", "ivx_world_time", "ivx_world_apply_motion", "ivx_md_eval", "ivx_md_apply_host",
     "ivx_world_set_force_generators", "ivx_world_set_dynamic_gravity", "ivx_world_apply_forces", "ivx_world_gravity_loads", "ivx_fg_apply_host",
@@ -305,6 +315,7 @@ def extra_struct_sizes():
         "ivx_cull_object": (CULL_OBJECT_DTYPE, 8), "ivx_draw_args": (DRAW_ARGS_DTYPE, 16), "ivx_draw_indexed_args": (DRAW_INDEXED_ARGS_DTYPE, 20),
         "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
         "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128), "ivx_bv_node": (BV_NODE_DTYPE, 32),
+        "ivx_fi_instance": (FI_INSTANCE_DTYPE, 48), "ivx_fi_view": (FI_VIEW_DTYPE, 72), "ivx_fi_view_result": (FI_VIEW_RESULT_DTYPE, 60),
         "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
         "ivx_force_generator": (FORCE_GENERATOR_DTYPE, 64),
         "ivx_uniform_medium": (UNIFORM_MEDIUM_DTYPE, 16), "ivx_drag_generator": (DRAG_GENERATOR_DTYPE, 16), "ivx_drag_map_view": (DRAG_MAP_VIEW_DTYPE, 16),
@@ -511,6 +522,12 @@ def lib():
         "ivx_bv_query_skips_boxes": (i32, [vp, sz, vp, sz, vp]),
         "ivx_bv_query_lists": (i32, [vp, vp, vp, sz, C.POINTER(sz)]),
         "ivx_cw_set_broad_phase": (i32, [vp, u32]),
+        "ivx_fi_set_instances": (i32, [vp, vp, sz]),
+        "ivx_fi_views": (i32, [vp, vp, sz, vp]),
+        "ivx_fi_download": (i32, [vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, C.POINTER(sz)]),
+        "ivx_fi_device_ptr": (vp, [vp, i32]),
+        "ivx_fi_views_host": (i32, [vp, sz, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
+        "ivx_cull_many_resident": (i32, [vp, sz, vp, vp, vp, sz, u32, vp]),
         "ivx_cw_transform": (i32, [vp, vp, vp, vp, vp]),
         "ivx_cw_contact": (i32, [vp, vp, vp, C.POINTER(i32)]),
         "ivx_cw_set_collidables": (i32, [vp, vp, sz]),

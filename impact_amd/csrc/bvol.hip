@@ -384,6 +384,8 @@ int ivx_bvol_view_of(ivx_ctx* c, const char* who, ivx_bvol_view* out) {
     out->n = st->n, out->serial = st->serial, out->pairs = &st->pairs, out->hierarchy = &st->hierarchy;
     out->world = st->n ? reinterpret_cast<const ivx_aabb*>(d + st->o_world) : nullptr;
     out->kinds = st->n ? reinterpret_cast<const uint32_t*>(d + st->o_kinds) : nullptr;
+    out->n_queried = st->queried ? st->n_queried : 0u;
+    out->masks = st->queried && st->n ? static_cast<const unsigned long long*>(st->masks.p) : nullptr;
     return IVX_OK;
 }
 

@@ -271,6 +271,8 @@ struct ivx_bvol_view {
     uint64_t serial = 0;
     ivx_buf* pairs = nullptr;
     void** hierarchy = nullptr;
+    const unsigned long long* masks = nullptr;  // the resident masks of the last queries call on this set (either form), n_queried rows; ...
+    uint32_t n_queried = 0;                     // ... 0: no queries call has left any since the set
 };
 int ivx_bvol_view_of(ivx_ctx* c, const char* who, ivx_bvol_view* out);  // IVX_ERR_STATE without a set
 void ivx_bvh_release(void* hierarchy);

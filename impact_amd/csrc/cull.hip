@@ -17,11 +17,14 @@
 //   the view's count record. No atomics anywhere: the order of a compacted list is (object, submesh) and two calls leave the same bytes.
 // PLACE — k_cull_place (mode 1), one wave per (tile, view): a drawn lane's slot is the tile's prefix plus the set bits of the mask below it; every
 //   lane whose own slot lies at or behind the view's count zeroes that slot — the two sets of slots are disjoint and together cover the region.
+// GATHER — k_cull_gather (ivx_cull_many_resident), one lane per (view, object): the pair and its flags from the frame-instance pairs the context
+//   holds (instances.hip), at the object's index there, to where the upload of the other entry points puts them.
 #include <cmath>
 #include <new>
 #include <vector>
 
 #include "device_common.hpp"
+#include "instances_internal.hpp"
 
 namespace {
 
@@ -129,6 +132,18 @@ __global__ __launch_bounds__(256) void k_cull_frusta(const ivx_cull_view* __rest
     ivx_culling_frustum f;
     derive_frustum(&v, &p, objs[i % n_obj].chunk_extent, &f);
     out[i] = f;
+}
+
+// pairs[v * n_obj + g] = src[v * src_n + index[g]] (index null: g), and the pair's flags beside it
+__global__ __launch_bounds__(256) void k_cull_gather(const ivx_cull_pair* __restrict__ src, uint32_t src_n, const uint32_t* __restrict__ index, uint32_t n_views, uint32_t n_obj,
+                                                     ivx_cull_pair* __restrict__ pairs, uint32_t* __restrict__ pair_flags) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_views * n_obj) return;
+    const uint32_t v = i / n_obj, g = i - v * n_obj;
+    const uint32_t o = index ? index[g] : g;
+    const ivx_cull_pair p = src[(size_t)v * src_n + (o < src_n ? o : 0u)];  // (the host has refused an index past src_n)
+    pairs[i] = p;
+    pair_flags[i] = p.flags;
 }
 
 __device__ __forceinline__ void store_args(char* __restrict__ region, uint32_t indexed, uint32_t slot, uint32_t index_count, uint32_t instance_count, uint32_t first_index,
@@ -275,13 +290,17 @@ struct CullJob {
     const uint32_t* view_flags;
     const uint32_t* pair_flags;
     uint32_t mode;
+    // ivx_cull_many_resident: the frame-instance pairs on the device ([n_views][fi_n]) in place of `pairs`, and which of them each object takes (null: its own index)
+    const ivx_cull_pair* fi_pairs;
+    uint32_t fi_n;
+    const uint32_t* object_indices;
 };
 
 int check_views_and_pairs(const char* who, const ivx_cull_view* views, size_t n_views, const ivx_cull_pair* pairs, const float* extents, size_t n_obj) {
     for (size_t v = 0; v < n_views; ++v)
         IVX_REQUIRE(views[v].kind <= 1u, IVX_ERR_INVALID, "%s: view %zu has kind %u (0 = frustum planes, 1 = orthographic box)", who, v, views[v].kind);
     for (size_t o = 0; o < n_obj; ++o) IVX_REQUIRE(extents[o] > 0.0f, IVX_ERR_INVALID, "%s: the chunk extent %g of object %zu is not positive", who, (double)extents[o], o);
-    for (size_t i = 0; i < n_views * n_obj; ++i)
+    for (size_t i = 0; i < n_views * n_obj && pairs; ++i)  // (pairs null: they are on the device, ivx_cull_many_resident)
         IVX_REQUIRE(pairs[i].scaling > 0.0f, IVX_ERR_INVALID, "%s: the scaling %g of pair %zu (view %zu, object %zu) is not positive", who, (double)pairs[i].scaling, i, i / n_obj,
                     i % n_obj);
     return IVX_OK;
@@ -318,11 +337,18 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
     if (n_views == 0) return done();
     // one staging block: views | pairs | records | pair flags | objects | view regions | tiles | tables
     ivx_layout l;
-    const size_t o_views = l.take(j.records ? 0 : n_views * sizeof(ivx_cull_view)), o_pairs = l.take(j.records ? 0 : n_pairs * sizeof(ivx_cull_pair)),
-                 o_recs = l.take(j.records ? n_pairs * sizeof(ivx_culling_frustum) : 0), o_flags = l.take(n_pairs * 4), o_objs = l.take(n_obj * sizeof(CullObj)),
-                 o_vout = l.take(n_views * sizeof(CullViewOut)), o_tiles = l.take(n_tiles * sizeof(uint2)), o_tables = l.take(table_bytes);
+    // (resident pairs: pairs and pair flags lie behind the upload, where k_cull_gather writes them, and the objects' indices ride the upload)
+    const bool resident = j.fi_pairs != nullptr;
+    size_t o_pairs = l.take(0), o_flags = 0;
+    const size_t o_views = l.take(j.records ? 0 : n_views * sizeof(ivx_cull_view));
+    if (!resident) o_pairs = l.take(j.records ? 0 : n_pairs * sizeof(ivx_cull_pair));
+    const size_t o_recs = l.take(j.records ? n_pairs * sizeof(ivx_culling_frustum) : 0);
+    if (!resident) o_flags = l.take(n_pairs * 4);
+    const size_t o_objs = l.take(n_obj * sizeof(CullObj)), o_vout = l.take(n_views * sizeof(CullViewOut)), o_tiles = l.take(n_tiles * sizeof(uint2)), o_tables = l.take(table_bytes),
+                 o_index = l.take(resident && j.object_indices ? n_obj * 4 : 0);
     const size_t upload_bytes = l.bytes;
     const size_t o_info = l.take(n_views * n_tiles * sizeof(uint4));
+    if (resident) o_pairs = l.take(n_pairs * sizeof(ivx_cull_pair)), o_flags = l.take(n_pairs * 4);
     if (int rc = ivx_staging_for(&st->staging, upload_bytes)) return rc;
     if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 20)) return rc;
     if (int rc = ivx_buf_grow(c, &st->args, regions.bytes, 1u << 20)) return rc;
@@ -333,10 +359,14 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
         if (n_pairs) memcpy(h + o_recs, j.frusta, n_pairs * sizeof(ivx_culling_frustum));
     } else {
         memcpy(h + o_views, j.views, n_views * sizeof(ivx_cull_view));
-        if (n_pairs) memcpy(h + o_pairs, j.pairs, n_pairs * sizeof(ivx_cull_pair));
+        if (n_pairs && !resident) memcpy(h + o_pairs, j.pairs, n_pairs * sizeof(ivx_cull_pair));
     }
-    uint32_t* flags = reinterpret_cast<uint32_t*>(h + o_flags);
-    for (size_t i = 0; i < n_pairs; ++i) flags[i] = j.records ? (j.pair_flags ? j.pair_flags[i] : 0u) : j.pairs[i].flags;
+    if (resident) {
+        if (j.object_indices) memcpy(h + o_index, j.object_indices, n_obj * 4);
+    } else {
+        uint32_t* flags = reinterpret_cast<uint32_t*>(h + o_flags);
+        for (size_t i = 0; i < n_pairs; ++i) flags[i] = j.records ? (j.pair_flags ? j.pair_flags[i] : 0u) : j.pairs[i].flags;
+    }
     CullObj* objs = reinterpret_cast<CullObj*>(h + o_objs);
     uint2* tiles = reinterpret_cast<uint2*>(h + o_tiles);
     size_t tile = 0, table_at = o_tables;
@@ -365,6 +395,10 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
     st->staging.pending = true;
     ivx_culling_frustum* d_frusta = static_cast<ivx_culling_frustum*>(st->frusta.p);
     const CullObj* d_objs = reinterpret_cast<const CullObj*>(d + o_objs);
+    if (n_pairs && resident)
+        IVX_KLAUNCH(k_cull_gather, dim3((uint32_t)((n_pairs + 255u) / 256u)), dim3(256), 0, c->stream, j.fi_pairs, j.fi_n,
+                    j.object_indices ? reinterpret_cast<const uint32_t*>(d + o_index) : (const uint32_t*)nullptr, (uint32_t)n_views, (uint32_t)n_obj,
+                    reinterpret_cast<ivx_cull_pair*>(d + o_pairs), reinterpret_cast<uint32_t*>(d + o_flags));
     if (n_pairs) {
         if (j.records)
             IVX_HIP_CHECK(ivx_memcpy_async(d_frusta, d + o_recs, n_pairs * sizeof(ivx_culling_frustum), hipMemcpyDeviceToDevice, c->stream));
@@ -430,7 +464,7 @@ int resident_tables(const char* who, ivx_grid* const* grids, size_t n, std::vect
 // zero counts, written here — no object names a context, and none is needed
 int many_enqueue(const char* who, ivx_grid* const* grids, size_t n, const ivx_cull_object* objects, bool records, const ivx_cull_view* views, size_t n_views,
                  const ivx_cull_pair* pairs, const ivx_culling_frustum* frusta, const uint32_t* view_flags, const uint32_t* pair_flags, uint32_t mode,
-                 ivx_cull_region* out_layout, ivx_cull_count* out_counts, ivx_ctx** ctx_out) {
+                 ivx_cull_region* out_layout, ivx_cull_count* out_counts, ivx_ctx** ctx_out, bool resident = false, const uint32_t* object_indices = nullptr) {
     *ctx_out = nullptr;
     IVX_REQUIRE(n_views <= MAX_VIEWS, IVX_ERR_INVALID, "%s: %zu views exceed %u per call", who, n_views, MAX_VIEWS);
     IVX_REQUIRE(mode <= 1u, IVX_ERR_INVALID, "%s: mode %u (0 = zeroed in place, 1 = compacted)", who, mode);
@@ -439,7 +473,7 @@ int many_enqueue(const char* who, ivx_grid* const* grids, size_t n, const ivx_cu
     if (records)
         IVX_REQUIRE(n_views == 0 || (view_flags && (frusta || n == 0)), IVX_ERR_INVALID, "%s: null argument", who);
     else
-        IVX_REQUIRE(n_views == 0 || (views && (pairs || n == 0)), IVX_ERR_INVALID, "%s: null argument", who);
+        IVX_REQUIRE(n_views == 0 || (views && (pairs || n == 0 || resident)), IVX_ERR_INVALID, "%s: null argument", who);
     if (!records)
         for (size_t v = 0; v < n_views; ++v)
             IVX_REQUIRE(views[v].kind <= 1u, IVX_ERR_INVALID, "%s: view %zu has kind %u (0 = frustum planes, 1 = orthographic box)", who, v, views[v].kind);
@@ -458,9 +492,19 @@ int many_enqueue(const char* who, ivx_grid* const* grids, size_t n, const ivx_cu
     if (!records && n_views)
         if (int rc = check_views_and_pairs(who, views, n_views, pairs, extents.data(), n)) return rc;
     ivx_ctx* c = grids[0]->ctx;
+    const ivx_cull_pair* fi_pairs = nullptr;
+    uint32_t fi_n = 0;
+    if (resident) {
+        if (int rc = ivx_fi_resident_pairs(c, who, n_views, &fi_pairs, &fi_n)) return rc;
+        for (size_t g = 0; g < n; ++g) {
+            const size_t o = object_indices ? object_indices[g] : g;
+            IVX_REQUIRE(o < fi_n, IVX_ERR_INVALID, "%s: object %zu takes the pairs of instance %zu, the context's frame instances have %u", who, g, o, fi_n);
+        }
+    }
     *ctx_out = c;
     ivx_many_other_context other_(c);
-    const CullJob j = {who, n, n_views, tables.data(), nullptr, counts.data(), extents.data(), objects, views, pairs, records, frusta, view_flags, pair_flags, mode};
+    const CullJob j = {who, n, n_views, tables.data(), nullptr, counts.data(), extents.data(), objects, views, pairs, records, frusta, view_flags, pair_flags, mode,
+                       n_views ? fi_pairs : nullptr, fi_n, object_indices};
     return cull_enqueue(c, j, out_layout);
 }
 
@@ -540,6 +584,13 @@ int ivx_cull_many_enqueue(ivx_grid* const* grids, size_t n, const ivx_cull_objec
     IVX_REQUIRE(out_layout || n_views == 0, IVX_ERR_INVALID, "ivx_cull_many_enqueue: null argument");
     ivx_ctx* c = nullptr;
     return many_enqueue("ivx_cull_many_enqueue", grids, n, objects, false, views, n_views, pairs, nullptr, nullptr, nullptr, mode, out_layout, nullptr, &c);
+}
+
+int ivx_cull_many_resident(ivx_grid* const* grids, size_t n, const ivx_cull_object* objects, const uint32_t* object_indices, const ivx_cull_view* views, size_t n_views,
+                           uint32_t mode, ivx_cull_region* out_layout) {
+    IVX_REQUIRE(out_layout || n_views == 0, IVX_ERR_INVALID, "ivx_cull_many_resident: null argument");
+    ivx_ctx* c = nullptr;
+    return many_enqueue("ivx_cull_many_resident", grids, n, objects, false, views, n_views, nullptr, nullptr, nullptr, nullptr, mode, out_layout, nullptr, &c, true, object_indices);
 }
 
 int ivx_cull_collect(ivx_ctx* c, ivx_cull_count* out_counts, size_t n_views) {

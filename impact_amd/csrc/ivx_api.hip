@@ -200,6 +200,7 @@ void ivx_shutdown(ivx_ctx* c) {
     ivx_buf_free(&c->drag_scratch);
     ivx_cull_release(c);
     ivx_bvol_release(c);
+    ivx_fi_release(c);
     if (c->aux_stream) {
         (void)hipStreamSynchronize(c->aux_stream);
         (void)hipStreamDestroy(c->aux_stream);

@@ -90,6 +90,7 @@ struct ivx_ctx {
     ivx_buf drag_scratch;  // device scratch of the drag entry points (drag.hip: triangle records, per-tile partials, samples, map); grown on demand, freed by ivx_shutdown
     void* cull_state;  // chunk culling (cull.hip): argument, count and frustum buffers, staging block, the last call's layout; made on first use, freed by ivx_cull_release
     void* bvol_state;  // bounding volumes (bvol.hip): world boxes, kinds, block boxes, pair and mask buffers, staging block; made on first use, freed by ivx_bvol_release
+    void* fi_state;    // frame instances (instances.hip): instances, kept masks of this call and the one before, pairs, lists, results, staging block; made on first use, freed by ivx_fi_release
 };
 
 // A device allocation (and / or a pinned host allocation) shared by several grids that came into being together — the fragments of an impact
@@ -342,6 +343,7 @@ static_assert(IVX_RB_FLAGS < IVX_RB_OCCUPIED && IVX_RB_OCCUPIED + 12u <= IVX_RB_
 void ivx_set_error(const char* fmt, ...);
 void ivx_cull_release(ivx_ctx* c);  // cull.hip (ivx_shutdown)
 void ivx_bvol_release(ivx_ctx* c);  // bvol.hip (ivx_shutdown)
+void ivx_fi_release(ivx_ctx* c);    // instances.hip (ivx_shutdown)
 // the occupied ranges the object holds (ivx_grid::occ_ref), refreshed first when something invalidated them; IVX_ERR_STATE when the grid has none yet
 int ivx_reference_occupied(ivx_grid* g, const char* who, uint32_t occ[12]);
 

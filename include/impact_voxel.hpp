@@ -496,6 +496,66 @@ private:
     Context* ctx_;
 };
 
+// ---- frame instances (impact_scene/src/model.rs:171-297, light.rs:85-848): kept sets, view transforms and cull pairs of every view of a pass ----
+// One instance per object of the context's BoundingVolumeSet; a pass after a `query` on that set. The light geometry, material buffering and
+// scene-graph group transforms stay with the caller.
+class FrameInstances {
+public:
+    struct Outputs {
+        std::vector<ivx_cull_pair> pairs;  // view-major, views x objects
+        std::vector<uint32_t> offsets;     // views + 1
+        std::vector<uint32_t> objects;     // the kept objects of every view, ascending within a view
+        std::vector<ivx_similarity> transforms;  // ... and their model-to-view transforms (the view's instance-transform range)
+        std::vector<uint64_t> kept_masks;  // views x ceil(objects / 64)
+    };
+    explicit FrameInstances(Context& ctx) : ctx_(&ctx) {}
+    void set_instances(const std::vector<ivx_fi_instance>& instances) { check(ivx_fi_set_instances(ctx_->handle(), instances.data(), instances.size())); }
+    // enqueue only: nothing waits and nothing comes back
+    void enqueue(const std::vector<ivx_fi_view>& views) { check(ivx_fi_views(ctx_->handle(), views.data(), views.size(), nullptr)); }
+    // ... or with the reductions of every view
+    std::vector<ivx_fi_view_result> views(const std::vector<ivx_fi_view>& views) {
+        std::vector<ivx_fi_view_result> r(views.size());
+        check(ivx_fi_views(ctx_->handle(), views.data(), views.size(), r.data()));
+        return r;
+    }
+    Outputs download(size_t n_views, size_t n_objects) {
+        Outputs o;
+        o.pairs.resize(n_views * n_objects), o.offsets.resize(n_views + 1), o.kept_masks.resize(n_views * ((n_objects + 63) / 64));
+        size_t total = 0;
+        check(ivx_fi_download(ctx_->handle(), o.pairs.data(), o.pairs.size(), o.offsets.data(), o.offsets.size(), nullptr, nullptr, 0, o.kept_masks.data(), o.kept_masks.size(), &total));
+        o.objects.resize(total), o.transforms.resize(total);
+        check(ivx_fi_download(ctx_->handle(), nullptr, 0, nullptr, 0, o.objects.data(), o.transforms.data(), total, nullptr, 0, nullptr));
+        return o;
+    }
+    void* device_ptr(int which) const { return ivx_fi_device_ptr(ctx_->handle(), which); }
+    // the cull of voxel objects under the views of the last pass, their pairs taken on the device (`object_indices` empty: object g is instance g)
+    std::vector<ivx_cull_region> enqueue_cull(const std::vector<VoxelObject*>& objects, const std::vector<uint32_t>& object_indices, const std::vector<ivx_cull_view>& views,
+                                              uint32_t mode, const std::vector<ivx_cull_object>& offsets = {}) {
+        std::vector<ivx_grid*> g;
+        for (VoxelObject* o : objects) g.push_back(o->handle());
+        std::vector<ivx_cull_region> layout(views.size());
+        check(ivx_cull_many_resident(g.data(), g.size(), offsets.empty() ? nullptr : offsets.data(), object_indices.empty() ? nullptr : object_indices.data(), views.data(),
+                                     views.size(), mode, layout.data()));
+        return layout;
+    }
+    // the whole stage on the host, with the functions the kernels run
+    static std::vector<ivx_fi_view_result> views_host(const std::vector<ivx_aabb>& world_boxes, const std::vector<ivx_fi_instance>& instances, const std::vector<uint64_t>& masks,
+                                                      size_t n_queries, const std::vector<ivx_fi_view>& views, const std::vector<uint64_t>& previous_kept,
+                                                      size_t n_previous_views, Outputs* out = nullptr) {
+        const size_t n = world_boxes.size(), nv = views.size();
+        std::vector<ivx_fi_view_result> r(nv);
+        if (out) out->pairs.resize(nv * n), out->offsets.resize(nv + 1), out->objects.resize(nv * n), out->transforms.resize(nv * n), out->kept_masks.resize(nv * ((n + 63) / 64));
+        check(ivx_fi_views_host(world_boxes.data(), n, instances.data(), masks.data(), n_queries, views.data(), nv, previous_kept.empty() ? nullptr : previous_kept.data(),
+                                n_previous_views, out ? out->pairs.data() : nullptr, out ? out->offsets.data() : nullptr, out ? out->objects.data() : nullptr,
+                                out ? out->transforms.data() : nullptr, nv * n, out ? out->kept_masks.data() : nullptr, r.data()));
+        if (out) out->objects.resize(out->offsets.back()), out->transforms.resize(out->offsets.back());
+        return r;
+    }
+
+private:
+    Context* ctx_;
+};
+
 // ---- motion drivers of kinematic bodies (impact_physics/src/driven_motion/): the reference's setup structs in their #[repr(C)] layouts ------
 // (all fields are f32: a record's parameters are the struct's bytes). `driver(kinematic_body_index)` gives the record ivx_world_set_motion_drivers takes.
 namespace detail {

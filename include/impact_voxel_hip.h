@@ -1170,6 +1170,132 @@ int ivx_bv_query_skips_boxes(const ivx_bv_query* queries, size_t n_queries, cons
 int ivx_bv_query_lists(ivx_ctx*, uint32_t* offsets, uint32_t* objects, size_t cap, size_t* n_out);
 int ivx_cw_set_broad_phase(ivx_world*, uint32_t which);
 
+/* ---- frame instances: kept sets, view transforms and cull pairs of every view of a frame (BufferModelInstancesAndBoundLights, engine/src/tasks.rs:779:
+ * impact_scene/src/model.rs:171-297 buffer_model_instances_for_rendering; impact_scene/src/light.rs:85-284, 383-450, 465-641, 747-787, 827-848
+ * bound_*_lights_and_buffer_shadow_casting_model_instances; impact_geometry/src/axis_aligned_box.rs:208-239; impact_math/src/transform/similarity.rs:278-284) ----
+ * The reference loops per view over the hits of a region query: it filters a hit by the instance's flags and by the light's own entity, composes
+ * model -> world -> view, appends to an instance range and reduces over the kept hits. Here ONE call does that for every view of a pass from
+ * the context's resident world boxes (ivx_bv_set*, ivx_cw_synchronize) and the resident masks of its last queries call (ivx_bv_queries or
+ * ivx_bv_queries_hierarchy), and leaves the ivx_cull_pair of every (view, object) where ivx_cull_many_resident reads it (csrc/instances.hip):
+ * set -> queries -> instances -> cull on the context's stream, and only the reductions come back, because the light geometry needs them.
+ * NOT here, it stays with the caller: the light geometry itself (cascade volumes, cubemap-face frusta, light-space orientation, texel snapping:
+ * impact_light), material property buffering, scene-graph group transforms (the caller passes model-to-world), declare_visible_this_frame. */
+/* One per object of the context's bounding-volume set, in the same index order. 48 bytes. */
+#define IVX_FI_ABSENT 1u                  /* a bounding volume without a model instance node (get_node -> None): kept by no view */
+#define IVX_FI_HIDDEN 2u                  /* ModelInstanceFlags::IS_HIDDEN */
+#define IVX_FI_CASTS_NO_SHADOWS 4u        /* ::CASTS_NO_SHADOWS */
+#define IVX_FI_SHADOWS_OFF_BY_DISTANCE 8u /* ::EXCEEDS_DIST_FOR_DISABLING_SHADOWING */
+#define IVX_FI_NO_SHADOW_FEATURES 16u     /* feature_ids_for_shadow_mapping().is_empty() (light.rs:408-417 tests these four) */
+#define IVX_FI_ALL_FLAGS 31u
+#define IVX_FI_NONE 0xFFFFFFFFu /* ivx_fi_view.exclude_entity: excludes nothing; ivx_fi_view.and_view: no other view */
+typedef struct {
+    ivx_similarity model_to_world;
+    uint32_t flags;  /* IVX_FI_* above; a view rejects by its reject_flags (IVX_FI_ABSENT is not implied: name it there) */
+    uint32_t entity; /* what a light's exclude_entity is compared with */
+    uint32_t reserved[2];
+} ivx_fi_instance;
+#define IVX_FI_VIEW_REACH 1u /* the reach filter and the two distance reductions from `point` and `squared_reach` (light.rs:419-436) */
+#define IVX_FI_VIEW_BOX 2u   /* the view-space box reduction */
+/* One view of a pass. 72 bytes. */
+typedef struct {
+    ivx_similarity world_to_view; /* the camera's view transform, camera-to-face o world-to-camera, or world-to-light: the caller computes it */
+    uint32_t query;               /* the row of the context's last queries call (either form) */
+    uint32_t reject_flags;        /* an instance with any of these flags is not kept */
+    uint32_t exclude_entity;      /* an instance with this entity is not kept (self-shadowing, light.rs:395, 756); IVX_FI_NONE: nobody */
+    uint32_t and_view;            /* IVX_FI_NONE, or a view of the context's PREVIOUS ivx_fi_views call: the object must have been kept by it too
+                                     (a cubemap face takes only the light's shadowing_models, light.rs:258-261) */
+    uint32_t instance_base;       /* the view's kept objects get instance indices instance_base, instance_base + 1, .. in ascending object index */
+    uint32_t flags;               /* IVX_FI_VIEW_* */
+    float point[3];               /* REACH: the light's position in world space */
+    float squared_reach;          /* REACH: the light's squared max reach */
+} ivx_fi_view;
+/* The reductions over a view's kept set. 60 bytes. */
+typedef struct {
+    uint32_t count;
+    ivx_aabb world_box;
+    ivx_aabb view_box;
+    float min_squared_distance, max_squared_distance;
+} ivx_fi_view_result;
+/* KEPT SET. With b the world box of object o, object o is kept by view v when ALL of:
+ *   bit o of mask row v.query is set;  (flags[o] & v.reject_flags) == 0;  entity[o] != v.exclude_entity;
+ *   v.and_view == IVX_FI_NONE, or bit o of kept row v.and_view of the context's previous ivx_fi_views call is set;
+ *   no bound of b is a NaN;
+ *   under IVX_FI_VIEW_REACH: NOT (d_close > v.squared_reach) — strict, so a box exactly at the reach is kept, and a NaN d_close is kept.
+ * DISTANCES — all f32, this order, no contraction. With p = v.point, per axis k (closest_interior_point_to: max with lower, then min with upper):
+ *     c[k] = b.lower[k] > p[k] ? b.lower[k] : p[k];   c[k] = b.upper[k] < c[k] ? b.upper[k] : c[k];   e[k] = p[k] - c[k]
+ *   d_close = (e[0] e[0] + e[1] e[1]) + e[2] e[2].
+ *   farthest_corner_from: m[k] = 0.5f (b.lower[k] + b.upper[k]);  f[k] = p[k] > m[k] ? b.lower[k] : b.upper[k]  (p at the centre takes the upper
+ *   corner);  g[k] = p[k] - f[k];  d_far = (g[0] g[0] + g[1] g[1]) + g[2] g[2].
+ * REDUCTIONS over the kept set: count; world_box = per component the minimum of the lowers and the maximum of the uppers of the world boxes;
+ *   view_box (IVX_FI_VIEW_BOX) = the same merge over ivx_bv_world_aabb's arithmetic with the WORLD box as the model box and v.world_to_view as
+ *   the similarity (aabb_of_transformed); min_squared_distance = the minimum of d_close, max_squared_distance = the maximum of d_far (REACH).
+ *   Every minimum and maximum is order_min / order_max, the total order of the bit patterns with -0.0 below +0.0 that the block boxes of a set
+ *   use: the result depends on no order of evaluation, +-0 and NaNs included (a positive NaN sorts above +inf, a negative one below -inf).
+ *   The device reduces 64 objects by cross-lane steps, 256 objects in LDS, and the 256-object tiles of a view in one final pass; no float atomic.
+ *   An empty kept set gives count 0, boxes with lower = +inf and upper = -inf, distances +inf / -inf; a reduction that was not asked for is
+ *   stored with the same empty values.
+ * COMPOSITION. For a kept pair, model_to_view = world_to_view * model_to_world by Similarity3 x Similarity3, a = world_to_view, b = model_to_world:
+ *     scaling = a.s b.s;   u = (a.s b.t.x, a.s b.t.y, a.s b.t.z)
+ *     translation = rotate(a.q, u) + a.t, with rotate(q, v) as the contact and collision kernels state it (glam's mul_vec3a): B = (q.x, q.y, q.z),
+ *       b2 = (B.x B.x + B.y B.y) + B.z B.z, dv = (v.x B.x + v.y B.y) + v.z B.z, cross = (B.y v.z - v.y B.z, B.z v.x - v.z B.x, B.x v.y - v.x B.y),
+ *       rotate = (v (q.w q.w - b2) + B (dv 2)) + cross (q.w 2), componentwise
+ *     rotation = a.q b.q (glam's mul_quat, sums left to right):  x = ((a.w b.x + a.x b.w) + a.y b.z) - a.z b.y
+ *       y = ((a.w b.y - a.x b.z) + a.y b.w) + a.z b.x    z = ((a.w b.z + a.x b.y) - a.y b.x) + a.z b.w    w = ((a.w b.w - a.x b.x) - a.y b.y) - a.z b.z
+ *   A restatement in f32 with a fixed operation order, not a bit-parity target (glam's is unpinned). The product of two positive scalings may
+ *   underflow to zero or overflow; the pair then carries that value, and ivx_cull_many_resident does not look at it.
+ * OUTPUTS, all resident (ivx_fi_device_ptr) and each downloadable (ivx_fi_download); W = ceil(n / 64):
+ *   pairs       ivx_cull_pair[n_views x n], view-major. A kept pair: the composed similarity, instance_idx = instance_base + its rank in the
+ *               view's kept list, flags 0. Every other pair: the identity similarity (rotation 0 0 0 1, translation 0, scaling 1), instance_idx 0,
+ *               IVX_CULL_PAIR_SKIP. Every byte is defined.
+ *   lists       offsets[n_views + 1]; objects[total], ascending object index within a view; transforms[total], the composed ivx_similarity of
+ *               each — the view's instance-transform range as the renderer's instance buffer wants it (InstanceModelViewTransform /
+ *               InstanceModelLightTransform). The device buffers hold n_views x n entries, so that no call waits for the total.
+ *   kept masks  uint64_t[n_views x W], bits past n zero. The context keeps them for the NEXT call's and_view; the set of the call before is
+ *               dropped by a buffer swap. A new set of bounding volumes drops them too (the next call then has no previous views).
+ *   results     ivx_fi_view_result[n_views].
+ * ivx_fi_set_instances: one upload from pinned staging; the instances stay resident until the next call. IVX_ERR_INVALID: a scaling that is not
+ *   positive (a NaN included), a flag bit outside IVX_FI_ALL_FLAGS; IVX_ERR_CAPACITY: n above IVX_BV_MAX_OBJECTS. A refused call leaves the
+ *   instances as they were.
+ * ivx_fi_views: a handful of launches on the context's stream, independent of n_views: decide (a wave per 64 objects walks the views), a
+ *   workgroup per view (the final pass of the reductions; the prefix of the kept words' popcounts), the offsets, and the emit (a lane per pair,
+ *   written out through LDS in whole lines). results == NULL: nothing waits and nothing comes back; else the n_views records, after one wait.
+ *   IVX_ERR_INVALID: more than IVX_FI_MAX_VIEWS views (the cull limit), a world_to_view scaling that is not positive, a query not below the
+ *   last queries call's count, an and_view that is neither IVX_FI_NONE nor below the previous call's view count, a reject_flags bit outside
+ *   IVX_FI_ALL_FLAGS, a flags bit outside REACH | BOX. IVX_ERR_STATE: no set; no queries call since the set; no instances, or instances whose n
+ *   is not the set's. n == 0 or n_views == 0 succeed with empty outputs (and count as the previous call of the next one). A refused call
+ *   leaves the previous state — outputs and kept masks —; a call that fails later leaves none. Inside an ivx_many_begin bracket what has been
+ *   recorded is flushed first.
+ * ivx_fi_download: the outputs of the last call; each pointer may be NULL, each capacity is in elements (pairs: n_views x n; offsets: n_views + 1;
+ *   objects and transforms share list_cap: the total; kept: n_views x W); too small: IVX_ERR_CAPACITY and nothing written. *n_listed (may be NULL)
+ *   is the total. IVX_ERR_STATE before the first successful ivx_fi_views.
+ * ivx_fi_device_ptr: the IVX_FI_PTR_* buffers. Context-owned and grow-only under the rules ivx_cull_device_ptr documents.
+ * ivx_fi_views_host: the whole stage on the host with the same functions, for callers without a device and for the tests: n world boxes, n
+ *   instances, masks[n_queries x W], previous_kept[n_previous_views x W] (may be NULL when that is 0). Same refusals as the two calls above for
+ *   the records. Each output may be NULL; objects / transforms hold list_cap entries (IVX_ERR_CAPACITY when the total exceeds it, nothing written).
+ *   The device leaves the same bytes. */
+#define IVX_FI_MAX_VIEWS 64u
+#define IVX_FI_PTR_INSTANCES 0
+#define IVX_FI_PTR_PAIRS 1
+#define IVX_FI_PTR_OFFSETS 2
+#define IVX_FI_PTR_OBJECTS 3
+#define IVX_FI_PTR_TRANSFORMS 4
+#define IVX_FI_PTR_KEPT_MASKS 5
+#define IVX_FI_PTR_RESULTS 6
+int ivx_fi_set_instances(ivx_ctx*, const ivx_fi_instance* instances, size_t n);
+int ivx_fi_views(ivx_ctx*, const ivx_fi_view* views, size_t n_views, ivx_fi_view_result* results);
+int ivx_fi_download(ivx_ctx*, ivx_cull_pair* pairs, size_t pair_cap, uint32_t* offsets, size_t offset_cap, uint32_t* objects, ivx_similarity* transforms, size_t list_cap,
+                    uint64_t* kept_masks, size_t kept_cap, size_t* n_listed);
+void* ivx_fi_device_ptr(ivx_ctx*, int which);
+int ivx_fi_views_host(const ivx_aabb* world_boxes, size_t n, const ivx_fi_instance* instances, const uint64_t* masks, size_t n_queries, const ivx_fi_view* views,
+                      size_t n_views, const uint64_t* previous_kept, size_t n_previous_views, ivx_cull_pair* pairs, uint32_t* offsets, uint32_t* objects,
+                      ivx_similarity* transforms, size_t list_cap, uint64_t* kept_masks, ivx_fi_view_result* results);
+/* ivx_cull_many_enqueue with the pair of (view v, grid g) taken ON THE DEVICE from the frame-instance pairs of the grids' context at
+ * (v, object_indices[g]) (object_indices == NULL: g itself): a small gather writes pairs and pair flags where the upload would have put them;
+ * the rest of the call, its bytes and ivx_cull_collect / ivx_cull_download are those of ivx_cull_many_enqueue. IVX_ERR_STATE when the context's
+ * last ivx_fi_views call had another n_views (or there was none); IVX_ERR_INVALID for an index not below that call's n. n == 0 touches no context. */
+int ivx_cull_many_resident(ivx_grid* const* grids, size_t n, const ivx_cull_object* objects, const uint32_t* object_indices, const ivx_cull_view* views, size_t n_views,
+                           uint32_t mode, ivx_cull_region* out_layout);
+
 /* ---- primitive collidables: follow the bodies, narrow phase over the pairs (impact_physics/src/collision.rs:175-261, 317-373
  * synchronize_collidables_with_rigid_bodies and the collision pass; collision/collidable/basic.rs:57-151, sphere.rs:105-157, capsule.rs:142-303;
  * impact_geometry/src/line.rs:26-145; material.rs:43-51) ----

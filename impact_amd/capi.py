@@ -220,8 +220,17 @@ assert FI_INSTANCE_DTYPE.itemsize == 48 and FI_VIEW_DTYPE.itemsize == 72 and FI_
 COLLIDABLE_DTYPE = np.dtype([("shape", "<u4"), ("kind", "<u4"), ("body", "<u4"), ("reserved", "<u4"), ("id", "<u8"), ("a", "<f4", (3,)), ("b", "<f4", (3,)), ("s", "<f4"),
                              ("response", "<f4", (3,))])
 CW_SPHERE, CW_PLANE, CW_CAPSULE, CW_VOXEL_OBJECT = 0, 1, 2, 3
-CW_PTR_WORLD_COLLIDABLES, CW_PTR_CONTACTS, CW_PTR_DEFERRED_PAIRS = 0, 1, 2
+CW_PTR_WORLD_COLLIDABLES, CW_PTR_CONTACTS, CW_PTR_DEFERRED_PAIRS, CW_PTR_FRAME_CONTACTS, CW_PTR_VOXEL_ROWS = 0, 1, 2, 3, 4
 assert COLLIDABLE_DTYPE.itemsize == 64
+# the collision frame (csrc/narrow.hip k_cw_rows, csrc/voxel_collision_api.hip): `ivx_cw_voxel_object` (what `ivx_cw_set_voxel_objects` attaches to a voxel
+# collidable) and `struct ivx_cw_voxel_row` (the dispatch of one deferred pair: an `ivx_collidable_query` or an `ivx_mutual_query` by field copies)
+CW_VOXEL_OBJECT_DTYPE = np.dtype([("grid", "<u8"), ("origin_offset", "<f4", (3,)), ("center_of_mass", "<f4", (3,))])
+CW_VOXEL_ROW_DTYPE = np.dtype([("generator", "<u4"), ("voxel", "<u4"), ("other", "<u4"), ("reserved", "<u4"), ("collidable_id_a", "<u8"), ("collidable_id_b", "<u8"),
+                               ("body_a", "<u4"), ("body_b", "<u4"), ("response", "<f4", (3,)), ("shape1", "<f4"), ("shape3", "<f4", (3,)), ("shape3b", "<f4", (3,)),
+                               ("rotation_a", "<f4", (4,)), ("translation_a", "<f4", (3,)), ("center_of_mass_a", "<f4", (3,)),
+                               ("rotation_b", "<f4", (4,)), ("translation_b", "<f4", (3,)), ("center_of_mass_b", "<f4", (3,))])
+CW_ROW_MUTUAL = 3
+assert CW_VOXEL_OBJECT_DTYPE.itemsize == 32 and CW_VOXEL_ROW_DTYPE.itemsize == 160
 # motion drivers of kinematic bodies (csrc/motion.hip): `ivx_motion_driver`; `p` holds the reference's setup struct of that kind
 MOTION_DRIVER_DTYPE = np.dtype([("kind", "<u4"), ("body", "<u4"), ("p", "<f4", (14,))])
 MD_CIRCULAR, MD_CONSTANT_ACCELERATION, MD_HARMONIC, MD_ORBITAL, MD_CONSTANT_ROTATION = 0, 1, 2, 3, 4
@@ -279,6 +288,7 @@ EXPORTED_SYMBOLS = [
     "ivx_bv_queries_hierarchy", "ivx_bv_queries_hierarchy_host", "ivx_bv_query_skips_boxes", "ivx_bv_query_lists",
     "ivx_fi_set_instances", "ivx_fi_views", "ivx_fi_download", "ivx_fi_device_ptr", "ivx_fi_views_host", "ivx_cull_many_resident",
     "ivx_cw_transform", "ivx_cw_contact", "ivx_cw_set_collidables", "ivx_cw_synchronize", "ivx_cw_download", "ivx_cw_collide", "ivx_cw_device_ptr",
+    "ivx_cw_to_object_space", "ivx_cw_voxel_row", "ivx_cw_set_voxel_objects", "ivx_cw_collide_frame", "ivx_cw_rows_download",
     "ivx_world_set_motion_drivers", "ivx_world_set_time", "ivx_world_time", "ivx_world_apply_motion", "ivx_md_eval", "ivx_md_apply_host",
     "ivx_world_set_force_generators", "ivx_world_set_dynamic_gravity", "ivx_world_apply_forces", "ivx_world_gravity_loads", "ivx_fg_apply_host",
     "ivx_world_set_medium", "ivx_world_medium", "ivx_world_set_drag_map", "ivx_world_set_drag_map_from_grid", "ivx_world_drag_map_download",
@@ -316,7 +326,8 @@ def extra_struct_sizes():
         "ivx_cull_region": (CULL_REGION_DTYPE, 16), "ivx_cull_count": (CULL_COUNT_DTYPE, 8),
         "ivx_aabb": (AABB_DTYPE, 24), "ivx_similarity": (SIMILARITY_DTYPE, 32), "ivx_bv_query": (BV_QUERY_DTYPE, 128), "ivx_bv_node": (BV_NODE_DTYPE, 32),
         "ivx_fi_instance": (FI_INSTANCE_DTYPE, 48), "ivx_fi_view": (FI_VIEW_DTYPE, 72), "ivx_fi_view_result": (FI_VIEW_RESULT_DTYPE, 60),
-        "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
+        "ivx_collidable": (COLLIDABLE_DTYPE, 64), "ivx_cw_voxel_object": (CW_VOXEL_OBJECT_DTYPE, 32), "ivx_cw_voxel_row": (CW_VOXEL_ROW_DTYPE, 160),
+        "ivx_motion_driver": (MOTION_DRIVER_DTYPE, 64),
         "ivx_force_generator": (FORCE_GENERATOR_DTYPE, 64),
         "ivx_uniform_medium": (UNIFORM_MEDIUM_DTYPE, 16), "ivx_drag_generator": (DRAG_GENERATOR_DTYPE, 16), "ivx_drag_map_view": (DRAG_MAP_VIEW_DTYPE, 16),
         "ivx_sdf_query_instance": (SDF_QUERY_INSTANCE_DTYPE, 48), "ivx_sdf_query_result": (SDF_QUERY_RESULT_DTYPE, 32),
@@ -535,6 +546,11 @@ def lib():
         "ivx_cw_download": (i32, [vp, vp, sz]),
         "ivx_cw_collide": (i32, [vp, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]),
         "ivx_cw_device_ptr": (vp, [vp, i32]),
+        "ivx_cw_to_object_space": (i32, [vp, vp, vp, vp, vp]),
+        "ivx_cw_voxel_row": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "ivx_cw_set_voxel_objects": (i32, [vp, vp, vp, sz]),
+        "ivx_cw_collide_frame": (i32, [vp, u32, vp, sz, C.POINTER(sz), C.POINTER(sz), vp, vp, sz, C.POINTER(sz)]),
+        "ivx_cw_rows_download": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "ivx_world_set_motion_drivers": (i32, [vp, vp, sz]),
         "ivx_world_set_time": (i32, [vp, f32]),
         "ivx_world_time": (i32, [vp, C.POINTER(f32)]),

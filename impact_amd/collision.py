@@ -6,8 +6,12 @@ plane and capsule collidables (impact_physics/src/collision.rs, collision/collid
   generate_contact_manifold                                                basic.rs:57-151        (`contact`, host arithmetic of the library)
   Collidable::from_descriptor                                              basic.rs:42-55         (`transform`)
 
-A frame: `synchronize()` -> `collide()` -> `PhysicsWorld.prepare_constraints(contacts)` -> `PhysicsWorld.step(dt)`. The world-space collidables,
-the world boxes, the pairs, the contacts and the deferred pairs stay in device buffers. Nothing here computes, and nothing falls back to the CPU.
+  VoxelObjectCollidable::new, generate_contact_manifold (voxel pairs)     impact_voxel collidable.rs:310-327, 138-215 (`to_object_space`, `voxel_row`)
+
+A frame: `synchronize()` -> `collide()` -> `PhysicsWorld.prepare_constraints(contacts)` -> `PhysicsWorld.step(dt)`. With voxel objects among the
+collidables: `set_voxel_objects()` once, then `synchronize()` -> `collide_frame()` -> `prepare_constraints(merged)` -> `step(dt)` — the deferred pairs'
+manifolds come back in the same call, behind the primitive contacts. The world-space collidables, the world boxes, the pairs, the contacts, the
+deferred pairs and their rows stay in device buffers. Nothing here computes, and nothing falls back to the CPU.
 """
 from __future__ import annotations
 
@@ -17,7 +21,8 @@ import numpy as np
 
 from . import capi
 from .bvol import BoundingVolumeSet
-from .capi import AABB_DTYPE, COLLIDABLE_DTYPE, CONTACT_DTYPE, check, ptr
+from .capi import (AABB_DTYPE, COLLIDABLE_DTYPE, COLLIDABLE_QUERY_DTYPE, CONTACT_DTYPE, CW_VOXEL_OBJECT_DTYPE, CW_VOXEL_ROW_DTYPE, MUTUAL_QUERY_DTYPE, check,
+                   ptr)
 
 NO_CONTACT, CONTACT, DEFERRED = 0, 1, 2  # `ivx_cw_contact`'s verdicts
 
@@ -80,6 +85,56 @@ def contact(a_world, b_world):
     return hit.value, (out[0] if hit.value == CONTACT else None)
 
 
+def to_object_space(position, orientation_xyzw, origin_offset):
+    """`ivx_cw_to_object_space`: the world -> object transform of a voxel body, float32 in the reference's order -> (rotation_xyzw, translation)"""
+    p, q, o = (np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((position, 3), (orientation_xyzw, 4), (origin_offset, 3)))
+    rotation, translation = np.zeros(4, dtype=np.float32), np.zeros(3, dtype=np.float32)
+    check(capi.lib().ivx_cw_to_object_space(ptr(p), ptr(q), ptr(o), ptr(rotation), ptr(translation)))
+    return rotation, translation
+
+
+def voxel_object_record(grid, origin_offset, center_of_mass) -> np.ndarray:
+    """an `ivx_cw_voxel_object`: `grid` is a device object (its handle is taken), None or a raw handle"""
+    r = np.zeros((), dtype=CW_VOXEL_OBJECT_DTYPE)
+    handle = getattr(grid, "h", grid)
+    r["grid"] = int(getattr(handle, "value", handle) or 0)
+    r["origin_offset"], r["center_of_mass"] = origin_offset, center_of_mass
+    return r
+
+
+def voxel_row(a_world, b_world, pose_a=None, pose_b=None, voxel_a=None, voxel_b=None) -> np.ndarray:
+    """`ivx_cw_voxel_row`: the dispatch of one deferred pair of world-space collidables. pose_* = (position, orientation_xyzw) of a voxel member's
+    body, voxel_* its `voxel_object_record` -> one CW_VOXEL_ROW_DTYPE record (`voxel` / `other` read 0 for member a, 1 for member b)"""
+    def pose(p):
+        return None if p is None else np.concatenate([np.asarray(p[0], dtype=np.float32).reshape(3), np.asarray(p[1], dtype=np.float32).reshape(4)])
+
+    def record(v):
+        return None if v is None else np.ascontiguousarray(v, dtype=CW_VOXEL_OBJECT_DTYPE).reshape(1)
+
+    pa, pb, va, vb = pose(pose_a), pose(pose_b), record(voxel_a), record(voxel_b)
+    out = np.zeros(1, dtype=CW_VOXEL_ROW_DTYPE)
+    check(capi.lib().ivx_cw_voxel_row(ptr(_one(a_world)), ptr(_one(b_world)), *(None if x is None else ptr(x) for x in (pa, pb, va, vb)), ptr(out)))
+    return out[0]
+
+
+def row_queries(rows, grid_handles=None):
+    """the rows as the generators' records, by plain field copies -> (ivx_collidable_query records, their row positions, ivx_mutual_query records, their
+    row positions). grid_handles: collidable index -> handle, for the mutual records' `a` / `b` (left zero without it)"""
+    rows = np.ascontiguousarray(rows, dtype=CW_VOXEL_ROW_DTYPE).reshape(-1)
+    is_mutual = rows["generator"] == capi.CW_ROW_MUTUAL
+    r, m = rows[~is_mutual], rows[is_mutual]
+    cq, mq = np.zeros(len(r), dtype=COLLIDABLE_QUERY_DTYPE), np.zeros(len(m), dtype=MUTUAL_QUERY_DTYPE)
+    cq["mode"], cq["rotation_xyzw"], cq["translation"] = r["generator"], r["rotation_a"], r["translation_a"]
+    for f in ("shape3", "shape3b", "shape1", "body_a", "body_b", "collidable_id_a", "collidable_id_b", "response"):
+        cq[f] = r[f]
+    for f in ("rotation_a", "translation_a", "center_of_mass_a", "rotation_b", "translation_b", "center_of_mass_b", "collidable_id_a", "collidable_id_b", "body_a", "body_b",
+              "response"):
+        mq[f] = m[f]
+    if grid_handles is not None:
+        mq["a"], mq["b"] = [grid_handles[int(i)] for i in m["voxel"]], [grid_handles[int(i)] for i in m["other"]]
+    return cq, np.nonzero(~is_mutual)[0], mq, np.nonzero(is_mutual)[0]
+
+
 class CollisionWorld:
     """The collidables of a `PhysicsWorld`. List planes last: a block of 64 consecutive collidables that holds one is never rejected as a whole."""
 
@@ -121,6 +176,39 @@ class CollisionWorld:
         check(lib.ivx_cw_collide(self.world.h, int(mode), ptr(contacts), capacity, C.byref(n), ptr(deferred), deferred_capacity, C.byref(m)))
         return contacts[: n.value], deferred[: m.value]
 
+    def set_voxel_objects(self, attachments) -> None:
+        """`ivx_cw_set_voxel_objects`: {collidable index: (grid, origin_offset, center_of_mass)}, replacing what was attached before. The grids' ranges
+        and probes are read at every `collide_frame`: call again only when an origin offset or a centre of mass moved (or after `set_collidables`)"""
+        index = np.array(sorted(attachments), dtype=np.uint32)
+        records = np.array([voxel_object_record(*attachments[int(i)]) for i in index], dtype=CW_VOXEL_OBJECT_DTYPE).reshape(-1)
+        check(capi.lib().ivx_cw_set_voxel_objects(self.world.h, ptr(index) if index.size else None, ptr(records) if index.size else None, index.size))
+
+    def collide_frame(self, mode: int = capi.BV_DYNAMIC_PAIRS, capacity: int | None = None, deferred_capacity: int | None = None):
+        """`ivx_cw_collide_frame` -> (merged contacts: the primitive ones, then one manifold per deferred pair in deferred-list order; n_primitive;
+        deferred pairs [m, 2] uint32; manifold offsets [m + 1] uint32 counted from n_primitive). A capacity of None: sized by a first call that leaves
+        the lists on the device."""
+        lib = capi.lib()
+        n, n_primitive, m = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        if capacity is None or deferred_capacity is None:
+            check(lib.ivx_cw_collide_frame(self.world.h, int(mode), None, 0, C.byref(n), C.byref(n_primitive), None, None, 0, C.byref(m)))
+            capacity = n.value if capacity is None else capacity
+            deferred_capacity = m.value if deferred_capacity is None else deferred_capacity
+        contacts, deferred = np.zeros(max(1, capacity), dtype=CONTACT_DTYPE), np.zeros((max(1, deferred_capacity), 2), dtype=np.uint32)
+        offsets = np.zeros(deferred_capacity + 1, dtype=np.uint32)
+        check(lib.ivx_cw_collide_frame(self.world.h, int(mode), ptr(contacts), capacity, C.byref(n), C.byref(n_primitive), ptr(deferred), ptr(offsets), deferred_capacity,
+                                       C.byref(m)))
+        return contacts[: n.value], n_primitive.value, deferred[: m.value], offsets[: m.value + 1]
+
+    def rows(self) -> np.ndarray:
+        """`ivx_cw_rows_download`: the CW_VOXEL_ROW_DTYPE records of the last `collide_frame`, in deferred-list order"""
+        lib, n = capi.lib(), C.c_size_t(0)
+        rc = lib.ivx_cw_rows_download(self.world.h, None, 0, C.byref(n))
+        if rc != capi.IVX_ERR_CAPACITY:
+            check(rc)
+        out = np.zeros(max(1, n.value), dtype=CW_VOXEL_ROW_DTYPE)
+        check(lib.ivx_cw_rows_download(self.world.h, ptr(out), n.value, C.byref(n)))
+        return out[: n.value]
+
     def device_ptr(self, which: int) -> int:
-        """`ivx_cw_device_ptr`: capi.CW_PTR_WORLD_COLLIDABLES / _CONTACTS / _DEFERRED_PAIRS"""
+        """`ivx_cw_device_ptr`: capi.CW_PTR_WORLD_COLLIDABLES / _CONTACTS / _DEFERRED_PAIRS / _FRAME_CONTACTS / _VOXEL_ROWS"""
         return int(capi.lib().ivx_cw_device_ptr(self.world.h, int(which)) or 0)

@@ -14,11 +14,16 @@
 // SCAN — k_cw_scan, one workgroup: exclusive prefix of the masks' popcounts, SCAN_ROUND waves a round with a carry; the two totals.
 // EMIT — k_cw_emit, the same lanes: a lane whose bit is set computes its contact again and writes it at its wave's offset plus the number of set
 //   bits below its own — pair order, no atomic. The deferred pairs likewise.
+// ROWS — k_cw_rows (ivx_cw_collide_frame only), one lane per deferred pair, right behind k_cw_emit: the dispatch of the pair (cw_rows.hpp) over the
+//   world-space records, the poses of the voxel members' bodies in the world's resident arrays and the attached offsets; row i of the deferred list.
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <new>
+#include <vector>
 
 #include "bvol_internal.hpp"
+#include "cw_rows.hpp"
 #include "device_common.hpp"
 #include "physics_internal.hpp"
 #include "vec3.hpp"
@@ -345,6 +350,38 @@ __global__ __launch_bounds__(GROUP) void k_cw_emit(const uint2* __restrict__ pai
     }
 }
 
+// what ivx_cw_set_voxel_objects attached to a collidable, as the device holds it (indexed by collidable; all zero: nothing attached)
+struct CwVoxel {
+    float origin_offset[3], center_of_mass[3];
+    uint32_t attached, reserved;
+};
+static_assert(sizeof(CwVoxel) == 32 && sizeof(ivx_cw_row) == 160 && sizeof(ivx_cw_voxel_object) == 32, "collision frame record layouts");
+static_assert(offsetof(ivx_rigid_body, orientation) == offsetof(ivx_rigid_body, position) + 12 &&
+                  offsetof(ivx_kinematic_body, orientation) == offsetof(ivx_kinematic_body, position) + 12,
+              "a body's pose is position[3] then orientation[4]");
+
+// a lane per deferred pair; `totals[1]` is the deferred count k_cw_scan left (max_rows: what the row buffer holds, never below it)
+__global__ __launch_bounds__(GROUP) void k_cw_rows(const uint2* __restrict__ deferred, const uint32_t* __restrict__ totals, uint32_t max_rows,
+                                                   const ivx_collidable* __restrict__ colls, const ivx_rigid_body* __restrict__ dyn,
+                                                   const ivx_kinematic_body* __restrict__ kin, const CwVoxel* __restrict__ vox, ivx_cw_row* __restrict__ rows) {
+    const uint32_t i = blockIdx.x * GROUP + threadIdx.x;
+    const uint32_t n = totals[1] < max_rows ? totals[1] : max_rows;
+    if (i >= n) return;
+    const uint2 pr = deferred[i];
+    auto member = [&](uint32_t index) {
+        ivx_cw_rows::Member m;
+        m.c = colls + index, m.index = index;
+        m.pose = nullptr, m.origin_offset = nullptr, m.center_of_mass = nullptr;
+        if (m.c->shape == IVX_CW_VOXEL_OBJECT) {
+            const uint32_t ref = m.c->body, body = ref & ~IVX_KINEMATIC_BODY;
+            m.pose = (ref & IVX_KINEMATIC_BODY) ? kin[body].position : dyn[body].position;
+            m.origin_offset = vox[index].origin_offset, m.center_of_mass = vox[index].center_of_mass;
+        }
+        return m;
+    };
+    ivx_cw_rows::voxel_row(member(pr.x), member(pr.y), rows + i);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 // world-owned state: device buffers that only grow, a pinned block the results of a call come back through (device_common.hpp)
 struct CwState {
@@ -356,6 +393,14 @@ struct CwState {
     uint64_t set_serial = 0;              // the context's bounding-volume set the last synchronize installed
     size_t n_contacts = 0, n_deferred = 0;
     uint32_t broad_phase = IVX_CW_BROAD_FLAT;  // where ivx_cw_collide takes its pairs from (ivx_cw_set_broad_phase)
+    // the collision frame (ivx_cw_collide_frame): the shapes of the set and what is attached to its voxel collidables, on the host and (CwVoxel per
+    // collidable) on the device; the rows of the last call; the pinned blocks its rows (when they outgrew the guess) and its merged list come through
+    std::vector<uint8_t> shapes;
+    std::vector<ivx_cw_voxel_object> objects;
+    uint32_t n_voxel = 0;
+    ivx_buf voxel_dev, rows;
+    ivx_staging staging_rows, staging_out;
+    size_t n_rows = 0, last_deferred = 0;
 };
 
 int state_of(ivx_world* w, CwState** out) {
@@ -382,10 +427,143 @@ int synchronized_state(ivx_world* w, const char* who, CwState** out) {
 void ivx_cw_release(ivx_world* w) {
     if (!w || !w->cw_state) return;
     CwState* s = static_cast<CwState*>(w->cw_state);
-    for (ivx_buf* b : {&s->local, &s->world, &s->scratch, &s->contacts, &s->deferred}) ivx_buf_free(b);
-    ivx_staging_release(&s->staging);
+    for (ivx_buf* b : {&s->local, &s->world, &s->scratch, &s->contacts, &s->deferred, &s->voxel_dev, &s->rows}) ivx_buf_free(b);
+    for (ivx_staging* g : {&s->staging, &s->staging_rows, &s->staging_out}) ivx_staging_release(g);
     delete s;
     w->cw_state = nullptr;
+}
+
+namespace {
+
+// What ivx_cw_collide and ivx_cw_collide_frame share: the pair pass (first wait), k_cw_test | k_cw_scan | k_cw_emit over the resident pairs, for the
+// frame k_cw_rows behind them, and the second wait, which brings the two counts and as much of the lists as was asked for (what lies behind the
+// counts is dropped by the caller).
+struct CollidePass {
+    CwState* st = nullptr;
+    uint32_t totals[2] = {0u, 0u};  // contacts, deferred pairs
+    const char* contacts = nullptr;  // in the world's pinned block: copy_contacts records, copy_deferred pairs
+    const char* deferred = nullptr;
+    const ivx_cw_row* rows = nullptr;  // (frame) totals[1] of them
+};
+int collide_pass(ivx_world* w, const char* who, uint32_t mode, size_t contacts_cap, size_t deferred_cap, bool frame, CollidePass* out) {
+    CwState* st;
+    if (int rc = synchronized_state(w, who, &st)) return rc;
+    out->st = st;
+    ivx_ctx* c = w->ctx;
+    IVX_REQUIRE(ivx_bvol_set_serial(c) == st->set_serial, IVX_ERR_STATE,
+                "%s: the context's set of bounding volumes has been replaced since ivx_cw_synchronize (synchronize again)", who);
+    ivx_many_other_context other_(c);
+    st->n_contacts = 0, st->n_deferred = 0, st->n_rows = 0;
+    size_t n_pairs = 0;
+    if (st->broad_phase == IVX_CW_BROAD_HIERARCHY) {
+        if (int rc = ivx_bvh_build_enqueue(c, who)) return rc;  // (nothing waits)
+        if (int rc = ivx_bvh_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) return rc;
+    } else if (int rc = ivx_bvol_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) {  // (either way the call's first wait: the grand total)
+        return rc;
+    }
+    if (n_pairs == 0) return IVX_OK;
+    const uint32_t np = (uint32_t)n_pairs, n_waves = (np + 63u) / 64u;
+    ivx_layout l;
+    const size_t o_mh = l.take((size_t)n_waves * 8), o_md = l.take((size_t)n_waves * 8), o_oh = l.take((size_t)n_waves * 4), o_od = l.take((size_t)n_waves * 4), o_tot = l.take(8);
+    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 16)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->contacts, n_pairs * sizeof(ivx_contact), 1u << 16)) return rc;  // (at most one contact per pair)
+    if (int rc = ivx_buf_grow(c, &st->deferred, n_pairs * 8, 1u << 16)) return rc;
+    // the frame's rows: a deferred pair has a voxel member, so there are no more than (voxel collidables) x (n - 1) of them. The host needs ALL rows;
+    // how many come with the counts is a guess from the last call (twice its deferred pairs, at least 256): a list that outgrew it is fetched below
+    size_t max_rows = 0, copy_rows = 0;
+    if (frame && st->n_voxel) {
+        max_rows = std::min<size_t>(n_pairs, (size_t)st->n_voxel * (st->n - 1u));
+        copy_rows = std::min<size_t>(max_rows, std::max<size_t>(256, 2 * st->last_deferred));
+        if (int rc = ivx_buf_grow(c, &st->rows, max_rows * sizeof(ivx_cw_row), 1u << 16)) return rc;
+    }
+    const size_t copy_contacts = contacts_cap < n_pairs ? contacts_cap : n_pairs, copy_deferred = deferred_cap < n_pairs ? deferred_cap : n_pairs;
+    ivx_layout h;
+    const size_t h_tot = h.take(8), h_contacts = h.take(copy_contacts * sizeof(ivx_contact)), h_deferred = h.take(copy_deferred * 8),
+                 h_rows = h.take(copy_rows * sizeof(ivx_cw_row));
+    if (int rc = ivx_staging_for(&st->staging, h.bytes)) return rc;
+    char* s = static_cast<char*>(st->scratch.p);
+    unsigned long long* d_mh = reinterpret_cast<unsigned long long*>(s + o_mh);
+    unsigned long long* d_md = reinterpret_cast<unsigned long long*>(s + o_md);
+    uint32_t* d_oh = reinterpret_cast<uint32_t*>(s + o_oh);
+    uint32_t* d_od = reinterpret_cast<uint32_t*>(s + o_od);
+    uint32_t* d_tot = reinterpret_cast<uint32_t*>(s + o_tot);
+    const uint2* d_pairs = static_cast<const uint2*>(ivx_bv_device_ptr(c, IVX_BV_PTR_PAIRS));
+    const ivx_collidable* d_colls = static_cast<const ivx_collidable*>(st->world.p);
+    IVX_REQUIRE(d_pairs && d_colls, IVX_ERR_STATE, "%s: no resident pair buffer", who);
+    const dim3 grid((np + GROUP - 1u) / GROUP);
+    IVX_KLAUNCH(k_cw_test, grid, dim3(GROUP), 0, c->stream, d_pairs, np, d_colls, d_mh, d_md);
+    IVX_KLAUNCH(k_cw_scan, dim3(1), dim3(SCAN_ROUND), 0, c->stream, (const unsigned long long*)d_mh, (const unsigned long long*)d_md, n_waves, d_oh, d_od, d_tot);
+    IVX_KLAUNCH(k_cw_emit, grid, dim3(GROUP), 0, c->stream, d_pairs, np, d_colls, (const unsigned long long*)d_mh, (const unsigned long long*)d_md, (const uint32_t*)d_oh,
+                (const uint32_t*)d_od, static_cast<ivx_contact*>(st->contacts.p), static_cast<uint2*>(st->deferred.p));
+    if (max_rows)
+        IVX_KLAUNCH(k_cw_rows, dim3(((uint32_t)max_rows + GROUP - 1u) / GROUP), dim3(GROUP), 0, c->stream, static_cast<const uint2*>(st->deferred.p), (const uint32_t*)d_tot,
+                    (uint32_t)max_rows, d_colls, (const ivx_rigid_body*)w->dyn.p, (const ivx_kinematic_body*)w->kin.p, static_cast<const CwVoxel*>(st->voxel_dev.p),
+                    static_cast<ivx_cw_row*>(st->rows.p));
+    IVX_HIP_CHECK(hipGetLastError());
+    // the call's second wait: the two counts, and as much of the lists as the caller's buffers could hold (what lies behind the counts is dropped)
+    char* hs = static_cast<char*>(st->staging.p);
+    IVX_HIP_CHECK(ivx_memcpy_async(hs + h_tot, d_tot, 8, hipMemcpyDeviceToHost, c->stream));
+    if (copy_contacts) IVX_HIP_CHECK(ivx_memcpy_async(hs + h_contacts, st->contacts.p, copy_contacts * sizeof(ivx_contact), hipMemcpyDeviceToHost, c->stream));
+    if (copy_deferred) IVX_HIP_CHECK(ivx_memcpy_async(hs + h_deferred, st->deferred.p, copy_deferred * 8, hipMemcpyDeviceToHost, c->stream));
+    if (copy_rows) IVX_HIP_CHECK(ivx_memcpy_async(hs + h_rows, st->rows.p, copy_rows * sizeof(ivx_cw_row), hipMemcpyDeviceToHost, c->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    memcpy(out->totals, hs + h_tot, 8);
+    st->n_contacts = out->totals[0], st->n_deferred = out->totals[1];
+    out->contacts = hs + h_contacts, out->deferred = hs + h_deferred;
+    if (frame) {
+        const size_t n_rows = out->totals[1];
+        IVX_REQUIRE(n_rows <= max_rows, IVX_ERR_STATE, "%s: %zu deferred pairs for %u voxel collidables among %u", who, n_rows, st->n_voxel, st->n);
+        out->rows = reinterpret_cast<const ivx_cw_row*>(hs + h_rows);
+        if (n_rows > copy_rows) {  // (the list outgrew the guess: all rows, one more wait)
+            if (int rc = ivx_staging_for(&st->staging_rows, n_rows * sizeof(ivx_cw_row))) return rc;
+            IVX_HIP_CHECK(ivx_memcpy_async(st->staging_rows.p, st->rows.p, n_rows * sizeof(ivx_cw_row), hipMemcpyDeviceToHost, c->stream));
+            IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+            out->rows = static_cast<const ivx_cw_row*>(st->staging_rows.p);
+        }
+        st->n_rows = n_rows, st->last_deferred = n_rows;
+    }
+    return IVX_OK;
+}
+
+}  // namespace
+
+int ivx_cw_frame_pairs(ivx_world* w, const char* who, uint32_t mode, size_t contacts_cap, size_t deferred_cap, ivx_cw_frame_pass* out) {
+    CollidePass p;
+    if (int rc = collide_pass(w, who, mode, contacts_cap, deferred_cap, true, &p)) return rc;
+    out->n_primitive = p.totals[0], out->n_deferred = p.totals[1];
+    out->rows = p.rows, out->contacts = reinterpret_cast<const ivx_contact*>(p.contacts), out->deferred = reinterpret_cast<const uint32_t*>(p.deferred);
+    out->objects = p.st->objects.data(), out->n_collidables = p.st->n;
+    return IVX_OK;
+}
+
+int ivx_cw_frame_reserve(ivx_world* w, size_t n_primitive, size_t total, ivx_contact** list) {
+    CwState* st = static_cast<CwState*>(w->cw_state);
+    ivx_ctx* c = w->ctx;
+    if (st->contacts.bytes < total * sizeof(ivx_contact)) {  // grow, keeping what k_cw_emit wrote: the copy on the stream, one wait, then the old block goes
+        const size_t bytes = std::max<size_t>(total * sizeof(ivx_contact) * 3 / 2, 1u << 16);
+        void* fresh = nullptr;
+        IVX_HIP_CHECK(hipMalloc(&fresh, bytes));
+        hipError_t e = n_primitive ? ivx_memcpy_async(fresh, st->contacts.p, n_primitive * sizeof(ivx_contact), hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
+        if (e == hipSuccess) e = ivx_stream_sync(c->stream);
+        if (e != hipSuccess) (void)hipFree(fresh);
+        IVX_HIP_CHECK(e);
+        if (st->contacts.p) (void)hipFree(st->contacts.p);
+        st->contacts.p = fresh, st->contacts.bytes = bytes;
+    }
+    *list = static_cast<ivx_contact*>(st->contacts.p);
+    return IVX_OK;
+}
+
+int ivx_cw_frame_finish(ivx_world* w, size_t total, ivx_contact* out) {
+    CwState* st = static_cast<CwState*>(w->cw_state);
+    ivx_ctx* c = w->ctx;
+    if (out && total) {
+        if (int rc = ivx_staging_for(&st->staging_out, total * sizeof(ivx_contact))) return rc;
+        IVX_HIP_CHECK(ivx_memcpy_async(st->staging_out.p, st->contacts.p, total * sizeof(ivx_contact), hipMemcpyDeviceToHost, c->stream));
+    }
+    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+    if (out && total) memcpy(out, st->staging_out.p, total * sizeof(ivx_contact));
+    return IVX_OK;
 }
 
 extern "C" {
@@ -431,12 +609,23 @@ int ivx_cw_set_collidables(ivx_world* w, const ivx_collidable* collidables, size
     if (int rc = state_of(w, &st)) return rc;
     ivx_many_other_context other_(w->ctx);
     st->has_collidables = false, st->synchronized = false, st->n = 0;  // (until this call's set stands)
+    st->objects.clear(), st->n_voxel = 0, st->n_rows = 0, st->last_deferred = 0;  // (what was attached to the set before goes with it)
+    uint32_t n_voxel = 0;
+    for (size_t i = 0; i < n; ++i) n_voxel += collidables[i].shape == IVX_CW_VOXEL_OBJECT;
     if (n) {
         IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));  // (a synchronize in flight reads the records this call replaces)
         if (int rc = ivx_buf_grow(w->ctx, &st->local, n * sizeof(ivx_collidable), 1u << 16)) return rc;
         if (int rc = ivx_buf_grow(w->ctx, &st->world, n * sizeof(ivx_collidable), 1u << 16)) return rc;
         IVX_HIP_CHECK(ivx_memcpy_sync(st->local.p, collidables, n * sizeof(ivx_collidable), hipMemcpyHostToDevice));
+        if (n_voxel) {  // nothing attached yet
+            if (int rc = ivx_buf_grow(w->ctx, &st->voxel_dev, n * sizeof(CwVoxel), 1u << 12)) return rc;
+            IVX_HIP_CHECK(ivx_memset_async(st->voxel_dev.p, 0, n * sizeof(CwVoxel), w->ctx->stream));
+        }
     }
+    st->shapes.resize(n);
+    for (size_t i = 0; i < n; ++i) st->shapes[i] = (uint8_t)collidables[i].shape;
+    st->objects.assign(n, ivx_cw_voxel_object{});
+    st->n_voxel = n_voxel;
     st->n = (uint32_t)n, st->need_dyn = need_dyn, st->need_kin = need_kin;
     st->has_collidables = true;
     return IVX_OK;
@@ -488,60 +677,93 @@ int ivx_cw_collide(ivx_world* w, uint32_t mode, ivx_contact* out, size_t cap, si
     IVX_REQUIRE(mode <= IVX_BV_DYNAMIC_PAIRS, IVX_ERR_INVALID, "%s: mode %u (0 = all pairs, 1 = no phantom and at least one dynamic member)", who, mode);
     IVX_REQUIRE(out || cap == 0, IVX_ERR_INVALID, "%s: null contact buffer of capacity %zu", who, cap);
     IVX_REQUIRE(deferred_pairs || deferred_cap == 0, IVX_ERR_INVALID, "%s: null deferred pair buffer of capacity %zu", who, deferred_cap);
-    CwState* st;
-    if (int rc = synchronized_state(w, who, &st)) return rc;
-    ivx_ctx* c = w->ctx;
-    IVX_REQUIRE(ivx_bvol_set_serial(c) == st->set_serial, IVX_ERR_STATE,
-                "%s: the context's set of bounding volumes has been replaced since ivx_cw_synchronize (synchronize again)", who);
-    ivx_many_other_context other_(c);
-    st->n_contacts = 0, st->n_deferred = 0;
-    size_t n_pairs = 0;
-    if (st->broad_phase == IVX_CW_BROAD_HIERARCHY) {
-        if (int rc = ivx_bvh_build_enqueue(c, who)) return rc;  // (nothing waits)
-        if (int rc = ivx_bvh_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) return rc;
-    } else if (int rc = ivx_bvol_pairs_enqueue(c, who, mode, false, 0, &n_pairs)) {  // (either way the call's first wait: the grand total)
-        return rc;
-    }
-    if (n_pairs == 0) return IVX_OK;
-    const uint32_t np = (uint32_t)n_pairs, n_waves = (np + 63u) / 64u;
-    ivx_layout l;
-    const size_t o_mh = l.take((size_t)n_waves * 8), o_md = l.take((size_t)n_waves * 8), o_oh = l.take((size_t)n_waves * 4), o_od = l.take((size_t)n_waves * 4), o_tot = l.take(8);
-    if (int rc = ivx_buf_grow(c, &st->scratch, l.bytes, 1u << 16)) return rc;
-    if (int rc = ivx_buf_grow(c, &st->contacts, n_pairs * sizeof(ivx_contact), 1u << 16)) return rc;  // (at most one contact per pair)
-    if (int rc = ivx_buf_grow(c, &st->deferred, n_pairs * 8, 1u << 16)) return rc;
-    const size_t copy_contacts = out ? (cap < n_pairs ? cap : n_pairs) : 0, copy_deferred = deferred_pairs ? (deferred_cap < n_pairs ? deferred_cap : n_pairs) : 0;
-    ivx_layout h;
-    const size_t h_tot = h.take(8), h_contacts = h.take(copy_contacts * sizeof(ivx_contact)), h_deferred = h.take(copy_deferred * 8);
-    if (int rc = ivx_staging_for(&st->staging, h.bytes)) return rc;
-    char* s = static_cast<char*>(st->scratch.p);
-    unsigned long long* d_mh = reinterpret_cast<unsigned long long*>(s + o_mh);
-    unsigned long long* d_md = reinterpret_cast<unsigned long long*>(s + o_md);
-    uint32_t* d_oh = reinterpret_cast<uint32_t*>(s + o_oh);
-    uint32_t* d_od = reinterpret_cast<uint32_t*>(s + o_od);
-    uint32_t* d_tot = reinterpret_cast<uint32_t*>(s + o_tot);
-    const uint2* d_pairs = static_cast<const uint2*>(ivx_bv_device_ptr(c, IVX_BV_PTR_PAIRS));
-    const ivx_collidable* d_colls = static_cast<const ivx_collidable*>(st->world.p);
-    IVX_REQUIRE(d_pairs && d_colls, IVX_ERR_STATE, "%s: no resident pair buffer", who);
-    const dim3 grid((np + GROUP - 1u) / GROUP);
-    IVX_KLAUNCH(k_cw_test, grid, dim3(GROUP), 0, c->stream, d_pairs, np, d_colls, d_mh, d_md);
-    IVX_KLAUNCH(k_cw_scan, dim3(1), dim3(SCAN_ROUND), 0, c->stream, (const unsigned long long*)d_mh, (const unsigned long long*)d_md, n_waves, d_oh, d_od, d_tot);
-    IVX_KLAUNCH(k_cw_emit, grid, dim3(GROUP), 0, c->stream, d_pairs, np, d_colls, (const unsigned long long*)d_mh, (const unsigned long long*)d_md, (const uint32_t*)d_oh,
-                (const uint32_t*)d_od, static_cast<ivx_contact*>(st->contacts.p), static_cast<uint2*>(st->deferred.p));
-    IVX_HIP_CHECK(hipGetLastError());
-    // the call's second wait: the two counts, and as much of the two lists as the caller's buffers could hold (what lies behind the counts is dropped)
-    char* hs = static_cast<char*>(st->staging.p);
-    IVX_HIP_CHECK(ivx_memcpy_async(hs + h_tot, d_tot, 8, hipMemcpyDeviceToHost, c->stream));
-    if (copy_contacts) IVX_HIP_CHECK(ivx_memcpy_async(hs + h_contacts, st->contacts.p, copy_contacts * sizeof(ivx_contact), hipMemcpyDeviceToHost, c->stream));
-    if (copy_deferred) IVX_HIP_CHECK(ivx_memcpy_async(hs + h_deferred, st->deferred.p, copy_deferred * 8, hipMemcpyDeviceToHost, c->stream));
-    IVX_HIP_CHECK(ivx_stream_sync(c->stream));
-    uint32_t totals[2];
-    memcpy(totals, hs + h_tot, 8);
-    st->n_contacts = totals[0], st->n_deferred = totals[1];
+    CollidePass p;
+    if (int rc = collide_pass(w, who, mode, out ? cap : 0, deferred_pairs ? deferred_cap : 0, false, &p)) return rc;
+    const uint32_t* totals = p.totals;
     *n_out = totals[0], *n_deferred = totals[1];
     IVX_REQUIRE(!out || totals[0] <= cap, IVX_ERR_CAPACITY, "%s: %u contacts, the buffer holds %zu", who, totals[0], cap);
     IVX_REQUIRE(!deferred_pairs || totals[1] <= deferred_cap, IVX_ERR_CAPACITY, "%s: %u deferred pairs, the buffer holds %zu", who, totals[1], deferred_cap);
-    if (out && totals[0]) memcpy(out, hs + h_contacts, (size_t)totals[0] * sizeof(ivx_contact));
-    if (deferred_pairs && totals[1]) memcpy(deferred_pairs, hs + h_deferred, (size_t)totals[1] * 8);
+    if (out && totals[0]) memcpy(out, p.contacts, (size_t)totals[0] * sizeof(ivx_contact));
+    if (deferred_pairs && totals[1]) memcpy(deferred_pairs, p.deferred, (size_t)totals[1] * 8);
+    return IVX_OK;
+}
+
+int ivx_cw_to_object_space(const float position[3], const float orientation_xyzw[4], const float origin_offset[3], float rotation_out[4], float translation_out[3]) {
+    IVX_REQUIRE(position && orientation_xyzw && origin_offset && rotation_out && translation_out, IVX_ERR_INVALID, "ivx_cw_to_object_space: null argument");
+    const float pose[7] = {position[0], position[1], position[2], orientation_xyzw[0], orientation_xyzw[1], orientation_xyzw[2], orientation_xyzw[3]};
+    ivx_cw_rows::to_object_space(pose, origin_offset, rotation_out, translation_out);
+    return IVX_OK;
+}
+
+int ivx_cw_voxel_row(const ivx_collidable* a_world, const ivx_collidable* b_world, const float pose_a[7], const float pose_b[7], const ivx_cw_voxel_object* voxel_a,
+                     const ivx_cw_voxel_object* voxel_b, ivx_cw_row* out) {
+    const char* who = "ivx_cw_voxel_row";
+    IVX_REQUIRE(a_world && b_world && out, IVX_ERR_INVALID, "%s: null argument", who);
+    IVX_REQUIRE(a_world->shape <= IVX_CW_VOXEL_OBJECT && b_world->shape <= IVX_CW_VOXEL_OBJECT, IVX_ERR_INVALID,
+                "%s: shapes %u, %u (0 sphere, 1 plane, 2 capsule, 3 voxel object)", who, a_world->shape, b_world->shape);
+    IVX_REQUIRE(a_world->shape == IVX_CW_VOXEL_OBJECT || b_world->shape == IVX_CW_VOXEL_OBJECT, IVX_ERR_INVALID, "%s: neither member is a voxel object", who);
+    ivx_cw_rows::Member m[2];
+    for (int k = 0; k < 2; ++k) {
+        const ivx_collidable* c = k ? b_world : a_world;
+        const float* pose = k ? pose_b : pose_a;
+        const ivx_cw_voxel_object* v = k ? voxel_b : voxel_a;
+        const bool voxel = c->shape == IVX_CW_VOXEL_OBJECT;
+        IVX_REQUIRE(!voxel || (pose && v), IVX_ERR_INVALID, "%s: member %c is a voxel object and needs its body's pose and its record", who, k ? 'b' : 'a');
+        m[k].c = c, m[k].index = (uint32_t)k;
+        m[k].pose = voxel ? pose : nullptr;
+        m[k].origin_offset = voxel ? v->origin_offset : nullptr, m[k].center_of_mass = voxel ? v->center_of_mass : nullptr;
+    }
+    ivx_cw_rows::voxel_row(m[0], m[1], out);
+    return IVX_OK;
+}
+
+int ivx_cw_set_voxel_objects(ivx_world* w, const uint32_t* collidable_index, const ivx_cw_voxel_object* objects, size_t n) {
+    const char* who = "ivx_cw_set_voxel_objects";
+    IVX_REQUIRE(w && ((collidable_index && objects) || n == 0), IVX_ERR_INVALID, "%s: null argument", who);
+    CwState* st = static_cast<CwState*>(w->cw_state);
+    IVX_REQUIRE(st && st->has_collidables, IVX_ERR_STATE, "%s: the world holds no collidables (call ivx_cw_set_collidables first)", who);
+    static thread_local std::vector<ivx_cw_voxel_object> fresh;
+    fresh.assign(st->n, ivx_cw_voxel_object{});
+    for (size_t k = 0; k < n; ++k) {
+        const uint32_t i = collidable_index[k];
+        IVX_REQUIRE(i < st->n, IVX_ERR_INVALID, "%s: attachment %zu names collidable %u, the world has %u", who, k, i, st->n);
+        IVX_REQUIRE(st->shapes[i] == IVX_CW_VOXEL_OBJECT, IVX_ERR_INVALID, "%s: attachment %zu: collidable %u has shape %u, not a voxel object", who, k, i, (uint32_t)st->shapes[i]);
+        IVX_REQUIRE(objects[k].grid, IVX_ERR_INVALID, "%s: attachment %zu: null grid", who, k);
+        IVX_REQUIRE(objects[k].grid->ctx == w->ctx, IVX_ERR_INVALID, "%s: attachment %zu: the grid belongs to another context than the world", who, k);
+        IVX_REQUIRE(!fresh[i].grid, IVX_ERR_INVALID, "%s: collidable %u is named twice", who, i);
+        fresh[i] = objects[k];
+    }
+    ivx_ctx* c = w->ctx;
+    ivx_many_other_context other_(c);
+    if (st->n_voxel) {  // (a set without voxel collidables took no attachment above and has no device array)
+        IVX_HIP_CHECK(ivx_stream_sync(c->stream));
+        if (int rc = ivx_staging_for(&st->staging_rows, (size_t)st->n * sizeof(CwVoxel))) return rc;
+        CwVoxel* h = static_cast<CwVoxel*>(st->staging_rows.p);
+        memset(h, 0, (size_t)st->n * sizeof(CwVoxel));
+        for (uint32_t i = 0; i < st->n; ++i)
+            if (fresh[i].grid) {
+                for (int d = 0; d < 3; ++d) h[i].origin_offset[d] = fresh[i].origin_offset[d], h[i].center_of_mass[d] = fresh[i].center_of_mass[d];
+                h[i].attached = 1u;
+            }
+        IVX_HIP_CHECK(ivx_memcpy_sync(st->voxel_dev.p, h, (size_t)st->n * sizeof(CwVoxel), hipMemcpyHostToDevice));
+    }
+    st->objects = fresh;
+    return IVX_OK;
+}
+
+int ivx_cw_rows_download(ivx_world* w, ivx_cw_row* rows, size_t cap, size_t* n_rows) {
+    const char* who = "ivx_cw_rows_download";
+    IVX_REQUIRE(n_rows, IVX_ERR_INVALID, "%s: null argument", who);
+    *n_rows = 0;
+    CwState* st;
+    if (int rc = synchronized_state(w, who, &st)) return rc;
+    *n_rows = st->n_rows;
+    IVX_REQUIRE(cap >= st->n_rows, IVX_ERR_CAPACITY, "%s: the last frame has %zu rows, the buffer holds %zu", who, st->n_rows, cap);
+    IVX_REQUIRE(rows || st->n_rows == 0, IVX_ERR_INVALID, "%s: null buffer", who);
+    if (st->n_rows == 0) return IVX_OK;
+    ivx_many_other_context other_(w->ctx);
+    IVX_HIP_CHECK(ivx_memcpy_async(rows, st->rows.p, st->n_rows * sizeof(ivx_cw_row), hipMemcpyDeviceToHost, w->ctx->stream));
+    IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));
     return IVX_OK;
 }
 
@@ -562,6 +784,8 @@ void* ivx_cw_device_ptr(ivx_world* w, int which) {
         case IVX_CW_PTR_WORLD_COLLIDABLES: return st->synchronized && st->n ? st->world.p : nullptr;
         case IVX_CW_PTR_CONTACTS: return st->contacts.p;
         case IVX_CW_PTR_DEFERRED_PAIRS: return st->deferred.p;
+        case IVX_CW_PTR_FRAME_CONTACTS: return st->contacts.p;
+        case IVX_CW_PTR_VOXEL_ROWS: return st->rows.p;
         default: return nullptr;
     }
 }

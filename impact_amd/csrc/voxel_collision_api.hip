@@ -1,6 +1,7 @@
 // Voxel collision host code of libimpact_voxel_hip.so: contacts of a voxel object with a sphere, plane or capsule collidable, the collision probes
-// that follow an object's mesh, mutual contacts of two voxel objects and their mutual absorption; single calls and the `_many` forms. Host-side
-// orchestration only: the kernels are those of contacts.hip, collide.hip and edit.hip behind their ivx_launch_* functions.
+// that follow an object's mesh, mutual contacts of two voxel objects and their mutual absorption; single calls and the `_many` forms; and the
+// host side of ivx_cw_collide_frame, which runs both `_many` generator families over the rows narrow.hip made of a frame's deferred pairs.
+// Host-side orchestration only: the kernels are those of contacts.hip, collide.hip and edit.hip behind their ivx_launch_* functions.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -9,7 +10,9 @@
 #include <new>
 #include <vector>
 
+#include "cw_rows.hpp"
 #include "ivx_host.hpp"
+#include "physics_internal.hpp"
 #include "vec3.hpp"
 
 namespace {
@@ -270,12 +273,12 @@ int contacts_download(ivx_grid* g, const char* who, const uint32_t* d_total, con
 // the context's pinned, device-visible scratch (ivx_ctx::pinned_scratch): at least `bytes`
 int ctx_pinned_scratch(ivx_ctx* c, size_t bytes) { return ivx_mapped_grow(&c->pinned_scratch, bytes, std::max<size_t>(2 * bytes, 1 << 20), c->stream); }
 
-// The second half of the two batched contact calls, once the count phase is on the stream and has written every query's total into the pinned
-// block: wait; the totals into out_offsets; the capacity check; the pinned block grown for all contacts (it may move: the totals are kept aside);
+// The batched contact calls (the two `_many` generators, and ivx_cw_collide_frame over both families at once) in pieces. Once the count phase is
+// on the stream and has written every query's total into the pinned block: wait, the totals into out_offsets (n + 1) and aside into `counts`
+// (the pinned block may move afterwards) -> *run, the contacts of all queries |
 // `emit(i, list, count)` for every query that found any, under the recorder (many_phase; `chain`: the object that stands for query i), its
-// contacts going to list[0 .. count); wait; copy out.
-int contacts_many_finish(ivx_ctx* c, ivx_grid* const* chain, size_t n, const char* who, ivx_contact* out, size_t cap, uint32_t* out_offsets,
-                         const std::function<int(size_t, ivx_contact*, uint32_t)>& emit) {
+// contacts going to list[0 .. count) = `list` + out_offsets[i]: the destination is the caller's (the pinned block, or the world's contact buffer).
+int contacts_many_wait_totals(ivx_ctx* c, size_t n, uint32_t* out_offsets, std::vector<uint32_t>& counts, size_t* run_out) {
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
     const uint32_t* totals = static_cast<const uint32_t*>(c->pinned_scratch.p);
     size_t run = 0;
@@ -284,14 +287,26 @@ int contacts_many_finish(ivx_ctx* c, ivx_grid* const* chain, size_t n, const cha
         run += totals[i];
     }
     out_offsets[n] = (uint32_t)run;
+    counts.assign(totals, totals + n);
+    *run_out = run;
+    return IVX_OK;
+}
+int contacts_many_emit(ivx_grid* const* chain, size_t n, const std::vector<uint32_t>& counts, const uint32_t* out_offsets, ivx_contact* list,
+                       const std::function<int(size_t, ivx_contact*, uint32_t)>& emit) {
+    return many_phase(chain, n, [&](size_t i) -> int { return counts[i] ? emit(i, list + out_offsets[i], counts[i]) : IVX_OK; });
+}
+// The second half of the two `_many` calls: the totals; the capacity check; the pinned block grown for all contacts; the emit passes into it;
+// wait; copy out.
+int contacts_many_finish(ivx_ctx* c, ivx_grid* const* chain, size_t n, const char* who, ivx_contact* out, size_t cap, uint32_t* out_offsets,
+                         const std::function<int(size_t, ivx_contact*, uint32_t)>& emit) {
+    static thread_local std::vector<uint32_t> counts;
+    size_t run = 0;
+    int rc;
+    if ((rc = contacts_many_wait_totals(c, n, out_offsets, counts, &run))) return rc;
     IVX_REQUIRE(run <= cap, IVX_ERR_CAPACITY, "%s: %zu contacts exceed the capacity %zu", who, run, cap);
     if (run == 0) return IVX_OK;
-    static thread_local std::vector<uint32_t> counts;
-    counts.assign(totals, totals + n);
-    int rc;
     if ((rc = ctx_pinned_scratch(c, run * sizeof(ivx_contact)))) return rc;
-    ivx_contact* list_dev = static_cast<ivx_contact*>(c->pinned_scratch.dev);
-    if ((rc = many_phase(chain, n, [&](size_t i) -> int { return counts[i] ? emit(i, list_dev + out_offsets[i], counts[i]) : IVX_OK; }))) return rc;
+    if ((rc = contacts_many_emit(chain, n, counts, out_offsets, static_cast<ivx_contact*>(c->pinned_scratch.dev), emit))) return rc;
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
     memcpy(out, c->pinned_scratch.p, run * sizeof(ivx_contact));
     return IVX_OK;
@@ -334,6 +349,62 @@ static int voxel_object_contacts(ivx_grid* g, const char* who, int mode, const f
     return contacts_download(g, who, d_total, d_out, out, cap, n_out);
 }
 
+namespace {
+// ivx_voxel_object_contacts_many in pieces (ivx_cw_collide_frame runs the same ones over its rows). check: what a query must satisfy | plan: what
+// may wait or allocate, ahead of the recording — occupied ranges, the chunk box, a range of the object's scratch for counts and offsets | launch:
+// the count pass (pass 0: the scan writes the total to d_total) or the emit pass (pass 1: the contacts go to d_out[0 .. cap_i)), recorded.
+struct CollidablePlan {
+    struct Box {
+        int32_t vlo[3], vhi[3];
+        uint32_t lo[3], cc[3];
+        bool hit;
+        size_t off;  // where this query's counts and offsets start in its object's scratch
+    };
+    std::vector<Box> box;
+    // (an object may appear more than once — near a sphere AND the ground plane, the reference's collision pass visits every collidable near an
+    // object —: each query gets a range of its own in the object's scratch, the recorded chains of one object must not share counts)
+    std::vector<std::pair<ivx_grid*, size_t>> scratch_need;
+    void begin(size_t n) {
+        box.assign(n, Box{});
+        scratch_need.clear();
+    }
+};
+int collidable_check(ivx_ctx* c, ivx_grid* g, const ivx_collidable_query& q, const char* who, size_t i) {
+    IVX_REQUIRE(g && g->ctx == c, IVX_ERR_INVALID, "%s: object %zu is null or belongs to another context", who, i);
+    IVX_REQUIRE(q.mode >= 0 && q.mode <= 2, IVX_ERR_INVALID, "%s: query %zu: mode %d", who, i, q.mode);
+    return require_whole_object(g, who, false, "object", i);
+}
+int collidable_plan_row(CollidablePlan& plan, size_t i, ivx_grid* g, const ivx_collidable_query& q, const char* who) {
+    uint32_t occ[12];
+    if (int rc = ivx_reference_occupied(g, who, occ)) return rc;
+    CollidablePlan::Box& b = plan.box[i];
+    b.hit = contacts_box(g, q.mode, q.rotation_xyzw, q.translation, q.shape3, q.shape3b, q.shape1, occ, b.vlo, b.vhi, b.lo, b.cc);
+    if (!b.hit) return IVX_OK;
+    const size_t need = (2 * (size_t)b.cc[0] * b.cc[1] * b.cc[2] * 4 + 64 + 255) & ~(size_t)255;
+    auto it = std::find_if(plan.scratch_need.begin(), plan.scratch_need.end(), [&](const std::pair<ivx_grid*, size_t>& e) { return e.first == g; });
+    if (it == plan.scratch_need.end()) {
+        plan.scratch_need.emplace_back(g, (size_t)0);
+        it = plan.scratch_need.end() - 1;
+    }
+    b.off = it->second;
+    it->second += need;
+    return IVX_OK;
+}
+int collidable_plan_scratch(const CollidablePlan& plan) {
+    for (const auto& e : plan.scratch_need)
+        if (int rc = ensure_dev_scratch(e.first, e.second)) return rc;
+    return IVX_OK;
+}
+int collidable_launch(const CollidablePlan& plan, size_t i, ivx_grid* g, const ivx_collidable_query& q, int pass, uint32_t* d_total, ivx_contact* d_out, uint32_t cap_i) {
+    const CollidablePlan::Box& b = plan.box[i];
+    const size_t n_box = (size_t)b.cc[0] * b.cc[1] * b.cc[2];
+    char* base = static_cast<char*>(g->dev_scratch) + b.off;
+    return ivx_launch_sphere_contacts(g, b.lo, b.cc, b.vlo, b.vhi, q.rotation_xyzw, q.translation, q.shape3, q.shape3b, q.shape1, q.collidable_id_a, q.collidable_id_b,
+                                      q.body_a, q.body_b, q.response, reinterpret_cast<uint32_t*>(base), reinterpret_cast<uint32_t*>(base + n_box * 4), d_total, d_out,
+                                      cap_i, pass, q.mode);
+}
+}  // namespace
+
 // One collidable per object, N objects, in the launches of one (many.hpp): the reference's collision pass walks every voxel object of the
 // scene against the collidables near it (impact_voxel/src/collidable.rs:1051-1286: the per-pair dispatch) — here the pairs (object i,
 // collidable i) of one call. Two recorded phases, two waits for ALL objects where the single-object call has two per object: (1) count + scan
@@ -348,58 +419,20 @@ int ivx_voxel_object_contacts_many(ivx_grid* const* grids, size_t n, const ivx_c
     IVX_REQUIRE(grids && queries && (out || cap == 0), IVX_ERR_INVALID, "%s: null argument", who);
     ivx_ctx* c = grids[0] ? grids[0]->ctx : nullptr;
     int rc;
-    for (size_t i = 0; i < n; ++i) {
-        ivx_grid* g = grids[i];
-        IVX_REQUIRE(g && g->ctx == c, IVX_ERR_INVALID, "%s: object %zu is null or belongs to another context", who, i);
-        IVX_REQUIRE(queries[i].mode >= 0 && queries[i].mode <= 2, IVX_ERR_INVALID, "%s: query %zu: mode %d", who, i, queries[i].mode);
-        if ((rc = require_whole_object(g, who, false, "object", i))) return rc;
-    }
+    for (size_t i = 0; i < n; ++i)
+        if ((rc = collidable_check(c, grids[i], queries[i], who, i))) return rc;
     IVX_REQUIRE(!ivx_many_recording(), IVX_ERR_STATE, "%s: not inside an ivx_many_begin bracket (the call waits for its own phases)", who);
-    struct Box {
-        int32_t vlo[3], vhi[3];
-        uint32_t lo[3], cc[3];
-        bool hit;
-        size_t off;  // where this query's counts and offsets start in its object's scratch
-    };
-    static thread_local std::vector<Box> box;
-    box.assign(n, Box{});
-    // (an object may appear more than once — near a sphere AND the ground plane, the reference's collision pass visits every collidable near an
-    // object —: each query gets a range of its own in the object's scratch, the recorded chains of one object must not share counts)
-    static thread_local std::vector<std::pair<ivx_grid*, size_t>> scratch_need;
-    scratch_need.clear();
-    // what may wait or allocate, ahead of the recording: occupied ranges, the objects' scratch for counts and offsets, the pinned block
-    for (size_t i = 0; i < n; ++i) {
-        const ivx_collidable_query& q = queries[i];
-        uint32_t occ[12];
-        if ((rc = ivx_reference_occupied(grids[i], who, occ))) return rc;
-        Box& b = box[i];
-        b.hit = contacts_box(grids[i], q.mode, q.rotation_xyzw, q.translation, q.shape3, q.shape3b, q.shape1, occ, b.vlo, b.vhi, b.lo, b.cc);
-        if (!b.hit) continue;
-        const size_t need = (2 * (size_t)b.cc[0] * b.cc[1] * b.cc[2] * 4 + 64 + 255) & ~(size_t)255;
-        auto it = std::find_if(scratch_need.begin(), scratch_need.end(), [&](const std::pair<ivx_grid*, size_t>& e) { return e.first == grids[i]; });
-        if (it == scratch_need.end()) {
-            scratch_need.emplace_back(grids[i], (size_t)0);
-            it = scratch_need.end() - 1;
-        }
-        b.off = it->second;
-        it->second += need;
-    }
-    for (const auto& e : scratch_need)
-        if ((rc = ensure_dev_scratch(e.first, e.second))) return rc;
+    static thread_local CollidablePlan plan;
+    plan.begin(n);
+    for (size_t i = 0; i < n; ++i)
+        if ((rc = collidable_plan_row(plan, i, grids[i], queries[i], who))) return rc;
+    if ((rc = collidable_plan_scratch(plan))) return rc;
     uint32_t* totals_dev;
     if ((rc = contacts_many_totals(c, n, &totals_dev))) return rc;
-    auto launch = [&](size_t i, int pass, uint32_t* d_total, ivx_contact* d_out, uint32_t cap_i) -> int {
-        const ivx_collidable_query& q = queries[i];
-        const Box& b = box[i];
-        ivx_grid* g = grids[i];
-        const size_t n_box = (size_t)b.cc[0] * b.cc[1] * b.cc[2];
-        char* base = static_cast<char*>(g->dev_scratch) + b.off;
-        return ivx_launch_sphere_contacts(g, b.lo, b.cc, b.vlo, b.vhi, q.rotation_xyzw, q.translation, q.shape3, q.shape3b, q.shape1, q.collidable_id_a, q.collidable_id_b,
-                                          q.body_a, q.body_b, q.response, reinterpret_cast<uint32_t*>(base), reinterpret_cast<uint32_t*>(base + n_box * 4), d_total, d_out,
-                                          cap_i, pass, q.mode);
-    };
-    if ((rc = many_phase(grids, n, [&](size_t i) -> int { return box[i].hit ? launch(i, 0, totals_dev + i, nullptr, 0u) : IVX_OK; }))) return rc;
-    return contacts_many_finish(c, grids, n, who, out, cap, out_offsets, [&](size_t i, ivx_contact* list, uint32_t count) { return launch(i, 1, nullptr, list, count); });
+    if ((rc = many_phase(grids, n, [&](size_t i) -> int { return plan.box[i].hit ? collidable_launch(plan, i, grids[i], queries[i], 0, totals_dev + i, nullptr, 0u) : IVX_OK; })))
+        return rc;
+    return contacts_many_finish(c, grids, n, who, out, cap, out_offsets,
+                                [&](size_t i, ivx_contact* list, uint32_t count) { return collidable_launch(plan, i, grids[i], queries[i], 1, nullptr, list, count); });
 }
 
 int ivx_sphere_voxel_object_contacts(ivx_grid* g, const float rotation_xyzw[4], const float translation[3], const float sphere_center[3], float sphere_radius,
@@ -845,6 +878,67 @@ int ivx_mutual_voxel_object_contacts(ivx_grid* a, const float rotation_a[4], con
     return contacts_download(a, who, d_offsets + n_wg, d_out, out, cap, n_out);
 }
 
+namespace {
+// ivx_mutual_voxel_object_contacts_many in pieces (ivx_cw_collide_frame runs the same ones over its rows). check | plan: mutual_prepare and the
+// pair's range of counts and offsets in the context's device scratch, which plan_scratch then grows | count: A's probes in B's field, B's in A's,
+// the scan with its total to d_total | emit: both passes into list[0 .. count), recorded.
+struct MutualPlan {
+    struct Pair {
+        ivx_mutual_pass pass[2];
+        uint32_t wg_a, wg_b;
+        size_t off;  // of the pair's counts / offsets in the context's scratch (u32 words)
+        bool hit;
+    };
+    std::vector<Pair> pr;
+    size_t words = 0;
+    uint32_t* base = nullptr;
+    void begin(size_t n) {
+        pr.assign(n, Pair{});
+        words = 0, base = nullptr;
+    }
+};
+int mutual_check(ivx_ctx* c, const ivx_mutual_query& q, const char* who, size_t i) {
+    IVX_REQUIRE(q.a && q.b && q.a != q.b && q.a->ctx == c && q.b->ctx == c, IVX_ERR_INVALID, "%s: pair %zu: two different objects of the call's context are needed", who, i);
+    for (ivx_grid* g : {q.a, q.b})
+        if (int rc = require_whole_object(g, who, true, "pair", i)) return rc;
+    return IVX_OK;
+}
+int mutual_plan_row(MutualPlan& plan, size_t i, const ivx_mutual_query& q, const char* who) {
+    MutualPlan::Pair& p = plan.pr[i];
+    if (int rc = mutual_prepare(who, q.a, q.rotation_a, q.translation_a, q.center_of_mass_a, q.b, q.rotation_b, q.translation_b, q.center_of_mass_b, q.collidable_id_a,
+                                q.collidable_id_b, q.body_a, q.body_b, q.response, p.pass, &p.hit))
+        return rc;
+    p.wg_a = (q.a->n_probe_points + 255u) / 256u, p.wg_b = (q.b->n_probe_points + 255u) / 256u;
+    if (p.wg_a + p.wg_b == 0) p.hit = false;
+    p.off = plan.words;
+    if (p.hit) plan.words += 2 * (size_t)(p.wg_a + p.wg_b) + 16;
+    return IVX_OK;
+}
+// counts and offsets of all pairs: one block of the context's device scratch
+int mutual_plan_scratch(MutualPlan& plan, ivx_ctx* c) {
+    if (int rc = ivx_buf_grow(c, &c->dev_scratch, plan.words * 4 + 64, 1 << 20)) return rc;
+    plan.base = static_cast<uint32_t*>(c->dev_scratch.p);
+    return IVX_OK;
+}
+int mutual_count(const MutualPlan& plan, size_t i, const ivx_mutual_query& q, ivx_ctx* c, uint32_t* d_total) {
+    const MutualPlan::Pair& p = plan.pr[i];
+    if (!p.hit) return IVX_OK;
+    const uint32_t n_wg = p.wg_a + p.wg_b;
+    uint32_t* d_counts = plan.base + p.off;
+    uint32_t* d_offsets = d_counts + n_wg;
+    int r;
+    if ((r = ivx_launch_mutual_pass(q.a, q.b, &p.pass[0], d_counts, nullptr, nullptr, 0u, 0))) return r;
+    if ((r = ivx_launch_mutual_pass(q.b, q.a, &p.pass[1], d_counts + p.wg_a, nullptr, nullptr, 0u, 0))) return r;
+    return ivx_launch_scan_counts(c, n_wg, d_counts, d_offsets, d_total, q.a);
+}
+int mutual_emit(const MutualPlan& plan, size_t i, const ivx_mutual_query& q, ivx_contact* list, uint32_t count) {
+    const MutualPlan::Pair& p = plan.pr[i];
+    const uint32_t* d_offsets = plan.base + p.off + (p.wg_a + p.wg_b);
+    const int r = ivx_launch_mutual_pass(q.a, q.b, &p.pass[0], nullptr, d_offsets, list, count, 1);
+    return r ? r : ivx_launch_mutual_pass(q.b, q.a, &p.pass[1], nullptr, d_offsets + p.wg_a, list, count, 1);
+}
+}  // namespace
+
 // The same for a LIST of pairs in the launches of one (many.hpp) — the reference's narrow phase visits every pair of voxel objects the broad
 // phase hands it (collidable.rs:859-1049 per pair) —: per pair count (A's probes in B's field) | count (B's in A's) | scan, recorded for all
 // pairs and issued merged, the totals written by the scans into host-mapped memory; one wait; then the emit passes of all pairs into one
@@ -857,60 +951,116 @@ int ivx_mutual_voxel_object_contacts_many(const ivx_mutual_query* queries, size_
     IVX_REQUIRE(queries && (out || cap == 0), IVX_ERR_INVALID, "%s: null argument", who);
     ivx_ctx* c = queries[0].a ? queries[0].a->ctx : nullptr;
     int rc;
-    for (size_t i = 0; i < n; ++i) {
-        const ivx_mutual_query& q = queries[i];
-        IVX_REQUIRE(q.a && q.b && q.a != q.b && q.a->ctx == c && q.b->ctx == c, IVX_ERR_INVALID, "%s: pair %zu: two different objects of the call's context are needed", who, i);
-        for (ivx_grid* g : {q.a, q.b})
-            if ((rc = require_whole_object(g, who, true, "pair", i))) return rc;
-    }
+    for (size_t i = 0; i < n; ++i)
+        if ((rc = mutual_check(c, queries[i], who, i))) return rc;
     IVX_REQUIRE(!ivx_many_recording(), IVX_ERR_STATE, "%s: not inside an ivx_many_begin bracket (the call waits for its own phases)", who);
-    struct Pair {
-        ivx_mutual_pass pass[2];
-        uint32_t wg_a, wg_b;
-        size_t off;  // of the pair's counts / offsets in the context's scratch (u32 words)
-        bool hit;
-    };
-    static thread_local std::vector<Pair> pr;
-    pr.assign(n, Pair{});
-    size_t words = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const ivx_mutual_query& q = queries[i];
-        Pair& p = pr[i];
-        if ((rc = mutual_prepare(who, q.a, q.rotation_a, q.translation_a, q.center_of_mass_a, q.b, q.rotation_b, q.translation_b, q.center_of_mass_b, q.collidable_id_a,
-                                 q.collidable_id_b, q.body_a, q.body_b, q.response, p.pass, &p.hit)))
-            return rc;
-        p.wg_a = (q.a->n_probe_points + 255u) / 256u, p.wg_b = (q.b->n_probe_points + 255u) / 256u;
-        if (p.wg_a + p.wg_b == 0) p.hit = false;
-        p.off = words;
-        if (p.hit) words += 2 * (size_t)(p.wg_a + p.wg_b) + 16;
-    }
-    // counts and offsets of all pairs: one block of the context's device scratch; totals and contacts: its pinned block
-    if ((rc = ivx_buf_grow(c, &c->dev_scratch, words * 4 + 64, 1 << 20))) return rc;
+    static thread_local MutualPlan plan;
+    plan.begin(n);
+    for (size_t i = 0; i < n; ++i)
+        if ((rc = mutual_plan_row(plan, i, queries[i], who))) return rc;
+    // totals and contacts: the context's pinned block
+    if ((rc = mutual_plan_scratch(plan, c))) return rc;
     uint32_t* totals_dev;
     if ((rc = contacts_many_totals(c, n, &totals_dev))) return rc;
-    uint32_t* base = static_cast<uint32_t*>(c->dev_scratch.p);
     std::vector<ivx_grid*> chain(n);  // (the recorder's chains go by pair: the first object of each stands for it)
     for (size_t i = 0; i < n; ++i) chain[i] = queries[i].a;
-    if ((rc = many_phase(chain.data(), n, [&](size_t i) -> int {
-             const Pair& p = pr[i];
-             if (!p.hit) return IVX_OK;
-             const ivx_mutual_query& q = queries[i];
-             const uint32_t n_wg = p.wg_a + p.wg_b;
-             uint32_t* d_counts = base + p.off;
-             uint32_t* d_offsets = d_counts + n_wg;
-             int r;
-             if ((r = ivx_launch_mutual_pass(q.a, q.b, &p.pass[0], d_counts, nullptr, nullptr, 0u, 0))) return r;
-             if ((r = ivx_launch_mutual_pass(q.b, q.a, &p.pass[1], d_counts + p.wg_a, nullptr, nullptr, 0u, 0))) return r;
-             return ivx_launch_scan_counts(c, n_wg, d_counts, d_offsets, totals_dev + i, q.a);
-         })))
-        return rc;
-    return contacts_many_finish(c, chain.data(), n, who, out, cap, out_offsets, [&](size_t i, ivx_contact* list, uint32_t count) -> int {
-        const Pair& p = pr[i];
-        const ivx_mutual_query& q = queries[i];
-        const uint32_t* d_offsets = base + p.off + (p.wg_a + p.wg_b);
-        const int r = ivx_launch_mutual_pass(q.a, q.b, &p.pass[0], nullptr, d_offsets, list, count, 1);
-        return r ? r : ivx_launch_mutual_pass(q.b, q.a, &p.pass[1], nullptr, d_offsets + p.wg_a, list, count, 1);
-    });
+    if ((rc = many_phase(chain.data(), n, [&](size_t i) -> int { return mutual_count(plan, i, queries[i], c, totals_dev + i); }))) return rc;
+    return contacts_many_finish(c, chain.data(), n, who, out, cap, out_offsets,
+                                [&](size_t i, ivx_contact* list, uint32_t count) -> int { return mutual_emit(plan, i, queries[i], list, count); });
+}
+
+// The whole collision pass of a frame (include/impact_voxel_hip.h): narrow.hip's pair pass, primitive narrow phase and rows (two waits), then the
+// two generator families over the rows — planned with the pieces above, their count passes and scans recorded in ONE phase so that collidable
+// rows and mutual rows merge launch by launch (third wait: the totals), their emit passes writing behind the primitive contacts in the world's
+// contact buffer (fourth wait: the list).
+int ivx_cw_collide_frame(ivx_world* w, uint32_t mode, ivx_contact* out, size_t cap, size_t* n_out, size_t* n_primitive, uint32_t* deferred_pairs,
+                         uint32_t* manifold_offsets, size_t deferred_cap, size_t* n_deferred) {
+    const char* who = "ivx_cw_collide_frame";
+    IVX_REQUIRE(n_out && n_primitive && n_deferred, IVX_ERR_INVALID, "%s: null argument", who);
+    *n_out = 0, *n_primitive = 0, *n_deferred = 0;
+    IVX_REQUIRE(w, IVX_ERR_INVALID, "%s: null world", who);
+    IVX_REQUIRE(mode <= IVX_BV_DYNAMIC_PAIRS, IVX_ERR_INVALID, "%s: mode %u (0 = all pairs, 1 = no phantom and at least one dynamic member)", who, mode);
+    IVX_REQUIRE(out || cap == 0, IVX_ERR_INVALID, "%s: null contact buffer of capacity %zu", who, cap);
+    IVX_REQUIRE((deferred_pairs && manifold_offsets) || deferred_cap == 0, IVX_ERR_INVALID, "%s: null deferred pair or offset buffer of capacity %zu", who, deferred_cap);
+    IVX_REQUIRE(!ivx_many_recording(), IVX_ERR_STATE, "%s: not inside an ivx_many_begin bracket (the call waits for its own phases)", who);
+    const bool lists = deferred_pairs && manifold_offsets;
+    ivx_cw_frame_pass fp;
+    int rc;
+    if ((rc = ivx_cw_frame_pairs(w, who, mode, out ? cap : 0, lists ? deferred_cap : 0, &fp))) return rc;
+    const size_t np = fp.n_primitive, nd = fp.n_deferred;
+    *n_out = np, *n_primitive = np, *n_deferred = nd;
+    ivx_ctx* c = w->ctx;
+    // the rows as the generators' queries, by field copies; the object that stands for row i in the recorder
+    static thread_local std::vector<ivx_collidable_query> cq;
+    static thread_local std::vector<ivx_mutual_query> mq;
+    static thread_local std::vector<ivx_grid*> chain;
+    static thread_local std::vector<uint32_t> offsets, counts;
+    static thread_local CollidablePlan cplan;
+    static thread_local MutualPlan mplan;
+    cq.assign(nd, ivx_collidable_query{}), mq.assign(nd, ivx_mutual_query{}), chain.assign(nd, nullptr), offsets.assign(nd + 1, 0u);
+    for (size_t i = 0; i < nd; ++i) {
+        const ivx_cw_row& r = fp.rows[i];
+        IVX_REQUIRE(r.voxel < fp.n_collidables && r.other < fp.n_collidables && r.generator <= IVX_CW_ROW_MUTUAL, IVX_ERR_STATE, "%s: row %zu is not a dispatch", who, i);
+        ivx_grid* g = fp.objects[r.voxel].grid;
+        IVX_REQUIRE(g, IVX_ERR_STATE, "%s: deferred pair %zu names voxel collidable %u, which has no object attached (ivx_cw_set_voxel_objects)", who, i, r.voxel);
+        chain[i] = g;
+        if (r.generator == IVX_CW_ROW_MUTUAL) {
+            ivx_grid* b = fp.objects[r.other].grid;
+            IVX_REQUIRE(b, IVX_ERR_STATE, "%s: deferred pair %zu names voxel collidable %u, which has no object attached (ivx_cw_set_voxel_objects)", who, i, r.other);
+            ivx_mutual_query& q = mq[i];
+            q.a = g, q.b = b;
+            memcpy(q.rotation_a, r.rotation_a, 16), memcpy(q.translation_a, r.translation_a, 12), memcpy(q.center_of_mass_a, r.center_of_mass_a, 12);
+            memcpy(q.rotation_b, r.rotation_b, 16), memcpy(q.translation_b, r.translation_b, 12), memcpy(q.center_of_mass_b, r.center_of_mass_b, 12);
+            q.collidable_id_a = r.collidable_id_a, q.collidable_id_b = r.collidable_id_b, q.body_a = r.body_a, q.body_b = r.body_b;
+            memcpy(q.response, r.response, 12);
+            if ((rc = mutual_check(c, q, who, i))) return rc;
+        } else {
+            ivx_collidable_query& q = cq[i];
+            q.mode = (int32_t)r.generator;
+            memcpy(q.rotation_xyzw, r.rotation_a, 16), memcpy(q.translation, r.translation_a, 12);
+            memcpy(q.shape3, r.shape3, 12), memcpy(q.shape3b, r.shape3b, 12);
+            q.shape1 = r.shape1, q.body_a = r.body_a, q.body_b = r.body_b, q.collidable_id_a = r.collidable_id_a, q.collidable_id_b = r.collidable_id_b;
+            memcpy(q.response, r.response, 12);
+            if ((rc = collidable_check(c, g, q, who, i))) return rc;
+        }
+    }
+    size_t run = 0;
+    const auto mutual = [&](size_t i) { return fp.rows[i].generator == IVX_CW_ROW_MUTUAL; };
+    if (nd) {
+        cplan.begin(nd), mplan.begin(nd);
+        for (size_t i = 0; i < nd; ++i)
+            if ((rc = mutual(i) ? mutual_plan_row(mplan, i, mq[i], who) : collidable_plan_row(cplan, i, chain[i], cq[i], who))) return rc;
+        if ((rc = collidable_plan_scratch(cplan))) return rc;
+        if ((rc = mutual_plan_scratch(mplan, c))) return rc;
+        uint32_t* totals_dev;
+        if ((rc = contacts_many_totals(c, nd, &totals_dev))) return rc;
+        if ((rc = many_phase(chain.data(), nd, [&](size_t i) -> int {
+                 if (mutual(i)) return mutual_count(mplan, i, mq[i], c, totals_dev + i);
+                 return cplan.box[i].hit ? collidable_launch(cplan, i, chain[i], cq[i], 0, totals_dev + i, nullptr, 0u) : IVX_OK;
+             })))
+            return rc;
+        if ((rc = contacts_many_wait_totals(c, nd, offsets.data(), counts, &run))) return rc;
+    }
+    const size_t total = np + run;
+    *n_out = total;
+    IVX_REQUIRE(!out || total <= cap, IVX_ERR_CAPACITY, "%s: %zu contacts (%zu primitive), the buffer holds %zu", who, total, np, cap);
+    IVX_REQUIRE(!lists || nd <= deferred_cap, IVX_ERR_CAPACITY, "%s: %zu deferred pairs, the buffers hold %zu", who, nd, deferred_cap);
+    if (run) {
+        ivx_contact* list;
+        if ((rc = ivx_cw_frame_reserve(w, np, total, &list))) return rc;
+        if ((rc = contacts_many_emit(chain.data(), nd, counts, offsets.data(), list + np, [&](size_t i, ivx_contact* at, uint32_t count) -> int {
+                 return mutual(i) ? mutual_emit(mplan, i, mq[i], at, count) : collidable_launch(cplan, i, chain[i], cq[i], 1, nullptr, at, count);
+             })))
+            return rc;
+        if ((rc = ivx_cw_frame_finish(w, total, out))) return rc;
+    } else if (out && np) {
+        memcpy(out, fp.contacts, np * sizeof(ivx_contact));  // (no manifold: the primitive contacts came with the counts, as in ivx_cw_collide)
+    }
+    if (lists) {
+        if (nd) memcpy(deferred_pairs, fp.deferred, nd * 8);
+        memcpy(manifold_offsets, offsets.data(), (nd + 1) * 4);
+    }
+    return IVX_OK;
 }
 
 // apply_mutual_absorption (interaction/absorption.rs:891-1079)

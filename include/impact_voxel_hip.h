@@ -1387,6 +1387,85 @@ int ivx_cw_collide(ivx_world*, uint32_t mode, ivx_contact* out, size_t cap, size
 /* IVX_CW_PTR_*: the world collidables, the contacts and the deferred pairs of the last calls; world-owned and grow-only, NULL before they exist */
 void* ivx_cw_device_ptr(ivx_world*, int which);
 
+/* ---- collision frame: the deferred pairs' contacts in the same call (impact_voxel/src/collidable.rs:138-215 generate_contact_manifold,
+ * 310-327 VoxelObjectCollidable::new; impact_math/src/transform/isometry.rs:112-134) ----
+ * A frame with voxel objects among the collidables: ivx_cw_synchronize -> ivx_cw_collide_frame -> ivx_world_set_contacts -> ivx_world_step. The
+ * voxel objects' world -> object transforms are derived on the device from the world's resident bodies; only the merged contact list and its
+ * bookkeeping cross to the host. csrc/narrow.hip (k_cw_rows), csrc/cw_rows.hpp (the arithmetic), csrc/voxel_collision_api.hip (the host side). */
+/* The voxel object behind a collidable of shape IVX_CW_VOXEL_OBJECT. 32 bytes: grid 0, origin_offset 8, center_of_mass 20. */
+typedef struct ivx_cw_voxel_object {
+    ivx_grid* grid;
+    float origin_offset[3];  /* the body frame's origin in model space (the local centre of mass the body was seated on) */
+    float center_of_mass[3]; /* the mutual generator's argument, model space */
+} ivx_cw_voxel_object;
+/* The dispatch of one deferred pair: which generator, and its arguments. 160 bytes, a multiple of 8. Offsets: generator 0, voxel 4, other 8,
+ * reserved 12, collidable_id_a 16, collidable_id_b 24, body_a 32, body_b 36, response 40, shape1 52, shape3 56, shape3b 68, rotation_a 80,
+ * translation_a 96, center_of_mass_a 108, rotation_b 120, translation_b 136, center_of_mass_b 148. It becomes an ivx_collidable_query
+ * (generators 0 to 2: mode = generator, rotation_xyzw = rotation_a, translation = translation_a, the other fields by their names) or an
+ * ivx_mutual_query (generator 3: every field by its name; the handles a / b are those of collidables `voxel` / `other`) by plain field copies.
+ * What a generator does not take is zero. */
+#define IVX_CW_ROW_MUTUAL 3u
+struct ivx_cw_voxel_row { /* (no typedef: the function below has the name) */
+    uint32_t generator;  /* 0 sphere, 1 plane, 2 capsule (ivx_collidable_query.mode), IVX_CW_ROW_MUTUAL */
+    uint32_t voxel;      /* collidable index of the voxel object the generator runs on; mutual: of object A */
+    uint32_t other;      /* collidable index of the other member; mutual: of object B */
+    uint32_t reserved;
+    uint64_t collidable_id_a, collidable_id_b;
+    uint32_t body_a, body_b;
+    float response[3];
+    float shape1;
+    float shape3[3], shape3b[3];
+    float rotation_a[4], translation_a[3], center_of_mass_a[3]; /* transform_to_object_space of `voxel` */
+    float rotation_b[4], translation_b[3], center_of_mass_b[3]; /* mutual only: of `other` */
+};
+#define IVX_CW_PTR_FRAME_CONTACTS 3 /* the merged list of the last ivx_cw_collide_frame (the buffer of IVX_CW_PTR_CONTACTS: the primitive part comes first) */
+#define IVX_CW_PTR_VOXEL_ROWS 4     /* struct ivx_cw_voxel_row of every deferred pair of the last ivx_cw_collide_frame */
+/* Host arithmetic; k_cw_rows runs the same two functions and gives the same bytes. All f32, the forms of ivx_cw_transform above, no contraction.
+ * ivx_cw_to_object_space — VoxelObjectCollidable::new's transform_to_object_space for a body at position p with orientation q = (x, y, z, w) whose
+ *   frame has its origin at o (model space): the inverse of transform_to_world_space.applied_to_translation(-o) in the reference's order,
+ *     t_w = qrot(q, -o) + p;  rotation = conj(q) = (-x, -y, -z, w);  translation = -qrot(rotation, t_w)
+ * ivx_cw_voxel_row — generate_contact_manifold (collidable.rs:138-215) for one deferred pair of WORLD-SPACE collidables (a, b), at least one a voxel
+ *   object. pose_* = position[3] then orientation_xyzw[4] of the member's body, voxel_* = its ivx_cw_voxel_object (the grid is not read); both are
+ *   read for voxel members only and may be NULL otherwise. combined(r1, r2) = (r2[0] > r1[0] ? r2[0] : r1[0], sqrt(r1[1] r2[1]), sqrt(r1[2] r2[2])).
+ *     voxel, voxel:  generator 3; A = a, B = b: ids (a, b), bodies (a, b), response = combined(a, b); rotation / translation_a and _b =
+ *       ivx_cw_to_object_space of each member, center_of_mass_a / _b theirs
+ *     voxel v, plane c (either order):  generator 1; the voxel object is A: bodies (v, c), response = combined(v, c); the ids take the plane first:
+ *       ids (c, v); shape3 = the plane's normal, shape1 = its displacement
+ *     voxel v, sphere or capsule c (either order):  generator 0 / 2; c is A: bodies (c, v), ids (c, v), response = combined(c, v); shape3 = centre /
+ *       segment start, shape1 = radius, capsule: shape3b = segment vector
+ *     generators 0 to 2: rotation_a / translation_a = ivx_cw_to_object_space of v
+ *   out->voxel / out->other are written as 0 for member a and 1 for member b (the kernel writes the pair's collidable indices). IVX_ERR_INVALID:
+ *   no voxel member, a shape above 3, a voxel member without its pose or record. */
+int ivx_cw_to_object_space(const float position[3], const float orientation_xyzw[4], const float origin_offset[3], float rotation_out[4], float translation_out[3]);
+int ivx_cw_voxel_row(const ivx_collidable* a_world, const ivx_collidable* b_world, const float pose_a[7], const float pose_b[7], const ivx_cw_voxel_object* voxel_a,
+                     const ivx_cw_voxel_object* voxel_b, struct ivx_cw_voxel_row* out);
+/* Attaches objects[k] to collidable collidable_index[k] of the world's set; the n attachments REPLACE the ones before (n == 0: none). Resident
+ * until replaced; ivx_cw_set_collidables drops them. The offsets and centres of mass are uploaded to a device array indexed by collidable; the
+ * grids' occupied ranges, probes and buffers are read at every ivx_cw_collide_frame, so an edit needs no new call unless the origin offset or the
+ * centre of mass moved. IVX_ERR_INVALID: an index past the set, an index whose shape is not a voxel object, a null grid, a grid of another
+ * context than the world's, the same index twice; IVX_ERR_STATE: no collidables set. A refused call leaves the attachments as they were. */
+int ivx_cw_set_voxel_objects(ivx_world*, const uint32_t* collidable_index, const ivx_cw_voxel_object* objects, size_t n);
+/* The whole collision pass of a frame. The pair pass and the primitive narrow phase of ivx_cw_collide (same code, same modes, the broad phase
+ * ivx_cw_set_broad_phase selected); right behind them k_cw_rows, a lane per deferred pair: ivx_cw_voxel_row over the world-space records, the
+ * pose of each voxel member's body as the world's resident arrays hold it (behind ivx_world_step_enqueue: that step's bodies, with no wait) and
+ * the attached offsets and centres of mass. The rows come to the host with the counts; the voxel generators of ivx_voxel_object_contacts_many
+ * and ivx_mutual_voxel_object_contacts_many then run over them in merged launches (csrc/many.hpp), their emit passes writing behind the
+ * primitive contacts. out: the primitive contacts (*n_primitive of them, what ivx_cw_collide returns), then one manifold per deferred pair IN
+ * DEFERRED-LIST ORDER: manifold i is out[*n_primitive + manifold_offsets[i] .. *n_primitive + manifold_offsets[i + 1]) (n_deferred + 1 offsets),
+ * the very list the single-pair generator returns for row i, first contact flagged IVX_CONTACT_MANIFOLD_START — ready for ivx_world_set_contacts.
+ * deferred_pairs (2 x uint32_t each) and manifold_offsets share deferred_cap: room for deferred_cap pairs and deferred_cap + 1 offsets.
+ * *n_out (all contacts), *n_primitive and *n_deferred are the numbers found even when a capacity is exceeded; the call then returns
+ * IVX_ERR_CAPACITY and writes no list. out == NULL with cap == 0 leaves the merged list on the device only (IVX_CW_PTR_FRAME_CONTACTS), and
+ * likewise the deferred list and the offsets. The call waits four times: the pair total; counts, deferred pairs and rows; the generators'
+ * totals; the list (a growth of a buffer, or a deferred list more than twice the last call's, waits once more).
+ * IVX_ERR_STATE: before ivx_cw_synchronize; the context's set replaced since; a deferred pair names a voxel collidable with no object attached;
+ * inside an ivx_many_begin bracket (the call waits for its own phases). The generators' own preconditions report as they do in the `_many`
+ * calls: current derived state, and current probes for both members of a voxel-voxel pair. */
+int ivx_cw_collide_frame(ivx_world*, uint32_t mode, ivx_contact* out, size_t cap, size_t* n_out, size_t* n_primitive, uint32_t* deferred_pairs,
+                         uint32_t* manifold_offsets, size_t deferred_cap, size_t* n_deferred);
+/* The rows of the last ivx_cw_collide_frame, in deferred-list order (cap >= its *n_deferred, else IVX_ERR_CAPACITY). Waits for the stream. */
+int ivx_cw_rows_download(ivx_world*, struct ivx_cw_voxel_row* rows, size_t cap, size_t* n_rows);
+
 /* ---- motion drivers of kinematic bodies (impact_physics/src/driven_motion.rs and the files under driven_motion/; csrc/motion.hip) -----------
  * A kinematic body whose state is a function of the simulation time. One record per driver, 64 bytes: `body` indexes the world's kinematic
  * bodies (WITHOUT the IVX_KINEMATIC_BODY bit), `p` holds the reference's setup struct of that kind, field by field in its #[repr(C)] order:

@@ -1,8 +1,8 @@
-// C ABI entry points of libimpact_voxel_hip.so (see include/impact_voxel_hip.h for the contract and
-// the reference interfaces each function replaces). Host-side orchestration only: every compute call
-// launches the HIP kernels in this directory on the context's stream.
+// C ABI entry points of libimpact_voxel_hip.so (include/impact_voxel_hip.h has the contract and the reference interfaces each function
+// replaces) that no unit of their own holds yet: contexts and the life cycle of grids, staged copies, upload and download, single-call sampling
+// and deriving, inertia, regions, the resident SDF program and tables, halos, the recorder phases of the many-object calls. (The step, edits,
+// meshes, split and clip, voxel collision: step_api, edit_api, mesh_api, extraction_api, voxel_collision_api.hip.) Host-side orchestration only.
 #include <algorithm>
-#include <array>
 #include <functional>
 #include <cmath>
 #include <chrono>
@@ -36,11 +36,10 @@ int ensure_host_scratch(ivx_grid* g, size_t bytes) {
     return IVX_OK;
 }
 
-// Host<->device copies. Small ones (the scalars and tables the entry points hand back: up to a few hundred KB) go through the
-// grid's pinned staging buffer as ONE stream-ordered copy and ONE wait (a blocking copy from pageable memory costs a wait for
-// the stream, a staging copy inside the runtime and a second wait); large ones (whole planes) stay plain blocking copies.
-constexpr size_t STAGED_COPY_MAX = 1u << 20;
 }  // namespace
+// Host<->device copies. Small ones (the scalars and tables the entry points hand back: up to a few hundred KB, STAGED_COPY_MAX) go through
+// the grid's pinned staging buffer as ONE stream-ordered copy and ONE wait (a blocking copy from pageable memory costs a wait for
+// the stream, a staging copy inside the runtime and a second wait); large ones (whole planes) stay plain blocking copies.
 int d2h(ivx_grid* g, void* dst, const void* src, size_t bytes) {
     if (bytes == 0) return IVX_OK;
     if (bytes <= STAGED_COPY_MAX) {
@@ -120,7 +119,7 @@ int ivx_launch_halo_pack(ivx_grid* g, int side, void* buf) {
 }
 
 // the occupied ranges in the reference's sense (see ivx_grid::occ_ref): cached, recomputed only when something invalidated them
-static int reference_occupied(ivx_grid* g, uint32_t occ[12]) {
+int reference_occupied(ivx_grid* g, uint32_t occ[12]) {
     if (!g->occ_ref_valid) {
         uint32_t* d_occ = g->rscalar + 16;
         int rc;
@@ -364,13 +363,11 @@ extern "C++" int grid_create_pooled(ivx_ctx* c, const uint32_t* ccs, size_t n, f
     return IVX_OK;
 }
 
-static void ivx_edit_state_free(struct ivx_edit_state* e);
 void ivx_grid_destroy(ivx_grid* g) {
     if (!g) return;
     (void)ivx_stream_sync(g->ctx->stream);
     ivx_sampler_free(g);  // (a pre-pass running ahead on the second stream is waited for)
-    ivx_edit_state_free(g->edit);
-    g->edit = nullptr;
+    edit_free(g);
     ivx_submesh_manager_free(g->submesh_manager);  // (host mirrors of the incremental remesh and of the probes' ranges)
     ivx_probe_manager_free(g->probe_manager);
     g->submesh_manager = nullptr, g->probe_manager = nullptr;
@@ -671,292 +668,6 @@ int ivx_region_face_pairs(ivx_grid* g, int side, const void* neighbour_face_labe
     return IVX_OK;
 }
 
-// ---- the edit path (§8f-2): ONE wait per edit, and only the chunks the edit can have changed are swept -------------------------------------
-// ivx_absorb_*_enqueue puts on the stream: the edit kernel over the touched chunk box; the derive sweep over that box grown by one chunk
-// each way (ivx_launch_derive_box: what the reference patches chunk by chunk, object/intersection.rs:255-262, 532-598) with the region
-// forest of all other chunks reset; the global region resolve (interaction/absorption.rs:631); the count pass of the remesh for the chunks
-// whose meshes the edit invalidates (ivx_launch_box_mesh_needs); one copy of all small results into pinned memory. ivx_absorb_collect waits
-// for the doorbell behind them. Round 3 swept the whole object's active list (5 388 chunks of the 512^3 body for a bite that touches 80)
-// and ivx_mesh_sync counted the whole object again and read its sizes back.
-struct ivx_edit_state {
-    // the edit in flight
-    int pending = 0, nothing = 0, staged = 0;
-    uint32_t lo[3] = {0, 0, 0}, cc[3] = {0, 0, 0}, blo[3] = {0, 0, 0}, bcc[3] = {0, 0, 0};
-    size_t off_type = 0, off_cnt = 0, off_touch = 0, off_needs = 0, total = 0;
-    void* pinned = nullptr;  // results of the edit in flight: host-mapped, written by the step's gather launch ahead of the doorbell
-    void* pinned_dev = nullptr;
-    size_t pinned_bytes = 0;
-    char* d_results = nullptr;  // the edit's accumulators on the device (its own allocation: zero between edits — cleared behind every collect)
-    size_t d_results_bytes = 0;
-    // what the meshes of the last edit's invalidated chunks need (chunk -> vertices, indices, kind | flags << 8): valid until voxels change again
-    // (ascending by chunk — the grown box is walked in chunk-linear order —, looked up by binary search: a hash map's insertions were most of an
-    // edit's collect for the small objects of a many-object frame)
-    std::vector<std::array<uint32_t, 4>> needs;  // chunk, vertices, indices, kind | flags << 8
-    // early delivery of what the invalidated meshes need (ivx_mesh_sync_enqueue with a null set while the edit is in flight): the role that
-    // counts them writes its records into the pinned block behind the results and rings a bell there
-    int early_armed = 0, early_taken = 0;
-    uint32_t early_seq = 0;
-    size_t off_early = 0, off_bell = 0;
-};
-static void ivx_edit_state_free(ivx_edit_state* e) {
-    if (!e) return;
-    if (e->pinned) (void)hipHostFree(e->pinned);
-    if (e->d_results) (void)hipFree(e->d_results);
-    delete e;
-}
-static ivx_edit_state* edit_state(ivx_grid* g) {
-    if (!g->edit) g->edit = new (std::nothrow) ivx_edit_state();
-    return g->edit;
-}
-extern "C++" bool edit_needs_lookup(ivx_grid* g, uint32_t chunk, uint32_t out3[3]) {
-    if (!g->edit) return false;
-    const auto& v = g->edit->needs;
-    const auto it = std::lower_bound(v.begin(), v.end(), chunk, [](const std::array<uint32_t, 4>& a, uint32_t c) { return a[0] < c; });
-    if (it == v.end() || (*it)[0] != chunk) return false;
-    out3[0] = (*it)[1], out3[1] = (*it)[2], out3[2] = (*it)[3];
-    return true;
-}
-
-static int absorb_enqueue(ivx_grid* g, const char* who, int capsule, const float center[3], const float seg[3], float influence_radius, float shape_radius,
-                          const float densities[256]) {
-    IVX_REQUIRE(g && center && densities && (seg || !capsule), IVX_ERR_INVALID, "%s: null argument", who);
-    ivx_many_other_context other_(g->ctx);
-    IVX_REQUIRE(influence_radius >= 0.0f && shape_radius >= 0.0f, IVX_ERR_INVALID, "%s: negative radius", who);
-    IVX_REQUIRE(g->regions_valid, IVX_ERR_STATE, "%s: derived state and regions must be current (ivx_derive_state + ivx_label_regions)", who);
-    IVX_REQUIRE(g->x_off == 0 && g->gx == g->cc[0] && !g->has_ghost[0] && !g->has_ghost[1], IVX_ERR_STATE, "%s: not available on a slab of a decomposed grid",
-                who);
-    ivx_edit_state* e = edit_state(g);
-    IVX_REQUIRE(e, IVX_ERR_CAPACITY, "%s: out of host memory", who);
-    IVX_REQUIRE(!e->pending, IVX_ERR_STATE, "%s: an edit of this object is in flight (ivx_absorb_collect first)", who);
-    int rc;
-    // the touched voxel ranges start from the object's occupied ranges (voxel_ranges_touching_aab, intersection.rs:766-782)
-    uint32_t occ[12];
-    if ((rc = reference_occupied(g, occ))) return rc;
-    int32_t vlo[3], vhi[3];
-    uint32_t lo[3], cc[3];
-    e->nothing = 0;
-    for (int d = 0; d < 3; ++d) {
-        float a = center[d] - influence_radius, b = center[d] + influence_radius;  // Sphere::compute_aabb
-        if (capsule) {  // Capsule::compute_aabb: the boxes of the two end spheres (capsule.rs:132-137)
-            const float end = center[d] + seg[d];
-            const float a1 = end - influence_radius, b1 = end + influence_radius;
-            a = a1 < a ? a1 : a;
-            b = b1 > b ? b1 : b;
-        }
-        const float fl = std::floor(a), ce = std::ceil(b);
-        // `as usize` saturates at 0; the occupied ranges bound the other side
-        const long s_ = fl > 0.0f ? (fl < 2.0e9f ? (long)fl : 2000000000L) : 0, e_ = ce > 0.0f ? (ce < 2.0e9f ? (long)ce : 2000000000L) : 0;
-        vlo[d] = (int32_t)std::max<long>((long)occ[6 + 2 * d], s_);
-        vhi[d] = (int32_t)std::min<long>((long)occ[7 + 2 * d], e_);
-        if (vlo[d] >= vhi[d]) {
-            e->nothing = 1;  // nothing touched: the collect reports zeros
-            e->pending = 1;
-            return IVX_OK;
-        }
-        lo[d] = (uint32_t)vlo[d] / 16u;
-        cc[d] = ((uint32_t)vhi[d] + 15u) / 16u - lo[d];
-    }
-    uint32_t blo[3], bcc[3];  // the box the derive sweep goes over: one chunk more each way
-    for (int d = 0; d < 3; ++d) {
-        blo[d] = lo[d] > 0u ? lo[d] - 1u : 0u;
-        const uint32_t bhi = std::min(lo[d] + cc[d] + 1u, g->cc[d]);
-        bcc[d] = bhi - blo[d];
-        e->lo[d] = lo[d], e->cc[d] = cc[d], e->blo[d] = blo[d], e->bcc[d] = bcc[d];
-    }
-    // scratch: [10 f64 removed moments][256 u32 by type][2 u32 counters][pad][u32 touched ranges of the box's chunks][uint4 needs of the grown box's]
-    const size_t box_chunks = (size_t)cc[0] * cc[1] * cc[2], grown = (size_t)bcc[0] * bcc[1] * bcc[2];
-    e->off_type = 80, e->off_cnt = e->off_type + 1024, e->off_touch = e->off_cnt + 16;
-    e->off_needs = (e->off_touch + box_chunks * 4 + 15) & ~(size_t)15;
-    e->total = e->off_needs + grown * 16;
-    hipStream_t s = g->ctx->stream;
-    // (a density table other than the resident one rides in the block's LAST kilobyte — not right behind this edit's results: nothing clears it
-    // there, and a later, larger edit would read its floats as the touched words of its box: 1.0f is "touched, voxels 0..0, 0..0, 0..8" — five
-    // chunks invalidated for nothing in one of 3 600 random edit sequences, profiles/round5/README.md)
-    const size_t need_bytes = ((e->total + 255) & ~(size_t)255) + 1024;
-    if (e->d_results_bytes < need_bytes) {  // (grown on demand; a fresh block starts zeroed, later ones are cleared behind every collect)
-        IVX_HIP_CHECK(ivx_stream_sync(s));
-        if (e->d_results) (void)hipFree(e->d_results);
-        e->d_results = nullptr, e->d_results_bytes = 0;
-        const size_t cap = std::max<size_t>(2 * need_bytes, 1 << 16);
-        IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->d_results), cap));
-        IVX_HIP_CHECK(ivx_memset_async(e->d_results, 0, cap, s));
-        e->d_results_bytes = cap;
-    }
-    char* base = e->d_results;
-    const size_t off_dens = e->d_results_bytes - 1024;
-    const float* d_dens = g->dens_dev;
-    if (!(g->has_dens && memcmp(g->dens_host, densities, sizeof(g->dens_host)) == 0)) {  // another table than the resident one
-        if ((rc = h2d(g, base + off_dens, densities, 1024))) return rc;
-        d_dens = reinterpret_cast<const float*>(base + off_dens);
-    }
-    // the edit; its first block also zeroes the region scalars the sweep behind it starts from
-    if ((rc = ivx_launch_absorb(g, capsule, lo, cc, vlo, vhi, center, seg, influence_radius, shape_radius, d_dens, reinterpret_cast<double*>(base),
-                                reinterpret_cast<uint32_t*>(base + e->off_type), reinterpret_cast<uint32_t*>(base + e->off_cnt),
-                                reinterpret_cast<uint32_t*>(base + e->off_touch), g->rscalar)))
-        return rc;
-    e->needs.clear();  // (voxels change: what an earlier edit's chunks needed is history)
-    // derived state and chunk-local regions of the grown box, the other chunks' region nodes reset; then the global resolve, whose first
-    // launch also counts what the invalidated chunks' meshes need, and whose last (the gather of ivx_absorb_collect) copies the edit's small
-    // results to the host ahead of the doorbell: seven launches, no copy or fill operation on the stream
-    if ((rc = ivx_launch_derive_box(g, IVX_PART_REGIONS, blo, bcc, nullptr))) return rc;
-    e->staged = e->total <= STAGED_COPY_MAX;
-    e->off_early = (e->total + 63) & ~(size_t)63;
-    e->off_bell = e->off_early + grown * 16;
-    const size_t pinned_need = e->off_bell + 64;
-    if (e->staged && e->pinned_bytes < pinned_need) {
-        IVX_HIP_CHECK(ivx_stream_sync(s));
-        if (e->pinned) (void)hipHostFree(e->pinned);
-        e->pinned = e->pinned_dev = nullptr, e->pinned_bytes = 0;
-        const size_t cap = std::max<size_t>(2 * pinned_need, 1 << 16);
-        IVX_HIP_CHECK(hipHostMalloc(&e->pinned, cap, hipHostMallocMapped));
-        IVX_HIP_CHECK(hipHostGetDevicePointer(&e->pinned_dev, e->pinned, 0));
-        memset(e->pinned, 0, cap);
-        e->pinned_bytes = cap;
-    }
-    for (int d = 0; d < 3; ++d) g->post1_needs_box[d] = lo[d], g->post1_needs_box[3 + d] = cc[d], g->post1_needs_box[6 + d] = blo[d], g->post1_needs_box[9 + d] = bcc[d];
-    g->post1_needs_touched = reinterpret_cast<const uint32_t*>(base + e->off_touch);
-    g->post1_needs_out = reinterpret_cast<uint32_t*>(base + e->off_needs);
-    e->early_armed = 0, e->early_taken = 0;
-    if (e->staged && g->early_needs_on) {  // (the words [2], [3] behind the two counters are the block's spare: zero between edits like the rest)
-        e->early_seq += 1u;
-        g->post1_needs_early = reinterpret_cast<uint32_t*>(static_cast<char*>(e->pinned_dev) + e->off_early);
-        g->post1_needs_counter = reinterpret_cast<uint32_t*>(base + e->off_cnt) + 2;
-        g->post1_needs_bell = reinterpret_cast<uint32_t*>(static_cast<char*>(e->pinned_dev) + e->off_bell);
-        g->post1_needs_seq = e->early_seq;
-        // (the bell's place moves with the size of the box: whatever an earlier, larger edit left there must not read as this edit's number)
-        *reinterpret_cast<volatile uint32_t*>(static_cast<char*>(e->pinned) + e->off_bell) = 0u;
-        e->early_armed = 1;
-    }
-    g->preset_fresh |= IVX_SCRATCH_REGIONS;  // (the region scalars were zeroed by the edit kernel, before the box sweep listed its multi-region chunks)
-    g->regions_labelled_locally = 1;         // (... and the sweep labelled the box: no stand-alone local pass in front of the resolve)
-    rc = step_enqueue_untimed(g, IVX_STAGE_REGIONS);  // (nobody reads this call's stage times)
-    g->regions_labelled_locally = 0;
-    if (rc) return rc;
-    if (e->staged) {
-        g->gather_copy_src = reinterpret_cast<const uint32_t*>(base);
-        g->gather_copy_dst = static_cast<uint32_t*>(e->pinned_dev);
-        // (with early delivery the needs records are in the host-mapped block already: the gather copies the words in front of them only)
-        g->gather_copy_words = (uint32_t)(((e->early_armed ? e->off_needs : e->total) + 3) / 4);
-    }
-    e->pending = 1;
-    return IVX_OK;
-}
-
-// The records of the edit's count role — a uint4 per chunk of the grown box: bit 31 | kind | flags << 8, vertices, indices, chunk — become
-// e->needs, ascending by chunk; with `invalidated_chunks`, the chunks they name are marked there.
-static void edit_take_needs(ivx_grid* g, const uint32_t* needs, uint8_t* invalidated_chunks) {
-    ivx_edit_state* e = g->edit;
-    const size_t grown = (size_t)e->bcc[0] * e->bcc[1] * e->bcc[2];
-    e->needs.clear();
-    for (size_t b = 0; b < grown; ++b) {
-        const uint32_t w = needs[4 * b];
-        if (!(w & 0x80000000u)) continue;
-        const uint32_t c = needs[4 * b + 3];
-        if (invalidated_chunks) invalidated_chunks[c] = 1;
-        e->needs.push_back({c, needs[4 * b + 1], needs[4 * b + 2], w & 0xFFFFu});
-    }
-    if (!std::is_sorted(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; }))
-        std::sort(e->needs.begin(), e->needs.end(), [](const std::array<uint32_t, 4>& a, const std::array<uint32_t, 4>& b) { return a[0] < b[0]; });
-    g->needs_current = 1;
-}
-
-static int absorb_collect(ivx_grid* g, const char* who, ivx_absorb_result* out, uint32_t* emptied_by_type, uint8_t* invalidated_chunks) {
-    IVX_REQUIRE(g && out, IVX_ERR_INVALID, "%s: null argument", who);
-    ivx_many_other_context other_(g->ctx);
-    ivx_edit_state* e = g->edit;
-    IVX_REQUIRE(e && e->pending, IVX_ERR_STATE, "%s: no edit of this object is in flight", who);
-    e->pending = 0;
-    memset(out, 0, sizeof(*out));
-    if (emptied_by_type) memset(emptied_by_type, 0, 256 * sizeof(uint32_t));
-    if (invalidated_chunks) memset(invalidated_chunks, 0, g->n_chunks);
-    if (e->nothing) return IVX_OK;
-    int rc;
-    if ((rc = rederive_collect(g))) return rc;  // (the doorbell behind everything enqueued: one wait)
-    mesh_sync_stream_drained(g);                // (... a sync enqueued while this edit was in flight included)
-    std::vector<char> hostbuf;
-    const char* hb;
-    if (e->staged) {
-        hb = static_cast<const char*>(e->pinned);
-    } else {
-        hostbuf.resize(e->total);
-        if ((rc = d2h(g, hostbuf.data(), e->d_results, e->total))) return rc;
-        hb = hostbuf.data();
-    }
-    // (the accumulators and the touched words start the next edit from zero — and that edit's box may be larger than this one's: everything this
-    // edit wrote is cleared now, off the next edit's path; the block beyond has never been written)
-    if (!ivx_many_zero(g->ctx, g, e->d_results, (e->total + 3) & ~(size_t)3)) IVX_HIP_CHECK(ivx_memset_async(e->d_results, 0, e->total, g->ctx->stream));
-    const double* rem = reinterpret_cast<const double*>(hb);
-    const double ex = (double)g->extent, e3 = ex * ex * ex, e4 = e3 * ex, e5 = e4 * ex;
-    const double f[10] = {e3, 0.5 * e4, 0.5 * e4, 0.5 * e4, e5 / 3.0, e5 / 3.0, e5 / 3.0, 0.25 * e5, 0.25 * e5, 0.25 * e5};
-    for (int q = 0; q < 10; ++q) out->removed_moments[q] = rem[q] * f[q];
-    const uint32_t* by_type = reinterpret_cast<const uint32_t*>(hb + e->off_type);
-    uint64_t emptied = 0;
-    for (int t = 0; t < 256; ++t) {
-        emptied += by_type[t];
-        if (emptied_by_type) emptied_by_type[t] = by_type[t];
-    }
-    out->emptied_voxels = emptied;
-    const uint32_t* cnt = reinterpret_cast<const uint32_t*>(hb + e->off_cnt);
-    out->touched_chunks = cnt[0];
-    out->removed_chunks = cnt[1];
-    if (cnt[1]) g->occ_ref_valid = 0;  // `if removed_chunks { self.update_occupied_ranges() }` (intersection.rs:384-386, 520-522)
-    // handle_chunk_voxels_modified (intersection.rs:560-598): the touched chunk, and a neighbour when the touched voxel range of the chunk
-    // comes within two voxels of the face they share — decided on the device per chunk of the grown box, with what its mesh needs now
-    const uint32_t* needs = reinterpret_cast<const uint32_t*>(e->early_armed ? static_cast<const char*>(e->pinned) + e->off_early : hb + e->off_needs);
-    edit_take_needs(g, needs, invalidated_chunks);  // (an early sync may have taken them from the same records)
-    return IVX_OK;
-}
-
-// what the edit in flight invalidates and what those meshes need, from the records its count role delivers early (ivx_edit_state::early_*):
-// waits for the role's bell — a third of the way down the edit's chain —, not for the edit
-extern "C++" int edit_early_needs(ivx_grid* g, const char* who, std::vector<uint32_t>& list) {
-    ivx_edit_state* e = g->edit;
-    IVX_REQUIRE(e && e->pending, IVX_ERR_STATE, "%s: a null set stands for the chunks of an edit in flight, and none is", who);
-    if (e->nothing) return IVX_OK;
-    IVX_REQUIRE(e->early_armed, IVX_ERR_STATE,
-                "%s: the edit in flight does not deliver its mesh needs early (ivx_grid_set_early_mesh_needs before the edit; or its results do not fit the "
-                "host-mapped block): collect it and pass its set",
-                who);
-    if (!e->early_taken) {
-        (void)ivx_many_break();
-        bool rung = false;
-        const int rc = doorbell_wait(reinterpret_cast<const volatile uint32_t*>(static_cast<const char*>(e->pinned) + e->off_bell), e->early_seq, 2000000u, g->ctx->stream, &rung);
-        if (rc) return rc;
-        IVX_REQUIRE(rung, IVX_ERR_HIP, "%s: the edit's mesh needs never arrived", who);
-        edit_take_needs(g, reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->pinned) + e->off_early), nullptr);
-        e->early_taken = 1;
-    }
-    for (const auto& n : e->needs) list.push_back(n[0]);
-    return IVX_OK;
-}
-
-extern "C" {
-int ivx_absorb_sphere_enqueue(ivx_grid* g, const float center[3], float influence_radius, float sphere_radius, const float densities[256]) {
-    return absorb_enqueue(g, "ivx_absorb_sphere_enqueue", 0, center, nullptr, influence_radius, sphere_radius, densities);
-}
-int ivx_absorb_capsule_enqueue(ivx_grid* g, const float segment_start[3], const float segment_vector[3], float influence_radius, float capsule_radius,
-                               const float densities[256]) {
-    return absorb_enqueue(g, "ivx_absorb_capsule_enqueue", 1, segment_start, segment_vector, influence_radius, capsule_radius, densities);
-}
-int ivx_absorb_collect(ivx_grid* g, ivx_absorb_result* out, uint32_t* emptied_by_type, uint8_t* invalidated_chunks) {
-    return absorb_collect(g, "ivx_absorb_collect", out, emptied_by_type, invalidated_chunks);
-}
-
-int ivx_absorb_sphere(ivx_grid* g, const float center[3], float influence_radius, float sphere_radius, const float densities[256], ivx_absorb_result* out,
-                      uint32_t* emptied_by_type, uint8_t* invalidated_chunks) {
-    IVX_REQUIRE(out, IVX_ERR_INVALID, "ivx_absorb_sphere: null argument");
-    const int rc = absorb_enqueue(g, "ivx_absorb_sphere", 0, center, nullptr, influence_radius, sphere_radius, densities);
-    return rc ? rc : absorb_collect(g, "ivx_absorb_sphere", out, emptied_by_type, invalidated_chunks);
-}
-
-int ivx_absorb_capsule(ivx_grid* g, const float segment_start[3], const float segment_vector[3], float influence_radius, float capsule_radius,
-                       const float densities[256], ivx_absorb_result* out, uint32_t* emptied_by_type, uint8_t* invalidated_chunks) {
-    IVX_REQUIRE(out, IVX_ERR_INVALID, "ivx_absorb_capsule: null argument");
-    const int rc = absorb_enqueue(g, "ivx_absorb_capsule", 1, segment_start, segment_vector, influence_radius, capsule_radius, densities);
-    return rc ? rc : absorb_collect(g, "ivx_absorb_capsule", out, emptied_by_type, invalidated_chunks);
-}
-}  // extern "C"
-
 int ivx_grid_set_sdf_program(ivx_grid* g, const ivx_sdf_processed_node* nodes, size_t n_nodes, uint32_t stack_size, const uint32_t grid_shape[3],
                              const float shifted_grid_center[3], uint8_t voxel_type) {
     IVX_REQUIRE(g && grid_shape && shifted_grid_center && (n_nodes == 0 || nodes), IVX_ERR_INVALID, "ivx_grid_set_sdf_program: null argument");
@@ -1107,16 +818,12 @@ extern "C++" int many_fail(ivx_grid* const* grids, size_t n, int rc) {
     for (size_t i = 0; i < n; ++i) {
         ivx_grid* g = grids[i];
         if (!g) continue;
-        if (g->edit && g->edit->pending) {
-            ivx_absorb_result tmp;
-            (void)absorb_collect(g, "ivx_*_many (drain)", &tmp, nullptr, nullptr);
-        }
+        edit_abandon(g);
         mesh_sync_abandon(g);
         if (g->pending_stages || g->gather_launched) {
             ivx_step_result tmp;
             (void)ivx_voxel_step_collect(g, &tmp);
         }
-        if (g->edit) g->edit->pending = 0;
         g->pending_stages = 0;
         g->gather_launched = 0;
         g->results_in_block = 0;
@@ -1144,57 +851,6 @@ extern "C++" int many_phase(ivx_grid* const* grids, size_t n, const std::functio
         fprintf(stderr, "[ivx many]   phase: objects %.1f us, flush %.1f us\n", 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count(),
                 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t1).count());
     return first ? first : rc;
-}
-
-// one absorber per object: spheres (segments3 == NULL) or capsules (segment vectors, 3 floats per object)
-static int absorb_many(ivx_grid* const* grids, size_t n, const char* who, const float* points3, const float* segments3, const float* influence_radii,
-                       const float* shape_radii, const float densities[256], ivx_absorb_result* out, uint8_t* const* invalidated_chunks) {
-    if (n == 0) return IVX_OK;  // (a manager without voxel objects)
-    int rc = many_check(grids, n, who);
-    if (rc) return rc;
-    ManyClock clk("absorb");
-    IVX_REQUIRE(points3 && influence_radii && shape_radii && densities && out, IVX_ERR_INVALID, "%s: null argument", who);
-    // (what an object's enqueue may have to wait for — its occupied ranges, a density table that is not the resident one — before the recording starts)
-    for (size_t i = 0; i < n; ++i) {
-        uint32_t occ[12];
-        if (grids[i]->regions_valid && (rc = reference_occupied(grids[i], occ))) return rc;
-        // (... and the object's edit buffers, which its first edit would otherwise allocate — with a wait on the stream — in the middle of the batch)
-        ivx_edit_state* e = edit_state(grids[i]);
-        IVX_REQUIRE(e, IVX_ERR_CAPACITY, "%s: out of host memory", who);
-        if (!e->d_results) {
-            const size_t cap = 1 << 16;
-            IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->d_results), cap));
-            IVX_HIP_CHECK(ivx_memset_async(e->d_results, 0, cap, grids[i]->ctx->stream));
-            e->d_results_bytes = cap;
-        }
-        if (!e->pinned) {
-            const size_t cap = 1 << 16;
-            IVX_HIP_CHECK(hipHostMalloc(&e->pinned, cap, hipHostMallocMapped));
-            IVX_HIP_CHECK(hipHostGetDevicePointer(&e->pinned_dev, e->pinned, 0));
-            e->pinned_bytes = cap;
-        }
-    }
-    clk.lap("prepare");
-    if ((rc = many_phase(grids, n, [&](size_t i) {
-             return absorb_enqueue(grids[i], who, segments3 ? 1 : 0, points3 + 3 * i, segments3 ? segments3 + 3 * i : nullptr, influence_radii[i], shape_radii[i], densities);
-         })))
-        return many_fail(grids, n, rc);
-    clk.lap("enqueue + flush");
-    if ((rc = many_phase(grids, n, [&](size_t i) { return (grids[i]->edit && grids[i]->edit->pending && !grids[i]->edit->nothing) ? ivx_step_collect_launch(grids[i]) : IVX_OK; })))
-        return many_fail(grids, n, rc);
-    clk.lap("gathers");
-    rc = many_phase(grids, n, [&](size_t i) { return absorb_collect(grids[i], who, &out[i], nullptr, invalidated_chunks ? invalidated_chunks[i] : nullptr); });
-    clk.lap("collect");
-    return many_fail(grids, n, rc);
-}
-int ivx_absorb_sphere_many(ivx_grid* const* grids, size_t n, const float* centers3, const float* influence_radii, const float* sphere_radii,
-                           const float densities[256], ivx_absorb_result* out, uint8_t* const* invalidated_chunks) {
-    return absorb_many(grids, n, "ivx_absorb_sphere_many", centers3, nullptr, influence_radii, sphere_radii, densities, out, invalidated_chunks);
-}
-int ivx_absorb_capsule_many(ivx_grid* const* grids, size_t n, const float* segment_starts3, const float* segment_vectors3, const float* influence_radii,
-                            const float* capsule_radii, const float densities[256], ivx_absorb_result* out, uint8_t* const* invalidated_chunks) {
-    IVX_REQUIRE(n == 0 || segment_vectors3, IVX_ERR_INVALID, "ivx_absorb_capsule_many: null argument");
-    return absorb_many(grids, n, "ivx_absorb_capsule_many", segment_starts3, segment_vectors3, influence_radii, capsule_radii, densities, out, invalidated_chunks);
 }
 
 int ivx_halo_clear(ivx_grid* g, int side) {

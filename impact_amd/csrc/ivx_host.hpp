@@ -1,8 +1,8 @@
-// What the host units of the C ABI (ivx_api.hip, step_api.hip, voxel_collision_api.hip, extraction_api.hip, mesh_api.hip) share and nothing else
-// links against: staged copies, the objects' device scratch, the bounded wait for a doorbell, the recorder phases of the many-object calls, what
-// the extraction calls need of the grid life cycle, the regions and the step, what crosses between the mesh unit and the edit and step paths,
-// and the host mirrors of the reference's range allocators. Defined in ivx_api.hip unless said otherwise (the functions hidden: the library
-// exports what it exported before).
+// What the host units of the C ABI (ivx_api.hip, step_api.hip, edit_api.hip, voxel_collision_api.hip, extraction_api.hip, mesh_api.hip) share
+// and nothing else links against: staged copies, the objects' device scratch, the cached occupied ranges, the bounded wait for a doorbell, the
+// recorder phases of the many-object calls, what the extraction calls need of the grid life cycle, the regions and the step, what crosses
+// between the edit unit, the mesh unit and the rest, the overlap ranges of two objects, and the host mirrors of the reference's range
+// allocators. Defined in ivx_api.hip unless said otherwise (the functions hidden: the library exports what it exported before).
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -24,13 +24,17 @@ int dev_alloc(T** p, size_t count) {
     return IVX_OK;
 }
 
-// Host<->device copies through the grid's pinned staging buffer: ONE stream-ordered copy and ONE wait (large ones: plain blocking copies)
+// Host<->device copies through the grid's pinned staging buffer: ONE stream-ordered copy and ONE wait (larger than STAGED_COPY_MAX: plain
+// blocking copies; an edit with larger results than that brings them back by such a copy)
+constexpr size_t STAGED_COPY_MAX = 1u << 20;
 int d2h(ivx_grid* g, void* dst, const void* src, size_t bytes);
 int h2d(ivx_grid* g, void* dst, const void* src, size_t bytes);
 // the object's device scratch (ivx_grid::dev_scratch) holds at least `bytes`; a growth waits for the stream and keeps nothing
 int ensure_dev_scratch(ivx_grid* g, size_t bytes);
 // a shared allocation (ivx_block, ivx_internal.hpp) let go of by one holder: freed with the last
 void block_release(ivx_block* b);
+// the occupied ranges in the reference's sense (ivx_grid::occ_ref), cached (ivx_reference_occupied: this behind a check that the object was derived)
+int reference_occupied(ivx_grid* g, uint32_t occ[12]);
 
 // A doorbell: a word of host-mapped memory that a kernel writes last (in-order stream: everything enqueued before it is complete too). A short
 // chain is over before the runtime's blocking wait has gone to sleep and been woken again: the word is polled for at most `budget_ns` (0: never),
@@ -105,7 +109,14 @@ struct ManyClock {
     }
 };
 
-// ---- the mesh unit (mesh_api.hip) and the edit and step paths (ivx_api.hip, step_api.hip) --------------------------------------------------------------
+// ---- the edit unit (edit_api.hip), the mesh unit (mesh_api.hip) and the rest (ivx_api.hip, step_api.hip, voxel_collision_api.hip) ----------------------
+// grid -> edit: the edit state is given up (ivx_grid_destroy) | many -> edit: the edit in flight, if any, is collected, its results discarded (many_fail)
+void edit_free(ivx_grid* g);
+void edit_abandon(ivx_grid* g);
+// edit -> collision (voxel_collision_api.hip): the voxel ranges that hold two objects' overlap, b's frame -> a's; false: the boxes do not meet
+bool host_intersection_ranges(const ivx_grid* a, const uint32_t occ_a[12], const float rotation_a[4], const float translation_a[3], const ivx_grid* b,
+                              const uint32_t occ_b[12], const float rotation_b[4], const float translation_b[3], long ra_lo[3], long ra_hi[3], long rb_lo[3],
+                              long rb_hi[3], float q_ba[4], float t_ba[3]);
 // mesh -> edit: what the mesh of `chunk` needs (vertices, indices, kind | flags << 8) when the last edit counted it | the chunks the edit in
 // flight invalidates, from the records its count role delivers early (waits for the role's bell, not for the edit)
 bool edit_needs_lookup(ivx_grid* g, uint32_t chunk, uint32_t out3[3]);

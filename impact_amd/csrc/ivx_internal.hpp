@@ -150,6 +150,25 @@ struct ivx_sampler {
     } ahead;
 };
 
+// What an edit hands the step's launches (ivx_grid::needs_role, ::gather_copy): set by the edit's enqueue, consumed and reset by the launch.
+// The mesh-needs role the next k_step_post1 launch hosts (`out` non-null) may deliver its records EARLY (ivx_mesh_sync_enqueue with a null set
+// while the edit is in flight): into host-mapped memory, its last workgroup ringing a bell — the host places the meshes while the region stages run.
+struct ivx_needs_role {
+    uint32_t box[12];         // touched box lo, cc; grown box lo, cc
+    const uint32_t* touched;  // the touched words of the touched box's chunks
+    uint32_t* out;            // a uint4 record per chunk of the grown box
+    uint32_t* early;          // host-mapped twin of `out` (null: no early delivery)
+    uint32_t* counter;        // workgroups of the role that are through (device word, zero at the start)
+    uint32_t* bell;           // host-mapped: `seq` once all are
+    uint32_t seq;
+};
+// ... and the words the next k_step_gather launch copies to host-mapped memory ahead of the doorbell (the edit's small results)
+struct ivx_gather_copy {
+    const uint32_t* src;
+    uint32_t* dst;  // (device address of host-mapped memory)
+    uint32_t words;
+};
+
 struct ivx_grid {
     ivx_ctx* ctx;
     uint32_t cc[3];
@@ -231,21 +250,11 @@ struct ivx_grid {
     // a derive sweep of its own rebuilds it first (ivx_ensure_active_list)
     int active_list_stale;
     int regions_labelled_locally;  // (set around the resolve stage of an edit: the box sweep has labelled the chunk-local regions)
-    struct ivx_edit_state* edit;   // host state of the edit path (ivx_absorb_*_enqueue / _collect)
+    struct ivx_edit_state* edit;   // host state of the edit path (edit_api.hip, and opaque outside it)
     // handed to the next k_step_post1 / k_step_gather launch and consumed by it (the edit path's riders on the step's launches)
-    uint32_t post1_needs_box[12];         // touched box lo, cc; grown box lo, cc
-    const uint32_t* post1_needs_touched;
-    uint32_t* post1_needs_out;            // non-null: the next post1 launch hosts the mesh-needs role
-    // ... which also delivers its records EARLY (ivx_mesh_sync_enqueue with a null set while the edit is in flight): straight into host-mapped
-    // memory, the role's last workgroup ringing a bell behind them — the host places the invalidated meshes while the region stages still run
-    int early_needs_on;                   // ivx_grid_set_early_mesh_needs: the edits of this object deliver early (a system-scope fence per workgroup of the role: ~4 us per edit)
-    uint32_t* post1_needs_early;          // host-mapped twin of post1_needs_out (null: no early delivery)
-    uint32_t* post1_needs_counter;        // workgroups of the role that are through (device word, zero at the start)
-    uint32_t* post1_needs_bell;           // host-mapped: post1_needs_seq once all are
-    uint32_t post1_needs_seq;
-    const uint32_t* gather_copy_src;
-    uint32_t* gather_copy_dst;            // (device address of host-mapped memory)
-    uint32_t gather_copy_words;
+    ivx_needs_role needs_role;
+    ivx_gather_copy gather_copy;
+    int early_needs_on;            // ivx_grid_set_early_mesh_needs: the edits of this object deliver early (a system-scope fence per workgroup of the role: ~4 us per edit)
     uint64_t gather_flush_id;      // the recorder's flush count when the gather was recorded (many.hpp)
     int gather_launched;           // the step's gather is on the stream (or recorded): ivx_voxel_step_collect only waits
     int sn_tail_zero;  // the mesher's hand-off counter, list cursors and census word (IVX_SN_TAIL_WORDS) are known to be zero (ivx_launch_sn_emit_list)

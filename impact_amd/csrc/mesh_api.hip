@@ -1,7 +1,7 @@
 // Mesh host code of libimpact_voxel_hip.so: where an object's mesh arrays live and how they grow, the full remesh, the incremental remesh
 // (VoxelObjectMesh::sync_with_voxel_object) with its host mirror of the ChunkSubmeshManager, and what hands the arrays to a caller: download,
 // device pointers, export and import. Host-side orchestration only: the kernels are the mesher's, behind the ivx_launch_* functions of
-// surface_nets.hip. What the edit and step paths (ivx_api.hip, step_api.hip) and this unit ask of each other is declared in ivx_host.hpp.
+// surface_nets.hip. What the edit and step units (edit_api.hip, step_api.hip) and this unit ask of each other is declared in ivx_host.hpp.
 #include <algorithm>
 #include <array>
 #include <cstring>

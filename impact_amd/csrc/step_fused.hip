@@ -82,8 +82,8 @@ struct StepArgs {
     uint32_t record_max_pairs;
     unsigned long long* record_head;  // (optional) a second place for the record's first record_head_words words
     uint32_t record_head_words;
-    // edit path: what the meshes of the chunks an edit invalidates need, as a role of k_step_post1 (ivx_grid::post1_needs); a block of small
-    // results copied to host-mapped memory by k_step_gather ahead of the doorbell (ivx_grid::gather_copy_*)
+    // edit path: what the meshes of the chunks an edit invalidates need, as a role of k_step_post1 (ivx_grid::needs_role); a block of small
+    // results copied to host-mapped memory by k_step_gather ahead of the doorbell (ivx_grid::gather_copy)
     sn::BoxNeeds needs_box;
     const uint32_t* needs_touched;
     uint32_t* needs_out;
@@ -401,17 +401,17 @@ int ivx_launch_step_post1(ivx_grid* g, uint32_t stages) {
         a.nb[4] = groups < (uint32_t)g->partial_blocks ? groups : (uint32_t)g->partial_blocks;
         a.n_partials = a.nb[4];
     }
-    if (g->post1_needs_out) {  // (edit path: consumed by this launch)
+    if (g->needs_role.out) {  // (edit path: consumed by this launch)
+        const ivx_needs_role& r = g->needs_role;
         for (int d = 0; d < 3; ++d) {
-            a.needs_box.t_lo[d] = g->post1_needs_box[d], a.needs_box.t_cc[d] = g->post1_needs_box[3 + d];
-            a.needs_box.b_lo[d] = g->post1_needs_box[6 + d], a.needs_box.b_cc[d] = g->post1_needs_box[9 + d];
+            a.needs_box.t_lo[d] = r.box[d], a.needs_box.t_cc[d] = r.box[3 + d];
+            a.needs_box.b_lo[d] = r.box[6 + d], a.needs_box.b_cc[d] = r.box[9 + d];
         }
-        a.needs_touched = g->post1_needs_touched;
-        a.needs_out = g->post1_needs_out;
-        a.needs_early = g->post1_needs_early, a.needs_counter = g->post1_needs_counter, a.needs_bell = g->post1_needs_bell, a.needs_seq = g->post1_needs_seq;
-        g->post1_needs_early = nullptr;
+        a.needs_touched = r.touched;
+        a.needs_out = r.out;
+        a.needs_early = r.early, a.needs_counter = r.counter, a.needs_bell = r.bell, a.needs_seq = r.seq;
         a.nb[5] = a.needs_box.b_cc[0] * a.needs_box.b_cc[1] * a.needs_box.b_cc[2];
-        g->post1_needs_out = nullptr;
+        g->needs_role = {};
     }
     if ((stages & IVX_STAGE_REMESH) && g->ghost_event) {
         // a slab whose ghost layers are still on their way (slab_comm.cpp): the count of the chunk planes that read nothing of them as a launch
@@ -529,8 +529,8 @@ int ivx_launch_step_assign(ivx_grid* g, bool with_mesher_general, bool with_ccl)
 int ivx_launch_step_gather(ivx_grid* g) {
     StepArgs a = make_args(g);
     a.seq = ++g->result_seq;
-    a.copy_src = g->gather_copy_src, a.copy_dst = g->gather_copy_dst, a.copy_words = g->gather_copy_words;  // (consumed by this launch)
-    g->gather_copy_words = 0;
+    a.copy_src = g->gather_copy.src, a.copy_dst = g->gather_copy.dst, a.copy_words = g->gather_copy.words;  // (consumed by this launch)
+    g->gather_copy = {};
     g->timing.hand_to_gather(&a.ticks_dev, &a.ticks_host, &a.n_ticks, &a.tick);  // (stamped slots since the last collect: their words go out with the results)
     if (!ivx_many_try(g->ctx, g, IVX_MK_GATHER, 1u, a)) IVX_KLAUNCH(k_step_gather, dim3(1), dim3(64), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());

@@ -1,7 +1,8 @@
 // Voxel collision host code of libimpact_voxel_hip.so: contacts of a voxel object with a sphere, plane or capsule collidable, the collision probes
-// that follow an object's mesh, mutual contacts of two voxel objects and their mutual absorption; single calls and the `_many` forms; and the
-// host side of ivx_cw_collide_frame, which runs both `_many` generator families over the rows narrow.hip made of a frame's deferred pairs.
-// Host-side orchestration only: the kernels are those of contacts.hip, collide.hip and edit.hip behind their ivx_launch_* functions.
+// that follow an object's mesh, mutual contacts of two voxel objects; single calls and the `_many` forms; the host side of
+// ivx_cw_collide_frame, which runs both `_many` generator families over the rows narrow.hip made of a frame's deferred pairs; and the overlap
+// geometry of two objects (host_intersection_ranges), which their mutual absorption (edit_api.hip) asks for as well.
+// Host-side orchestration only: the kernels are those of contacts.hip and collide.hip behind their ivx_launch_* functions.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -14,6 +15,7 @@
 #include "ivx_host.hpp"
 #include "physics_internal.hpp"
 #include "vec3.hpp"
+#include "voxel_ranges.hpp"
 
 namespace {
 using namespace ivx_vec;  // V3, Q4, ld3, st3, qrot, qmul, splitmix
@@ -23,30 +25,6 @@ void qrot3(const float q[4], const float v[3], float out[3]) { st3(out, qrot(q, 
 void qmul4(const float a[4], const float b[4], float o[4]) {
     const Q4 r = qmul(Q4{a[0], a[1], a[2], a[3]}, Q4{b[0], b[1], b[2], b[3]});
     o[0] = r.x, o[1] = r.y, o[2] = r.z, o[3] = r.w;
-}
-
-// voxel_ranges_touching_aab (intersection.rs:766-782): the voxels a box in voxel units touches, clamped onto the occupied ranges; not checked for
-// emptiness (the reference does not either). `as usize` stops at 0 below (NaN included); `saturate`: ... and at 2e9 above, which the mutual forms
-// need for the bounds of an overlap box. The collidable forms have never saturated and still do not: the two conversions agree for every bound
-// below 2^31 voxels, past it the unsaturated one wraps in the int32 ranges of chunk_box where the reference finds nothing touched.
-void clamped_ranges(const uint32_t occ[12], const float lo_f[3], const float hi_f[3], bool saturate, long lo[3], long hi[3]) {
-    auto index = [saturate](float f) -> long { return f > 0.0f ? (!saturate || f < 2.0e9f ? (long)f : 2000000000L) : 0; };
-    for (int d = 0; d < 3; ++d) {
-        lo[d] = std::max<long>((long)occ[6 + 2 * d], index(std::floor(lo_f[d])));
-        hi[d] = std::min<long>((long)occ[7 + 2 * d], index(std::ceil(hi_f[d])));
-    }
-}
-// the voxel ranges as the kernels take them and the box of chunks that holds them (meaningless when a range is empty: false)
-bool chunk_box(const long rlo[3], const long rhi[3], int32_t vlo[3], int32_t vhi[3], uint32_t lo[3], uint32_t cc[3]) {
-    bool any = true;
-    for (int d = 0; d < 3; ++d) {
-        vlo[d] = (int32_t)rlo[d];
-        vhi[d] = (int32_t)rhi[d];
-        any = any && vlo[d] < vhi[d];
-        lo[d] = (uint32_t)vlo[d] / 16u;
-        cc[d] = ((uint32_t)vhi[d] + 15u) / 16u - lo[d];
-    }
-    return any;
 }
 
 // the chunk box and voxel ranges a collidable touches of an object (mode 0 sphere: centre shape3, radius shape1; 1 plane: unit normal shape3,
@@ -216,6 +194,8 @@ bool host_box_bounds(const HBox& a, const float bc[3], const float bq[4], const 
     return any;
 }
 
+}  // namespace
+
 // determine_voxel_ranges_encompassing_intersection (object/intersection.rs:706-746) from the two objects' occupied ranges and world -> object
 // transforms; also transform_from_b_to_a = world_to_a * world_to_b.inverted() (impact_math/src/transform/isometry.rs:128-134, 200-205).
 // The ranges are not checked for emptiness (the reference does not either). false: the occupied boxes do not meet.
@@ -260,6 +240,7 @@ bool host_intersection_ranges(const ivx_grid* a, const uint32_t occ_a[12], const
     return true;
 }
 
+namespace {
 // the end of the single calls: the total, then that many contacts, each a copy and a wait
 int contacts_download(ivx_grid* g, const char* who, const uint32_t* d_total, const ivx_contact* d_out, ivx_contact* out, size_t cap, size_t* n_out) {
     uint32_t total = 0;
@@ -1059,117 +1040,6 @@ int ivx_cw_collide_frame(ivx_world* w, uint32_t mode, ivx_contact* out, size_t c
     if (lists) {
         if (nd) memcpy(deferred_pairs, fp.deferred, nd * 8);
         memcpy(manifold_offsets, offsets.data(), (nd + 1) * 4);
-    }
-    return IVX_OK;
-}
-
-// apply_mutual_absorption (interaction/absorption.rs:891-1079)
-int ivx_absorb_mutual(ivx_grid* a, const float rotation_a[4], const float translation_a[3], const float densities_a[256], ivx_grid* b, const float rotation_b[4],
-                      const float translation_b[3], const float densities_b[256], float smoothness, ivx_absorb_result* out_a, ivx_absorb_result* out_b,
-                      uint8_t* invalidated_chunks_a, uint8_t* invalidated_chunks_b) {
-    const char* who = "ivx_absorb_mutual";
-    IVX_REQUIRE(a && b && rotation_a && translation_a && densities_a && rotation_b && translation_b && densities_b && out_a && out_b, IVX_ERR_INVALID,
-                "%s: null argument", who);
-    IVX_REQUIRE(a != b && a->ctx == b->ctx, IVX_ERR_INVALID, "%s: two different objects of one context are needed", who);
-    IVX_REQUIRE(smoothness >= 0.0f, IVX_ERR_INVALID, "%s: negative smoothness", who);
-    int rc;
-    for (ivx_grid* g : {a, b})
-        if ((rc = require_whole_object(g, who, false))) return rc;
-    memset(out_a, 0, sizeof(*out_a));
-    memset(out_b, 0, sizeof(*out_b));
-    if (invalidated_chunks_a) memset(invalidated_chunks_a, 0, a->n_chunks);
-    if (invalidated_chunks_b) memset(invalidated_chunks_b, 0, b->n_chunks);
-    uint32_t occ_a[12], occ_b[12];
-    if ((rc = ivx_reference_occupied(a, who, occ_a))) return rc;
-    if ((rc = ivx_reference_occupied(b, who, occ_b))) return rc;
-    long ra_lo[3], ra_hi[3], rb_lo[3], rb_hi[3];
-    float q_ba[4], t_ba[3];
-    if (!host_intersection_ranges(a, occ_a, rotation_a, translation_a, b, occ_b, rotation_b, translation_b, ra_lo, ra_hi, rb_lo, rb_hi, q_ba, t_ba)) return IVX_OK;
-    // the snapshot of A's distances covers A's overlap ranges padded by one B voxel (in A voxels), inside A's grid
-    const long pad = (long)std::ceil(b->extent * (1.0f / a->extent));
-    for (int d = 0; d < 3; ++d) {
-        ra_lo[d] = std::max<long>(0, ra_lo[d] - pad);
-        ra_hi[d] = std::min<long>(ra_hi[d] + pad, (long)a->cc[d] * 16);
-    }
-    int32_t s_lo[3], s_hi[3], vb_lo[3], vb_hi[3];
-    uint32_t lo_a[3], cc_a[3], lo_b[3], cc_b[3];
-    const bool a_runs = chunk_box(ra_lo, ra_hi, s_lo, s_hi, lo_a, cc_a), b_runs = chunk_box(rb_lo, rb_hi, vb_lo, vb_hi, lo_b, cc_b);
-    const size_t snap_bytes = a_runs ? (size_t)(s_hi[0] - s_lo[0]) * (size_t)(s_hi[1] - s_lo[1]) * (size_t)(s_hi[2] - s_lo[2]) : 0;
-    if (!a_runs && !b_runs) return IVX_OK;
-    // scratch (A's): per object [10 f64 removed moments][256 u32 by type][2 u32 counters][pad][n_chunks u32 touched ranges], then the two density
-    // tables, then the snapshot
-    const size_t off_type = 80, off_cnt = off_type + 1024, off_touch = off_cnt + 16;
-    // (the touched ranges are indexed by the chunk's position in the object's chunk box; the boxes are known further down, a whole grid bounds them)
-    const size_t blk_a = (off_touch + (size_t)a->n_chunks * 4 + 255) & ~(size_t)255, blk_b = (off_touch + (size_t)b->n_chunks * 4 + 255) & ~(size_t)255;
-    const size_t off_dens = blk_a + blk_b, off_snap = off_dens + 2048;
-    if ((rc = ensure_dev_scratch(a, off_snap + snap_bytes + 256))) return rc;
-    char* base = static_cast<char*>(a->dev_scratch);
-    IVX_HIP_CHECK(ivx_memset_async(base, 0, off_dens, a->ctx->stream));
-    if ((rc = h2d(a, base + off_dens, densities_a, 1024))) return rc;
-    if ((rc = h2d(a, base + off_dens + 1024, densities_b, 1024))) return rc;
-    int8_t* d_snap = reinterpret_cast<int8_t*>(base + off_snap);
-    if (a_runs) {
-        if ((rc = ivx_launch_sdf_snapshot(a, s_lo, s_hi, d_snap))) return rc;
-        if ((rc = ivx_launch_absorb_mutual(a, 0, lo_a, cc_a, s_lo, s_hi, b, nullptr, s_lo, s_hi, q_ba, t_ba, smoothness, reinterpret_cast<float*>(base + off_dens),
-                                           reinterpret_cast<double*>(base), reinterpret_cast<uint32_t*>(base + off_type),
-                                           reinterpret_cast<uint32_t*>(base + off_cnt), reinterpret_cast<uint32_t*>(base + off_touch))))
-            return rc;
-    }
-    if (b_runs) {
-        char* bb = base + blk_a;
-        if ((rc = ivx_launch_absorb_mutual(b, 1, lo_b, cc_b, vb_lo, vb_hi, a, d_snap, s_lo, s_hi, q_ba, t_ba, smoothness,
-                                           reinterpret_cast<float*>(base + off_dens + 1024), reinterpret_cast<double*>(bb),
-                                           reinterpret_cast<uint32_t*>(bb + off_type), reinterpret_cast<uint32_t*>(bb + off_cnt),
-                                           reinterpret_cast<uint32_t*>(bb + off_touch))))
-            return rc;
-    }
-    std::vector<char> hostbuf(off_dens);
-    if ((rc = d2h(a, hostbuf.data(), base, off_dens))) return rc;
-    if (a_runs && (rc = rederive(a))) return rc;
-    if (b_runs && (rc = rederive(b))) return rc;
-    for (int w = 0; w < 2; ++w) {
-        ivx_grid* g = w ? b : a;
-        if (!(w ? b_runs : a_runs)) continue;
-        const char* hb = hostbuf.data() + (w ? blk_a : 0);
-        ivx_absorb_result* out = w ? out_b : out_a;
-        uint8_t* inval = w ? invalidated_chunks_b : invalidated_chunks_a;
-        const uint32_t* lo = w ? lo_b : lo_a;
-        const uint32_t* cc = w ? cc_b : cc_a;
-        const double* rem = reinterpret_cast<const double*>(hb);
-        const double e = (double)g->extent, e3 = e * e * e, e4 = e3 * e, e5 = e4 * e;
-        const double f[10] = {e3, 0.5 * e4, 0.5 * e4, 0.5 * e4, e5 / 3.0, e5 / 3.0, e5 / 3.0, 0.25 * e5, 0.25 * e5, 0.25 * e5};
-        for (int q = 0; q < 10; ++q) out->removed_moments[q] = rem[q] * f[q];
-        const uint32_t* by_type = reinterpret_cast<const uint32_t*>(hb + off_type);
-        uint64_t emptied = 0;
-        for (int t = 0; t < 256; ++t) emptied += by_type[t];
-        out->emptied_voxels = emptied;
-        const uint32_t* cnt = reinterpret_cast<const uint32_t*>(hb + off_cnt);
-        out->touched_chunks = cnt[0];
-        out->removed_chunks = cnt[1];
-        if (cnt[1]) g->occ_ref_valid = 0;  // (intersection.rs:255-257)
-        if (!inval) continue;
-        const uint32_t* touched = reinterpret_cast<const uint32_t*>(hb + off_touch);  // handle_chunk_voxels_modified (intersection.rs:560-598)
-        for (uint32_t i = lo[0]; i < lo[0] + cc[0]; ++i)
-            for (uint32_t j = lo[1]; j < lo[1] + cc[1]; ++j)
-                for (uint32_t k = lo[2]; k < lo[2] + cc[2]; ++k) {
-                    const uint32_t c = (i * g->cc[1] + j) * g->cc[2] + k;
-                    const uint32_t wd = touched[((i - lo[0]) * cc[1] + (j - lo[1])) * cc[2] + (k - lo[2])];
-                    if (!wd) continue;
-                    inval[c] = 1;
-                    const uint32_t idx[3] = {i, j, k};
-                    for (int d = 0; d < 3; ++d) {
-                        const uint32_t rlo = (wd >> (4 * d)) & 15u, rhi = ((wd >> (12 + 4 * d)) & 15u) + 1u;
-                        uint32_t n3[3] = {i, j, k};
-                        if (idx[d] > 0 && rlo < 2) {
-                            n3[d] = idx[d] - 1;
-                            inval[(n3[0] * g->cc[1] + n3[1]) * g->cc[2] + n3[2]] = 1;
-                        }
-                        if (idx[d] + 1 < g->cc[d] && 16u - rhi < 2) {
-                            n3[d] = idx[d] + 1;
-                            inval[(n3[0] * g->cc[1] + n3[1]) * g->cc[2] + n3[2]] = 1;
-                        }
-                    }
-                }
     }
     return IVX_OK;
 }

@@ -1389,49 +1389,23 @@ int ivx_launch_phys_pre_solve(ivx_world* w, float dt) {
     return IVX_OK;
 }
 
+// ---- the solve: ivx_solve::solve_plan (solve_plan.hpp) says which form runs and what is enqueued, in order; each operation is written once below ----
+using ivx_solve::solve_switches;
+static ivx_solve::SolveTrace solve_trace;
+
+// One workgroup, the phase's mutable body state in LDS or in global memory (the plan's in_lds)
 template <bool LDS, int PHASE>
-static int launch_solve(ivx_world* w, size_t lds, ReplayView rv = ReplayView(), const uint32_t* replay_flag = nullptr) {
+static int launch_solve_as(ivx_world* w, size_t lds, const ReplayView& rv, const uint32_t* replay_flag) {
     if (LDS) IVX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve<LDS, PHASE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     IVX_KLAUNCH((k_solve<LDS, PHASE>), dim3(1), dim3(SOLVE_THREADS), LDS ? lds : 0, w->ctx->stream, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur].p,
                        reinterpret_cast<float4*>(w->acc[w->cur].p), w->cb.p, w->items.p + w->sched.item_offset[PHASE],
                        reinterpret_cast<const uint2*>(w->item_bodies.p) + w->sched.item_offset[PHASE], w->level_start.p + w->sched.level_offset[PHASE],
                        w->sched.n_levels[PHASE], rv, replay_flag);
-    IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
-
-// number of workgroups the solve is spread over: as many as the widest level fills with one chain per thread, at most 16 (all
-// resident: 256 CUs); 1 = the single-workgroup kernel with the bodies in LDS. ivx_world_set_solver_groups overrides (tests force
-// either path on small scenes).
-// (co-residency of the G working workgroups is what the grid barrier rests on: G x spread blocks must fit the device beside nothing else of
-// this launch — checked against the occupancy query; a world whose barrier ever timed out stays on one workgroup)
-static uint32_t solver_groups(const ivx_world* w) {
-    if (w->mg_disabled) return 1u;
-    static const int resident = [] {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_solve_mg<0>, (int)MG_THREADS, 0) != hipSuccess) per_cu = 0;
-        int per_cu1 = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu1, k_solve_mg<1>, (int)MG_THREADS, 0) != hipSuccess) per_cu1 = 0;
-        return per_cu < per_cu1 ? per_cu : per_cu1;
-    }();
-    const uint32_t fit = (uint32_t)(resident > 0 ? resident : 0) * (uint32_t)w->ctx->n_cu / 8u;  // (/ 8: every eighth block works, see k_solve_mg)
-    if (fit < 2u) return 1u;
-    if (w->solver_groups_forced && w->solver_groups_forced <= 16u) return w->solver_groups_forced < fit ? w->solver_groups_forced : fit;
-    const uint32_t widest = w->sched.max_level_items[0] > w->sched.max_level_items[1] ? w->sched.max_level_items[0] : w->sched.max_level_items[1];
-    if (widest <= 256u) return 1u;  // (a level that fits one workgroup at one wave per SIMD gains nothing from more)
-    uint32_t g = (widest + 159u) / 160u;  // (a few more waves than the widest level has tiles: measured on the 4096-body pile, 8 workgroups 0.85 ms, 5: 0.89, 16: 0.86)
-    g = g < 16u ? g : 16u;
-    return g < fit ? g : fit;
-}
-
-// developer switch (never set in production): IVX_SOLVER_DRY bit 0 = walk the levels without running the chains, bit 1 = without the grid
-// barrier — how tools/time_pile.py splits a level's time into arithmetic and synchronisation (results are garbage with either)
-static uint32_t ivx_solver_dry() {
-    static const uint32_t v = [] {
-        const char* e = getenv("IVX_SOLVER_DRY");
-        return e ? (uint32_t)atoi(e) : 0u;
-    }();
-    return v;
+template <int PHASE>
+static int launch_solve(ivx_world* w, const ivx_solve::SolvePlan& pl, const ReplayView& rv, const uint32_t* replay_flag) {
+    return pl.in_lds[PHASE] ? launch_solve_as<true, PHASE>(w, pl.lds_bytes[PHASE], rv, replay_flag) : launch_solve_as<false, PHASE>(w, 0, rv, replay_flag);
 }
 
 // this step's prepared contacts and body constants into the schedule's packed records (run_chain_mg; the positional phase's second pass reads
@@ -1451,263 +1425,169 @@ static int pack_items_mg(ivx_world* w, hipStream_t stream) {
     IVX_KLAUNCH((k_pack_items<PHASE>), dim3(w->sched.n_tiles[PHASE]), dim3(64), 0, stream, w->tile_first.p + w->sched.tile_offset[PHASE], w->items.p + w->sched.item_offset[PHASE],
                        reinterpret_cast<const uint2*>(w->item_bodies.p) + w->sched.item_offset[PHASE], reinterpret_cast<const uint4*>(w->item_tags.p) + w->sched.item_offset[PHASE],
                        w->pc[w->cur].p, w->cb.p, reinterpret_cast<float4*>(w->packed[PHASE]));
-    IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
 
-// One phase's solve on `stream`. Everything a launch shares between its workgroups is the phase's own — barrier counter and census table
-// (barrier_words[PHASE], + 4 + 20 PHASE), shared body records (dynst, second half for the positional phase) — because the two phases run side
-// by side (ivx_launch_phys_solve).
+// One phase's tile-dataflow solve on `stream`. Everything a launch shares between its workgroups is the phase's own — barrier counter and
+// census table (barrier_words[PHASE], + 4 + 20 PHASE), shared body records (dynst, second half for the positional phase) — because the two
+// phases run side by side.
 template <int PHASE>
-static int launch_solve_mg(ivx_world* w, uint32_t groups, hipStream_t stream, ReplayView rv = ReplayView(), const uint32_t* replay_flag = nullptr) {
+static int launch_solve_mg(ivx_world* w, uint32_t groups, hipStream_t stream, const ReplayView& rv, const uint32_t* replay_flag) {
     uint32_t& count = PHASE ? w->barrier_count1 : w->barrier_count;
     const uint32_t base = count;
     count += groups * 2u;  // (two grid barriers per launch: behind the set-up and census, and before the write-back)
-    static const uint32_t spread = [] {  // (developer switch; 8 = the working workgroups share one XCD, 1 = consecutive blocks; see k_solve_mg)
-        const char* e = getenv("IVX_SOLVER_SPREAD");
-        const int v = e ? atoi(e) : 8;
-        return (uint32_t)(v < 1 ? 1 : (v > 8 ? 8 : v));
-    }();
+    const uint32_t spread = solve_switches().spread_mg();
     IVX_KLAUNCH((k_solve_mg<PHASE>), dim3(groups * spread), dim3(MG_THREADS), 0, stream, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur].p,
                        reinterpret_cast<float4*>(w->acc[w->cur].p), w->n_contacts, w->cb.p, reinterpret_cast<float4*>(w->dynst.p + (PHASE ? w->body_cap * 16 : 0)),
                        w->items.p + w->sched.item_offset[PHASE],
                        reinterpret_cast<const uint2*>(w->item_bodies.p) + w->sched.item_offset[PHASE], w->level_start.p + w->sched.level_offset[PHASE],
                        w->tile_base.p + w->sched.level_offset[PHASE], reinterpret_cast<const float4*>(w->packed[PHASE]),
-                       w->sched.n_levels[PHASE], w->barrier_words + PHASE, base, w->mg_err_dev, ivx_solver_dry(), spread, rv, replay_flag, w->barrier_words + 4 + 20 * PHASE,
+                       w->sched.n_levels[PHASE], w->barrier_words + PHASE, base, w->mg_err_dev, solve_switches().dry, spread, rv, replay_flag, w->barrier_words + 4 + 20 * PHASE,
                        w->tile_first.p + w->sched.tile_offset[PHASE], w->sched.n_tiles[PHASE]);
-    IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
 
-// The chain-stationary solve: can this world's schedule run on it, and should it? Needs every phase that has levels in stationary form
-// (build_stationary), one workgroup of CS_THREADS per CU and an eighth of the CUs (one XCD's worth) per phase for its workgroups.
-static bool solver_stationary(const ivx_world* w) {
-    if (w->mg_disabled || w->solver_groups_forced == 1u || (w->solver_groups_forced >= 2u && w->solver_groups_forced <= 16u)) return false;
-    for (int p = 0; p < 2; ++p)
-        if (w->sched.n_levels[p] && !w->sched.cs_feasible[p]) return false;
-    if (!w->sched.n_levels[0] && !w->sched.n_levels[1]) return false;
-    static const int per_cu = [] {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_solve_cs, (int)CS_THREADS, 0) != hipSuccess) n = 0;
-        return n;
-    }();
-    if (per_cu < 1) return false;
-    for (int p = 0; p < 2; ++p)
-        if (w->sched.n_levels[p] && (((uint32_t)w->sched.chain_start.size() - 1u + 31u) / 32u + PHYS_CS_WAVES - 1u) / PHYS_CS_WAVES > (uint32_t)w->ctx->n_cu / 8u) return false;
-    if (w->solver_groups_forced == PHYS_SOLVER_STATIONARY) return true;
-    // One workgroup with the bodies in LDS (k_solve) walks a level in ~4-5 us whatever its width — a barrier and the contacts' trip from memory —,
-    // the chain-stationary solve in ~2.3 (velocity) / ~3.5 (positional) plus ~25 us of launches and census around it: it wins wherever the chain of
-    // levels is long, wide or not (81 bodies of 48 contacts each on a ground plane: 297 + 99 levels of at most 79 chains, 0.55 -> 0.21 ms;
-    // tools/time_world_frames.py). A handful of levels stays with the one workgroup.
-    const uint32_t widest = w->sched.max_level_items[0] > w->sched.max_level_items[1] ? w->sched.max_level_items[0] : w->sched.max_level_items[1];
-    return widest > 256u || w->sched.n_levels[0] + w->sched.n_levels[1] >= 48u;
+// rounds of a phase's chain-stationary schedule (what IVX_SOLVER_TRACE stamps)
+static size_t cs_rounds(const ivx_world* w, int p) {
+    return w->sched.n_levels[p] ? w->sched.cs_round_start_host[w->sched.cs[p].round_start_offset + w->sched.cs[p].n_tiles] : 0u;
 }
-
-static int launch_solve_cs(ivx_world* w) {
-    hipStream_t s = w->ctx->stream;
-    const bool replay = w->sched.n_levels[1] && w->sched.n_kin_items > 0;
-    uint32_t* flag = w->barrier_words + 2;
-    float4* dyn_vel = reinterpret_cast<float4*>(w->dynst.p);
-    float4* dyn_pos = reinterpret_cast<float4*>(w->dynst.p + w->body_cap * 16);
-    static const uint32_t spread = [] {  // (developer switch; 8 = a phase's workgroups share one XCD under round-robin placement, 1 = consecutive blocks)
-        const char* e = getenv("IVX_SOLVER_SPREAD");
-        const int v = e ? atoi(e) : 8;
-        return (uint32_t)(v < 2 ? 1 : 8);
-    }();
-    // developer switch: IVX_SOLVER_TRACE=<file> — every round's four clock stamps of the first solve launch of each step, dumped as
-    // [phase][round][4] u64 behind a header of {rounds of phase 0, rounds of phase 1} (tools/solver_trace.py reads it); the step then waits
-    static const char* trace_path = getenv("IVX_SOLVER_TRACE");
-    static unsigned long long* trace_dev = nullptr;
-    static size_t trace_cap = 0;
-    const size_t n_rounds[2] = {w->sched.n_levels[0] ? w->sched.cs_round_start_host[w->sched.cs[0].round_start_offset + w->sched.cs[0].n_tiles] : 0u,
-                                w->sched.n_levels[1] ? w->sched.cs_round_start_host[w->sched.cs[1].round_start_offset + w->sched.cs[1].n_tiles] : 0u};
-    if (trace_path && 4 * (n_rounds[0] + n_rounds[1]) > trace_cap) {
-        if (trace_dev) (void)hipFree(trace_dev);
-        trace_cap = 4 * (n_rounds[0] + n_rounds[1]);
-        IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&trace_dev), trace_cap * 8));
+// One phase's arguments of a chain-stationary launch; `on` = false or no levels: the phase sits this launch out. Counts the launch's grid
+// barrier on the phase's counter.
+static CsPhase cs_phase_args(ivx_world* w, int p, bool on, const ReplayView& rv, const uint32_t* replay_flag) {
+    CsPhase a = {};
+    if (!on || !w->sched.n_levels[p]) return a;
+    const ivx_contact_schedule::CsSchedule& cs = w->sched.cs[p];
+    a.item = w->cs_item.p + cs.slot_offset;
+    a.bodies = reinterpret_cast<const uint2*>(w->cs_bodies.p) + cs.slot_offset;
+    a.vers = w->cs_vers.p + cs.slot_offset;
+    a.round_start = w->cs_round_start.p + cs.round_start_offset;
+    a.round_mask = w->cs_round_mask.p + cs.round_offset;
+    a.round_level = w->cs_round_level.p + cs.round_offset;
+    a.nap = solve_switches().nap;
+    a.dynst = reinterpret_cast<float4*>(w->dynst.p + (p ? w->body_cap * 16 : 0));
+    a.counter = w->barrier_words + p;
+    a.xcc_table = w->barrier_words + 64 + 32 * p;
+    a.slot_of = w->cs_slot_of.p;
+    a.replay_flag = replay_flag;
+    a.trace = solve_switches().trace_path && !replay_flag ? solve_trace.dev + (p ? 4 * cs_rounds(w, 0) : 0) : nullptr;
+    a.rv = rv;
+    a.n_tiles = cs.n_tiles;
+    a.n_groups = (cs.n_tiles + PHYS_CS_WAVES - 1u) / PHYS_CS_WAVES;
+    a.n_first = p ? 0u : 1u;
+    a.n_passes = p ? w->cfg.n_positional_correction_iterations : w->cfg.n_iterations + 1u;
+    uint32_t& count = p ? w->barrier_count1 : w->barrier_count;
+    a.counter_base = count;
+    count += a.n_groups;  // (one grid barrier per launch: behind the census)
+    return a;
+}
+// IVX_SOLVER_TRACE: room for this schedule's stamps, zeroed / the stamps and the rounds' levels to the file, behind a wait
+static int solve_trace_clear(ivx_world* w, hipStream_t s) {
+    const size_t need = 4 * (cs_rounds(w, 0) + cs_rounds(w, 1));
+    if (need > solve_trace.cap) {
+        if (solve_trace.dev) (void)hipFree(solve_trace.dev);
+        solve_trace.cap = need;
+        IVX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&solve_trace.dev), solve_trace.cap * 8));
     }
-    if (trace_path) IVX_HIP_CHECK(ivx_memset_async(trace_dev, 0, trace_cap * 8, s));
-    static const uint32_t nap = [] {  // (developer switch: IVX_SOLVER_NAP = tenths of a level a wave wakes ahead of its round; 0 = never sleeps)
-        const char* e = getenv("IVX_SOLVER_NAP");
-        return (uint32_t)(e ? atoi(e) : 20);
-    }();
-    auto phase_args = [&](int p, bool on, const ReplayView& rv, const uint32_t* replay_flag) {
-        CsPhase a = {};
-        if (!on || !w->sched.n_levels[p]) return a;
-        const ivx_contact_schedule::CsSchedule& cs = w->sched.cs[p];
-        a.item = w->cs_item.p + cs.slot_offset;
-        a.bodies = reinterpret_cast<const uint2*>(w->cs_bodies.p) + cs.slot_offset;
-        a.vers = w->cs_vers.p + cs.slot_offset;
-        a.round_start = w->cs_round_start.p + cs.round_start_offset;
-        a.round_mask = w->cs_round_mask.p + cs.round_offset;
-        a.round_level = w->cs_round_level.p + cs.round_offset;
-        a.nap = nap;
-        a.dynst = p ? dyn_pos : dyn_vel;
-        a.counter = w->barrier_words + p;
-        a.xcc_table = w->barrier_words + 64 + 32 * p;
-        a.slot_of = w->cs_slot_of.p;
-        a.replay_flag = replay_flag;
-        a.trace = trace_path && !replay_flag ? trace_dev + (p ? 4 * n_rounds[0] : 0) : nullptr;
-        a.rv = rv;
-        a.n_tiles = cs.n_tiles;
-        a.n_groups = (cs.n_tiles + PHYS_CS_WAVES - 1u) / PHYS_CS_WAVES;
-        a.n_first = p ? 0u : 1u;
-        a.n_passes = p ? w->cfg.n_positional_correction_iterations : w->cfg.n_iterations + 1u;
-        uint32_t& count = p ? w->barrier_count1 : w->barrier_count;
-        a.counter_base = count;
-        count += a.n_groups;  // (one grid barrier per launch: behind the census)
-        return a;
-    };
-    auto launch = [&](const CsPhase& v, const CsPhase& p) -> int {
-        const uint32_t blocks = spread > 1u ? spread * (v.n_groups > p.n_groups ? v.n_groups : p.n_groups) : v.n_groups + p.n_groups;
-        if (!blocks) return IVX_OK;
-        IVX_KLAUNCH(k_solve_cs, dim3(blocks), dim3(CS_THREADS), 0, s, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur].p,
-                    reinterpret_cast<float4*>(w->acc[w->cur].p), w->n_contacts, w->cb.p, v, p, w->mg_err_dev, ivx_solver_dry(), spread);
-        IVX_HIP_CHECK(hipGetLastError());
-        return IVX_OK;
-    };
-    const uint32_t body_blocks = (w->n_dyn + 255u) / 256u;
-    ReplayView pass1, pass2;
-    if (replay) {
-        pass1.applied = w->kin_applied.p;
-        pass2.qstart = reinterpret_cast<const float4*>(w->kin_qstart.p);
-        IVX_HIP_CHECK(ivx_memset_async(flag, 0, sizeof(uint32_t), s));
-    }
-    if (body_blocks) {
-        IVX_KLAUNCH(k_cs_init, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb.p, w->sched.n_levels[0] ? dyn_vel : nullptr, w->sched.n_levels[1] ? dyn_pos : nullptr, nullptr);
-        IVX_HIP_CHECK(hipGetLastError());
-    }
-    const CsPhase v = phase_args(0, true, ReplayView(), nullptr), p1 = phase_args(1, true, pass1, nullptr);
-    w->solver_groups_used = v.n_groups + p1.n_groups;
-    int rc;
-    if ((rc = launch(v, p1))) return rc;
-    if (replay) {  // the positional phase again where a kinematic orientation moved (ReplayView): its bodies' records from the untouched body array
-        IVX_KLAUNCH(k_kin_prefix, dim3(w->n_kin), dim3(64), 0, s, w->n_kin, w->n_dyn, w->kin_offsets.p, w->kin_list.p, w->kin_applied.p,
-                    reinterpret_cast<float4*>(w->kin_qstart.p), w->cb.p, flag);
-        if (body_blocks) IVX_KLAUNCH(k_cs_init, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb.p, nullptr, dyn_pos, flag);
-        IVX_HIP_CHECK(hipGetLastError());
-        const CsPhase none = phase_args(0, false, ReplayView(), nullptr), p2 = phase_args(1, true, pass2, flag);
-        if ((rc = launch(none, p2))) return rc;
-    }
-    if (trace_path) {
-        IVX_HIP_CHECK(ivx_stream_sync(s));
-        std::vector<unsigned long long> host(trace_cap + 2);
-        host[0] = n_rounds[0], host[1] = n_rounds[1];
-        IVX_HIP_CHECK(ivx_memcpy_sync(host.data() + 2, trace_dev, trace_cap * 8, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(trace_path, "wb")) {
-            fwrite(host.data(), 8, 2 + 4 * (n_rounds[0] + n_rounds[1]), f);
-            for (int p = 0; p < 2; ++p)
-                if (n_rounds[p]) fwrite(w->sched.cs_round_level_host.data() + w->sched.cs[p].round_offset, 4, n_rounds[p], f);
-            fclose(f);
-        }
-    }
-    if (body_blocks) {
-        IVX_KLAUNCH(k_cs_finish, dim3(body_blocks), dim3(256), 0, s, w->n_dyn, w->cb.p, w->sched.n_levels[0] ? dyn_vel : nullptr, w->sched.n_levels[1] ? dyn_pos : nullptr);
-        IVX_HIP_CHECK(hipGetLastError());
+    IVX_HIP_CHECK(ivx_memset_async(solve_trace.dev, 0, solve_trace.cap * 8, s));
+    return IVX_OK;
+}
+static int solve_trace_dump(ivx_world* w, hipStream_t s) {
+    const size_t n_rounds[2] = {cs_rounds(w, 0), cs_rounds(w, 1)};
+    IVX_HIP_CHECK(ivx_stream_sync(s));
+    std::vector<unsigned long long> host(solve_trace.cap + 2);
+    host[0] = n_rounds[0], host[1] = n_rounds[1];
+    IVX_HIP_CHECK(ivx_memcpy_sync(host.data() + 2, solve_trace.dev, solve_trace.cap * 8, hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(solve_switches().trace_path, "wb")) {
+        fwrite(host.data(), 8, 2 + 4 * (n_rounds[0] + n_rounds[1]), f);
+        for (int p = 0; p < 2; ++p)
+            if (n_rounds[p]) fwrite(w->sched.cs_round_level_host.data() + w->sched.cs[p].round_offset, 4, n_rounds[p], f);
+        fclose(f);
     }
     return IVX_OK;
 }
 
 int ivx_launch_phys_solve(ivx_world* w) {
-    if (w->n_contacts == 0) return IVX_OK;
+    using namespace ivx_solve;
+    // (co-residency of a launch's working workgroups is checked against the occupancy answers, asked once; 0 where there is none)
+    const auto blocks_per_cu = [](auto kernel, uint32_t threads) {
+        int n = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, (int)threads, 0) == hipSuccess ? n : 0;
+    };
+    static const int mg_blocks_per_cu = std::min(blocks_per_cu(k_solve_mg<0>, MG_THREADS), blocks_per_cu(k_solve_mg<1>, MG_THREADS));
+    static const int cs_blocks_per_cu = blocks_per_cu(k_solve_cs, CS_THREADS);
+    const ivx_contact_schedule& sc = w->sched;
+    const SolvePlanIn in = {w->n_contacts, w->n_dyn, w->n_kin, {sc.n_levels[0], sc.n_levels[1]}, {sc.max_level_items[0], sc.max_level_items[1]},
+                            {sc.cs_feasible[0] != 0, sc.cs_feasible[1] != 0}, sc.n_chains(), sc.n_kin_items, w->solver_groups_forced, w->mg_disabled != 0,
+                            (uint32_t)w->ctx->n_cu, mg_blocks_per_cu, cs_blocks_per_cu, solve_switches().serial, solve_switches().trace_path != nullptr};
+    const SolvePlan pl = solve_plan(in);
+    if (!pl.form) return IVX_OK;
     int rc;
-    if (solver_stationary(w)) {
-        if ((rc = ivx_world_ensure_form(w, 2u))) return rc;
-        w->solver_kind_used = 2u;
-        return launch_solve_cs(w);
+    if ((rc = ivx_world_ensure_form(w, pl.form))) return rc;
+    w->solver_kind_used = pl.kind;
+    w->solver_groups_used = pl.groups;
+    // the views and the flag of the positional phase's two passes (ReplayView): [pass]; empty without a replay
+    uint32_t* const flag = w->barrier_words + 2;
+    ReplayView view[3];
+    if (pl.replay) {
+        view[1].applied = w->kin_applied.p;
+        view[2].qstart = reinterpret_cast<const float4*>(w->kin_qstart.p);
     }
-    if ((rc = ivx_world_ensure_form(w, 1u))) return rc;
-    const uint32_t groups = solver_groups(w);
-    w->solver_groups_used = groups;
-    w->solver_kind_used = groups > 1u ? 1u : 0u;
-    // the positional phase runs twice when kinematic bodies take part in it (ReplayView): counts, then — where an orientation moves — again
-    const bool replay = w->sched.n_levels[1] && w->sched.n_kin_items > 0;
-    uint32_t* flag = w->barrier_words + 2;
-    ReplayView pass1, pass2;
-    if (replay) {
-        pass1.applied = w->kin_applied.p;
-        pass2.qstart = reinterpret_cast<const float4*>(w->kin_qstart.p);
-    }
-    auto before_positional = [&](hipStream_t st) -> int {
-        if (!replay) return IVX_OK;
-        IVX_HIP_CHECK(ivx_memset_async(flag, 0, sizeof(uint32_t), st));
-        IVX_KLAUNCH(k_kin_snapshot, dim3((w->n_dyn + 255u) / 256u + 1u), dim3(256), 0, st, w->n_dyn, w->cb.p, reinterpret_cast<float4*>(w->kin_snap.p));
-        IVX_HIP_CHECK(hipGetLastError());
-        return IVX_OK;
-    };
-    auto between_passes = [&](hipStream_t st) -> int {
-        IVX_KLAUNCH(k_kin_prefix, dim3(w->n_kin), dim3(64), 0, st, w->n_kin, w->n_dyn, w->kin_offsets.p, w->kin_list.p, w->kin_applied.p,
-                           reinterpret_cast<float4*>(w->kin_qstart.p), w->cb.p, flag);
-        IVX_KLAUNCH(k_kin_restore, dim3((w->n_dyn + 255u) / 256u + 1u), dim3(256), 0, st, w->n_dyn, w->cb.p, reinterpret_cast<const float4*>(w->kin_snap.p), flag);
-        IVX_HIP_CHECK(hipGetLastError());
-        return IVX_OK;
-    };
-    if (groups > 1u) {
-        // THE TWO PHASES SIDE BY SIDE. The velocity phase reads and writes velocities (and the accumulated impulses); the positional phase reads
-        // and writes positions and orientations; what either reads of the other's — the configuration the velocity items are linearised
-        // about, inverse masses and inertia — is in its packed records, taken from the body array before either starts (the reference runs the
-        // positional correction on the configuration the step began with, solver.rs:496-602, and integrates afterwards). Each phase is a chain
-        // of dependent tiles a handful of waves deep — 183 and 147 levels on the 4096-body pile, of which 135 are the fill of one sweep over
-        // the lattice —, so one after the other they cost the sum, on two streams the longer one.
-        hipStream_t s0 = w->ctx->stream, s1 = s0;
-        static const bool serial = [] {
-            const char* e = getenv("IVX_SOLVER_SERIAL");  // (developer switch: the phases one after the other on the context's stream)
-            return e && atoi(e) != 0;
-        }();
-        const bool both = w->sched.n_levels[0] && w->sched.n_levels[1] && !serial;
-        if (both) {
+    float4* const dyn_vel = sc.n_levels[0] ? reinterpret_cast<float4*>(w->dynst.p) : nullptr;
+    float4* const dyn_pos = sc.n_levels[1] ? reinterpret_cast<float4*>(w->dynst.p + w->body_cap * 16) : nullptr;
+    const dim3 body_blocks((w->n_dyn + 255u) / 256u);
+    hipStream_t stream[2] = {w->ctx->stream, w->side_stream};
+    for (uint32_t i = 0; i < pl.n_steps; ++i) {
+        const Step st = pl.step[i];
+        const hipStream_t s = stream[st.stream];
+        const uint32_t* const under = st.pass == 2u ? flag : nullptr;  // pass 2 runs where pass 1 left the flag raised
+        rc = IVX_OK;
+        switch (st.op) {
+        case PACK_ITEMS: rc = st.phase == 0u ? pack_items_mg<0>(w, s) : pack_items_mg<1>(w, s); break;
+        case FORK:
             if (!w->side_stream) {
                 IVX_HIP_CHECK(hipStreamCreateWithFlags(&w->side_stream, hipStreamNonBlocking));
                 IVX_HIP_CHECK(hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming));
                 IVX_HIP_CHECK(hipEventCreateWithFlags(&w->ev_join, hipEventDisableTiming));
             }
-            s1 = w->side_stream;
+            stream[1] = w->side_stream;
+            IVX_HIP_CHECK(ivx_event_record(w->ev_fork, s));
+            IVX_HIP_CHECK(hipStreamWaitEvent(stream[1], w->ev_fork, 0));
+            break;
+        case JOIN_RECORD: IVX_HIP_CHECK(ivx_event_record(w->ev_join, s)); break;
+        case JOIN_WAIT: IVX_HIP_CHECK(hipStreamWaitEvent(s, w->ev_join, 0)); break;
+        case CLEAR_FLAG: IVX_HIP_CHECK(ivx_memset_async(flag, 0, sizeof(uint32_t), s)); break;
+        case SNAPSHOT:
+            IVX_KLAUNCH(k_kin_snapshot, dim3(body_blocks.x + 1u), dim3(256), 0, s, w->n_dyn, w->cb.p, reinterpret_cast<float4*>(w->kin_snap.p));
+            break;
+        case SOLVE:
+            if (pl.kind) rc = st.phase == 0u ? launch_solve_mg<0>(w, pl.groups, s, view[st.pass], under) : launch_solve_mg<1>(w, pl.groups, s, view[st.pass], under);
+            else rc = st.phase == 0u ? launch_solve<0>(w, pl, view[st.pass], under) : launch_solve<1>(w, pl, view[st.pass], under);
+            break;
+        case KIN_PREFIX:
+            IVX_KLAUNCH(k_kin_prefix, dim3(w->n_kin), dim3(64), 0, s, w->n_kin, w->n_dyn, w->kin_offsets.p, w->kin_list.p, w->kin_applied.p,
+                        reinterpret_cast<float4*>(w->kin_qstart.p), w->cb.p, flag);
+            break;
+        case RESTORE:
+            IVX_KLAUNCH(k_kin_restore, dim3(body_blocks.x + 1u), dim3(256), 0, s, w->n_dyn, w->cb.p, reinterpret_cast<const float4*>(w->kin_snap.p), flag);
+            break;
+        case CS_INIT:  // (pass 2: the positional records again, from the untouched body array)
+            IVX_KLAUNCH(k_cs_init, body_blocks, dim3(256), 0, s, w->n_dyn, w->cb.p, under ? nullptr : dyn_vel, dyn_pos, under);
+            break;
+        case CS_SOLVE: {  // one launch runs both phases; pass 2 the positional phase alone
+            const CsPhase v = cs_phase_args(w, 0, !under, ReplayView(), nullptr), p = cs_phase_args(w, 1, true, view[st.pass], under);
+            const uint32_t spread = solve_switches().spread_cs();
+            const uint32_t blocks = spread > 1u ? spread * (v.n_groups > p.n_groups ? v.n_groups : p.n_groups) : v.n_groups + p.n_groups;
+            if (blocks)
+                IVX_KLAUNCH(k_solve_cs, dim3(blocks), dim3(CS_THREADS), 0, s, w->n_dyn, w->cfg.positional_correction_factor, w->pc[w->cur].p,
+                            reinterpret_cast<float4*>(w->acc[w->cur].p), w->n_contacts, w->cb.p, v, p, w->mg_err_dev, solve_switches().dry, spread);
+            break;
         }
-        if (w->sched.n_levels[0] && (rc = pack_items_mg<0>(w, s0))) return rc;
-        if (w->sched.n_levels[1] && (rc = pack_items_mg<1>(w, s0))) return rc;
-        if (both) {
-            IVX_HIP_CHECK(ivx_event_record(w->ev_fork, s0));
-            IVX_HIP_CHECK(hipStreamWaitEvent(s1, w->ev_fork, 0));
+        case CS_FINISH: IVX_KLAUNCH(k_cs_finish, body_blocks, dim3(256), 0, s, w->n_dyn, w->cb.p, dyn_vel, dyn_pos); break;
+        case TRACE_CLEAR: rc = solve_trace_clear(w, s); break;
+        case TRACE_DUMP: rc = solve_trace_dump(w, s); break;
         }
-        if (w->sched.n_levels[1] && both) {  // (the side stream first: its launches are in flight while the host enqueues the velocity phase)
-            if ((rc = before_positional(s1))) return rc;
-            if ((rc = launch_solve_mg<1>(w, groups, s1, pass1))) return rc;
-            if (replay) {
-                if ((rc = between_passes(s1))) return rc;
-                if ((rc = launch_solve_mg<1>(w, groups, s1, pass2, flag))) return rc;
-            }
-            IVX_HIP_CHECK(ivx_event_record(w->ev_join, s1));
-        }
-        if (w->sched.n_levels[0] && (rc = launch_solve_mg<0>(w, groups, s0))) return rc;
-        if (w->sched.n_levels[1] && !both) {
-            if ((rc = before_positional(s0))) return rc;
-            if ((rc = launch_solve_mg<1>(w, groups, s0, pass1))) return rc;
-            if (replay) {
-                if ((rc = between_passes(s0))) return rc;
-                if ((rc = launch_solve_mg<1>(w, groups, s0, pass2, flag))) return rc;
-            }
-        }
-        if (both) IVX_HIP_CHECK(hipStreamWaitEvent(s0, w->ev_join, 0));
-        return IVX_OK;
-    }
-    // the phase's mutable body state (24 / 28 bytes per dynamic body) goes to LDS when it fits one CU
-    const size_t lds0 = (size_t)w->n_dyn * 24, lds1 = (size_t)w->n_dyn * 28;
-    if (w->sched.n_levels[0]) {
-        if (lds0 <= 140 * 1024) rc = launch_solve<true, 0>(w, lds0);
-        else rc = launch_solve<false, 0>(w, 0);
         if (rc) return rc;
-    }
-    if (w->sched.n_levels[1]) {
-        if ((rc = before_positional(w->ctx->stream))) return rc;
-        if (lds1 <= 140 * 1024) rc = launch_solve<true, 1>(w, lds1, pass1);
-        else rc = launch_solve<false, 1>(w, 0, pass1);
-        if (rc) return rc;
-        if (replay) {
-            if ((rc = between_passes(w->ctx->stream))) return rc;
-            if (lds1 <= 140 * 1024) rc = launch_solve<true, 1>(w, lds1, pass2, flag);
-            else rc = launch_solve<false, 1>(w, 0, pass2, flag);
-            if (rc) return rc;
-        }
+        IVX_HIP_CHECK(hipGetLastError());
     }
     return IVX_OK;
 }

@@ -1,12 +1,13 @@
 // Device-side layouts and the host-side world object of the rigid-body / contact-solver part
-// (a15-a19). See physics.hip for the kernels, contact_schedule.hpp for the host bookkeeping of the contact set and physics_api.hip for
-// the entry points that tie them together.
+// (a15-a19). See physics.hip for the kernels, contact_schedule.hpp for the host bookkeeping of the contact set, solve_plan.hpp for what a
+// solve launches and physics_api.hip for the entry points that tie them together.
 #pragma once
 #include <cstdint>
 #include <vector>
 
 #include "contact_schedule.hpp"
 #include "device_common.hpp"
+#include "solve_plan.hpp"
 #include "vec3.hpp"
 
 // Arithmetic the step's advance of configurations (physics.hip, post_solve_body) and the constant-rotation motion driver (motion.hip) share,
@@ -63,7 +64,6 @@ struct PhysContact {
 static_assert(sizeof(PhysContact) == 96, "PhysContact layout");
 
 #define PHYS_LEVEL_TILE 4096
-#define PHYS_SOLVER_STATIONARY 255u  // ivx_world_set_solver_groups: force the chain-stationary solve where the schedule allows it
 
 // What the world holds on the device. Every array that only grows is an ivx_dev_array; physics_api.hip keeps ONE table of them (world_arrays:
 // which group an array belongs to, the host vector it is uploaded from) that the growth, the uploads and ivx_world_destroy walk.

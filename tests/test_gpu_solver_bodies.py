@@ -214,3 +214,33 @@ def test_stages_without_contacts_are_the_free_step(ctx):
         pu.assert_bodies_close(ws.bodies()[0], o.bodies()[0], what=f"free frame {frame}: ")
     for w in (ws, wf):
         w.close()
+
+
+# ---- f. body counts around the one-workgroup kernel's LDS limit -------------------------------------------------------------------------
+@pytest.mark.parametrize("n_dyn", [5120, 5121, 5973, 5974])
+def test_body_counts_around_the_lds_limit(ctx, n_dyn):
+    """k_solve keeps a phase's mutable body state in LDS while it fits 143 360 bytes, at 24 bytes a body in the velocity phase and 28 in the
+    positional phase (solve_plan.hpp): 5120 is the last count with both phases in LDS, 5121 the first with the positional phase in global
+    memory (k_solve<false, 1>, both passes of a replay), 5973 the last with the velocity phase in LDS, 5974 the first with both in global
+    memory (k_solve<false, 0>). Section (d)'s scene and asserts on one workgroup, word for word against a chain-stationary world"""
+    scene = solver_scenes.sparse_scene(n_dyn)
+    free = np.setdiff1d(np.arange(n_dyn), scene["constrained"])
+    assert len(free) > n_dyn // 2 and 0 in scene["constrained"] and n_dyn - 1 in scene["constrained"]
+    w = make_world(ctx, scene, "one_workgroup", 1)
+    w2 = make_world(ctx, scene, "chain_stationary", 1)
+    o = ol.OraclePhysics(scene["dyn"], scene["kin"], scene["config"])
+    for frame, cs in enumerate(scene["frames"]):
+        pu.step_both(w, o, cs, scene["dt"])
+        assert_kernel(w, "one_workgroup", 1)
+        w2.perform_physics_step(cs, scene["dt"])
+        assert_kernel(w2, "chain_stationary", 1)
+        assert_same_words(w, w2, f"n_dyn {n_dyn} frame {frame}:")
+        (d, k), (od, ok) = w.bodies(), o.bodies()
+        pu.assert_bodies_close(d, od, what=f"n_dyn {n_dyn} frame {frame}: ")
+        pu.compare_contact_state(w, o)
+        for f in ("position", "orientation", "velocity", "angular_axis", "angular_speed"):
+            np.testing.assert_allclose(k[f], ok[f], rtol=1e-6, atol=1e-7, err_msg=f"n_dyn {n_dyn} frame {frame} kinematic {f}")
+        for f in ("momentum", "angular_momentum"):
+            np.testing.assert_array_equal(d[f][free].view(np.uint32), scene["dyn"][f][free].view(np.uint32), err_msg=f"free bodies' {f}")
+    w.close()
+    w2.close()

@@ -25,7 +25,6 @@
 //   Leaves are decided by the flat kernel's own function; a node is skipped only where bvol_internal.hpp's node decision proves that no proper
 //   leaf below can be hit in f32; the irregular objects (a NaN bound, lower > upper) are listed by k_bvh_nodes and decided outside the walk.
 #include <algorithm>
-#include <new>
 #include <vector>
 
 #include "bvol_internal.hpp"
@@ -599,9 +598,9 @@ bool queries_host(const ivx_aabb* world, size_t n, const ivx_bv_node* nodes, con
 
 }  // namespace
 
-void ivx_bvh_release(void* hierarchy) {
-    if (!hierarchy) return;
-    BvhState* s = static_cast<BvhState*>(hierarchy);
+void ivx_bvh_release(void** hierarchy) {
+    BvhState* s = ivx_state_take<BvhState>(hierarchy);
+    if (!s) return;
     for (ivx_buf* b : {&s->tree, &s->walk, &s->sorting}) ivx_buf_free(b);
     delete s;
 }
@@ -617,12 +616,8 @@ void* ivx_bvh_device_ptr(void* hierarchy, uint64_t set_serial, int which) {
 int ivx_bvh_build_enqueue(ivx_ctx* c, const char* who) {
     ivx_bvol_view view;
     if (int rc = ivx_bvol_view_of(c, who, &view)) return rc;
-    BvhState* st = static_cast<BvhState*>(*view.hierarchy);
-    if (!st) {
-        st = new (std::nothrow) BvhState();
-        IVX_REQUIRE(st, IVX_ERR_CAPACITY, "%s: out of host memory", who);
-        *view.hierarchy = st;
-    }
+    BvhState* st;
+    if (int rc = ivx_state_for(view.hierarchy, who, &st)) return rc;
     st->built = false;  // (until this call's tree stands)
     const uint32_t n = view.n;
     if (n >= 2u) {
@@ -669,9 +664,7 @@ int ivx_bvh_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool check
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
     if (int rc = check_status(status, who)) return rc;
     const unsigned long long grand = status.grand;
-    IVX_REQUIRE(grand < (1ull << 31), IVX_ERR_CAPACITY, "%s: %llu intersecting pairs: too many for one call", who, grand);
-    *n_pairs = (size_t)grand;
-    IVX_REQUIRE(!check_cap || grand <= cap, IVX_ERR_CAPACITY, "%s: %llu intersecting pairs, the buffer holds %zu", who, grand, cap);
+    if (int rc = ivx_bvol_pairs_total(who, grand, check_cap, cap, n_pairs)) return rc;
     if (grand == 0) return IVX_OK;
     ivx_layout s;
     const size_t o_other = s.take((size_t)grand * 8), o_hist = s.take((size_t)tiles_of((size_t)grand) * 256u * 4);
@@ -739,11 +732,7 @@ int ivx_bv_hierarchy_download(ivx_ctx* c, ivx_bv_node* nodes, size_t node_cap, u
 
 int ivx_bv_pairs_hierarchy(ivx_ctx* c, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n_out) {
     const char* who = "ivx_bv_pairs_hierarchy";
-    IVX_REQUIRE(n_out, IVX_ERR_INVALID, "%s: null argument", who);
-    *n_out = 0;
-    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
-    IVX_REQUIRE(mode <= IVX_BV_DYNAMIC_PAIRS, IVX_ERR_INVALID, "%s: mode %u (0 = all pairs, 1 = no phantom and at least one dynamic member)", who, mode);
-    IVX_REQUIRE(pairs || cap == 0, IVX_ERR_INVALID, "%s: null pair buffer of capacity %zu", who, cap);
+    if (int rc = ivx_bvol_pairs_check(who, c, mode, pairs, cap, n_out)) return rc;
     ivx_bvol_view view;
     BvhState* st;
     if (int rc = current_tree(c, who, &view, &st)) return rc;
@@ -762,8 +751,8 @@ int ivx_bv_pairs_hierarchy(ivx_ctx* c, uint32_t mode, uint32_t* pairs, size_t ca
 int ivx_bv_query_skips_boxes(const ivx_bv_query* queries, size_t n_queries, const ivx_aabb* boxes, size_t n_boxes, uint8_t* skips) {
     const char* who = "ivx_bv_query_skips_boxes";
     IVX_REQUIRE((queries && boxes && skips) || n_queries == 0 || n_boxes == 0, IVX_ERR_INVALID, "%s: null argument", who);
-    for (size_t q = 0; q < n_queries && n_boxes != 0; ++q)
-        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    if (n_boxes != 0)
+        if (int rc = ivx_bvol_query_kinds_check(who, queries, n_queries)) return rc;
     for (size_t q = 0; q < n_queries; ++q)
         for (size_t b = 0; b < n_boxes; ++b) skips[q * n_boxes + b] = ivx_bv_query_skips_node(queries + q, boxes[b]) ? 1u : 0u;
     return IVX_OK;
@@ -775,8 +764,7 @@ int ivx_bv_queries_hierarchy_host(const ivx_aabb* world, size_t n, const ivx_bv_
     IVX_REQUIRE(n <= IVX_BV_MAX_OBJECTS, IVX_ERR_CAPACITY, "%s: %zu objects exceed %u", who, n, IVX_BV_MAX_OBJECTS);
     IVX_REQUIRE(n_queries <= IVX_BV_MAX_QUERIES, IVX_ERR_CAPACITY, "%s: %zu queries exceed %u per call", who, n_queries, IVX_BV_MAX_QUERIES);
     IVX_REQUIRE(queries || n_queries == 0, IVX_ERR_INVALID, "%s: null queries", who);
-    for (size_t q = 0; q < n_queries; ++q)
-        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    if (int rc = ivx_bvol_query_kinds_check(who, queries, n_queries)) return rc;
     IVX_REQUIRE((world && leaf_objects) || n == 0, IVX_ERR_INVALID, "%s: null argument", who);
     IVX_REQUIRE(nodes || n < 2, IVX_ERR_INVALID, "%s: null node buffer", who);
     if (n_queries == 0) return IVX_OK;

@@ -6,7 +6,7 @@
 //   interaction.rs:202-222 (a voxel object's entry). The reference answers all of these from a bounding volume hierarchy; its tests and fuzz targets
 //   use the `_brute_force` forms as ground truth. This file IS the brute-force form: no hierarchy, no sort, no atomics (the hierarchy: bvh.hip).
 //
-// WORLD — k_bv_world, one wave per 64 consecutive objects: a lane derives its object's world box (world_aabb below, the very function the host
+// WORLD — k_bv_world, one wave per 64 consecutive objects: a lane derives its object's world box (ivx_bv_world_aabb_of, the very function the host
 //   export runs) or takes it as given, then a shuffle min / max tree in input order leaves the block's box. Minima and maxima are taken in the total
 //   order of the bit patterns (-0.0 below +0.0), which keeps the block test below conservative under the sign-bit decision; a box with a NaN bound
 //   intersects nothing and stays out of the block box. k_bv_total, one wave: the box around the block boxes.
@@ -23,7 +23,6 @@
 //   (upload and buffers; counts, download and wait) are shared with bvh.hip's form, which fills the masks through the tree instead.
 // LISTS — ivx_bv_query_lists: the resident masks of either form as per-query object lists; the four kernels are described where they stand.
 #include <cmath>
-#include <new>
 #include <vector>
 
 #include "bvol_internal.hpp"
@@ -34,50 +33,26 @@ namespace {
 constexpr uint32_t SEG_BLOCKS = 8;     // column blocks per segment (512 columns)
 constexpr uint32_t SCAN_ROUND = 1024;  // rows per round of k_bv_scan (its workgroup)
 
-// ---- shared host / device arithmetic (f32, fixed operation order; the file is compiled without contraction) ---------------------------------
-__host__ __device__ __forceinline__ uint32_t f_bits(float v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return __float_as_uint(v);
-#else
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    return u;
-#endif
-}
-__host__ __device__ __forceinline__ float f_abs(float v) { return ivx_bv_abs(v); }
-__host__ __device__ __forceinline__ void world_aabb(const ivx_aabb& m, const ivx_similarity& s, ivx_aabb* out) { ivx_bv_world_aabb_of(m, s, out); }  // (bvol_internal.hpp: narrow.hip runs it too)
-
-// ---- device side -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool any_negative(float d0, float d1, float d2, float d3, float d4, float d5) { return ivx_bv_any_negative(d0, d1, d2, d3, d4, d5); }  // (bvol_internal.hpp)
-// box_lies_outside
+// ---- device side (the box rules: bvol_internal.hpp) ------------------------------------------------------------------------------------------
+// ivx_bv_lies_outside's rule, as six differences into ivx_bv_any_negative (the form k_bv_pair_walk is measured with)
 __device__ __forceinline__ bool lies_outside(const ivx_aabb& self, const ivx_aabb& other) {
-    return any_negative(other.upper[0] - self.lower[0], other.upper[1] - self.lower[1], other.upper[2] - self.lower[2], self.upper[0] - other.lower[0],
-                        self.upper[1] - other.lower[1], self.upper[2] - other.lower[2]);
+    return ivx_bv_any_negative(other.upper[0] - self.lower[0], other.upper[1] - self.lower[1], other.upper[2] - self.lower[2], self.upper[0] - other.lower[0],
+                               self.upper[1] - other.lower[1], self.upper[2] - other.lower[2]);
 }
-// the bit pattern of a float as a signed integer that orders like the float, with -0.0 below +0.0
-__device__ __forceinline__ int32_t order_key(float v) {
-    const int32_t b = (int32_t)__float_as_uint(v);
-    return b < 0 ? (int32_t)((uint32_t)b ^ 0x7FFFFFFFu) : b;
-}
-__device__ __forceinline__ float order_min(float a, float b) { return order_key(b) < order_key(a) ? b : a; }
-__device__ __forceinline__ float order_max(float a, float b) { return order_key(b) > order_key(a) ? b : a; }
+// ivx_bv_has_nan's rule, as three unordered pairs
 __device__ __forceinline__ bool has_nan(const ivx_aabb& b) {
     return __builtin_isunordered(b.lower[0], b.lower[1]) || __builtin_isunordered(b.lower[2], b.upper[0]) || __builtin_isunordered(b.upper[1], b.upper[2]);
 }
-// the box that is outside everything and neutral under order_min / order_max
-__device__ __forceinline__ ivx_aabb neutral_box() {
-    ivx_aabb b;
-    for (int k = 0; k < 3; ++k) b.lower[k] = INFINITY, b.upper[k] = -INFINITY;
-    return b;
-}
+// (stays: k_bv_world's code differs when it calls ivx_bv_world_aabb_of without this forced-inline step in between)
+__device__ __forceinline__ void world_aabb(const ivx_aabb& m, const ivx_similarity& s, ivx_aabb* out) { ivx_bv_world_aabb_of(m, s, out); }
 // min / max over the wave, lane l with lane l ^ d, d = 1, 2, .. 32: every lane ends with the result
 __device__ __forceinline__ ivx_aabb wave_union(ivx_aabb b) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            b.lower[k] = order_min(b.lower[k], __shfl_xor(b.lower[k], d, 64));
-            b.upper[k] = order_max(b.upper[k], __shfl_xor(b.upper[k], d, 64));
+            b.lower[k] = ivx_bv_order_min(b.lower[k], __shfl_xor(b.lower[k], d, 64));
+            b.upper[k] = ivx_bv_order_max(b.upper[k], __shfl_xor(b.upper[k], d, 64));
         }
     return b;
 }
@@ -89,29 +64,24 @@ __global__ __launch_bounds__(256) void k_bv_world(const ivx_aabb* __restrict__ m
     const uint32_t lane = threadIdx.x & 63u, blk = wave_index();
     if (blk * 64u >= n) return;  // (whole waves)
     const uint32_t o = blk * 64u + lane;
-    ivx_aabb b = neutral_box();
+    ivx_aabb b = ivx_bv_neutral_box();
     if (o < n) {
         if (DERIVE) world_aabb(model[o], sims[o], &b);
         else b = model[o];
     }
     world[o] = b;  // (the buffer holds whole blocks: the slots behind n get the neutral box, which the pair walk reads and finds outside)
-    if (has_nan(b)) b = neutral_box();
+    if (has_nan(b)) b = ivx_bv_neutral_box();
     b = wave_union(b);
     if (lane == 0u) blocks[blk] = b;
 }
 
 __global__ __launch_bounds__(64) void k_bv_total(const ivx_aabb* __restrict__ blocks, uint32_t n_blocks, ivx_aabb* __restrict__ total) {
     const uint32_t lane = threadIdx.x;
-    ivx_aabb t = neutral_box();
+    ivx_aabb t = ivx_bv_neutral_box();
     for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64u)
-        if (b0 + lane < n_blocks) {
-            const ivx_aabb b = blocks[b0 + lane];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) t.lower[k] = order_min(t.lower[k], b.lower[k]), t.upper[k] = order_max(t.upper[k], b.upper[k]);
-        }
+        if (b0 + lane < n_blocks) ivx_bv_union(&t, blocks[b0 + lane]);
     t = wave_union(t);
-    if (order_key(t.lower[0]) > order_key(t.upper[0]))  // no box without a NaN bound at all
-        for (int k = 0; k < 3; ++k) t.lower[k] = 0.0f, t.upper[k] = 0.0f;
+    ivx_bv_frame_finish(&t);  // (no box without a NaN bound at all)
     if (lane == 0u) *total = t;
 }
 
@@ -127,7 +97,7 @@ __global__ __launch_bounds__(256) void k_bv_pair_walk(const ivx_aabb* __restrict
     if (cb_end <= rb) return;  // wholly left of the diagonal: k_bv_rows starts behind these segments
     const uint32_t row = rb * 64u + lane;
     const bool live = row < n;
-    ivx_aabb self = neutral_box();
+    ivx_aabb self = ivx_bv_neutral_box();
     uint32_t row_kind = 0u;
     if (live) self = world[row], row_kind = kinds[row];
     const bool row_ok = live & ((mode == 0u) | (row_kind != IVX_BV_PHANTOM));
@@ -183,7 +153,7 @@ __global__ __launch_bounds__(256) void k_bv_query(const ivx_aabb* __restrict__ w
     if (tile >= n_words) return;  // (whole waves)
     const uint32_t o = tile * 64u + lane;
     const bool live = o < n;
-    ivx_aabb b = neutral_box();
+    ivx_aabb b = ivx_bv_neutral_box();
     if (live) b = world[o];
     float c[3], h[3];
     ivx_bv_center_half(b, c, h);
@@ -250,7 +220,7 @@ struct BvState {
     ivx_buf pairs, masks;
     ivx_buf lists;  // ivx_bv_query_lists: per-word prefixes | per-query totals | offsets
     ivx_buf hits;   // ... and the objects
-    ivx_staging staging;  // (with its event: behind the last upload from the block)
+    ivx_staging staging;
     bool has_set = false;
     uint32_t n = 0;
     bool queried = false;      // a queries call (either form) has left masks of the set that stands
@@ -262,21 +232,7 @@ struct BvState {
     size_t o_kinds = 0, o_world = 0, o_blocks = 0, o_total = 0;
 };
 
-int state_of(ivx_ctx* c, BvState** out) {
-    if (!c->bvol_state) {
-        BvState* s = new (std::nothrow) BvState();
-        IVX_REQUIRE(s, IVX_ERR_CAPACITY, "bounding volumes: out of host memory");
-        const hipError_t e = hipEventCreateWithFlags(&s->staging.staged, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            delete s;
-            ivx_set_error("bounding volumes: %s", hipGetErrorString(e));
-            return IVX_ERR_HIP;
-        }
-        c->bvol_state = s;
-    }
-    *out = static_cast<BvState*>(c->bvol_state);
-    return IVX_OK;
-}
+int state_of(ivx_ctx* c, BvState** out) { return ivx_state_for(&c->bvol_state, "bounding volumes", out); }
 
 int check_set_arguments(const char* who, const ivx_similarity* sims, const uint32_t* kinds, size_t n) {
     IVX_REQUIRE(n <= IVX_BV_MAX_OBJECTS, IVX_ERR_CAPACITY, "%s: %zu objects exceed %u", who, n, IVX_BV_MAX_OBJECTS);
@@ -334,14 +290,11 @@ int set_enqueue(ivx_ctx* c, const ivx_aabb* boxes, const ivx_similarity* sims, c
     if (int rc = ivx_staging_for(&st->staging, l.upload_bytes)) return rc;
     if (int rc = ivx_buf_grow(c, &st->set, l.bytes, 1u << 16)) return rc;
     char* h = static_cast<char*>(st->staging.p);
-    char* d = static_cast<char*>(st->set.p);
     memcpy(h + l.o_in, boxes, n * sizeof(ivx_aabb));
     if (sims) memcpy(h + l.o_sims, sims, n * sizeof(ivx_similarity));
     memset(h + l.o_kinds, 0, n_blocks * 64u * 4);
     if (kinds) memcpy(h + l.o_kinds, kinds, n * 4);
-    IVX_HIP_CHECK(ivx_memcpy_async(d, h, l.upload_bytes, hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
-    st->staging.pending = true;
+    if (int rc = ivx_staging_upload(&st->staging, st->set.p, l.upload_bytes, c->stream)) return rc;
     return set_launch(c, st, l, n, sims != nullptr);
 }
 
@@ -368,13 +321,12 @@ int set_state(ivx_ctx* c, const char* who, BvState** out) {
 }  // namespace
 
 void ivx_bvol_release(ivx_ctx* c) {
-    if (!c || !c->bvol_state) return;
-    BvState* s = static_cast<BvState*>(c->bvol_state);
+    BvState* s = c ? ivx_state_take<BvState>(&c->bvol_state) : nullptr;
+    if (!s) return;
     for (ivx_buf* b : {&s->set, &s->scratch, &s->pairs, &s->masks, &s->lists, &s->hits}) ivx_buf_free(b);
     ivx_staging_release(&s->staging);
-    ivx_bvh_release(s->hierarchy);
+    ivx_bvh_release(&s->hierarchy);
     delete s;
-    c->bvol_state = nullptr;
 }
 
 int ivx_bvol_view_of(ivx_ctx* c, const char* who, ivx_bvol_view* out) {
@@ -443,9 +395,7 @@ int ivx_bvol_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool chec
     unsigned long long grand = 0;
     IVX_HIP_CHECK(ivx_memcpy_async(&grand, d_grand, 8, hipMemcpyDeviceToHost, c->stream));
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
-    IVX_REQUIRE(grand < (1ull << 31), IVX_ERR_CAPACITY, "%s: %llu intersecting pairs: too many for one call", who, grand);
-    *n_pairs = (size_t)grand;
-    IVX_REQUIRE(!check_cap || grand <= cap, IVX_ERR_CAPACITY, "%s: %llu intersecting pairs, the buffer holds %zu", who, grand, cap);
+    if (int rc = ivx_bvol_pairs_total(who, grand, check_cap, cap, n_pairs)) return rc;
     if (grand == 0) return IVX_OK;
     if (int rc = ivx_buf_grow(c, &st->pairs, (size_t)grand * 8, 1u << 16)) return rc;
     IVX_KLAUNCH(k_bv_pair_walk<true>, walk_grid, dim3(256), 0, c->stream, d_world, d_kinds, d_blocks, n, n_blocks, n_seg, mode, d_counts, (const uint32_t*)d_rows,
@@ -454,13 +404,33 @@ int ivx_bvol_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool chec
     return IVX_OK;
 }
 
+int ivx_bvol_pairs_check(const char* who, ivx_ctx* c, uint32_t mode, const uint32_t* pairs, size_t cap, size_t* n_out) {
+    IVX_REQUIRE(n_out, IVX_ERR_INVALID, "%s: null argument", who);
+    *n_out = 0;
+    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
+    IVX_REQUIRE(mode <= IVX_BV_DYNAMIC_PAIRS, IVX_ERR_INVALID, "%s: mode %u (0 = all pairs, 1 = no phantom and at least one dynamic member)", who, mode);
+    IVX_REQUIRE(pairs || cap == 0, IVX_ERR_INVALID, "%s: null pair buffer of capacity %zu", who, cap);
+    return IVX_OK;
+}
+
+int ivx_bvol_pairs_total(const char* who, unsigned long long grand, bool check_cap, size_t cap, size_t* n_pairs) {
+    IVX_REQUIRE(grand < (1ull << 31), IVX_ERR_CAPACITY, "%s: %llu intersecting pairs: too many for one call", who, grand);
+    *n_pairs = (size_t)grand;
+    IVX_REQUIRE(!check_cap || grand <= cap, IVX_ERR_CAPACITY, "%s: %llu intersecting pairs, the buffer holds %zu", who, grand, cap);
+    return IVX_OK;
+}
+
+int ivx_bvol_query_kinds_check(const char* who, const ivx_bv_query* queries, size_t n) {
+    for (size_t q = 0; q < n; ++q)
+        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
+    return IVX_OK;
+}
+
 int ivx_bvol_queries_check(const char* who, ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries) {
     IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
     IVX_REQUIRE(n_queries <= IVX_BV_MAX_QUERIES, IVX_ERR_CAPACITY, "%s: %zu queries exceed %u per call", who, n_queries, IVX_BV_MAX_QUERIES);
     IVX_REQUIRE(queries || n_queries == 0, IVX_ERR_INVALID, "%s: null queries", who);
-    for (size_t q = 0; q < n_queries; ++q)
-        IVX_REQUIRE(queries[q].kind <= IVX_BV_QUERY_ORIENTED_BOX, IVX_ERR_INVALID, "%s: query %zu has kind %u (0 box, 1 sphere, 2 frustum, 3 oriented box)", who, q, queries[q].kind);
-    return IVX_OK;
+    return ivx_bvol_query_kinds_check(who, queries, n_queries);
 }
 
 int ivx_bvol_queries_begin(ivx_ctx* c, const char* who, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, ivx_bvol_query_run* run) {
@@ -479,9 +449,7 @@ int ivx_bvol_queries_begin(ivx_ctx* c, const char* who, const ivx_bv_query* quer
     st->queried = false, st->n_listed = 0u;  // (until this call's masks stand)
     char* s = static_cast<char*>(st->scratch.p);
     memcpy(st->staging.p, queries, n_queries * sizeof(ivx_bv_query));
-    IVX_HIP_CHECK(ivx_memcpy_async(s + o_q, st->staging.p, n_queries * sizeof(ivx_bv_query), hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
-    st->staging.pending = true;
+    if (int rc = ivx_staging_upload(&st->staging, s + o_q, n_queries * sizeof(ivx_bv_query), c->stream)) return rc;
     run->d_queries = reinterpret_cast<const ivx_bv_query*>(s + o_q);
     run->d_masks = static_cast<unsigned long long*>(st->masks.p);
     run->d_counts = reinterpret_cast<uint32_t*>(s + o_c);
@@ -511,7 +479,7 @@ int ivx_bv_world_aabb(const ivx_aabb* model, const ivx_similarity* similarity, i
     IVX_REQUIRE(model && similarity && out, IVX_ERR_INVALID, "ivx_bv_world_aabb: null argument");
     IVX_REQUIRE(similarity->scaling > 0.0f, IVX_ERR_INVALID, "ivx_bv_world_aabb: the scaling %g is not positive", (double)similarity->scaling);
     ivx_aabb b;
-    world_aabb(*model, *similarity, &b);
+    ivx_bv_world_aabb_of(*model, *similarity, &b);
     *out = b;
     return IVX_OK;
 }
@@ -522,7 +490,7 @@ int ivx_bv_frustum_query(const float planes[6][4], ivx_bv_query* out) {
     out->kind = IVX_BV_QUERY_FRUSTUM;
     for (int p = 0; p < 6; ++p) {
         for (int k = 0; k < 4; ++k) out->u.frustum.planes[p][k] = planes[p][k];
-        out->u.frustum.corners[p] = (((f_bits(planes[p][0]) >> 31) ^ 1u) << 2) | (((f_bits(planes[p][1]) >> 31) ^ 1u) << 1) | ((f_bits(planes[p][2]) >> 31) ^ 1u);
+        out->u.frustum.corners[p] = (((ivx_bv_bits(planes[p][0]) >> 31) ^ 1u) << 2) | (((ivx_bv_bits(planes[p][1]) >> 31) ^ 1u) << 1) | ((ivx_bv_bits(planes[p][2]) >> 31) ^ 1u);
     }
     return IVX_OK;
 }
@@ -581,11 +549,7 @@ int ivx_bv_download(ivx_ctx* c, ivx_aabb* world_boxes, size_t cap, ivx_aabb* tot
 
 int ivx_bv_pairs(ivx_ctx* c, uint32_t mode, uint32_t* pairs, size_t cap, size_t* n_out) {
     const char* who = "ivx_bv_pairs";
-    IVX_REQUIRE(n_out, IVX_ERR_INVALID, "%s: null argument", who);
-    *n_out = 0;
-    IVX_REQUIRE(c, IVX_ERR_INVALID, "%s: null context", who);
-    IVX_REQUIRE(mode <= IVX_BV_DYNAMIC_PAIRS, IVX_ERR_INVALID, "%s: mode %u (0 = all pairs, 1 = no phantom and at least one dynamic member)", who, mode);
-    IVX_REQUIRE(pairs || cap == 0, IVX_ERR_INVALID, "%s: null pair buffer of capacity %zu", who, cap);
+    if (int rc = ivx_bvol_pairs_check(who, c, mode, pairs, cap, n_out)) return rc;
     BvState* st;
     if (int rc = set_state(c, who, &st)) return rc;
     if (st->n < 2u) return IVX_OK;

@@ -275,7 +275,7 @@ struct ivx_bvol_view {
     uint32_t n_queried = 0;                     // ... 0: no queries call has left any since the set
 };
 int ivx_bvol_view_of(ivx_ctx* c, const char* who, ivx_bvol_view* out);  // IVX_ERR_STATE without a set
-void ivx_bvh_release(void* hierarchy);
+void ivx_bvh_release(void** hierarchy);  // (the slot: empty afterwards)
 void* ivx_bvh_device_ptr(void* hierarchy, uint64_t set_serial, int which);  // IVX_BV_PTR_NODES / _LEAF_OBJECTS
 // ivx_bv_build_hierarchy and the pair pass of ivx_bv_pairs_hierarchy, with ivx_bvol_pairs_enqueue's contract (narrow.hip drives both)
 int ivx_bvh_build_enqueue(ivx_ctx* c, const char* who);
@@ -292,6 +292,7 @@ struct ivx_bvol_query_run {
     uint32_t n = 0, n_words = 0, n_queries = 0;
     size_t mask_bytes = 0;
 };
+int ivx_bvol_query_kinds_check(const char* who, const ivx_bv_query* queries, size_t n);  // every kind is one of the four (IVX_ERR_INVALID names the first that is not)
 int ivx_bvol_queries_check(const char* who, ivx_ctx* c, const ivx_bv_query* queries, size_t n_queries);
 int ivx_bvol_queries_begin(ivx_ctx* c, const char* who, const ivx_bv_query* queries, size_t n_queries, uint64_t* masks, ivx_bvol_query_run* run);
 int ivx_bvol_queries_finish(ivx_ctx* c, const ivx_bvol_query_run& run, uint64_t* masks, uint32_t* counts);
@@ -307,3 +308,7 @@ uint64_t ivx_bvol_set_serial(const ivx_ctx* c);
 // The pair pass of ivx_bv_pairs over the context's set, up to and including the emit launch into the context's pair buffer (ivx_bv_device_ptr):
 // waits once, for the grand total (*n_pairs, set before any refusal). check_cap: refuse (IVX_ERR_CAPACITY, nothing emitted) when it exceeds cap.
 int ivx_bvol_pairs_enqueue(ivx_ctx* c, const char* who, uint32_t mode, bool check_cap, size_t cap, size_t* n_pairs);
+// What ivx_bv_pairs and ivx_bv_pairs_hierarchy refuse before they look at the set (*n_out is zero afterwards), and what both pair passes refuse once
+// the grand total is known: 2^31 pairs or more, then (*n_pairs set) a total beyond the caller's buffer.
+int ivx_bvol_pairs_check(const char* who, ivx_ctx* c, uint32_t mode, const uint32_t* pairs, size_t cap, size_t* n_out);
+int ivx_bvol_pairs_total(const char* who, unsigned long long grand, bool check_cap, size_t cap, size_t* n_pairs);

@@ -20,7 +20,6 @@
 // GATHER — k_cull_gather (ivx_cull_many_resident), one lane per (view, object): the pair and its flags from the frame-instance pairs the context
 //   holds (instances.hip), at the object's index there, to where the upload of the other entry points puts them.
 #include <cmath>
-#include <new>
 #include <vector>
 
 #include "device_common.hpp"
@@ -250,29 +249,13 @@ __global__ __launch_bounds__(256) void k_cull_place(const uint2* __restrict__ ti
 // context-owned state: device buffers that only grow, a pinned staging block for the one upload of a call (device_common.hpp), and the layout of the last call
 struct CullState {
     ivx_buf args, frusta, scratch;
-    void* d_counts = nullptr;  // MAX_VIEWS records
-    ivx_staging staging;       // (with its event: behind the last upload from the block)
+    ivx_buf counts;  // ivx_cull_count[MAX_VIEWS], made by the first enqueue (n_views != 0 only behind one)
+    ivx_staging staging;
     uint32_t n_views = 0, n_obj = 0, total = 0;
     ivx_cull_region regions[MAX_VIEWS];
 };
 
-int state_of(ivx_ctx* c, CullState** out) {
-    if (!c->cull_state) {
-        CullState* s = new (std::nothrow) CullState();
-        IVX_REQUIRE(s, IVX_ERR_CAPACITY, "chunk culling: out of host memory");
-        hipError_t e = hipMalloc(&s->d_counts, MAX_VIEWS * sizeof(ivx_cull_count));
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->staging.staged, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            if (s->d_counts) (void)hipFree(s->d_counts);
-            delete s;
-            ivx_set_error("chunk culling: %s", hipGetErrorString(e));
-            return IVX_ERR_HIP;
-        }
-        c->cull_state = s;
-    }
-    *out = static_cast<CullState*>(c->cull_state);
-    return IVX_OK;
-}
+int state_of(ivx_ctx* c, CullState** out) { return ivx_state_for(&c->cull_state, "chunk culling", out); }
 
 // what a call culls: the objects' tables (device pointers, or host arrays to upload), and either views + pairs or ready records
 struct CullJob {
@@ -309,6 +292,7 @@ int check_views_and_pairs(const char* who, const ivx_cull_view* views, size_t n_
 int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
     CullState* st;
     if (int rc = state_of(c, &st)) return rc;
+    if (int rc = ivx_buf_grow(c, &st->counts, MAX_VIEWS * sizeof(ivx_cull_count), 0)) return rc;
     st->n_views = 0, st->n_obj = 0, st->total = 0;  // (until this call's layout stands: a call that fails leaves nothing to download)
     const size_t n_obj = j.n_obj, n_views = j.n_views, n_pairs = n_obj * n_views;
     // slots and tiles
@@ -390,9 +374,7 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
     }
     CullViewOut* vout = reinterpret_cast<CullViewOut*>(h + o_vout);
     for (size_t v = 0; v < n_views; ++v) vout[v].offset = st->regions[v].offset, vout[v].indexed = st->regions[v].stride == 20u ? 1u : 0u, vout[v].pad = 0u;
-    IVX_HIP_CHECK(ivx_memcpy_async(d, h, upload_bytes, hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
-    st->staging.pending = true;
+    if (int rc = ivx_staging_upload(&st->staging, d, upload_bytes, c->stream)) return rc;  // (ahead of k_cull_gather, which reads the indices it brings)
     ivx_culling_frustum* d_frusta = static_cast<ivx_culling_frustum*>(st->frusta.p);
     const CullObj* d_objs = reinterpret_cast<const CullObj*>(d + o_objs);
     if (n_pairs && resident)
@@ -406,7 +388,7 @@ int cull_enqueue(ivx_ctx* c, const CullJob& j, ivx_cull_region* out_layout) {
             IVX_KLAUNCH(k_cull_frusta, dim3((uint32_t)((n_pairs + 255u) / 256u)), dim3(256), 0, c->stream, reinterpret_cast<const ivx_cull_view*>(d + o_views), (uint32_t)n_views,
                         reinterpret_cast<const ivx_cull_pair*>(d + o_pairs), d_objs, (uint32_t)n_obj, d_frusta);
     }
-    ivx_cull_count* d_counts = static_cast<ivx_cull_count*>(st->d_counts);
+    ivx_cull_count* d_counts = static_cast<ivx_cull_count*>(st->counts.p);
     if (n_tiles == 0) {  // no submesh anywhere: empty regions, zero counts
         IVX_HIP_CHECK(ivx_memset_async(d_counts, 0, n_views * sizeof(ivx_cull_count), c->stream));
         return done();
@@ -435,7 +417,7 @@ int cull_collect(ivx_ctx* c, const char* who, ivx_cull_count* out_counts, size_t
     IVX_REQUIRE(c->cull_state, IVX_ERR_STATE, "%s: nothing has been culled on this context", who);
     CullState* st = static_cast<CullState*>(c->cull_state);
     IVX_REQUIRE(n_views == st->n_views, IVX_ERR_INVALID, "%s: the last call had %u views, not %zu", who, st->n_views, n_views);
-    if (n_views) IVX_HIP_CHECK(ivx_memcpy_async(out_counts, st->d_counts, n_views * sizeof(ivx_cull_count), hipMemcpyDeviceToHost, c->stream));
+    if (n_views) IVX_HIP_CHECK(ivx_memcpy_async(out_counts, st->counts.p, n_views * sizeof(ivx_cull_count), hipMemcpyDeviceToHost, c->stream));
     IVX_HIP_CHECK(ivx_stream_sync(c->stream));
     return IVX_OK;
 }
@@ -511,13 +493,11 @@ int many_enqueue(const char* who, ivx_grid* const* grids, size_t n, const ivx_cu
 }  // namespace
 
 void ivx_cull_release(ivx_ctx* c) {
-    if (!c || !c->cull_state) return;
-    CullState* s = static_cast<CullState*>(c->cull_state);
-    for (ivx_buf* b : {&s->args, &s->frusta, &s->scratch}) ivx_buf_free(b);
-    if (s->d_counts) (void)hipFree(s->d_counts);
+    CullState* s = c ? ivx_state_take<CullState>(&c->cull_state) : nullptr;
+    if (!s) return;
+    for (ivx_buf* b : {&s->args, &s->frusta, &s->scratch, &s->counts}) ivx_buf_free(b);
     ivx_staging_release(&s->staging);
     delete s;
-    c->cull_state = nullptr;
 }
 
 extern "C" {
@@ -630,7 +610,7 @@ int ivx_cull_download(ivx_ctx* c, uint32_t view, void* args, size_t args_bytes, 
     IVX_REQUIRE(!frusta || n_frusta >= st->n_obj, IVX_ERR_CAPACITY, "ivx_cull_download: a view has %u frustum records, the buffer holds %zu", st->n_obj, n_frusta);
     ivx_many_other_context other_(c);
     if (args && region_bytes) IVX_HIP_CHECK(ivx_memcpy_async(args, static_cast<char*>(st->args.p) + r.offset, region_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (count) IVX_HIP_CHECK(ivx_memcpy_async(count, static_cast<ivx_cull_count*>(st->d_counts) + view, sizeof(ivx_cull_count), hipMemcpyDeviceToHost, c->stream));
+    if (count) IVX_HIP_CHECK(ivx_memcpy_async(count, static_cast<ivx_cull_count*>(st->counts.p) + view, sizeof(ivx_cull_count), hipMemcpyDeviceToHost, c->stream));
     if (frusta && st->n_obj)
         IVX_HIP_CHECK(ivx_memcpy_async(frusta, static_cast<ivx_culling_frustum*>(st->frusta.p) + (size_t)view * st->n_obj, st->n_obj * sizeof(ivx_culling_frustum),
                                        hipMemcpyDeviceToHost, c->stream));
@@ -643,7 +623,7 @@ void* ivx_cull_device_ptr(ivx_ctx* c, int which) {
     CullState* st = static_cast<CullState*>(c->cull_state);
     switch (which) {
         case IVX_CULL_PTR_ARGS: return st->args.p;
-        case IVX_CULL_PTR_COUNTS: return st->d_counts;
+        case IVX_CULL_PTR_COUNTS: return st->counts.p;  // (null only if the first enqueue could not make it)
         case IVX_CULL_PTR_FRUSTA: return st->frusta.p;
         default: return nullptr;
     }

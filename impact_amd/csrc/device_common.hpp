@@ -2,6 +2,8 @@
 // device buffers that only grow, host-mapped blocks that only grow, the pinned staging block a call's one upload or download goes through, and
 // the layout of the parts of one allocation.
 #pragma once
+#include <new>
+
 #include "ivx_internal.hpp"
 
 // `b` holds at least `bytes` afterwards. A buffer that has to grow waits for the stream first (what is in flight may still read the old one) and
@@ -74,8 +76,11 @@ struct ivx_layout {
     }
 };
 
-// A pinned host block that only grows. An owner that uploads from it asynchronously creates `staged`, records it behind the upload and sets
-// `pending`: the next ivx_staging_for then waits until that upload has left the block. An owner that waits for the stream itself leaves both alone.
+// A pinned host block that only grows, and the two ways an owner uses it:
+//   asynchronous  ivx_staging_for, fill the block, ivx_staging_upload (one copy from the block's start) — or copies of the owner's own from offsets
+//                 of the block and ivx_staging_sent behind the last of them. The next ivx_staging_for waits until that upload has left the block.
+//   synchronous   ivx_staging_for alone: the owner waits for the stream itself before it touches the block again, and never calls `sent`.
+// `staged` and `pending` belong to ivx_staging_sent and ivx_staging_for; no owner writes them.
 struct ivx_staging {
     void* p = nullptr;
     size_t bytes = 0;
@@ -96,10 +101,42 @@ static inline int ivx_staging_for(ivx_staging* st, size_t bytes) {
     st->bytes = bytes;
     return IVX_OK;
 }
+// the copies out of the block have just been enqueued on `s`: the event behind them (made on first use) says when the block is free again
+static inline int ivx_staging_sent(ivx_staging* st, hipStream_t s) {
+    if (!st->staged) IVX_HIP_CHECK(hipEventCreateWithFlags(&st->staged, hipEventDisableTiming));
+    IVX_HIP_CHECK(ivx_event_record(st->staged, s));
+    st->pending = true;
+    return IVX_OK;
+}
+// the first `bytes` of the block to `dst` on the device
+static inline int ivx_staging_upload(ivx_staging* st, void* dst, size_t bytes, hipStream_t s) {
+    IVX_HIP_CHECK(ivx_memcpy_async(dst, st->p, bytes, hipMemcpyHostToDevice, s));
+    return ivx_staging_sent(st, s);
+}
 static inline void ivx_staging_release(ivx_staging* st) {
     if (st->p) (void)hipHostFree(st->p);
     if (st->staged) (void)hipEventDestroy(st->staged);
     *st = ivx_staging();
+}
+
+// The record a subsystem hangs off a `void*` slot of the context or the world. `for`: the record in the slot, made (value-initialised) on first
+// use; `what` names the owner in the one out-of-memory message. `take`: the record leaves the slot (null: there was none) — the owner's release
+// function frees its members and deletes it.
+template <class S>
+static inline int ivx_state_for(void** slot, const char* what, S** out) {
+    if (!*slot) {
+        S* s = new (std::nothrow) S();
+        IVX_REQUIRE(s, IVX_ERR_CAPACITY, "%s: out of host memory", what);
+        *slot = s;
+    }
+    *out = static_cast<S*>(*slot);
+    return IVX_OK;
+}
+template <class S>
+static inline S* ivx_state_take(void** slot) {
+    S* s = static_cast<S*>(*slot);
+    *slot = nullptr;
+    return s;
 }
 
 // ---- store forms of the device code -------------------------------------------------------------------------------------------------------

@@ -43,7 +43,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "ivx_internal.hpp"
@@ -547,7 +546,6 @@ int fg_install(ivx_world* w, FgState* st) {
     const size_t at_records = l.take(n_field * sizeof(FgGravBody));
     if (int rc = ivx_buf_grow(w->ctx, &st->dev, l.bytes, 1u << 12)) return rc;
     if (int rc = ivx_staging_for(&st->staging, upload)) return rc;
-    if (!st->staging.staged) IVX_HIP_CHECK(hipEventCreateWithFlags(&st->staging.staged, hipEventDisableTiming));
     char* h = static_cast<char*>(st->staging.p);
     memset(h, 0, upload);  // (the loads start as the reference's: zero)
     if (n) memcpy(h + at_gens, st->gens.data(), n * sizeof(ivx_force_generator));
@@ -563,9 +561,7 @@ int fg_install(ivx_world* w, FgState* st) {
             if (media->slots[s].n_theta) rows[s] = ivx_drag_map_view{static_cast<const ivx_drag_load*>(media->slots[s].buf.p), media->slots[s].n_theta, 0u};
     }
     // (stream-ordered behind an apply that still reads the plan this one replaces)
-    IVX_HIP_CHECK(ivx_memcpy_async(st->dev.p, h, upload, hipMemcpyHostToDevice, w->ctx->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, w->ctx->stream));
-    st->staging.pending = true;
+    if (int rc = ivx_staging_upload(&st->staging, st->dev.p, upload, w->ctx->stream)) return rc;
     st->at_offsets = at_offsets, st->at_entries = at_entries, st->at_ranks = at_ranks, st->at_field = at_field, st->at_loads = at_loads, st->at_records = at_records;
     st->at_drag = at_drag, st->at_drag_offsets = at_drag_offsets, st->at_maps = at_maps;
     st->plan_dyn = (uint32_t)n_dyn;
@@ -586,12 +582,11 @@ void fg_needs(FgState* st) {
 }
 
 void fg_state_release(ivx_world* w) {
-    if (!w->fg_state) return;
-    FgState* st = static_cast<FgState*>(w->fg_state);
+    FgState* st = ivx_state_take<FgState>(&w->fg_state);
+    if (!st) return;
     ivx_buf_free(&st->dev);
     ivx_staging_release(&st->staging);
     delete st;
-    w->fg_state = nullptr;
 }
 
 // after one of the three sets has changed: all gone — the state leaves (the medium and the maps stay); else a new plan
@@ -609,26 +604,8 @@ int fg_sets_changed(ivx_world* w, FgState* st) {
     return fg_install(w, st);
 }
 
-int fg_state_for(ivx_world* w, const char* who, FgState** out) {
-    FgState* st = static_cast<FgState*>(w->fg_state);
-    if (!st) {
-        st = new (std::nothrow) FgState();
-        IVX_REQUIRE(st, IVX_ERR_CAPACITY, "%s: out of host memory", who);
-        w->fg_state = st;
-    }
-    *out = st;
-    return IVX_OK;
-}
-int fg_media_for(ivx_world* w, const char* who, FgMedia** out) {
-    FgMedia* m = static_cast<FgMedia*>(w->fg_media);
-    if (!m) {
-        m = new (std::nothrow) FgMedia();
-        IVX_REQUIRE(m, IVX_ERR_CAPACITY, "%s: out of host memory", who);
-        w->fg_media = m;
-    }
-    *out = m;
-    return IVX_OK;
-}
+int fg_state_for(ivx_world* w, const char* who, FgState** out) { return ivx_state_for(&w->fg_state, who, out); }
+int fg_media_for(ivx_world* w, const char* who, FgMedia** out) { return ivx_state_for(&w->fg_media, who, out); }
 // the slot's rows of the resident table are stale (another address or n_theta): the next apply uploads the plan again
 void fg_maps_changed(ivx_world* w) {
     FgState* st = static_cast<FgState*>(w->fg_state);
@@ -688,10 +665,9 @@ void fg_apply_host(const ivx_force_generator* gens, size_t n, const uint32_t* fi
 void ivx_fg_release(ivx_world* w) {
     if (!w) return;
     fg_state_release(w);
-    if (FgMedia* m = static_cast<FgMedia*>(w->fg_media)) {
+    if (FgMedia* m = ivx_state_take<FgMedia>(&w->fg_media)) {
         for (FgMedia::Slot& s : m->slots) ivx_buf_free(&s.buf);
         delete m;
-        w->fg_media = nullptr;
     }
 }
 

@@ -21,7 +21,6 @@
 // No atomic anywhere: two calls leave the same bytes. Every minimum and maximum is taken in the total order of the bit patterns
 // (ivx_bv_order_min / _max, bvol_internal.hpp), so no result depends on the partition above.
 #include <cmath>
-#include <new>
 #include <vector>
 
 #include "bvol_internal.hpp"
@@ -246,21 +245,7 @@ struct FiState {
     size_t o_objects = 0, o_transforms = 0;
 };
 
-int state_of(ivx_ctx* c, FiState** out) {
-    if (!c->fi_state) {
-        FiState* s = new (std::nothrow) FiState();
-        IVX_REQUIRE(s, IVX_ERR_CAPACITY, "frame instances: out of host memory");
-        const hipError_t e = hipEventCreateWithFlags(&s->staging.staged, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            delete s;
-            ivx_set_error("frame instances: %s", hipGetErrorString(e));
-            return IVX_ERR_HIP;
-        }
-        c->fi_state = s;
-    }
-    *out = static_cast<FiState*>(c->fi_state);
-    return IVX_OK;
-}
+int state_of(ivx_ctx* c, FiState** out) { return ivx_state_for(&c->fi_state, "frame instances", out); }
 
 int check_instances(const char* who, const ivx_fi_instance* instances, size_t n) {
     IVX_REQUIRE(n <= IVX_BV_MAX_OBJECTS, IVX_ERR_CAPACITY, "%s: %zu instances exceed %u", who, n, IVX_BV_MAX_OBJECTS);
@@ -296,12 +281,11 @@ void empty_result(ivx_fi_view_result* r) {
 }  // namespace
 
 void ivx_fi_release(ivx_ctx* c) {
-    if (!c || !c->fi_state) return;
-    FiState* s = static_cast<FiState*>(c->fi_state);
+    FiState* s = c ? ivx_state_take<FiState>(&c->fi_state) : nullptr;
+    if (!s) return;
     for (ivx_buf* b : {&s->inst, &s->scratch, &s->pairs, &s->lists, &s->results, &s->kept[0], &s->kept[1]}) ivx_buf_free(b);
     ivx_staging_release(&s->staging);
     delete s;
-    c->fi_state = nullptr;
 }
 
 int ivx_fi_resident_pairs(ivx_ctx* c, const char* who, size_t n_views, const ivx_cull_pair** d_pairs, uint32_t* n) {
@@ -329,9 +313,7 @@ int ivx_fi_set_instances(ivx_ctx* c, const ivx_fi_instance* instances, size_t n)
         if (int rc = ivx_buf_grow(c, &st->inst, bytes, 1u << 16)) return rc;
         memcpy(st->staging.p, instances, bytes);
         (void)ivx_many_break();
-        IVX_HIP_CHECK(ivx_memcpy_async(st->inst.p, st->staging.p, bytes, hipMemcpyHostToDevice, c->stream));
-        IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
-        st->staging.pending = true;
+        if (int rc = ivx_staging_upload(&st->staging, st->inst.p, bytes, c->stream)) return rc;
     }
     st->has_inst = true, st->n_inst = (uint32_t)n;
     return IVX_OK;
@@ -373,9 +355,7 @@ int ivx_fi_views(ivx_ctx* c, const ivx_fi_view* views, size_t n_views, ivx_fi_vi
     char* d_lists = static_cast<char*>(st->lists.p);
     memcpy(st->staging.p, views, n_views * sizeof(ivx_fi_view));
     (void)ivx_many_break();
-    IVX_HIP_CHECK(ivx_memcpy_async(s + o_views, st->staging.p, n_views * sizeof(ivx_fi_view), hipMemcpyHostToDevice, c->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, c->stream));
-    st->staging.pending = true;
+    if (int rc = ivx_staging_upload(&st->staging, s + o_views, n_views * sizeof(ivx_fi_view), c->stream)) return rc;
     const ivx_fi_view* d_views = reinterpret_cast<const ivx_fi_view*>(s + o_views);
     const ivx_fi_instance* d_inst = static_cast<const ivx_fi_instance*>(st->inst.p);
     float* d_partials = reinterpret_cast<float*>(s + o_partials);

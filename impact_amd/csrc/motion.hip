@@ -20,7 +20,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "ivx_internal.hpp"
@@ -225,12 +224,11 @@ struct MdState {
 }  // namespace
 
 void ivx_md_release(ivx_world* w) {
-    if (!w || !w->md_state) return;
-    MdState* st = static_cast<MdState*>(w->md_state);
+    MdState* st = w ? ivx_state_take<MdState>(&w->md_state) : nullptr;
+    if (!st) return;
     ivx_buf_free(&st->dev);
     ivx_staging_release(&st->staging);
     delete st;
-    w->md_state = nullptr;
 }
 
 int ivx_motion_ready(ivx_world* w, const char* who) {
@@ -265,28 +263,21 @@ int ivx_world_set_motion_drivers(ivx_world* w, const ivx_motion_driver* drivers,
     }
     MdPlan plan;
     if (int rc = md_build_plan(who, drivers, n, w->n_kin, &plan)) return rc;
-    MdState* st = static_cast<MdState*>(w->md_state);
-    if (!st) {
-        st = new (std::nothrow) MdState();
-        IVX_REQUIRE(st, IVX_ERR_CAPACITY, "%s: out of host memory", who);
-        w->md_state = st;
-    }
+    MdState* st;
+    if (int rc = ivx_state_for(&w->md_state, who, &st)) return rc;
     st->n_driven = 0;  // (until this call's set stands)
     const size_t n_driven = plan.bodies.size();
     ivx_layout l;
     const size_t at_drivers = l.take(n * sizeof(ivx_motion_driver)), at_bodies = l.take(n_driven * 4), at_offsets = l.take((n_driven + 1) * 4);
     if (int rc = ivx_buf_grow(w->ctx, &st->dev, l.bytes, 1u << 12)) return rc;
     if (int rc = ivx_staging_for(&st->staging, l.bytes)) return rc;
-    if (!st->staging.staged) IVX_HIP_CHECK(hipEventCreateWithFlags(&st->staging.staged, hipEventDisableTiming));
     char* h = static_cast<char*>(st->staging.p);
     memset(h, 0, l.bytes);
     memcpy(h + at_drivers, plan.sorted.data(), n * sizeof(ivx_motion_driver));
     memcpy(h + at_bodies, plan.bodies.data(), n_driven * 4);
     memcpy(h + at_offsets, plan.offsets.data(), (n_driven + 1) * 4);
     // (stream-ordered behind an apply that still reads the set this one replaces)
-    IVX_HIP_CHECK(ivx_memcpy_async(st->dev.p, h, l.bytes, hipMemcpyHostToDevice, w->ctx->stream));
-    IVX_HIP_CHECK(ivx_event_record(st->staging.staged, w->ctx->stream));
-    st->staging.pending = true;
+    if (int rc = ivx_staging_upload(&st->staging, st->dev.p, l.bytes, w->ctx->stream)) return rc;
     st->at_bodies = at_bodies, st->at_offsets = at_offsets;
     st->need_kin = plan.bodies.back() + 1u;
     st->n_driven = (uint32_t)n_driven;

@@ -19,7 +19,6 @@
 #include <cfloat>
 #include <cmath>
 #include <cstddef>
-#include <new>
 #include <vector>
 
 #include "bvol_internal.hpp"
@@ -386,7 +385,7 @@ __global__ __launch_bounds__(GROUP) void k_cw_rows(const uint2* __restrict__ def
 // world-owned state: device buffers that only grow, a pinned block the results of a call come back through (device_common.hpp)
 struct CwState {
     ivx_buf local, world, scratch, contacts, deferred;
-    ivx_staging staging;  // (no event: the call waits for the stream before it reads the block)
+    ivx_staging staging;  // (the synchronous path: the call waits for the stream before it reads the block)
     bool has_collidables = false, synchronized = false;
     uint32_t n = 0;
     uint32_t need_dyn = 0, need_kin = 0;  // body counts the collidables' indices were checked against need at least
@@ -403,15 +402,7 @@ struct CwState {
     size_t n_rows = 0, last_deferred = 0;
 };
 
-int state_of(ivx_world* w, CwState** out) {
-    if (!w->cw_state) {
-        CwState* s = new (std::nothrow) CwState();
-        IVX_REQUIRE(s, IVX_ERR_CAPACITY, "collidables: out of host memory");
-        w->cw_state = s;
-    }
-    *out = static_cast<CwState*>(w->cw_state);
-    return IVX_OK;
-}
+int state_of(ivx_world* w, CwState** out) { return ivx_state_for(&w->cw_state, "collidables", out); }
 
 int synchronized_state(ivx_world* w, const char* who, CwState** out) {
     IVX_REQUIRE(w, IVX_ERR_INVALID, "%s: null world", who);
@@ -425,12 +416,11 @@ int synchronized_state(ivx_world* w, const char* who, CwState** out) {
 }  // namespace
 
 void ivx_cw_release(ivx_world* w) {
-    if (!w || !w->cw_state) return;
-    CwState* s = static_cast<CwState*>(w->cw_state);
+    CwState* s = w ? ivx_state_take<CwState>(&w->cw_state) : nullptr;
+    if (!s) return;
     for (ivx_buf* b : {&s->local, &s->world, &s->scratch, &s->contacts, &s->deferred, &s->voxel_dev, &s->rows}) ivx_buf_free(b);
     for (ivx_staging* g : {&s->staging, &s->staging_rows, &s->staging_out}) ivx_staging_release(g);
     delete s;
-    w->cw_state = nullptr;
 }
 
 namespace {

@@ -104,19 +104,6 @@ void joint_refs_drop(ivx_world* w) {
     w->joint_refs_host.clear();
 }
 
-// `st` holds the bytes of an upload that has just been enqueued on `s`: the event behind it says when the block is free again
-int staging_sent(ivx_staging* st, hipStream_t s) {
-    IVX_HIP_CHECK(ivx_event_record(st->staged, s));
-    st->pending = true;
-    return IVX_OK;
-}
-// ... and the block before it is filled: the upload before has left it, it holds `bytes`, its event exists
-int staging_take(ivx_staging* st, size_t bytes) {
-    if (int rc = ivx_staging_for(st, bytes)) return rc;
-    if (!st->staged) IVX_HIP_CHECK(hipEventCreateWithFlags(&st->staged, hipEventDisableTiming));
-    return IVX_OK;
-}
-
 int fetch_body_position(ivx_world* w, uint32_t ref, float out[3]) {
     IVX_HIP_CHECK(ivx_stream_sync(w->ctx->stream));
     const void* src = (ref & IVX_KINEMATIC_BODY) ? static_cast<const void*>(w->kin.p[ref & 0x7FFFFFFFu].position) : static_cast<const void*>(w->dyn.p[ref].position);
@@ -173,11 +160,11 @@ struct StagedUploads {
         if (items.empty()) return IVX_OK;
         hipStream_t s = w->ctx->stream;
         ivx_staging* st = &w->stage_sched;
-        if (int rc = staging_take(st, total)) return rc;
+        if (int rc = ivx_staging_for(st, total)) return rc;
         char* block = static_cast<char*>(st->p);
         for (const Item& it : items) memcpy(block + it.off, it.src, it.bytes);
         for (const Item& it : items) IVX_HIP_CHECK(ivx_memcpy_async(it.dst, block + it.off, it.bytes, hipMemcpyHostToDevice, s));
-        if (int rc = staging_sent(st, s)) return rc;
+        if (int rc = ivx_staging_sent(st, s)) return rc;
         items.clear();
         total = 0;
         return IVX_OK;
@@ -344,8 +331,7 @@ static int set_contacts_fast(ivx_world* w, const ivx_contact* contacts, size_t n
     if (!h.same_as_resident(contacts, n, static_cast<ivx_contact*>(w->stage_contacts.p))) return IVX_OK;
     hipStream_t s = w->ctx->stream;
     w->n_prev = w->n_contacts;
-    IVX_HIP_CHECK(ivx_memcpy_async(w->contacts.p, w->stage_contacts.p, bytes, hipMemcpyHostToDevice, s));
-    if (int rc = staging_sent(&w->stage_contacts, s)) return rc;
+    if (int rc = ivx_staging_upload(&w->stage_contacts, w->contacts.p, bytes, s)) return rc;
     *done = true;
     return world_prepare_launches(w, nullptr);
 }
@@ -380,7 +366,7 @@ int ivx_world_set_contacts(ivx_world* w, const ivx_contact* contacts, size_t n, 
     lap("validate + interlock");
     // 2. the ConstraintCache: every id keeps its slot; the contacts in slot order go straight into the pinned block their upload is made from
     const uint32_t nc = h.register_contacts(eff, n_eff);
-    if ((rc = staging_take(&w->stage_contacts, (size_t)nc * sizeof(ivx_contact)))) return rc;
+    if ((rc = ivx_staging_for(&w->stage_contacts, (size_t)nc * sizeof(ivx_contact)))) return rc;
     h.write_slot_order(eff, static_cast<ivx_contact*>(w->stage_contacts.p));
     w->n_prev = w->n_contacts;  // size of the state arrays written by the previous prepare
     w->n_contacts = nc;
@@ -400,10 +386,7 @@ int ivx_world_set_contacts(ivx_world* w, const ivx_contact* contacts, size_t n, 
             if (a.group == G_KIN_LISTS || a.group == G_KIN_SCRATCH)
                 if ((rc = ivx_dev_grow(a.p, a.cap, a.unit, a.need, s))) return rc;
     // (no wait here: the copies below are stream-ordered behind whatever still reads these buffers; a buffer that grew was waited for as it grew)
-    if (nc) {
-        IVX_HIP_CHECK(ivx_memcpy_async(w->contacts.p, w->stage_contacts.p, (size_t)nc * sizeof(ivx_contact), hipMemcpyHostToDevice, s));
-        if ((rc = staging_sent(&w->stage_contacts, s))) return rc;
-    }
+    if (nc && (rc = ivx_staging_upload(&w->stage_contacts, w->contacts.p, (size_t)nc * sizeof(ivx_contact), s))) return rc;
     StagedUploads up(w);
     if (nc) up.add(w->prev_slot.p, h.prev_slot_host.data(), nc * sizeof(int32_t));
     if (!same_schedule && h.n_kin_items)

@@ -180,10 +180,8 @@ __global__ __launch_bounds__(256) void k_probe_select(ProbeSelectArgs a) {
 }
 __device__ __forceinline__ void probe_select_small_body(const ProbeSelectArgs& a, uint32_t bid, uint32_t nb) { probe_select_body<PROBE_SMALLV, true>(a, bid, nb); }
 __device__ __forceinline__ void probe_select_full_body(const ProbeSelectArgs& a, uint32_t bid, uint32_t nb) { probe_select_body<PROBE_MAXV, false>(a, bid, nb); }
-IVX_MANY_TWIN(k_probe_select_small_many, ProbeSelectArgs, probe_select_small_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_probe_select_small, k_probe_select_small_many, ProbeSelectArgs, 256)
-IVX_MANY_TWIN(k_probe_select_full_many, ProbeSelectArgs, probe_select_full_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_probe_select_full, k_probe_select_full_many, ProbeSelectArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_PROBE_SELECT_SMALL, k_probe_select_small_many, ProbeSelectArgs, probe_select_small_body, 256)
+IVX_MANY_DECLARE(IVX_MK_PROBE_SELECT_FULL, k_probe_select_full_many, ProbeSelectArgs, probe_select_full_body, 256)
 
 // exclusive scan over n counts (one workgroup); offsets[n] = total
 struct ScanCountsArgs {
@@ -201,8 +199,7 @@ __device__ __forceinline__ void scan_counts_body(const ScanCountsArgs& a, uint32
     }
 }
 __global__ __launch_bounds__(256) void k_scan_counts(ScanCountsArgs a) { scan_counts_body(a, 0u, 1u); }
-IVX_MANY_TWIN(k_scan_counts_many, ScanCountsArgs, scan_counts_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_scan_counts, k_scan_counts_many, ScanCountsArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_SCAN_COUNTS, k_scan_counts_many, ScanCountsArgs, scan_counts_body, 256)
 
 struct ProbeGatherArgs {
     const ivx_submesh* submeshes;
@@ -244,9 +241,7 @@ __device__ __forceinline__ void probe_gather_body(const ProbeGatherArgs& a, uint
 }
 
 __global__ __launch_bounds__(64) void k_probe_gather(ProbeGatherArgs a) { probe_gather_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_probe_gather_many, ProbeGatherArgs, probe_gather_body, __launch_bounds__(64))
-IVX_MANY_LAUNCHER(many_probe_gather, k_probe_gather_many, ProbeGatherArgs, 64)
-static_assert(sizeof(ProbeSelectArgs) % 8 == 0 && sizeof(ProbeGatherArgs) % 8 == 0, "argument blocks travel as 8-byte words");
+IVX_MANY_DECLARE(IVX_MK_PROBE_GATHER, k_probe_gather_many, ProbeGatherArgs, probe_gather_body, 64)
 
 // ---- mutual contacts -------------------------------------------------------------------------------------------------------------
 struct MutParams {
@@ -387,8 +382,7 @@ __device__ __forceinline__ void mut_count_body(const MutCountArgs& a, uint32_t b
     if (threadIdx.x == 0) a.counts[bid] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
 }
 __global__ __launch_bounds__(256) void k_mut_count(MutCountArgs a) { mut_count_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_mut_count_many, MutCountArgs, mut_count_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_mut_count, k_mut_count_many, MutCountArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_MUT_COUNT, k_mut_count_many, MutCountArgs, mut_count_body, 256)
 
 __device__ __forceinline__ void mut_emit_body(const MutEmitArgs& a, uint32_t bid, uint32_t) {
     const MutParams& p = a.p;
@@ -427,18 +421,9 @@ __device__ __forceinline__ void mut_emit_body(const MutEmitArgs& a, uint32_t bid
     out[slot] = c;
 }
 __global__ __launch_bounds__(256) void k_mut_emit(MutEmitArgs a) { mut_emit_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_mut_emit_many, MutEmitArgs, mut_emit_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_mut_emit, k_mut_emit_many, MutEmitArgs, 256)
-static_assert(sizeof(ScanCountsArgs) % 8 == 0 && sizeof(MutCountArgs) % 8 == 0 && sizeof(MutEmitArgs) % 8 == 0, "argument blocks travel as 8-byte words");
+IVX_MANY_DECLARE(IVX_MK_MUT_EMIT, k_mut_emit_many, MutEmitArgs, mut_emit_body, 256)
 
 }  // namespace
-
-static const int s_collide_many_registered = (ivx_many_register(IVX_MK_SCAN_COUNTS, many_scan_counts, sizeof(ScanCountsArgs)),
-                                              ivx_many_register(IVX_MK_MUT_COUNT, many_mut_count, sizeof(MutCountArgs)),
-                                              ivx_many_register(IVX_MK_MUT_EMIT, many_mut_emit, sizeof(MutEmitArgs)),
-                                              ivx_many_register(IVX_MK_PROBE_SELECT_SMALL, many_probe_select_small, sizeof(ProbeSelectArgs)),
-                                              ivx_many_register(IVX_MK_PROBE_SELECT_FULL, many_probe_select_full, sizeof(ProbeSelectArgs)),
-                                              ivx_many_register(IVX_MK_PROBE_GATHER, many_probe_gather, sizeof(ProbeGatherArgs)), 0);
 
 // d_slots = nullptr: every submesh (recompute); else the listed submesh slots (incremental sync), n_sub = their number. d_counts_host: optional
 // host-mapped copy of the counts (ivx_collision_probes_sync_many). Inside a recorded batch the launches are captured.
@@ -449,9 +434,9 @@ int ivx_launch_probe_select(ivx_grid* g, uint32_t n_sub, uint32_t log2_bs, uint3
     memset(&a, 0, sizeof(a));
     a.submeshes = g->submeshes, a.pos = g->positions, a.nrm = g->normals, a.idx = g->indices, a.corner_list = d_corner_list, a.sel = d_sel, a.counts = d_counts;
     a.counts_host = d_counts_host, a.err = d_err, a.slots = d_slots, a.log2_bs = log2_bs, a.inv_extent = 1.0f / g->extent;
-    if (n_blocks <= PROBE_SMALLV && !ivx_many_try(g->ctx, g, IVX_MK_PROBE_SELECT_SMALL, n_sub, a))
-        IVX_KLAUNCH((k_probe_select<PROBE_SMALLV, true>), dim3(n_sub), dim3(256), 0, g->ctx->stream, a);
-    if (!ivx_many_try(g->ctx, g, IVX_MK_PROBE_SELECT_FULL, n_sub, a)) IVX_KLAUNCH((k_probe_select<PROBE_MAXV, false>), dim3(n_sub), dim3(256), 0, g->ctx->stream, a);
+    // (both launches: each form returns at once for the submeshes that are the other's)
+    if (n_blocks <= PROBE_SMALLV) IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_PROBE_SELECT_SMALL, n_sub, (k_probe_select<PROBE_SMALLV, true>), a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_PROBE_SELECT_FULL, n_sub, (k_probe_select<PROBE_MAXV, false>), a);
     if (d_offsets) {
         ScanCountsArgs sa;
         memset(&sa, 0, sizeof(sa));
@@ -469,7 +454,7 @@ int ivx_launch_probe_gather(ivx_grid* g, uint32_t n_sub, uint32_t log2_bs, const
     memset(&a, 0, sizeof(a));
     a.submeshes = g->submeshes, a.pos = g->positions, a.sel = d_sel, a.counts = d_counts, a.offsets = d_offsets, a.points = g->probe_points;
     a.probe_chunk = g->probe_chunk, a.entries = d_entries, a.slots = d_slots, a.n_blocks = 1u << (3u * (4u - log2_bs));
-    if (!ivx_many_try(g->ctx, g, IVX_MK_PROBE_GATHER, n_sub, a)) IVX_KLAUNCH(k_probe_gather, dim3(n_sub), dim3(64), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_PROBE_GATHER, n_sub, k_probe_gather, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -512,12 +497,12 @@ int ivx_launch_mutual_pass(ivx_grid* prober, ivx_grid* sampled, const ivx_mutual
         MutCountArgs a;
         memset(&a, 0, sizeof(a));
         a.p = p, a.points = prober->probe_points, a.probe_chunk = prober->probe_chunk, a.counts = d_counts;
-        if (!ivx_many_try(prober->ctx, prober, IVX_MK_MUT_COUNT, n_wg, a)) IVX_KLAUNCH(k_mut_count, dim3(n_wg), dim3(256), 0, prober->ctx->stream, a);
+        IVX_MANY_LAUNCH(prober->ctx, prober, IVX_MK_MUT_COUNT, n_wg, k_mut_count, a);
     } else {
         MutEmitArgs a;
         memset(&a, 0, sizeof(a));
         a.p = p, a.points = prober->probe_points, a.probe_chunk = prober->probe_chunk, a.offsets = d_offsets, a.out = d_out, a.cap = cap;
-        if (!ivx_many_try(prober->ctx, prober, IVX_MK_MUT_EMIT, n_wg, a)) IVX_KLAUNCH(k_mut_emit, dim3(n_wg), dim3(256), 0, prober->ctx->stream, a);
+        IVX_MANY_LAUNCH(prober->ctx, prober, IVX_MK_MUT_EMIT, n_wg, k_mut_emit, a);
     }
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -527,8 +512,9 @@ int ivx_launch_scan_counts(ivx_ctx* ctx, uint32_t n, const uint32_t* d_counts, u
     ScanCountsArgs a;
     memset(&a, 0, sizeof(a));
     a.counts = d_counts, a.offsets = d_offsets, a.total_out = d_total_out, a.n = n;
+    // (own code, not IVX_MANY_LAUNCH: a scan that belongs to no object (`owner` null) is never recorded)
     if (owner && ivx_many_try(ctx, owner, IVX_MK_SCAN_COUNTS, 1u, a)) return IVX_OK;
-    IVX_KLAUNCH(k_scan_counts, dim3(1), dim3(256), 0, ctx->stream, a);
+    IVX_KLAUNCH(k_scan_counts, dim3(1), dim3(ivx_many_threads_IVX_MK_SCAN_COUNTS), 0, ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }

@@ -173,8 +173,7 @@ __device__ __forceinline__ void svc_count_body(const SvcCountArgs& a, uint32_t b
     if (threadIdx.x == 0) counts[bid] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
 }
 __global__ __launch_bounds__(256) void k_svc_count(SvcCountArgs a) { svc_count_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_svc_count_many, SvcCountArgs, svc_count_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_svc_count, k_svc_count_many, SvcCountArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_SVC_COUNT, k_svc_count_many, SvcCountArgs, svc_count_body, 256)
 
 // exclusive scan over the chunks of the box (one workgroup; the box of a collidable is a few dozen chunks)
 __device__ __forceinline__ void svc_scan_body(const SvcScanArgs& a, uint32_t, uint32_t) {
@@ -183,8 +182,7 @@ __device__ __forceinline__ void svc_scan_body(const SvcScanArgs& a, uint32_t, ui
     if (threadIdx.x == 0) *a.total = sum;
 }
 __global__ __launch_bounds__(256) void k_svc_scan(SvcScanArgs a) { svc_scan_body(a, 0u, 1u); }
-IVX_MANY_TWIN(k_svc_scan_many, SvcScanArgs, svc_scan_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_svc_scan, k_svc_scan_many, SvcScanArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_SVC_SCAN, k_svc_scan_many, SvcScanArgs, svc_scan_body, 256)
 
 __device__ __forceinline__ void svc_emit_body(const SvcEmitArgs& a, uint32_t bid, uint32_t) {
     const SvcParams& p = a.p;
@@ -231,15 +229,9 @@ __device__ __forceinline__ void svc_emit_body(const SvcEmitArgs& a, uint32_t bid
     }
 }
 __global__ __launch_bounds__(256) void k_svc_emit(SvcEmitArgs a) { svc_emit_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_svc_emit_many, SvcEmitArgs, svc_emit_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_svc_emit, k_svc_emit_many, SvcEmitArgs, 256)
-static_assert(sizeof(SvcCountArgs) % 8 == 0 && sizeof(SvcScanArgs) % 8 == 0 && sizeof(SvcEmitArgs) % 8 == 0, "argument blocks travel as 8-byte words");
+IVX_MANY_DECLARE(IVX_MK_SVC_EMIT, k_svc_emit_many, SvcEmitArgs, svc_emit_body, 256)
 
 }  // namespace
-
-static const int s_svc_many_registered = (ivx_many_register(IVX_MK_SVC_COUNT, many_svc_count, sizeof(SvcCountArgs)),
-                                          ivx_many_register(IVX_MK_SVC_SCAN, many_svc_scan, sizeof(SvcScanArgs)),
-                                          ivx_many_register(IVX_MK_SVC_EMIT, many_svc_emit, sizeof(SvcEmitArgs)), 0);
 
 int ivx_launch_sphere_contacts(ivx_grid* g, const uint32_t lo[3], const uint32_t cc[3], const int32_t vlo[3], const int32_t vhi[3],
                                const float rotation_xyzw[4], const float translation[3], const float center[3], const float seg_vec[3], float radius,
@@ -272,16 +264,16 @@ int ivx_launch_sphere_contacts(ivx_grid* g, const uint32_t lo[3], const uint32_t
         SvcCountArgs ca;
         memset(&ca, 0, sizeof(ca));
         ca.p = p, ca.flags = g->flags, ca.counts = d_counts;
-        if (!ivx_many_try(g->ctx, g, IVX_MK_SVC_COUNT, n_box, ca)) IVX_KLAUNCH(k_svc_count, dim3(n_box), dim3(256), 0, g->ctx->stream, ca);
+        IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_SVC_COUNT, n_box, k_svc_count, ca);
         SvcScanArgs sa;
         memset(&sa, 0, sizeof(sa));
         sa.counts = d_counts, sa.offsets = d_offsets, sa.total = d_total, sa.n = n_box;
-        if (!ivx_many_try(g->ctx, g, IVX_MK_SVC_SCAN, 1u, sa)) IVX_KLAUNCH(k_svc_scan, dim3(1), dim3(256), 0, g->ctx->stream, sa);
+        IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_SVC_SCAN, 1u, k_svc_scan, sa);
     } else {
         SvcEmitArgs ea;
         memset(&ea, 0, sizeof(ea));
         ea.p = p, ea.flags = g->flags, ea.offsets = d_offsets, ea.out = d_out, ea.cap = cap;
-        if (!ivx_many_try(g->ctx, g, IVX_MK_SVC_EMIT, n_box, ea)) IVX_KLAUNCH(k_svc_emit, dim3(n_box), dim3(256), 0, g->ctx->stream, ea);
+        IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_SVC_EMIT, n_box, k_svc_emit, ea);
     }
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;

@@ -168,8 +168,7 @@ __global__ __launch_bounds__(256) void k_chunk_pre(ChunkPreArgs a) {
     ivx_stage_stamp(a.tick);
     chunk_pre_body(a, blockIdx.x, gridDim.x);
 }
-IVX_MANY_TWIN(k_chunk_pre_many, ChunkPreArgs, chunk_pre_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_chunk_pre, k_chunk_pre_many, ChunkPreArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_CHUNK_PRE, k_chunk_pre_many, ChunkPreArgs, chunk_pre_body, 256)
 
 // (slab protocol) the chunks k_chunk_pre left pending, once the ghost layers are in: one thread per chunk of the two face planes. A pending chunk
 // whose ghost neighbour is Uniform is settled as k_chunk_pre would have settled it; any other joins the end of the active list — ahead of the
@@ -634,10 +633,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_
     ivx_stage_stamp(a.tick);
     derive_body<SIGNS>(a, blockIdx.x, gridDim.x);
 }
-IVX_MANY_TWIN(k_derive_planes_many, DeriveArgs, derive_body<false>, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVES, 8))))
-IVX_MANY_TWIN(k_derive_signs_many, DeriveArgs, derive_body<true>, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVES, 8))))
-IVX_MANY_LAUNCHER(many_derive_planes, k_derive_planes_many, DeriveArgs, 256)
-IVX_MANY_LAUNCHER(many_derive_signs, k_derive_signs_many, DeriveArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_DERIVE_PLANES, k_derive_planes_many, DeriveArgs, derive_body<false>, 256, __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVES, 8))))
+IVX_MANY_DECLARE(IVX_MK_DERIVE_SIGNS, k_derive_signs_many, DeriveArgs, derive_body<true>, 256, __attribute__((amdgpu_waves_per_eu(IVX_DERIVE_WAVES, 8))))
 
 // ---- the step's sweep, one chunk per WAVE (k_derive_wave) ------------------------------------------------------------------------------
 // derive_body<true> for one grid with no ghost layers, where the workgroup form spends its time between barriers: the four waves of a
@@ -1162,8 +1159,7 @@ __device__ __forceinline__ void list_rebuild_body(const ListRebuildArgs& a, uint
     }
 }
 __global__ __launch_bounds__(256) void k_list_rebuild(ListRebuildArgs a) { list_rebuild_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_list_rebuild_many, ListRebuildArgs, list_rebuild_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_list_rebuild, k_list_rebuild_many, ListRebuildArgs, 256)
+IVX_MANY_DECLARE(IVX_MK_LIST_REBUILD, k_list_rebuild_many, ListRebuildArgs, list_rebuild_body, 256)
 
 // update_occupied_ranges (object.rs:1149-1280): tight [lo,hi) ranges of non-empty chunks and voxels from
 // the per-chunk boxes written by k_derive. raw[0..6) = minima (chunk lo xyz, voxel lo xyz), raw[6..12) = maxima
@@ -1240,10 +1236,6 @@ static DeriveArgs derive_args(ivx_grid* g, const GridView& v, const DeriveFused&
     da.signs = g->chunk_signs, da.kface_out = g->kface, da.work_counts = ivx_wc(g), da.active_list = g->active_list, da.list_in = g->active_list, da.fz = fz;
     return da;
 }
-static_assert(sizeof(DeriveArgs) % 8 == 0 && sizeof(ChunkPreArgs) % 8 == 0 && sizeof(ListRebuildArgs) % 8 == 0, "argument blocks travel as 8-byte words");
-static const int s_many_registered_derive =
-    (ivx_many_register(IVX_MK_DERIVE_PLANES, many_derive_planes, sizeof(DeriveArgs)), ivx_many_register(IVX_MK_DERIVE_SIGNS, many_derive_signs, sizeof(DeriveArgs)),
-     ivx_many_register(IVX_MK_CHUNK_PRE, many_chunk_pre, sizeof(ChunkPreArgs)), ivx_many_register(IVX_MK_LIST_REBUILD, many_list_rebuild, sizeof(ListRebuildArgs)), 0);
 
 }  // namespace
 
@@ -1323,7 +1315,7 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
         if (g->ghost_event && g->ghost_split && ivx_has_interior_planes(g)) pa.defer_ghost = 1u;
         const uint32_t blocks = (g->n_chunks + 255u) / 256u;
         pa.tick = g->timing.take(ivx_many_recording());
-        if (!ivx_many_try(g->ctx, g, IVX_MK_CHUNK_PRE, blocks, pa)) IVX_KLAUNCH(k_chunk_pre, dim3(blocks), dim3(256), 0, g->ctx->stream, pa);
+        IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_CHUNK_PRE, blocks, k_chunk_pre, pa);
         face_settle = pa;
         face_settle.tick = nullptr;
     }
@@ -1358,13 +1350,14 @@ int ivx_launch_derive(ivx_grid* g, uint32_t parts, uint32_t preset_groups) {
         da.x_part = x_part;
         da.tick = g->timing.take(ivx_many_recording());
         if (g->signs_current) {
+            // (own code, not IVX_MANY_LAUNCH: what is not recorded goes out in one of two forms, the wave form with a grid of its own)
             if (ivx_many_try(g->ctx, g, IVX_MK_DERIVE_SIGNS, derive_grid, da)) return;
             if (x_part == IVX_XPART_ALL && v.ghost_sdf[0] == nullptr && v.ghost_sdf[1] == nullptr)
                 IVX_KLAUNCH(k_derive_wave, dim3(wave_grid), dim3(256), 0, g->ctx->stream, da);
             else
                 IVX_KLAUNCH(k_derive<true>, dim3(derive_grid), dim3(256), 0, g->ctx->stream, da);
         } else {
-            if (!ivx_many_try(g->ctx, g, IVX_MK_DERIVE_PLANES, derive_grid, da)) IVX_KLAUNCH(k_derive<false>, dim3(derive_grid), dim3(256), 0, g->ctx->stream, da);
+            IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_DERIVE_PLANES, derive_grid, k_derive<false>, da);
         }
     };
     if (g->ghost_event) {
@@ -1415,7 +1408,7 @@ int ivx_launch_derive_box(ivx_grid* g, uint32_t parts, const uint32_t lo[3], con
     DeriveArgs da = derive_args(g, v, fz);
     da.box = box;
     const uint32_t blocks = box.derive_blocks + (g->n_chunks + 255u) / 256u;
-    if (!ivx_many_try(g->ctx, g, IVX_MK_DERIVE_PLANES, blocks, da)) IVX_KLAUNCH(k_derive<false>, dim3(blocks), dim3(256), 0, g->ctx->stream, da);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_DERIVE_PLANES, blocks, k_derive<false>, da);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -1428,7 +1421,7 @@ int ivx_ensure_active_list(ivx_grid* g) {
     memset(&la, 0, sizeof(la));
     la.g = ivx_view(g), la.info = g->info, la.work_counts = ivx_wc(g), la.next_work_count = next_count, la.active_list = g->active_list, la.mesh_counts = g->chunk_counts;
     const uint32_t blocks = (g->n_chunks + 255u) / 256u;
-    if (!ivx_many_try(g->ctx, g, IVX_MK_LIST_REBUILD, blocks, la)) IVX_KLAUNCH(k_list_rebuild, dim3(blocks), dim3(256), 0, g->ctx->stream, la);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_LIST_REBUILD, blocks, k_list_rebuild, la);
     IVX_HIP_CHECK(hipGetLastError());
     g->active_list_stale = 0;
     return IVX_OK;

@@ -340,10 +340,7 @@ __device__ __forceinline__ void absorb_body(const AbsorbArgs& a_, uint32_t b, ui
 }
 
 __global__ __launch_bounds__(256) void k_absorb(AbsorbArgs a) { absorb_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_absorb_many, AbsorbArgs, absorb_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_absorb, k_absorb_many, AbsorbArgs, 256)
-static_assert(sizeof(AbsorbArgs) % 8 == 0, "argument blocks travel as 8-byte words");
-static const int s_many_registered_absorb = (ivx_many_register(IVX_MK_ABSORB, many_absorb, sizeof(AbsorbArgs)), 0);
+IVX_MANY_DECLARE(IVX_MK_ABSORB, k_absorb_many, AbsorbArgs, absorb_body, 256)
 
 // dense copy of the object's distances over a voxel box (Void chunks read 127, Uniform ones -128), x-major
 __global__ __launch_bounds__(256) void k_sdf_snapshot(GridView g, const int8_t* __restrict__ sdf, int3 lo, int3 n, int8_t* __restrict__ out) {
@@ -408,7 +405,7 @@ int ivx_launch_absorb_mutual(ivx_grid* g, int from_snapshot, const uint32_t lo[3
         aa.p = p, aa.sdf = g->sdf, aa.type = g->type, aa.info = g->info, aa.dens = d_dens, aa.removed10 = d_removed10, aa.by_type = d_by_type;
         aa.counters = d_counters, aa.touched_ranges = d_touched, aa.zero16 = d_zero16;
         const uint32_t blocks = cc[0] * cc[1] * cc[2];
-        if (!ivx_many_try(g->ctx, g, IVX_MK_ABSORB, blocks, aa)) IVX_KLAUNCH(k_absorb, dim3(blocks), dim3(256), 0, g->ctx->stream, aa);
+        IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_ABSORB, blocks, k_absorb, aa);
     }
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
@@ -448,7 +445,7 @@ int ivx_launch_absorb(ivx_grid* g, int capsule, const uint32_t lo[3], const uint
         aa.p = p, aa.sdf = g->sdf, aa.type = g->type, aa.info = g->info, aa.dens = d_dens, aa.removed10 = d_removed10, aa.by_type = d_by_type;
         aa.counters = d_counters, aa.touched_ranges = d_touched, aa.zero16 = d_zero16;
         const uint32_t blocks = cc[0] * cc[1] * cc[2];
-        if (!ivx_many_try(g->ctx, g, IVX_MK_ABSORB, blocks, aa)) IVX_KLAUNCH(k_absorb, dim3(blocks), dim3(256), 0, g->ctx->stream, aa);
+        IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_ABSORB, blocks, k_absorb, aa);
     }
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;

@@ -66,10 +66,7 @@ __device__ __forceinline__ void inertia_dense_body(const InertiaDenseArgs& a, ui
     }
 }
 __global__ __launch_bounds__(256) void k_inertia_dense(InertiaDenseArgs a) { inertia_dense_body(a, blockIdx.x, gridDim.x); }
-IVX_MANY_TWIN(k_inertia_dense_many, InertiaDenseArgs, inertia_dense_body, __launch_bounds__(256))
-IVX_MANY_LAUNCHER(many_inertia_dense, k_inertia_dense_many, InertiaDenseArgs, 256)
-static_assert(sizeof(InertiaDenseArgs) % 8 == 0, "argument blocks travel as 8-byte words");
-static const int s_many_registered_inertia = (ivx_many_register(IVX_MK_INERTIA_DENSE, many_inertia_dense, sizeof(InertiaDenseArgs)), 0);
+IVX_MANY_DECLARE(IVX_MK_INERTIA_DENSE, k_inertia_dense_many, InertiaDenseArgs, inertia_dense_body, 256)
 
 // Sum over chunks in chunk order, one THREAD per chunk: a Uniform chunk is 4096 voxels of one type
 // (compute_moments_for_uniform_chunk, inertia.rs:703-754) and its moments are closed forms of its origin
@@ -135,7 +132,7 @@ static void launch_inertia_dense(ivx_grid* g, const GridView& v, const float* d_
     memset(&a, 0, sizeof(a));
     a.g = v, a.x_off = g->x_off, a.flags = g->flags, a.dens = d_dens, a.chunk_moments = g->chunk_moments, a.work_counts = ivx_wc(g), a.active_list = g->active_list;
     const uint32_t blocks = ivx_list_grid(g);
-    if (!ivx_many_try(g->ctx, g, IVX_MK_INERTIA_DENSE, blocks, a)) IVX_KLAUNCH(k_inertia_dense, dim3(blocks), dim3(256), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_INERTIA_DENSE, blocks, k_inertia_dense, a);
 }
 
 int ivx_launch_inertia_dense(ivx_grid* g) {

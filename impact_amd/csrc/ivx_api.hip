@@ -792,20 +792,7 @@ int ivx_region_face_labels_enqueue(ivx_grid* g, int side, void* device_buf) {
 
 // ---- many objects per call (many.hpp) ---------------------------------------------------------------------------------------------------
 // The per-object host code runs object after object while the launches are recorded; one flush issues a launch per chain position for all of
-// them; the results come back through every object's own host-mapped block, their gathers launched as one.
-int ivx_many_begin(ivx_ctx* c);
-int ivx_many_flush(ivx_ctx* c);
-extern "C++" int many_check(ivx_grid* const* grids, size_t n, const char* who) {
-    IVX_REQUIRE(grids && grids[0], IVX_ERR_INVALID, "%s: null object list", who);
-    static thread_local std::vector<const ivx_grid*> seen;  // (a thousand objects a call: no quadratic search for the duplicate)
-    seen.assign(grids, grids + n);
-    std::sort(seen.begin(), seen.end());
-    for (size_t i = 0; i < n; ++i) {
-        IVX_REQUIRE(grids[i] && grids[i]->ctx == grids[0]->ctx, IVX_ERR_INVALID, "%s: object %zu is null or belongs to another context", who, i);
-        IVX_REQUIRE(i == 0 || seen[i] != seen[i - 1], IVX_ERR_INVALID, "%s: an object is listed twice", who);
-    }
-    return IVX_OK;
-}
+// them; the results come back through every object's own host-mapped block, their gathers launched as one (many_check, many_phase: many.cpp).
 // A many-object call that fails half way — an object's enqueue refused, a flush failed — must not leave the objects before it "in flight":
 // the stream is drained, every object's collect half runs with its results discarded, and whatever flag still says "pending" is cleared, so
 // that the next call on any of these objects starts clean (their derived state is what the launches that did run left: step them again).
@@ -832,25 +819,6 @@ extern "C++" int many_fail(ivx_grid* const* grids, size_t n, int rc) {
     }
     ivx_set_error("%s", keep);
     return rc;
-}
-// runs `f(i)` for every object under the recorder and flushes; the first error ends the batch (what was recorded still goes out; the caller
-// drains: many_fail)
-extern "C++" int many_phase(ivx_grid* const* grids, size_t n, const std::function<int(size_t)>& f) {
-    ivx_ctx* c = grids[0]->ctx;
-    int rc = ivx_many_begin(c);
-    if (rc) return rc;
-    int first = IVX_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (size_t i = 0; i < n && !first; ++i) {
-        ivx_many_object((uint32_t)i);
-        first = f(i);
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    rc = ivx_many_flush(c);
-    if (many_trace())
-        fprintf(stderr, "[ivx many]   phase: objects %.1f us, flush %.1f us\n", 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count(),
-                1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t1).count());
-    return first ? first : rc;
 }
 
 int ivx_halo_clear(ivx_grid* g, int side) {

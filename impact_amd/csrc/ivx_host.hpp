@@ -84,7 +84,7 @@ inline int require_whole_object(const ivx_grid* g, const char* who, bool needs_p
 }
 
 // many objects per call (many.hpp): the objects of one context, each listed once | `f(i)` for every object under the recorder, then the flush |
-// the drain after a failure half way
+// the drain after a failure half way (the first two in many.cpp: they need nothing of a grid but its context)
 int many_check(ivx_grid* const* grids, size_t n, const char* who);
 int many_phase(ivx_grid* const* grids, size_t n, const std::function<int(size_t)>& f);
 int many_fail(ivx_grid* const* grids, size_t n, int rc);

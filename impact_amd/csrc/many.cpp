@@ -7,17 +7,17 @@
 #include <new>
 #include <vector>
 
-#include "ivx_internal.hpp"
+#include "ivx_host.hpp"
 
 namespace {
 
-ivx_many_reg g_regs[IVX_MK_COUNT];
+using ivx_many::Entry;
+using ivx_many::Plan;
 
-struct Entry {
-    int kernel;
-    uint32_t blocks, off, bytes;
-    uint32_t payload_off, payload_bytes;  // IVX_MK_UPLOAD: the host words, kept in the arena until the flush stages them
-};
+// per kernel id: the twin's launcher and the size of its argument block (ivx_many_register)
+ivx_many_launch_fn g_launch[IVX_MK_COUNT];
+uint32_t g_arg_bytes[IVX_MK_COUNT];
+
 struct RangeArgs {  // IVX_MK_ZERO / IVX_MK_UPLOAD
     uint32_t* dst;
     const uint32_t* src;
@@ -30,17 +30,14 @@ __global__ __launch_bounds__(256) void k_range_many(const RangeArgs* __restrict_
     const RangeArgs a = argv[i];
     for (unsigned long long w = (unsigned long long)bid * 256u + threadIdx.x; w < a.words; w += (unsigned long long)nb * 256u) a.dst[w] = a.src ? a.src[w] : a.fill;
 }
-int many_range(hipStream_t s, const void* d_argv, const uint32_t* d_block_end, uint32_t n, uint32_t total) {
-    hipLaunchKernelGGL(k_range_many, dim3(total), dim3(256), 0, s, static_cast<const RangeArgs*>(d_argv), d_block_end, n);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-const int s_range_registered = (ivx_many_register(IVX_MK_ZERO, many_range, sizeof(RangeArgs)), ivx_many_register(IVX_MK_UPLOAD, many_range, sizeof(RangeArgs)), 0);
+IVX_MANY_REGISTER(IVX_MK_ZERO, k_range_many, RangeArgs, 256)
+IVX_MANY_REGISTER(IVX_MK_UPLOAD, k_range_many, RangeArgs, 256)
 constexpr int RING = 4;
 struct Recorder {
     ivx_ctx* ctx = nullptr;
     bool on = false;
     uint32_t cur = 0;
-    std::vector<std::vector<Entry>> chains;
+    ivx_many::Chains chains;
     std::vector<unsigned char> arena;
     size_t n_entries = 0;
     // staging: pinned host block + device block per ring slot, an event behind the slot's last copy
@@ -50,7 +47,7 @@ struct Recorder {
     hipEvent_t ev[RING] = {nullptr, nullptr, nullptr, nullptr};
     bool busy[RING] = {false, false, false, false};
     int slot = 0;
-    std::vector<uint32_t> cursor;
+    Plan plan;
     uint64_t flushes = 0, launches = 0, recorded = 0;  // (ivx_many_stats)
     // the bare bracket: chains by owner in order of first appearance (`explicit_cur`: the caller numbers its objects itself, ivx_many_object)
     bool explicit_cur = false;
@@ -78,72 +75,15 @@ struct ClearOnExit {
     ~ClearOnExit();
 };
 
-// The merged launches of a flush, in issue order: launch p takes the members [first[p], first[p + 1]) of `members` ((object, entry index)
-// pairs). Flat vectors kept in the recorder: the same chains recur frame after frame and nothing is allocated after the first.
-struct Plan {
-    std::vector<int> kernel;
-    std::vector<uint32_t> first;
-    std::vector<std::pair<uint32_t, uint32_t>> members;
-    std::vector<size_t> off_args, off_ends, off_payload;  // (off_payload: per member, uploads only)
-    std::vector<uint32_t> totals;
-    void clear() {
-        kernel.clear(), first.clear(), members.clear(), off_args.clear(), off_ends.clear(), off_payload.clear(), totals.clear();
-    }
-};
-thread_local Plan t_plan;
-
 int flush_recorded_checked(Recorder* r) {
     if (r->n_entries == 0) return IVX_OK;
     ClearOnExit clear_{r};
     OnDevice dev_{r->ctx->device};
     r->flushes += 1;
     hipStream_t s = r->ctx->stream;
-    Plan& plan = t_plan;
-    plan.clear();
-    const size_t n_obj = r->chains.size();
-    r->cursor.assign(n_obj, 0u);
-    size_t left = r->n_entries;
-    // the front of the chains, position by position: the first unfinished object's next kernel, and everybody whose next entry is that kernel.
-    // `lowest`: no object below it has entries left (the scan for the next kernel starts there instead of at object 0)
-    size_t lowest = 0;
-    while (left) {
-        while (lowest < n_obj && r->cursor[lowest] >= r->chains[lowest].size()) ++lowest;
-        const int k = r->chains[lowest][r->cursor[lowest]].kernel;
-        plan.kernel.push_back(k);
-        plan.first.push_back((uint32_t)plan.members.size());
-        for (size_t i = lowest; i < n_obj; ++i) {
-            // (an object's consecutive entries of this kernel merge as well)
-            while (r->cursor[i] < r->chains[i].size() && r->chains[i][r->cursor[i]].kernel == k) {
-                plan.members.emplace_back((uint32_t)i, r->cursor[i]);
-                r->cursor[i] += 1u;
-                left -= 1;
-                if (k != IVX_MK_ZERO && k != IVX_MK_UPLOAD) break;  // (range operations of one object may all go together; kernels of one object stay in order)
-            }
-        }
-    }
-    const size_t n_launch = plan.kernel.size();
-    plan.first.push_back((uint32_t)plan.members.size());
-    // lay out argument blocks and running block counts of every launch in one staging block (+ the words of the recorded uploads)
-    size_t bytes = 0;
-    plan.off_args.resize(n_launch), plan.off_ends.resize(n_launch), plan.totals.resize(n_launch);
-    plan.off_payload.assign(plan.members.size(), 0);
-    for (size_t p = 0; p < n_launch; ++p) {
-        if (plan.kernel[p] != IVX_MK_UPLOAD) continue;
-        for (uint32_t m = plan.first[p]; m < plan.first[p + 1]; ++m) {
-            const Entry& e = r->chains[plan.members[m].first][plan.members[m].second];
-            plan.off_payload[m] = bytes;
-            bytes += (e.payload_bytes + 15u) & ~15u;
-        }
-    }
-    for (size_t p = 0; p < n_launch; ++p) {
-        const uint32_t ab = g_regs[plan.kernel[p]].arg_bytes, nm = plan.first[p + 1] - plan.first[p];
-        plan.off_args[p] = bytes;
-        bytes += (size_t)ab * nm;
-        bytes = (bytes + 15) & ~(size_t)15;
-        plan.off_ends[p] = bytes;
-        bytes += 4 * (size_t)nm;
-        bytes = (bytes + 15) & ~(size_t)15;
-    }
+    Plan& plan = r->plan;
+    ivx_many::plan_flush(r->chains, g_arg_bytes, plan);
+    const size_t n_launch = plan.n_launches(), bytes = plan.bytes;
     const int sl = r->slot;
     r->slot = (r->slot + 1) % RING;
     if (!r->ev[sl]) IVX_HIP_CHECK(hipEventCreateWithFlags(&r->ev[sl], hipEventDisableTiming));
@@ -163,34 +103,29 @@ int flush_recorded_checked(Recorder* r) {
     }
     unsigned char* h = static_cast<unsigned char*>(r->pinned[sl]);
     for (size_t p = 0; p < n_launch; ++p) {
-        const uint32_t ab = g_regs[plan.kernel[p]].arg_bytes;
-        uint32_t run = 0;
-        uint32_t* ends = reinterpret_cast<uint32_t*>(h + plan.off_ends[p]);
+        const uint32_t ab = g_arg_bytes[plan.kernel[p]];
+        memcpy(h + plan.off_ends[p], plan.ends.data() + plan.first[p], 4 * (size_t)plan.n_members(p));
         for (uint32_t m = plan.first[p]; m < plan.first[p + 1]; ++m) {
             const Entry& e = r->chains[plan.members[m].first][plan.members[m].second];
-            const size_t mi = m - plan.first[p];
-            memcpy(h + plan.off_args[p] + mi * ab, r->arena.data() + e.off, ab);
-            if (plan.kernel[p] == IVX_MK_UPLOAD) {  // the words, and where the twin finds them on the device
+            unsigned char* args = h + plan.off_args[p] + (size_t)(m - plan.first[p]) * ab;
+            memcpy(args, r->arena.data() + e.off, ab);
+            if (ivx_many::is_upload(plan.kernel[p])) {  // the words, and where the twin finds them on the device
                 memcpy(h + plan.off_payload[m], r->arena.data() + e.payload_off, e.payload_bytes);
-                RangeArgs* ra = reinterpret_cast<RangeArgs*>(h + plan.off_args[p] + mi * ab);
-                ra->src = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(r->dev[sl]) + plan.off_payload[m]);
+                reinterpret_cast<RangeArgs*>(args)->src = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(r->dev[sl]) + plan.off_payload[m]);
             }
-            run += e.blocks;
-            ends[mi] = run;
         }
-        plan.totals[p] = run;
     }
     IVX_HIP_CHECK(hipMemcpyAsync(r->dev[sl], h, bytes, hipMemcpyHostToDevice, s));
     r->busy[sl] = true;  // (from here on the slot is in use by the stream, whatever happens below: the event goes behind the last twin issued)
     const unsigned char* d = static_cast<const unsigned char*>(r->dev[sl]);
     int rc = IVX_OK;
     for (size_t p = 0; p < n_launch && rc == IVX_OK; ++p) {
-        if (plan.totals[p] == 0) continue;
-        const ivx_many_reg& reg = g_regs[plan.kernel[p]];
-        if (!reg.fn) {
+        if (!plan.issued(p)) continue;
+        const ivx_many_launch_fn fn = g_launch[plan.kernel[p]];
+        if (!fn) {
             ivx_set_error("ivx_many: kernel %d has no twin registered", plan.kernel[p]);
             rc = IVX_ERR_STATE;
-        } else if (reg.fn(s, d + plan.off_args[p], reinterpret_cast<const uint32_t*>(d + plan.off_ends[p]), plan.first[p + 1] - plan.first[p], plan.totals[p]) != 0) {
+        } else if (fn(s, d + plan.off_args[p], reinterpret_cast<const uint32_t*>(d + plan.off_ends[p]), plan.n_members(p), plan.totals[p]) != 0) {
             ivx_set_error("ivx_many: launch of twin %d failed", plan.kernel[p]);
             rc = IVX_ERR_HIP;
         } else {
@@ -221,8 +156,8 @@ ClearOnExit::~ClearOnExit() {
 
 void ivx_many_register(int kernel, ivx_many_launch_fn fn, uint32_t arg_bytes) {
     if (kernel < 0 || kernel >= IVX_MK_COUNT) return;
-    g_regs[kernel].fn = fn;
-    g_regs[kernel].arg_bytes = arg_bytes;
+    g_launch[kernel] = fn;
+    g_arg_bytes[kernel] = arg_bytes;
 }
 
 bool ivx_many_recording() { return t_rec && t_rec->on; }
@@ -302,7 +237,7 @@ bool ivx_many_capture(const ivx_ctx* c, const void* owner, int kernel, uint32_t 
         (void)ivx_many_break();
         return false;
     }
-    if (g_regs[kernel].arg_bytes != arg_bytes || !g_regs[kernel].fn) return false;  // (no twin: the caller launches — behind a break)
+    if (kernel < 0 || kernel >= IVX_MK_COUNT || g_arg_bytes[kernel] != arg_bytes || !g_launch[kernel]) return false;  // (no twin: the caller launches — behind a break)
     if (!r->explicit_cur && (r->cur >= r->owners.size() || r->owners[r->cur] != owner)) {
         // a batch recorded through the bare bracket: the captures of an object go to that object's chain (chains in order of first appearance)
         size_t i = 0;
@@ -315,7 +250,6 @@ bool ivx_many_capture(const ivx_ctx* c, const void* owner, int kernel, uint32_t 
     Entry e;
     e.kernel = kernel;
     e.blocks = blocks;
-    e.bytes = arg_bytes;
     e.payload_off = e.payload_bytes = 0;
     e.off = (uint32_t)r->arena.size();
     r->arena.resize(r->arena.size() + ((arg_bytes + 15u) & ~15u));
@@ -396,3 +330,35 @@ int ivx_many_flush(ivx_ctx* c) {
 }
 
 }  // extern "C"
+
+// ---- the recorder phases of the many-object calls (ivx_host.hpp) ---------------------------------------------------------------------------
+int many_check(ivx_grid* const* grids, size_t n, const char* who) {
+    IVX_REQUIRE(grids && grids[0], IVX_ERR_INVALID, "%s: null object list", who);
+    static thread_local std::vector<const ivx_grid*> seen;  // (a thousand objects a call: no quadratic search for the duplicate)
+    seen.assign(grids, grids + n);
+    std::sort(seen.begin(), seen.end());
+    for (size_t i = 0; i < n; ++i) {
+        IVX_REQUIRE(grids[i] && grids[i]->ctx == grids[0]->ctx, IVX_ERR_INVALID, "%s: object %zu is null or belongs to another context", who, i);
+        IVX_REQUIRE(i == 0 || seen[i] != seen[i - 1], IVX_ERR_INVALID, "%s: an object is listed twice", who);
+    }
+    return IVX_OK;
+}
+// runs `f(i)` for every object under the recorder and flushes; the first error ends the batch (what was recorded still goes out; the caller
+// drains: many_fail)
+int many_phase(ivx_grid* const* grids, size_t n, const std::function<int(size_t)>& f) {
+    ivx_ctx* c = grids[0]->ctx;
+    int rc = ivx_many_begin(c);
+    if (rc) return rc;
+    int first = IVX_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t i = 0; i < n && !first; ++i) {
+        ivx_many_object((uint32_t)i);
+        first = f(i);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    rc = ivx_many_flush(c);
+    if (many_trace())
+        fprintf(stderr, "[ivx many]   phase: objects %.1f us, flush %.1f us\n", 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count(),
+                1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t1).count());
+    return first ? first : rc;
+}

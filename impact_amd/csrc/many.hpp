@@ -18,44 +18,13 @@
 #include <cstdint>
 #include <cstring>
 
+#include "many_plan.hpp"  // the kernel ids (ivx_many_kernel)
+
 struct ivx_ctx;
 
-// kernels with a twin
-enum ivx_many_kernel : int {
-    IVX_MK_ABSORB = 0,
-    IVX_MK_DERIVE_PLANES,
-    IVX_MK_DERIVE_SIGNS,
-    IVX_MK_CHUNK_PRE,
-    IVX_MK_LIST_REBUILD,
-    IVX_MK_POST1,
-    IVX_MK_POST2,
-    IVX_MK_EMIT,
-    IVX_MK_ASSIGN,
-    IVX_MK_GATHER,
-    IVX_MK_SN_EMIT_SLOTS,
-    IVX_MK_SN_EMIT_GENERAL_SLOTS,
-    IVX_MK_INERTIA_DENSE,
-    IVX_MK_CLIP,
-    IVX_MK_SVC_COUNT,  // collidable-against-voxel-object contacts: count | scan | emit (contacts.hip)
-    IVX_MK_SVC_SCAN,
-    IVX_MK_SVC_EMIT,
-    IVX_MK_SCAN_COUNTS,  // contacts between two voxel objects: count (probes of one against the other's field) | scan | emit (collide.hip)
-    IVX_MK_MUT_COUNT,
-    IVX_MK_MUT_EMIT,
-    IVX_MK_PROBE_SELECT_SMALL,  // collision probes of the listed chunk submeshes: select (two LDS sizes) | gather (collide.hip)
-    IVX_MK_PROBE_SELECT_FULL,
-    IVX_MK_PROBE_GATHER,
-    IVX_MK_ZERO,    // fill a device range with one word (the twin of a hipMemsetAsync of 0x00 or 0xFF bytes)
-    IVX_MK_UPLOAD,  // host words to a device range (the twin of a small hipMemcpyAsync host -> device): the words ride in the flush's one staging copy
-    IVX_MK_COUNT
-};
-
-// the twin's launcher: `d_argv` n argument blocks back to back (arg_bytes each), `d_block_end` the running block counts, `total` blocks in all
+// the twin's launcher: `d_argv` n argument blocks back to back, `d_block_end` the running block counts, `total` blocks in all
 typedef int (*ivx_many_launch_fn)(hipStream_t s, const void* d_argv, const uint32_t* d_block_end, uint32_t n, uint32_t total);
-struct ivx_many_reg {
-    ivx_many_launch_fn fn;
-    uint32_t arg_bytes;
-};
+// (IVX_MANY_REGISTER below, once per kernel id; `arg_bytes`: the size of an argument block)
 void ivx_many_register(int kernel, ivx_many_launch_fn fn, uint32_t arg_bytes);
 
 // recording state of the calling thread: null = launches are issued as they come
@@ -114,17 +83,31 @@ __device__ __forceinline__ uint32_t ivx_many_find(const uint32_t* __restrict__ b
     }
     return lo;
 }
-// The twin of a kernel whose body is `BODY(const ARGS&, bid, nb)`. The argument block comes by 8-byte words through the scalar cache.
-#define IVX_MANY_TWIN(name, ARGS, BODY, ...)                                                                                      \
-    __global__ __VA_ARGS__ void name(const ARGS* __restrict__ argv, const uint32_t* __restrict__ block_end, uint32_t n) {          \
-        const uint32_t i = ivx_many_find(block_end, n, blockIdx.x);                                                                \
-        const uint32_t b0 = i ? block_end[i - 1u] : 0u;                                                                            \
-        const ARGS a = argv[i];                                                                                                    \
-        BODY(a, blockIdx.x - b0, block_end[i] - b0);                                                                               \
-    }
-#define IVX_MANY_LAUNCHER(fn_name, twin, ARGS, threads)                                                                            \
-    static int fn_name(hipStream_t s, const void* d_argv, const uint32_t* d_block_end, uint32_t n, uint32_t total) {               \
+// A twin is declared ONCE, by its kernel id: the launcher, the registration under that id, the size rule of its argument block and the thread
+// count, which the launcher and IVX_MANY_LAUNCH below both read (a twin launched with other threads than its body was written for compiles, runs
+// and gives wrong bytes only inside a batch). This form for a twin kernel written by hand (k_clip_many, k_range_many) ...
+#define IVX_MANY_REGISTER(ID, twin, ARGS, threads)                                                                                 \
+    static_assert(sizeof(ARGS) % 8 == 0, "argument blocks travel as 8-byte words");                                                \
+    [[maybe_unused]] constexpr uint32_t ivx_many_threads_##ID = threads;                                                           \
+    static int ivx_many_launch_##ID(hipStream_t s, const void* d_argv, const uint32_t* d_block_end, uint32_t n, uint32_t total) {  \
         hipLaunchKernelGGL(twin, dim3(total), dim3(threads), 0, s, static_cast<const ARGS*>(d_argv), d_block_end, n);              \
         return hipGetLastError() == hipSuccess ? 0 : -3;                                                                           \
-    }
+    }                                                                                                                              \
+    static const int ivx_many_registered_##ID = (ivx_many_register(ID, ivx_many_launch_##ID, sizeof(ARGS)), 0);
+// ... and the whole of it for a kernel whose body is `BODY(const ARGS&, bid, nb)` (further attributes of the twin behind the thread count).
+// The argument block comes by 8-byte words through the scalar cache.
+#define IVX_MANY_DECLARE(ID, twin, ARGS, BODY, threads, ...)                                                                               \
+    __global__ __launch_bounds__(threads) __VA_ARGS__ void twin(const ARGS* __restrict__ argv, const uint32_t* __restrict__ block_end, uint32_t n) { \
+        const uint32_t i = ivx_many_find(block_end, n, blockIdx.x);                                                                        \
+        const uint32_t b0 = i ? block_end[i - 1u] : 0u;                                                                                    \
+        const ARGS a = argv[i];                                                                                                            \
+        BODY(a, blockIdx.x - b0, block_end[i] - b0);                                                                                       \
+    }                                                                                                                                      \
+    IVX_MANY_REGISTER(ID, twin, ARGS, threads)
+// Launch or record: the plain kernel `k` on the context's stream with the thread count declared for ID, unless the launch was written down for
+// the flush. For the sites of exactly this shape; the others keep their own code and say why.
+#define IVX_MANY_LAUNCH(c, owner, ID, blocks, k, args)                                                                                                       \
+    do {                                                                                                                                                     \
+        if (!ivx_many_try(c, owner, ID, blocks, args)) IVX_KLAUNCH(k, dim3(blocks), dim3(ivx_many_threads_##ID), 0, (c)->stream, args);                      \
+    } while (0)
 #endif

@@ -324,14 +324,13 @@ struct ClipManyArgs {
     uint8_t* c_type;
     ivx_chunk_info* c_info;
 };
-static_assert(sizeof(ClipManyArgs) % 8 == 0, "argument blocks travel as 8-byte words");
 __global__ __launch_bounds__(256) void k_clip_many(const ClipManyArgs* __restrict__ argv, const uint32_t* __restrict__ block_end, uint32_t n) {
     const uint32_t i = ivx_many_find(block_end, n, blockIdx.x);
     const uint32_t b0 = i ? block_end[i - 1u] : 0u;
     const ClipManyArgs& a = argv[i];
     clip_body(a.cp, a.p_sdf, a.p_type, a.p_info, a.c_sdf, a.c_type, a.c_info, blockIdx.x - b0);
 }
-IVX_MANY_LAUNCHER(many_clip, k_clip_many, ClipManyArgs, 256)
+IVX_MANY_REGISTER(IVX_MK_CLIP, k_clip_many, ClipManyArgs, 256)
 
 }  // namespace
 
@@ -368,8 +367,6 @@ int ivx_launch_split_repack(ivx_grid* src, ivx_grid* dst, const uint32_t off[3])
     return IVX_OK;
 }
 
-static const int s_clip_many_registered = (ivx_many_register(IVX_MK_CLIP, many_clip, sizeof(ClipManyArgs)), 0);
-
 int ivx_launch_clip(ivx_grid* parent, ivx_grid* child, const uint32_t lo[3], const uint32_t cc[3], const float* planes4, uint32_t n_planes, int extract) {
     ivx_planes_touched(parent);
     if (child) ivx_planes_touched(child);  // (no child: the region is discarded)
@@ -392,9 +389,10 @@ int ivx_launch_clip(ivx_grid* parent, ivx_grid* child, const uint32_t lo[3], con
     ma.cp = cp;
     ma.p_sdf = parent->sdf, ma.p_type = parent->type, ma.p_info = parent->info;
     ma.c_sdf = child->sdf, ma.c_type = child->type, ma.c_info = child->info;
-    // (recorded when the fragments of an impact are made together, ivx_copy_polyhedra: the clip belongs to the CHILD's chain)
+    // (recorded when the fragments of an impact are made together, ivx_copy_polyhedra: the clip belongs to the CHILD's chain. Own code, not
+    // IVX_MANY_LAUNCH: an extraction is never recorded, and the plain kernel takes the block's members as arguments of its own)
     if (!extract && ivx_many_try(child->ctx, child, IVX_MK_CLIP, cc[0] * cc[1] * cc[2], ma)) return IVX_OK;
-    IVX_KLAUNCH(k_clip, dim3(cc[0] * cc[1] * cc[2]), dim3(256), 0, parent->ctx->stream, cp, parent->sdf, parent->type, parent->info, child->sdf,
+    IVX_KLAUNCH(k_clip, dim3(cc[0] * cc[1] * cc[2]), dim3(ivx_many_threads_IVX_MK_CLIP), 0, parent->ctx->stream, cp, parent->sdf, parent->type, parent->info, child->sdf,
                        child->type, child->info);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;

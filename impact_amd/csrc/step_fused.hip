@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_POST1_W
     ivx_stage_stamp(a.tick);
     step_post1_body(a, blockIdx.x, gridDim.x);
 }
-IVX_MANY_TWIN(k_step_post1_many, StepArgs, step_post1_body, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IVX_POST1_WAVES, 8))))
+IVX_MANY_DECLARE(IVX_MK_POST1, k_step_post1_many, StepArgs, step_post1_body, 256, __attribute__((amdgpu_waves_per_eu(IVX_POST1_WAVES, 8))))
 
 // roles: 5 (the launch's FIRST blocks) exact numbering of the multi-region chunks, 0 region merge of multi-region chunks, 1 mesher scan,
 // 2 moments final (1 block), 3 occupied final (1 block), 4 the slab protocol's face pairs (component pairs across the upper x face, from the
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void k_step_post2(StepArgs a) {
     ivx_stage_stamp(a.tick);
     step_post2_body(a, blockIdx.x, gridDim.x);
 }
-IVX_MANY_TWIN(k_step_post2_many, StepArgs, step_post2_body, __launch_bounds__(256))
+IVX_MANY_DECLARE(IVX_MK_POST2, k_step_post2_many, StepArgs, step_post2_body, 256)
 
 // roles: 0 flatten the region forest, 1 mesher emit, 2 the slab protocol's record
 // ST: the mesher's single-type form (role_sn_emit; ivx_launch_step_emit says when)
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST ? IVX_EM
     ivx_stage_stamp(a.tick);
     step_emit_body<ST>(a, blockIdx.x, gridDim.x);
 }
-IVX_MANY_TWIN(k_step_emit_many, StepArgs, step_emit_body<false>, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
+IVX_MANY_DECLARE(IVX_MK_EMIT, k_step_emit_many, StepArgs, step_emit_body<false>, 256, __attribute__((amdgpu_waves_per_eu(4, 4))))
 
 // roles: 0 component ids, 1 the mesher's general pass over the chunks the main pass (k_step_emit) handed on — the launch after the main pass
 // anyway; as a launch of its own the general pass cost the step 4 us whether it had a chunk to do or not
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     ivx_stage_stamp(a.tick);
     step_assign_body(a, blockIdx.x, gridDim.x);
 }
-IVX_MANY_TWIN(k_step_assign_many, StepArgs, step_assign_body, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
+IVX_MANY_DECLARE(IVX_MK_ASSIGN, k_step_assign_many, StepArgs, step_assign_body, 256, __attribute__((amdgpu_waves_per_eu(4, 4))))
 
 // the results as a launch of their own (one block), ordered after everything enqueued so far
 __device__ __forceinline__ void step_gather_body(const StepArgs& a, uint32_t, uint32_t) {
@@ -313,19 +313,9 @@ __device__ __forceinline__ void step_gather_body(const StepArgs& a, uint32_t, ui
     if (threadIdx.x == 0u) __hip_atomic_store(a.host_block + IVX_RB_BELL, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __global__ __launch_bounds__(64) void k_step_gather(StepArgs a) { step_gather_body(a, 0u, 1u); }
-IVX_MANY_TWIN(k_step_gather_many, StepArgs, step_gather_body, __launch_bounds__(64))
-IVX_MANY_LAUNCHER(many_post1, k_step_post1_many, StepArgs, 256)
-IVX_MANY_LAUNCHER(many_post2, k_step_post2_many, StepArgs, 256)
-IVX_MANY_LAUNCHER(many_emit, k_step_emit_many, StepArgs, 256)
-IVX_MANY_LAUNCHER(many_assign, k_step_assign_many, StepArgs, 256)
-IVX_MANY_LAUNCHER(many_gather, k_step_gather_many, StepArgs, 64)
+IVX_MANY_DECLARE(IVX_MK_GATHER, k_step_gather_many, StepArgs, step_gather_body, 64)
 
 }  // namespace
-
-static_assert(sizeof(StepArgs) % 8 == 0, "argument blocks travel as 8-byte words");
-static const int s_many_registered = (ivx_many_register(IVX_MK_POST1, many_post1, sizeof(StepArgs)), ivx_many_register(IVX_MK_POST2, many_post2, sizeof(StepArgs)),
-                                      ivx_many_register(IVX_MK_EMIT, many_emit, sizeof(StepArgs)), ivx_many_register(IVX_MK_ASSIGN, many_assign, sizeof(StepArgs)),
-                                      ivx_many_register(IVX_MK_GATHER, many_gather, sizeof(StepArgs)), 0);
 
 static StepArgs make_args(ivx_grid* g) {
     StepArgs a;
@@ -422,7 +412,7 @@ int ivx_launch_step_post1(ivx_grid* g, uint32_t stages) {
             ai.x_part = IVX_XPART_INTERIOR;
             a.x_part = IVX_XPART_FACES;
             ai.tick = g->timing.take(ivx_many_recording());
-            if (!ivx_many_try(g->ctx, g, IVX_MK_POST1, ai.nb[0], ai)) IVX_KLAUNCH(k_step_post1, dim3(ai.nb[0]), dim3(256), 0, g->ctx->stream, ai);
+            IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_POST1, ai.nb[0], k_step_post1, ai);
         }
         (void)ivx_many_break();
         static const bool skip_wait = getenv("IVX_DEBUG_SKIP_GHOST_WAIT") && atoi(getenv("IVX_DEBUG_SKIP_GHOST_WAIT")) == 2;  // (developer switch, derive.hip)
@@ -432,7 +422,7 @@ int ivx_launch_step_post1(ivx_grid* g, uint32_t stages) {
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[3] + a.nb[4] + a.nb[5];
     if (total == 0) return IVX_OK;
     a.tick = g->timing.take(ivx_many_recording());
-    if (!ivx_many_try(g->ctx, g, IVX_MK_POST1, total, a)) IVX_KLAUNCH(k_step_post1, dim3(total), dim3(256), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_POST1, total, k_step_post1, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -476,7 +466,7 @@ int ivx_launch_step_post2(ivx_grid* g, uint32_t stages, const uint16_t* face_pai
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[2] + a.nb[3] + a.nb[4] + a.nb[5];
     if (total == 0) return IVX_OK;
     a.tick = g->timing.take(ivx_many_recording());
-    if (!ivx_many_try(g->ctx, g, IVX_MK_POST2, total, a)) IVX_KLAUNCH(k_step_post2, dim3(total), dim3(256), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_POST2, total, k_step_post2, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -503,8 +493,9 @@ int ivx_launch_step_emit(ivx_grid* g, uint32_t stages, bool general_in_assign, v
     const uint32_t total = a.nb[0] + a.nb[1] + a.nb[2];
     if (total == 0) return IVX_OK;
     a.tick = g->timing.take(ivx_many_recording());
+    // (own code, not IVX_MANY_LAUNCH: one launch in two forms, and the single-type form has no twin — it always goes out, behind a break)
     if (single_type) IVX_KLAUNCH(k_step_emit<true>, dim3(total), dim3(256), 0, g->ctx->stream, a);
-    else if (!ivx_many_try(g->ctx, g, IVX_MK_EMIT, total, a)) IVX_KLAUNCH(k_step_emit<false>, dim3(total), dim3(256), 0, g->ctx->stream, a);
+    else if (!ivx_many_try(g->ctx, g, IVX_MK_EMIT, total, a)) IVX_KLAUNCH(k_step_emit<false>, dim3(total), dim3(ivx_many_threads_IVX_MK_EMIT), 0, g->ctx->stream, a);
     IVX_HIP_CHECK(hipGetLastError());
     // the chunks the main pass hands on: a role of k_step_assign when that launch follows (the caller says so), else a launch of its own
     if ((stages & IVX_STAGE_REMESH) && !general_in_assign) return ivx_launch_sn_emit_general(g);
@@ -521,7 +512,7 @@ int ivx_launch_step_assign(ivx_grid* g, bool with_mesher_general, bool with_ccl)
     a.nb[1] = with_mesher_general ? sn::ivx_emit_general_grid(g, g->n_chunks) : 0u;
     if (a.nb[0] + a.nb[1] == 0u) return IVX_OK;
     a.tick = g->timing.take(ivx_many_recording());
-    if (!ivx_many_try(g->ctx, g, IVX_MK_ASSIGN, a.nb[0] + a.nb[1], a)) IVX_KLAUNCH(k_step_assign, dim3(a.nb[0] + a.nb[1]), dim3(256), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_ASSIGN, a.nb[0] + a.nb[1], k_step_assign, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
@@ -532,7 +523,7 @@ int ivx_launch_step_gather(ivx_grid* g) {
     a.copy_src = g->gather_copy.src, a.copy_dst = g->gather_copy.dst, a.copy_words = g->gather_copy.words;  // (consumed by this launch)
     g->gather_copy = {};
     g->timing.hand_to_gather(&a.ticks_dev, &a.ticks_host, &a.n_ticks, &a.tick);  // (stamped slots since the last collect: their words go out with the results)
-    if (!ivx_many_try(g->ctx, g, IVX_MK_GATHER, 1u, a)) IVX_KLAUNCH(k_step_gather, dim3(1), dim3(64), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_GATHER, 1u, k_step_gather, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }

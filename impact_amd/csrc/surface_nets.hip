@@ -113,13 +113,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_sn_emit_general_slots(SnEmitArgs a) {
     sn_emit_general_slots_body(a, blockIdx.x, gridDim.x);
 }
-IVX_MANY_TWIN(k_sn_emit_slots_many, SnEmitArgs, sn_emit_slots_body, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
-IVX_MANY_TWIN(k_sn_emit_general_slots_many, SnEmitArgs, sn_emit_general_slots_body, __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))))
-IVX_MANY_LAUNCHER(many_sn_emit_slots, k_sn_emit_slots_many, SnEmitArgs, 256)
-IVX_MANY_LAUNCHER(many_sn_emit_general_slots, k_sn_emit_general_slots_many, SnEmitArgs, 256)
-static_assert(sizeof(SnEmitArgs) % 8 == 0, "argument blocks travel as 8-byte words");
-static const int s_many_registered_sn = (ivx_many_register(IVX_MK_SN_EMIT_SLOTS, many_sn_emit_slots, sizeof(SnEmitArgs)),
-                                         ivx_many_register(IVX_MK_SN_EMIT_GENERAL_SLOTS, many_sn_emit_general_slots, sizeof(SnEmitArgs)), 0);
+IVX_MANY_DECLARE(IVX_MK_SN_EMIT_SLOTS, k_sn_emit_slots_many, SnEmitArgs, sn_emit_slots_body, 256, __attribute__((amdgpu_waves_per_eu(4, 4))))
+IVX_MANY_DECLARE(IVX_MK_SN_EMIT_GENERAL_SLOTS, k_sn_emit_general_slots_many, SnEmitArgs, sn_emit_general_slots_body, 256, __attribute__((amdgpu_waves_per_eu(4, 4))))
 
 // div_ranged against the `/` operator over the whole operand set the mesher hands it: t = d1 / (d1 - d2) for every pair of decoded
 // distances of opposite sign (surface_nets.rs:396-404; decoded 0 is +0.0 and counts as positive), and 1 / n for the edge counts.
@@ -289,9 +284,9 @@ int ivx_launch_sn_emit_list(ivx_grid* g, uint32_t n_records, const uint32_t* d_c
     a.cursor = ivx_sn_hard_count(g) + 1, a.vcap = (uint32_t)g->vcap, a.icap = (uint32_t)g->icap, a.scap = (uint32_t)g->scap;
     a.n_patch = n_patch, a.patch_entries = static_cast<const ivx_submesh*>(d_patch_entries), a.patch_slots = d_patch_slots;
     const uint32_t b_main = ivx_emit_grid(g, n_records), b_gen = ivx_emit_general_grid(g, n_records);
-    if (!ivx_many_try(g->ctx, g, IVX_MK_SN_EMIT_SLOTS, b_main, a)) IVX_KLAUNCH(k_sn_emit_slots, dim3(b_main), dim3(256), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_SN_EMIT_SLOTS, b_main, k_sn_emit_slots, a);
     IVX_HIP_CHECK(hipGetLastError());
-    if (!ivx_many_try(g->ctx, g, IVX_MK_SN_EMIT_GENERAL_SLOTS, b_gen, a)) IVX_KLAUNCH(k_sn_emit_general_slots, dim3(b_gen), dim3(256), 0, g->ctx->stream, a);
+    IVX_MANY_LAUNCH(g->ctx, g, IVX_MK_SN_EMIT_GENERAL_SLOTS, b_gen, k_sn_emit_general_slots, a);
     IVX_HIP_CHECK(hipGetLastError());
     return IVX_OK;
 }
